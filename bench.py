@@ -3,11 +3,17 @@
 
 A "step" is one pass of the hot path over one batch: ONE chip_decode_batch launch that inflates
 every unit of this GPU's shard (default 65,536 independent raw-deflate units of 64 KiB payload,
-dynamic-Huffman + LZ77, compressed/uncompressed ~0.5 -- BASELINE.json configs[2]; the stored and
-fixed-Huffman variants of configs[1] are measured in the same run and reported under "workloads").
+dynamic-Huffman + LZ77, compressed/uncompressed ~0.5 -- BASELINE.json configs[2]).
 Inputs are resident in HBM before the timed region; outputs stay in HBM.
 
+A plain run measures the headline workload alone.  `--full` adds everything else: the other
+BASELINE configs (the stored and fixed-Huffman variants of configs[1], mixed gzip + zstd, level-1
+encode; at world > 1 the sharded mixed workload), reported under "workloads", the CPU baselines,
+and the bit-exact check of every workload's timed output against its payload.
+`--dump-outputs DIR` writes what the headline workload's last timed step computed (see dump_outputs).
+
     python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -70,6 +76,42 @@ class stdout_to_stderr:
         os.close(self.saved)
 
 
+DUMP_SEED = 20261015
+DUMP_UNITS = 64  # whole output slots, 64 x 64 KiB as float32: 16 MiB
+DUMP_BYTES = 1 << 22  # single output bytes spread over the whole output: 16 MiB
+DUMP_PER_UNIT = 1 << 19  # per-unit result words as float64; larger batches are sampled (at most 12 MiB for three of them)
+
+
+def dump_selection(n_units, slot):
+    """The fixed sample --dump-outputs takes of a launch of n_units output slots of `slot` bytes: (units whose whole slot is
+    written, byte positions, units whose result words are written or None for all of them).  Depends on the sizes alone."""
+    rng = np.random.default_rng(DUMP_SEED)
+    units = np.sort(rng.choice(n_units, size=min(DUMP_UNITS, n_units), replace=False))
+    pos = np.sort(rng.integers(0, n_units * slot, size=DUMP_BYTES, dtype=np.int64))
+    words = None if n_units <= DUMP_PER_UNIT else np.sort(rng.choice(n_units, size=DUMP_PER_UNIT, replace=False))
+    return units, pos, words
+
+
+def dump_outputs(torch, out_dir, out, slot, words):
+    """--dump-outputs: what a caller of the timed path received from its last step, as DIR/<name>.npy.  `out` is the output
+    buffer (n_units slots of `slot` bytes), `words` the per-unit result arrays by name.  Written: each of `words` as float64,
+    `out_units` (DUMP_UNITS whole slots, float32, one row per unit) and `out_bytes` (DUMP_BYTES single bytes, float32), both
+    at the positions of dump_selection()."""
+    n_units = out.numel() // slot
+    units, pos, sel = dump_selection(n_units, slot)
+    dev = out.device
+    rows = torch.from_numpy(units).to(dev)[:, None] * slot + torch.arange(slot, dtype=torch.int64, device=dev)[None, :]
+    arrays = {"out_units": out[rows].to(torch.float32), "out_bytes": out[torch.from_numpy(pos).to(dev)].to(torch.float32)}
+    for name, t in words.items():
+        arrays[name] = (t if sel is None else t[torch.from_numpy(sel).to(dev)]).to(torch.float64)
+    arrays = {name: t.cpu().numpy() for name, t in arrays.items()}
+    assert sum(a.nbytes for a in arrays.values()) <= 64 * 10**6
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    log(f"[bench] wrote {', '.join(sorted(arrays))} to {out_dir}")
+
+
 def make_workload(kind, payload, n_units, threads, first_unit=0):
     from bench_support import synth
 
@@ -82,7 +124,7 @@ def make_workload(kind, payload, n_units, threads, first_unit=0):
     return packed, offs, lens
 
 
-def run_encode(torch, compu_amd, payload_dev, n_units, steps, warmup, dist, level=1):
+def run_encode(torch, compu_amd, payload_dev, n_units, steps, warmup, dist, level=1, verify=True, dump=None):
     """BASELINE.json configs[3]: level-1 encode of every unit (raw deflate), verified by inflating it again on the GPU."""
     dev = payload_dev.device
     cap = compu_amd.encode_bound(-15, UNIT)
@@ -101,14 +143,16 @@ def run_encode(torch, compu_amd, payload_dev, n_units, steps, warmup, dist, leve
     for _ in range(warmup):
         step()
     torch.cuda.synchronize()
-    d_out.fill_(0xA5)  # the verification below speaks for the timed launches (see run_workload)
+    poison = verify or dump is not None
+    if poison:
+        d_out.fill_(0xA5)  # the verification and the dump below speak for the timed launches (see run_workload)
     evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(steps)]
     if dist is not None:
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i, (a, b) in enumerate(evs):
-        if i == steps - 1:
+        if poison and i == steps - 1:
             d_out_len.fill_(-1)
             d_status.fill_(-99)
         a.record()
@@ -123,11 +167,14 @@ def run_encode(torch, compu_amd, payload_dev, n_units, steps, warmup, dist, leve
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     kernel_ms = [a.elapsed_time(b) for a, b in evs]
-    # verify: inflate the compressed units again and compare with the payload
-    back = torch.empty_like(payload_dev)
-    ol, iu, st = compu_amd.decode_batch(-15, d_out, d_out_off, d_out_len, back, d_in_off, d_in_len)
-    torch.cuda.synchronize()
-    ok = bool((d_status == 2).all().item()) and bool((st == 2).all().item()) and bool(torch.equal(back, payload_dev))
+    if dump is not None:
+        dump_outputs(torch, dump, d_out, cap, {"out_len": d_out_len, "status": d_status})
+    ok = None
+    if verify:  # inflate the compressed units again and compare with the payload
+        back = torch.empty_like(payload_dev)
+        ol, iu, st = compu_amd.decode_batch(-15, d_out, d_out_off, d_out_len, back, d_in_off, d_in_len)
+        torch.cuda.synchronize()
+        ok = bool((d_status == 2).all().item()) and bool((st == 2).all().item()) and bool(torch.equal(back, payload_dev))
     return {
         "elapsed_s": elapsed,
         "kernel_ms_avg": float(np.mean(kernel_ms)),
@@ -138,7 +185,7 @@ def run_encode(torch, compu_amd, payload_dev, n_units, steps, warmup, dist, leve
     }
 
 
-def run_workload(torch, compu_amd, packed, offs, lens, d_expect, n_units, steps, warmup, dist, verify=True, fmt=-15):
+def run_workload(torch, compu_amd, packed, offs, lens, d_expect, n_units, steps, warmup, dist, verify=True, fmt=-15, dump=None):
     dev = torch.device("cuda", torch.cuda.current_device())
     d_in = torch.from_numpy(packed).to(dev)
     d_in_off = torch.from_numpy(offs.astype(np.int64)).to(dev)
@@ -156,10 +203,11 @@ def run_workload(torch, compu_amd, packed, offs, lens, d_expect, n_units, steps,
     for _ in range(warmup):
         step()
     torch.cuda.synchronize()
-    # The verification below must speak for the TIMED launches, not for the warm-up: the output is poisoned before the timed region
-    # (some timed launch has to write all of it) and the result words before the last timed launch (that launch has to succeed; three
-    # small fills, 0.8 MB, between two steps).
-    if verify:
+    # The verification and the dump below must speak for the TIMED launches, not for the warm-up: the output is poisoned before the
+    # timed region (some timed launch has to write all of it) and the result words before the last timed launch (that launch has to
+    # succeed; three small fills, 0.8 MB, between two steps).
+    poison = verify or dump is not None
+    if poison:
         d_out.fill_(0xA5)
     evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(steps)]
     if dist is not None:
@@ -167,7 +215,7 @@ def run_workload(torch, compu_amd, packed, offs, lens, d_expect, n_units, steps,
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i, (a, b) in enumerate(evs):
-        if verify and i == steps - 1:
+        if poison and i == steps - 1:
             d_out_len.fill_(-1)
             d_in_used.fill_(-1)
             d_status.fill_(-99)
@@ -183,7 +231,9 @@ def run_workload(torch, compu_amd, packed, offs, lens, d_expect, n_units, steps,
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     kernel_ms = [a.elapsed_time(b) for a, b in evs]
-    ok = True
+    if dump is not None:
+        dump_outputs(torch, dump, d_out, UNIT, {"out_len": d_out_len, "in_used": d_in_used, "status": d_status})
+    ok = None
     if verify:
         ok = bool((d_status == 2).all().item()) and bool((d_out_len == UNIT).all().item()) and bool(torch.equal(d_out, d_expect))
         ok = ok and bool((d_in_used == d_in_len).all().item())
@@ -414,10 +464,13 @@ def main():
     ap.add_argument("--units", type=int, default=65536, help="units per GPU")
     ap.add_argument("--encode-level", type=int, default=1, help="--workload encode: 1 = cfg3 (fixed Huffman), 2..9 = dynamic-Huffman blocks")
     ap.add_argument("--workload", default="dynamic", choices=["dynamic", "fixed", "stored", "level1", "mixed", "encode"])
-    ap.add_argument("--extra", type=int, default=1, help="also measure the configs[1] variants (stored, fixed)")
+    ap.add_argument("--full", action="store_true", help="also the other BASELINE configs, the CPU baselines and the bit-exact verification "
+                    "(a plain run times the headline workload alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy (rank 0; see dump_outputs)")
+    ap.add_argument("--extra", type=int, default=1, help="with --full: also measure the other BASELINE configs (stored, fixed, mixed, encode)")
     ap.add_argument("--cpu-sample", type=int, default=65536, help="units the CPU baseline decodes (about 10-30 s of CPU work in total)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--mixed-units", type=int, default=131072, help="several GPUs: units per GPU of the mixed gzip+zstd workload (configs[4]: 1 M frames over 8 GPUs)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: leave out the CPU baselines")
+    ap.add_argument("--mixed-units", type=int, default=131072, help="several GPUs, with --full: units per GPU of the mixed gzip+zstd workload (configs[4]: 1 M frames over 8 GPUs)")
     ap.add_argument("--worker", action="store_true", help=argparse.SUPPRESS)  # set by self_launch() on the ranks it starts
     args = ap.parse_args()
 
@@ -468,25 +521,28 @@ def main():
     t0 = time.time()
     payload = synth.payloads(n_units, first_unit=first_unit, threads=threads)
     log(f"[bench] rank {rank}: generated {n_units} x 64 KiB payload units in {time.time() - t0:.1f}s ({threads} threads)")
-    d_expect = torch.from_numpy(payload).to(torch.device("cuda", local_rank))
+    # on the GPU: the encoder's input, and what the decoders' outputs are verified against
+    d_expect = torch.from_numpy(payload).to(torch.device("cuda", local_rank)) if args.full or args.workload == "encode" else None
 
     kinds = [args.workload]
-    if args.extra and world == 1:  # every BASELINE config in the one run the driver makes: cfg1 (stored, fixed), cfg4 (mixed), cfg3 (encode)
+    if args.full and args.extra and world == 1:  # every BASELINE config in one run: cfg1 (stored, fixed), cfg4 (mixed), cfg3 (encode)
         kinds += [k for k in ("stored", "fixed", "mixed", "encode") if k != args.workload]
-    elif args.extra and world > 1 and args.workload != "mixed":
-        kinds += ["mixed"]  # configs[4] is the one config that is DEFINED on several GPUs: it rides in every multi-GPU run, at its per-GPU size
+    elif args.full and args.extra and world > 1 and args.workload != "mixed":
+        kinds += ["mixed"]  # configs[4] is the one config that is DEFINED on several GPUs: it rides in every full multi-GPU run, at its per-GPU size
+    cpu_on = args.full and not args.no_cpu and rank == 0 and world == 1
     results = {}
     cpu = None
     cpu_extra = {}
     for kind in kinds:
         steps = args.steps if kind == args.workload else max(3, min(args.steps, 5))
+        dump = args.dump_outputs if kind == args.workload and rank == 0 else None
         if kind == "encode":
-            res = run_encode(torch, compu_amd, d_expect, n_units, steps, args.warmup, dist, level=args.encode_level)
+            res = run_encode(torch, compu_amd, d_expect, n_units, steps, args.warmup, dist, level=args.encode_level, verify=args.full, dump=dump)
             res["steps"] = steps
             res["units_per_gpu"] = n_units
             results[kind] = res
             log(f"[bench] encode: kernel {res['kernel_ms_avg']:.3f} ms avg, ratio {res['comp_bytes'] / res['out_bytes']:.3f}, verified={res['verified']}")
-            if rank == 0 and world == 1 and not args.no_cpu:
+            if cpu_on:
                 c = cpu_baseline_encode(payload, args.cpu_sample // 4, ncpu, level=args.encode_level)
                 if kind == args.workload:
                     cpu = c
@@ -502,14 +558,15 @@ def main():
                 k_payload = synth.payloads(k_units, first_unit=k_first, threads=threads)
                 k_expect = torch.from_numpy(k_payload).to(torch.device("cuda", local_rank))
         packed, offs, lens = make_workload(kind, k_payload, k_units, threads, k_first)
-        res = run_workload(torch, compu_amd, packed, offs, lens, k_expect, k_units, steps, args.warmup, dist, fmt=0 if kind == "mixed" else -15)
+        res = run_workload(torch, compu_amd, packed, offs, lens, k_expect, k_units, steps, args.warmup, dist, verify=args.full,
+                           fmt=0 if kind == "mixed" else -15, dump=dump)
         res["steps"] = steps
         res["units_per_gpu"] = k_units
         results[kind] = res
         log(f"[bench] {kind}: kernel {res['kernel_ms_avg']:.3f} ms avg, verified={res['verified']}")
-        if rank == 0 and world == 1 and not args.no_cpu and kind in ("stored", "fixed") and kind != args.workload:
+        if cpu_on and kind in ("stored", "fixed") and kind != args.workload:
             cpu_extra[kind] = cpu_baseline(packed, offs, lens, args.cpu_sample // 4, threads=ncpu, kind=kind, probes=False)
-        if rank == 0 and world == 1 and not args.no_cpu and kind in (args.workload, "mixed"):
+        if cpu_on and kind in (args.workload, "mixed"):
             uk = None
             if kind == "mixed":
                 uk = np.array([synth._splitmix64(first_unit + i) & 1 for i in range(n_units)], dtype=np.uint8)
@@ -528,10 +585,11 @@ def main():
         if dist is not None:
             t = torch.zeros(world + 1, dtype=torch.float64, device=torch.device("cuda", local_rank) if dist.get_backend() == "nccl" else "cpu")
             t[rank] = r["kernel_ms_avg"]
-            t[world] = 0.0 if r["verified"] else 1.0
+            t[world] = 1.0 if r["verified"] is False else 0.0
             dist.all_reduce(t, op=dist.ReduceOp.SUM)
             rank_ms_of[k] = [float(x) for x in t[:world].cpu()]
-            r["verified"] = bool(r["verified"]) and float(t[world]) == 0.0  # every rank's verification
+            if r["verified"] is not None:  # (None: not checked, a plain run)
+                r["verified"] = bool(r["verified"]) and float(t[world]) == 0.0  # every rank's verification
     rank_ms = rank_ms_of[args.workload]
     if rank != 0:
         if dist is not None:
@@ -572,7 +630,7 @@ def main():
             "sharding": f"units by index over {world} GPU(s), no collective",
         },
         "hbm_peak_frac_decompressed": round(value / (HBM_PEAK_GBPS * world), 5),
-        "verified_bit_exact": bool(all(r["verified"] for r in results.values())),
+        "verified_bit_exact": bool(all(r["verified"] for r in results.values())) if args.full else None,  # checked with --full
         "roofline": {
             "bound": "hbm",
             "kernel": {"mixed": "chip::inflate_kernel + chip::zstd_kernel", "encode": "chip::deflate_kernel" if args.encode_level == 1 else "chip::deflate_dyn_kernel"}.get(args.workload, "chip::inflate_kernel"),

@@ -1,10 +1,10 @@
-"""Turns the rocprofv3 outputs of tools/profile_round.sh (under gpurun_out/) into the summaries kept in profiles/:
-python tools/profiles_summarize.py <tag>   (run in the dev container after the gpurun call has merged its outputs)"""
+"""Turns the rocprofv3 outputs of tools/profile_round.sh (under its output directory) into the summaries kept in profiles/:
+python tools/profiles_summarize.py <tag> [<out>]   (<out>: the directory given to tools/profile_round.sh, default profile_out/)"""
 import csv, glob, json, os, sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 tag = sys.argv[1] if len(sys.argv) > 1 else "r04"
-G, P = os.path.join(ROOT, "gpurun_out"), os.path.join(ROOT, "profiles")
+G, P = os.path.join(ROOT, sys.argv[2] if len(sys.argv) > 2 else "profile_out"), os.path.join(ROOT, "profiles")
 
 
 def one(pattern):
@@ -14,10 +14,10 @@ def one(pattern):
     return hits[0]
 
 
-# 1. kernel stats of the default bench run, verbatim
+# 1. kernel stats of the full bench run, verbatim
 with open(one(f"{tag}_kt/**/*kernel_stats.csv")) as f, open(os.path.join(P, f"{tag}_kernel_stats.csv"), "w") as o:
     o.write(f.read())
-# 2. per-dispatch durations of the codec kernels in that run, in launch order.  bench.py's default run: dynamic (3 warm-up + 20
+# 2. per-dispatch durations of the codec kernels in that run, in launch order.  bench.py --full: dynamic (3 warm-up + 20
 # timed), stored, fixed (3 + 5 each), mixed (route + inflate + zstd per step, 3 + 5), encode (3 + 5, then one inflate that verifies it)
 rows = [r for r in csv.DictReader(open(one(f"{tag}_kt/**/*kernel_trace.csv"))) if any(k in r["Kernel_Name"] for k in ("inflate_kernel", "zstd_kernel", "deflate_kernel", "route_kernel"))]
 rows.sort(key=lambda r: int(r["Start_Timestamp"]))
