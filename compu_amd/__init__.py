@@ -19,6 +19,7 @@ from .api import (  # noqa: F401
     Encode,
     EncodeOp,
     F_COMPU_STATUS,
+    FMT_ZSTD,
     EncodeStatus,
     Encoder,
     Vec,
@@ -26,6 +27,8 @@ from .api import (  # noqa: F401
     ZlibOptions,
     ZlibStrategy,
     ZstdOptions,
+    ZstdEncoderOptions,
+    ZstdStrategy,
     decode_batch,
     decode_batch_host,
     decode_batch_multi,

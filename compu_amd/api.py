@@ -34,6 +34,10 @@ class _EncoderOpts(C.Structure):
     _fields_ = [("mode", C.c_int32), ("compression", C.c_int32), ("device", C.c_int32), ("strategy", C.c_int32), ("mem_level", C.c_int32)]
 
 
+class _ZstdEncoderOpts(C.Structure):
+    _fields_ = [("level", C.c_int32), ("strategy", C.c_int32), ("window_log", C.c_int32), ("device", C.c_int32)]
+
+
 _lib = None
 
 
@@ -99,6 +103,8 @@ def lib():
     L.chip_detect_batch.argtypes = [sz, vp, vp, vp, vp, vp]
     L.chip_encoder_new.restype = vp
     L.chip_encoder_new.argtypes = [C.POINTER(_EncoderOpts)]
+    L.chip_encoder_new_zstd.restype = vp
+    L.chip_encoder_new_zstd.argtypes = [C.POINTER(_ZstdEncoderOpts)]
     L.chip_encode.restype = _EncodeResult
     L.chip_encode.argtypes = [vp, vp, sz, vp, sz, C.c_int]
     L.chip_encoder_reset.restype = vp
@@ -229,6 +235,45 @@ class ZlibStrategy(enum.IntEnum):
     HuffmanOnly = 2
     Rle = 3
     Fixed = 4
+
+
+class ZstdStrategy(enum.IntEnum):
+    """src/encoder/zstd.rs:33-56"""
+
+    Default = 0
+    Fast = 1
+    DFast = 2
+    Greedy = 3
+    Lazy = 4
+    Lazy2 = 5
+    BtLazy2 = 6
+    BtOpt = 7
+    BtUltra = 8
+    BtUltra2 = 9
+
+
+class ZstdEncoderOptions:
+    """The encoder's ZstdOptions, src/encoder/zstd.rs:62-126 (defaults: level 3, strategy Default, window_log 27).  The decoder's
+    options are ZstdOptions."""
+
+    def __init__(self):
+        self._level = 3
+        self._strategy = ZstdStrategy.Default
+        self._window_log = 27
+
+    def level(self, level):
+        assert -131072 <= level <= 131072  # +-ZSTD_TARGETLENGTH_MAX, zstd.rs:82-83
+        self._level = level
+        return self
+
+    def strategy(self, strategy):
+        self._strategy = strategy
+        return self
+
+    def window_log(self, window_log):
+        assert 10 <= window_log <= 31  # ZSTD_WINDOWLOG_MIN .. ZSTD_WINDOWLOG_MAX_64, zstd.rs:96-101
+        self._window_log = window_log
+        return self
 
 
 class ZlibOptions:
@@ -545,6 +590,14 @@ class encoder_interface:
         h = lib().chip_encoder_new(C.byref(o))
         return Encoder(h) if h else None
 
+    @staticmethod
+    def zstd_hip(opts=None, device=-1):
+        """Interface::zstd(opts), src/encoder/zstd.rs:138-160; None when an option is out of range (apply() failing)."""
+        opts = opts or ZstdEncoderOptions()
+        o = _ZstdEncoderOpts(int(opts._level), int(opts._strategy), int(opts._window_log), device)
+        h = lib().chip_encoder_new_zstd(C.byref(o))
+        return Encoder(h) if h else None
+
 
 # ---- Buffer<N>, src/buffer.rs ---------------------------------------------------------------
 
@@ -831,7 +884,8 @@ def encode_bound(fmt, in_len):
 
 
 def encode_batch(fmt, level, in_buf, in_off, in_len, out_buf, out_off, out_cap, out_len=None, status=None, stream=None, strategy=0):
-    """chip_encode_batch_ex over device tensors: level 0 stored, 1 fixed Huffman, 2..9 (-1 = 6) dynamic Huffman blocks."""
+    """chip_encode_batch_ex over device tensors: level 0 stored, 1 fixed Huffman, 2..9 (-1 = 6) dynamic Huffman blocks; FMT_ZSTD:
+    zstd levels and ZstdStrategy values."""
     import torch
 
     n = in_len.numel()

@@ -117,7 +117,8 @@ int chip_stream_sync(void *stream) { return hipStreamSynchronize((hipStream_t)st
 int chip_trim(void)
 {
     pipes_trim();  // cached host-batch pipelines of the current device (streams, staging and device buffers)
-    const bool ok = chip::release_inflate_scratch() == hipSuccess;
+    bool ok = chip::release_inflate_scratch() == hipSuccess;
+    ok = chip::release_zstd_enc_scratch() == hipSuccess && ok;
     return chip::release_deflate_scratch() == hipSuccess && ok ? CHIP_OK : CHIP_E_LAUNCH;
 }
 
@@ -1117,6 +1118,8 @@ extern "C" {
 
 size_t chip_encode_bound(int format, size_t in_len)
 {
+    // zstd: raw blocks of 128 KiB (3-byte headers), the largest frame header (18 bytes) and the checksum
+    if (format == CHIP_FMT_ZSTD) return in_len + 3 * (in_len ? (in_len + (128u << 10) - 1) / (128u << 10) : 1) + 18 + 4;
     size_t blocks = in_len ? (in_len + 65534) / 65535 : 1;
     size_t wrap = format == CHIP_FMT_GZIP ? 18 : format == CHIP_FMT_ZLIB ? 6 : 0;
     // dynamic levels: a block holds at least 65472 tokens and costs at most 6 bytes more than its stored form
@@ -1135,6 +1138,32 @@ int chip_encode_batch_ex(int format, int level, int strategy, size_t n, const vo
                          void *stream)
 {
     if (n == 0) return CHIP_OK;
+    if (format == CHIP_FMT_ZSTD) {
+        if (n > 0x7fffffffull || !in_base || !in_off || !in_len || !out_base || !out_off || !out_cap || !out_len || !status ||
+            level < -131072 || level > 131072 || strategy < CHIP_ZSTD_STRATEGY_DEFAULT || strategy > CHIP_ZSTD_STRATEGY_BTULTRA2)
+            return CHIP_E_INVALID;
+        if (!device_ok()) return CHIP_E_NO_DEVICE;
+        BatchArgs a;
+        a.in_base = (const uint8_t *)in_base;
+        a.in_off = in_off;
+        a.in_len = in_len;
+        a.out_base = (uint8_t *)out_base;
+        a.out_off = out_off;
+        a.out_cap = out_cap;
+        a.out_len = out_len;
+        a.in_used = nullptr;
+        a.status = status;
+        a.n = (uint32_t)n;
+        a.format = format;
+        a.stats = nullptr;
+        a.resume = nullptr;
+#ifdef CHIP_STATS
+        a.stats = getenv("CHIP_STATS_PTR") ? (unsigned long long *)strtoull(getenv("CHIP_STATS_PTR"), nullptr, 0) : nullptr;
+#endif
+        const uint32_t wl = zenc::MAX_DIST_LOG;  // the batch frames use zstd's default window_log (27)
+        hipError_t e = launch_zstd_encode(a, level, strategy, wl, wl, ZF_FIRST | ZF_LAST | ZF_ONESHOT, nullptr, (hipStream_t)stream);
+        return e == hipSuccess ? CHIP_OK : CHIP_E_LAUNCH;
+    }
     if (level == -1) level = 6;  // zlib's Z_DEFAULT_COMPRESSION
     if (n > 0x7fffffffull || !in_base || !in_off || !in_len || !out_base || !out_off || !out_cap || !out_len || !status ||
         level < 0 || level > 9 || strategy < CHIP_STRATEGY_DEFAULT || strategy > CHIP_STRATEGY_FIXED ||
@@ -1191,6 +1220,9 @@ struct chip_encoder {
     bool started, finished;
     uint32_t check;
     uint64_t total_in;
+    // zstd (mode == CHIP_FMT_ZSTD): window_log of the options, and the repeat offsets + XXH64 state carried between segments
+    int wlog;
+    ZEncStream *d_zs;
 };
 
 namespace {
@@ -1222,7 +1254,10 @@ void enc_clear(chip_encoder *e)
 bool enc_segment(chip_encoder *e, bool final)
 {
     const size_t n = e->h_in_len;
-    const size_t bound = chip_encode_bound(e->mode, n) + 16;
+    const bool zstd = e->mode == CHIP_FMT_ZSTD;
+    // zstd: with a small window_log the blocks are smaller than the 128 KiB chip_encode_bound counts with
+    const size_t zblock = e->wlog < 17 ? (size_t)1 << e->wlog : (size_t)128 << 10;
+    const size_t bound = zstd ? n + 3 * (n / zblock + 1) + 22 + 16 : chip_encode_bound(e->mode, n) + 16;
     if (n + 16 > e->d_in_cap) {
         chip_device_free(e->d_in);
         e->d_in_cap = (n + 16) * 2;
@@ -1255,8 +1290,17 @@ bool enc_segment(chip_encoder *e, bool final)
     a.resume = nullptr;
     a.sel = nullptr;
     a.sel_n = nullptr;
-    const uint32_t flags = (e->started ? 0u : 1u) | (final ? 2u | 4u : 0u) | ((uint32_t)e->strategy << 8);
-    if (launch_deflate_l1(a, e->level, flags, e->check, e->total_in, &e->d_meta->check, e->stream) != hipSuccess) return false;
+    if (zstd) {
+        // a frame compressed in one call (Finish with the whole input buffered) is single-segment with Frame_Content_Size, as
+        // libzstd's one-call ZSTD_e_end; otherwise the header declares a window: the segments are at most 1 MiB and no match
+        // crosses them, so 2^20 (or the option's smaller window_log) covers every distance
+        const uint32_t flags = (e->started ? 0u : ZF_FIRST) | (final ? ZF_LAST : 0u) | (!e->started && final ? ZF_ONESHOT : 0u);
+        const uint32_t wl_single = e->wlog < 27 ? (uint32_t)e->wlog : 27u, wl_window = e->wlog < 20 ? (uint32_t)e->wlog : 20u;
+        if (launch_zstd_encode(a, e->level, e->strategy, wl_single, wl_window, flags, e->d_zs, e->stream) != hipSuccess) return false;
+    } else {
+        const uint32_t flags = (e->started ? 0u : 1u) | (final ? 2u | 4u : 0u) | ((uint32_t)e->strategy << 8);
+        if (launch_deflate_l1(a, e->level, flags, e->check, e->total_in, &e->d_meta->check, e->stream) != hipSuccess) return false;
+    }
     if (hipMemcpyAsync(e->h_meta, e->d_meta, sizeof m, hipMemcpyDeviceToHost, e->stream) != hipSuccess) return false;
     if (hipStreamSynchronize(e->stream) != hipSuccess) return false;
     if (e->h_meta->status != CHIP_ENC_FINISHED) return false;
@@ -1315,6 +1359,48 @@ chip_encoder *chip_encoder_new(const chip_encoder_opts *opts)
     return e;
 }
 
+chip_encoder *chip_encoder_new_zstd(const chip_zstd_encoder_opts *opts)
+{
+    // ZstdOptions::new(), src/encoder/zstd.rs:70-77: level 3 (ZSTD_CLEVEL_DEFAULT), strategy Default, window_log 27
+    int level = opts ? opts->level : 3;
+    const int strategy = opts ? opts->strategy : CHIP_ZSTD_STRATEGY_DEFAULT, wlog = opts ? opts->window_log : 27;
+    // what ZSTD_CCtx_setParameter refuses (apply() -> None, src/encoder/zstd.rs:107-124)
+    if (level < -131072 || level > 131072 || strategy < CHIP_ZSTD_STRATEGY_DEFAULT || strategy > CHIP_ZSTD_STRATEGY_BTULTRA2 ||
+        wlog < 10 || wlog > 31)
+        return nullptr;
+    if (level == 0) level = 3;
+    if (level > 22) level = 22;
+    if (!device_ok()) return nullptr;
+    int device = opts ? opts->device : -1;
+    if (device < 0 && hipGetDevice(&device) != hipSuccess) return nullptr;
+    DeviceGuard guard(device);
+    if (!guard.ok) return nullptr;
+    const Hooks hooks = current_hooks();
+    chip_encoder *e = (chip_encoder *)hooks.alloc(sizeof(chip_encoder));
+    if (!e) return nullptr;
+    memset(e, 0, sizeof *e);
+    e->hooks = hooks;
+    e->mode = CHIP_FMT_ZSTD;
+    e->level = level;
+    e->strategy = strategy;
+    e->wlog = wlog;
+    e->device = device;
+    if (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess) {
+        hooks.release(e);
+        return nullptr;
+    }
+    e->d_meta = (chip_encoder::EMeta *)chip_device_alloc(sizeof(chip_encoder::EMeta));
+    e->h_meta = (chip_encoder::EMeta *)chip_pinned_alloc(sizeof(chip_encoder::EMeta));
+    e->d_zs = (ZEncStream *)chip_device_alloc(sizeof(ZEncStream));
+    if (!e->d_meta || !e->h_meta || !e->d_zs || !enc_reserve(&e->h_in, &e->h_in_cap, 0, 65536) ||
+        !enc_reserve(&e->h_out, &e->h_out_cap, 0, 65536)) {
+        chip_encoder_free(e);
+        return nullptr;
+    }
+    enc_clear(e);
+    return e;
+}
+
 chip_encode_result chip_encode(chip_encoder *e, const uint8_t *in, size_t in_len, uint8_t *out, size_t out_len, int op)
 {
     chip_encode_result r = {in_len, out_len, CHIP_ENC_ERROR};
@@ -1346,6 +1432,17 @@ chip_encode_result chip_encode(chip_encoder *e, const uint8_t *in, size_t in_len
     if (e->delivered == e->h_out_len) e->h_out_len = e->delivered = 0;
     r.input_remain = in_len - taken;
     r.output_remain = out_len - k;
+    if (e->mode == CHIP_FMT_ZSTD) {
+        // ZSTD_compressStream2's return value -> EncodeStatus, src/encoder/zstd.rs:174-197.  It is 0 when no compressed byte
+        // waits for delivery, and for Flush also nothing is buffered, for Finish also the frame is closed; 0 is Finished for
+        // Finish and Continue otherwise, anything else NeedOutput when the output was filled to its last byte.
+        const bool waiting = e->h_out_len != 0;
+        const bool zero = !waiting && (op == CHIP_OP_PROCESS || (e->h_in_len == 0 && taken == in_len)) &&
+                          (op != CHIP_OP_FINISH || e->finished);
+        if (zero) r.status = op == CHIP_OP_FINISH ? CHIP_ENC_FINISHED : CHIP_ENC_CONTINUE;
+        else r.status = k == out_len ? CHIP_ENC_NEED_OUTPUT : CHIP_ENC_CONTINUE;
+        return r;
+    }
     // deflate() return code -> EncodeStatus, src/encoder/mod.rs:357-367: with Finish, anything short of
     // Z_STREAM_END is NeedOutput; otherwise Z_OK is Continue and a call without progress (Z_BUF_ERROR) NeedOutput
     if (op == CHIP_OP_FINISH) r.status = (e->finished && e->h_out_len == 0) ? CHIP_ENC_FINISHED : CHIP_ENC_NEED_OUTPUT;
@@ -1366,6 +1463,7 @@ void chip_encoder_free(chip_encoder *e)
     if (e->stream) {
         (void)hipStreamSynchronize(e->stream);
         chip::release_deflate_scratch_of(e->stream);  // the stream's token scratch goes with it
+        chip::release_zstd_enc_scratch_of(e->stream);
         (void)hipStreamDestroy(e->stream);
     }
     chip_pinned_free(e->h_in);
@@ -1374,6 +1472,7 @@ void chip_encoder_free(chip_encoder *e)
     chip_device_free(e->d_in);
     chip_device_free(e->d_out);
     chip_device_free(e->d_meta);
+    chip_device_free(e->d_zs);
     const Hooks hooks = e->hooks;
     hooks.release(e);
 }

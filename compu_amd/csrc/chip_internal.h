@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "../../include/compu_hip.h"
+#include "zstd_enc_core.h"
 
 namespace chip {
 
@@ -105,6 +106,19 @@ hipError_t launch_detect(size_t n, const uint8_t *in_base, const uint64_t *in_of
                          hipStream_t stream);
 hipError_t launch_deflate_l1(const BatchArgs &a, int level, uint32_t flags, uint32_t check_seed, uint64_t total_before,
                              uint32_t *check_out, hipStream_t stream);
+
+// zstd encoder (zstd_enc.hip).  Flags: ZF_FIRST writes the frame header (and starts the repeat offsets and the XXH64 state),
+// ZF_LAST ends the frame (last block, checksum), ZF_ONESHOT allows the single-segment header with Frame_Content_Size.
+constexpr uint32_t ZF_FIRST = 1u, ZF_LAST = 2u, ZF_ONESHOT = 4u;
+// what a streaming zstd encoder carries on the device from one segment to the next
+struct ZEncStream {
+    uint32_t rep[3], pad;
+    zenc::Xxh xxh;
+};
+hipError_t launch_zstd_encode(const BatchArgs &a, int level, int strategy, uint32_t wlog_single, uint32_t wlog_window, uint32_t flags,
+                              ZEncStream *stream_state, hipStream_t stream);
+hipError_t release_zstd_enc_scratch();                 // the zstd encoder's per-wave scratch of the current device (after a sync)
+void release_zstd_enc_scratch_of(hipStream_t stream);  // the same for one (drained) stream
 
 // Detection::detect (src/decoder/mod.rs:28-114) on device: first 2-4 bytes of a unit -> CHIP_DETECT_*.
 // The FLG table of mod.rs:44-55 is packed one word per CINFO; the 0x68 row never matches in the

@@ -183,6 +183,34 @@ using ZlibMode = decoder::ZlibMode;  // src/encoder/zlib_common.rs:28-37 (Deflat
 // src/encoder/zlib_common.rs:5-24
 enum class ZlibStrategy { Default = 0, Filtered = 1, HuffmanOnly = 2, Rle = 3, Fixed = 4 };
 
+// src/encoder/zstd.rs:33-56
+enum class ZstdStrategy { Default = 0, Fast = 1, DFast = 2, Greedy = 3, Lazy = 4, Lazy2 = 5, BtLazy2 = 6, BtOpt = 7, BtUltra = 8, BtUltra2 = 9 };
+
+// the encoder's ZstdOptions, src/encoder/zstd.rs:62-126 (defaults: level 3, Default strategy, window_log 27)
+struct ZstdOptions {
+    int32_t level_ = 3;
+    ZstdStrategy strategy_ = ZstdStrategy::Default;
+    int32_t window_log_ = 27;
+    ZstdOptions level(int32_t v) const
+    {
+        ZstdOptions o = *this;
+        o.level_ = v;
+        return o;
+    }
+    ZstdOptions strategy(ZstdStrategy s) const
+    {
+        ZstdOptions o = *this;
+        o.strategy_ = s;
+        return o;
+    }
+    ZstdOptions window_log(int32_t v) const
+    {
+        ZstdOptions o = *this;
+        o.window_log_ = v;
+        return o;
+    }
+};
+
 // src/encoder/zlib_common.rs:47-103 (defaults: Gzip, Default strategy, mem_level 8, compression 9, :59-66)
 struct ZlibOptions {
     ZlibMode mode_ = ZlibMode::Gzip;
@@ -290,6 +318,14 @@ struct Interface {
     {
         chip_encoder_opts o{static_cast<int32_t>(opts.mode_), opts.compression_, device, static_cast<int32_t>(opts.strategy_), opts.mem_level_};
         chip_encoder *h = chip_encoder_new(&o);
+        if (!h) return std::nullopt;
+        return Encoder(h);
+    }
+    // Interface::zstd(opts), src/encoder/zstd.rs:138-160 (nullopt for an option out of range, as apply() failing)
+    static std::optional<Encoder> zstd_hip(ZstdOptions opts = {}, int device = -1)
+    {
+        chip_zstd_encoder_opts o{opts.level_, static_cast<int32_t>(opts.strategy_), opts.window_log_, device};
+        chip_encoder *h = chip_encoder_new_zstd(&o);
         if (!h) return std::nullopt;
         return Encoder(h);
     }

@@ -252,12 +252,15 @@ chip_encoder *chip_encoder_reset(chip_encoder *e);
 /* drop_fn src/encoder/zlib_ng.rs:107-111 */
 void chip_encoder_free(chip_encoder *e);
 
-/* chip_encode_batch with a strategy (CHIP_STRATEGY_*); chip_encode_batch is strategy Default. */
+/* chip_encode_batch with a strategy (CHIP_STRATEGY_*, or CHIP_ZSTD_STRATEGY_* for CHIP_FMT_ZSTD); chip_encode_batch is strategy
+ * Default. */
 int chip_encode_batch_ex(int format, int level, int strategy, size_t n, const void *in_base, const uint64_t *in_off,
                          const uint32_t *in_len, void *out_base, const uint64_t *out_off, const uint32_t *out_cap,
                          uint32_t *out_len, int32_t *status, void *stream);
 
-/* Batched level-1 encode of n independent units (device pointers, one wavefront per unit).
+/* Batched encode of n independent units (device pointers, one wavefront per unit).  CHIP_FMT_ZSTD: level as in
+ * chip_zstd_encoder_opts, window_log 27; each unit becomes one zstd frame with the content checksum (single segment with
+ * Frame_Content_Size up to 2^27 bytes, a 2^27 window above).
  * out_len[i] = compressed size; status[i] = CHIP_ENC_FINISHED or CHIP_ENC_NEED_OUTPUT.  Each unit becomes
  * one complete stream of `format` (wrapper, one fixed-Huffman or stored deflate body, trailer).  The
  * range out_off[i] .. +out_cap[i] may be used as scratch beyond out_len[i]. */
@@ -272,6 +275,38 @@ size_t chip_encode_bound(int format, size_t in_len);
 int chip_encode_batch_host(int format, int level, size_t n, const void *in_base, const uint64_t *in_off, const uint32_t *in_len,
                            void *out_base, const uint64_t *out_off, const uint32_t *out_cap, uint32_t *out_len, int32_t *status,
                            int device, size_t slice_bytes);
+
+/* ---- zstd encoder: encoder::Interface::zstd, src/encoder/zstd.rs ------------------------------------------------------------ */
+
+/* ZstdStrategy src/encoder/zstd.rs:33-56 (ZSTD_strategy values; 0 = the level's own).  The GPU encoder has four level groups
+ * (DESIGN.md sec. 4.6): levels <= 2 greedy with a skip over runs without matches, 3..5 greedy with a repeat-offset probe, 6..12
+ * lazy, 13..22 lazy with two positions per hash slot; a strategy other than Default picks the group: Fast the first, Dfast and
+ * Greedy the second, Lazy and Lazy2 the third, Btlazy2 and the optimal-parsing strategies the fourth. */
+enum {
+    CHIP_ZSTD_STRATEGY_DEFAULT = 0,
+    CHIP_ZSTD_STRATEGY_FAST = 1,
+    CHIP_ZSTD_STRATEGY_DFAST = 2,
+    CHIP_ZSTD_STRATEGY_GREEDY = 3,
+    CHIP_ZSTD_STRATEGY_LAZY = 4,
+    CHIP_ZSTD_STRATEGY_LAZY2 = 5,
+    CHIP_ZSTD_STRATEGY_BTLAZY2 = 6,
+    CHIP_ZSTD_STRATEGY_BTOPT = 7,
+    CHIP_ZSTD_STRATEGY_BTULTRA = 8,
+    CHIP_ZSTD_STRATEGY_BTULTRA2 = 9
+};
+
+/* ZstdOptions src/encoder/zstd.rs:62-126 */
+typedef struct {
+    int32_t level;      /* -131072..131072 (0 = 3, above 22 = 22, as libzstd); default 3 */
+    int32_t strategy;   /* CHIP_ZSTD_STRATEGY_*; default Default */
+    int32_t window_log; /* 10..31, default 27: caps the match distance and the declared window (at most 2^27) */
+    int32_t device;     /* HIP device ordinal, -1 = current */
+} chip_zstd_encoder_opts;
+
+/* Interface::zstd(opts) src/encoder/zstd.rs:128-160.  NULL opts = ZstdOptions::new(); NULL on an option out of range.
+ * The encoder is driven by chip_encode / chip_encoder_reset / chip_encoder_free.  Every frame carries the content checksum
+ * (libzstd's default is without it).  chip_encode's status follows src/encoder/zstd.rs:174-197. */
+chip_encoder *chip_encoder_new_zstd(const chip_zstd_encoder_opts *opts);
 
 #ifdef __cplusplus
 }

@@ -1,13 +1,21 @@
-//! `hip` module: zlib / gzip / raw deflate encoding on an MI355X through `libcompu_hip.so`.
+//! `hip` module: zlib / gzip / raw deflate and zstd encoding on an MI355X through `libcompu_hip.so`.
 
 extern crate alloc;
 
 use core::ptr;
 
-use super::{Encode, EncodeOp, EncodeStatus, Encoder, Interface, ZlibOptions, ZlibStrategy};
+use super::{Encode, EncodeOp, EncodeStatus, Encoder, Interface, ZlibOptions, ZlibStrategy, ZstdOptions};
 use crate::hip_sys as sys;
 
 static HIP_ZLIB: Interface = Interface {
+    drop_fn,
+    reset_fn,
+    encode_fn,
+};
+
+//The zstd encoder is driven by the same three entry points; chip_encode picks the status rules of the encoder's kind
+//(src/encoder/zstd.rs:174-197 for zstd), so encode_fn passes the C status on unchanged.
+static HIP_ZSTD: Interface = Interface {
     drop_fn,
     reset_fn,
     encode_fn,
@@ -36,6 +44,26 @@ impl Interface {
         let instance = unsafe { sys::chip_encoder_new(&opts) };
         //like zlib_ng (src/encoder/zlib_ng.rs:84): the options live in the state, the replayed `opts` bytes are unused
         ptr::NonNull::new(instance as *mut u8).map(|instance| HIP_ZLIB.inner_encoder(instance, [0; 2]))
+    }
+
+    #[inline]
+    ///Creates encoder with `hip` interface for zstd
+    ///
+    ///Returns `None` if an option is out of range (as `ZstdOptions::apply` failing, src/encoder/zstd.rs:107-124) or if unable to
+    ///initialize it (no usable GPU, or lack of memory)
+    pub fn zstd_hip(opts: ZstdOptions) -> Option<Encoder> {
+        crate::mem::hip_install_allocator();
+        //`level`, `strategy` and `window_log` are private to `zstd.rs`; the maintainer adds `pub(super) const fn level_value(&self) -> i32`,
+        //`strategy_tag(&self) -> i32` (`self.strategy as i32`) and `window_log_value(&self) -> i32` next to `ZstdOptions::apply`
+        //(src/encoder/zstd.rs:105-125)
+        let opts = sys::chip_zstd_encoder_opts {
+            level: opts.level_value(),
+            strategy: opts.strategy_tag(),
+            window_log: opts.window_log_value(),
+            device: -1,
+        };
+        let instance = unsafe { sys::chip_encoder_new_zstd(&opts) };
+        ptr::NonNull::new(instance as *mut u8).map(|instance| HIP_ZSTD.inner_encoder(instance, [0; 2]))
     }
 }
 

@@ -43,6 +43,15 @@ pub struct chip_encoder_opts {
     pub mem_level: i32,
 }
 
+///`chip_zstd_encoder_opts`: the encoder's `ZstdOptions` (src/encoder/zstd.rs:62-126)
+#[repr(C)]
+pub struct chip_zstd_encoder_opts {
+    pub level: i32,
+    pub strategy: i32,
+    pub window_log: i32,
+    pub device: i32,
+}
+
 pub const CHIP_FMT_ZSTD: c_int = 100;
 ///route every unit of a batch by `Detection::detect` (src/decoder/mod.rs:28-114)
 pub const CHIP_FMT_DETECT: c_int = 0;
@@ -96,6 +105,7 @@ extern "C" {
     pub fn chip_detect_batch(n: usize, in_base: *const c_void, in_off: *const u64, in_len: *const u32, kind: *mut i32, stream: *mut c_void) -> c_int;
 
     pub fn chip_encoder_new(opts: *const chip_encoder_opts) -> *mut chip_encoder;
+    pub fn chip_encoder_new_zstd(opts: *const chip_zstd_encoder_opts) -> *mut chip_encoder;
     pub fn chip_encode(e: *mut chip_encoder, input: *const u8, input_len: usize, output: *mut u8, output_len: usize, op: c_int) -> chip_encode_result;
     pub fn chip_encoder_reset(e: *mut chip_encoder) -> *mut chip_encoder;
     pub fn chip_encoder_free(e: *mut chip_encoder);
