@@ -19,6 +19,7 @@ from .api import (  # noqa: F401
     Encode,
     EncodeOp,
     F_COMPU_STATUS,
+    FMT_BROTLI,
     FMT_ZSTD,
     EncodeStatus,
     Encoder,

@@ -182,6 +182,7 @@ class ZlibMode(enum.IntEnum):
 
 
 FMT_ZSTD = 100
+FMT_BROTLI = 101  # decoder only (Interface::brotli_c)
 
 
 class ZstdOptions:
@@ -506,6 +507,13 @@ class decoder_interface:
         o = _DecoderOpts(opts._window_log if opts else 0, device)
         h = lib().chip_decoder_new(FMT_ZSTD, C.byref(o))
         return Decoder(h, FMT_ZSTD) if h else None
+
+    @staticmethod
+    def brotli_hip(device=-1):
+        """Interface::brotli_c(), src/decoder/brotli_c.rs:17-27; None on failure."""
+        o = _DecoderOpts(0, device)
+        h = lib().chip_decoder_new(FMT_BROTLI, C.byref(o))
+        return Decoder(h, FMT_BROTLI) if h else None
 
 
 # ---- Encoder ---------------------------------------------------------------------------------

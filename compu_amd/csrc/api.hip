@@ -119,6 +119,7 @@ int chip_trim(void)
     pipes_trim();  // cached host-batch pipelines of the current device (streams, staging and device buffers)
     bool ok = chip::release_inflate_scratch() == hipSuccess;
     ok = chip::release_zstd_enc_scratch() == hipSuccess && ok;
+    ok = chip::release_brotli_scratch() == hipSuccess && ok;
     return chip::release_deflate_scratch() == hipSuccess && ok ? CHIP_OK : CHIP_E_LAUNCH;
 }
 
@@ -168,6 +169,7 @@ int chip_decode_batch_ex(int format, uint32_t flags, size_t n, const void *in_ba
     case CHIP_FMT_GZIP:
     case CHIP_FMT_AUTO: e = launch_inflate(a, (hipStream_t)stream); break;
     case CHIP_FMT_ZSTD: e = launch_zstd_decode(a, 0, (hipStream_t)stream); break;
+    case CHIP_FMT_BROTLI: e = launch_brotli_decode(a, (hipStream_t)stream); break;  // CHIP_F_COMPU_STATUS changes nothing
     case CHIP_FMT_DETECT:
         // Detection::detect routes every unit: one pass buckets the batch by format, then each decoder runs over its own
         // (homogeneous) list of units -- all of it one critical section of the (device, stream) slot (inflate.hip)
@@ -528,7 +530,8 @@ int chip_decode_batch_multi(int format, size_t n, const void *in_base, const uin
     if (n == 0) return CHIP_OK;
     if (!host_args_ok(n, in_base, in_off, in_len, out_base, out_off, out_cap, out_len, status) || !in_used) return CHIP_E_INVALID;
     switch (format) {
-    case CHIP_FMT_DEFLATE: case CHIP_FMT_ZLIB: case CHIP_FMT_GZIP: case CHIP_FMT_AUTO: case CHIP_FMT_ZSTD: case CHIP_FMT_DETECT: break;
+    case CHIP_FMT_DEFLATE: case CHIP_FMT_ZLIB: case CHIP_FMT_GZIP: case CHIP_FMT_AUTO: case CHIP_FMT_ZSTD: case CHIP_FMT_BROTLI:
+    case CHIP_FMT_DETECT: break;
     default: return CHIP_E_INVALID;
     }
     const int visible = chip_device_count();
@@ -659,6 +662,41 @@ int chip_detect_batch(size_t n, const void *in_base, const uint64_t *in_off, con
 
 const char *chip_decoder_strerror(int format, int32_t code)
 {
+    if (format == CHIP_FMT_BROTLI) {
+        // BrotliDecoderErrorString(code), src/decoder/brotli_c.rs (describe_error_fn)
+        switch (code) {
+        case 0: return "NO_ERROR";
+        case 1: return "SUCCESS";
+        case 2: return "NEEDS_MORE_INPUT";
+        case 3: return "NEEDS_MORE_OUTPUT";
+        case -1: return "EXUBERANT_NIBBLE";
+        case -2: return "RESERVED";
+        case -3: return "EXUBERANT_META_NIBBLE";
+        case -4: return "SIMPLE_HUFFMAN_ALPHABET";
+        case -5: return "SIMPLE_HUFFMAN_SAME";
+        case -6: return "CL_SPACE";
+        case -7: return "HUFFMAN_SPACE";
+        case -8: return "CONTEXT_MAP_REPEAT";
+        case -9: return "BLOCK_LENGTH_1";
+        case -10: return "BLOCK_LENGTH_2";
+        case -11: return "TRANSFORM";
+        case -12: return "DICTIONARY";
+        case -13: return "WINDOW_BITS";
+        case -14: return "PADDING_1";
+        case -15: return "PADDING_2";
+        case -16: return "DISTANCE";
+        case -19: return "DICTIONARY_NOT_SET";
+        case -20: return "INVALID_ARGUMENTS";
+        case -21: return "CONTEXT_MODES";
+        case -22: return "TREE_GROUPS";
+        case -25: return "CONTEXT_MAP";
+        case -26: return "RING_BUFFER_1";
+        case -27: return "RING_BUFFER_2";
+        case -30: return "BLOCK_TYPE_TREES";
+        case -31: return "UNREACHABLE";
+        default: return "INVALID";
+        }
+    }
     if (format == CHIP_FMT_ZSTD) {
         // ZSTD_getErrorName(code as usize), src/decoder/zstd.rs:159-164
         switch (code < 0 ? -code : code) {
@@ -763,9 +801,10 @@ bool dec_run(chip_decoder *d)
         if (hipMemcpyAsync(d->d_in + from, d->h_in + from, in_len - from, hipMemcpyHostToDevice, d->stream) != hipSuccess) return false;
         d->d_in_len = in_len;
     }
-    const bool inflate = d->format != CHIP_FMT_ZSTD;
+    const bool inflate = d->format != CHIP_FMT_ZSTD && d->format != CHIP_FMT_BROTLI;
+    const bool brotli = d->format == CHIP_FMT_BROTLI;
     if (!inflate && !d->d_zres) {
-        d->d_zres = (uint32_t *)chip_device_alloc(ZRES_BYTES);
+        d->d_zres = (uint32_t *)chip_device_alloc(brotli ? ZRES_HDR * 4 : ZRES_BYTES);  // brotli: the header only
         if (!d->d_zres || hipMemsetAsync(d->d_zres, 0, ZRES_HDR * 4, d->stream) != hipSuccess) return false;
     }
     size_t cap = d->d_out_cap;
@@ -801,7 +840,9 @@ bool dec_run(chip_decoder *d)
         a.format = d->format;
         a.stats = nullptr;
         a.resume = inflate ? d->d_meta->resume : d->d_zres;
-        hipError_t e = inflate ? launch_inflate(a, d->stream) : launch_zstd_decode(a, d->window_log_max, d->stream);
+        hipError_t e = inflate  ? launch_inflate(a, d->stream)
+                       : brotli ? launch_brotli_decode(a, d->stream)
+                                : launch_zstd_decode(a, d->window_log_max, d->stream);
         if (e != hipSuccess) return false;
         if (hipMemcpyAsync(d->h_meta, d->d_meta, sizeof(Meta), hipMemcpyDeviceToHost, d->stream) != hipSuccess) return false;
         if (!inflate && hipMemcpyAsync(d->h_zhdr, d->d_zres, ZRES_HDR * 4, hipMemcpyDeviceToHost, d->stream) != hipSuccess) return false;
@@ -810,6 +851,8 @@ bool dec_run(chip_decoder *d)
         if (inflate) {
             for (uint32_t k = 0; k < RESUME_WORDS; k++) d->resume[k] = d->h_meta->resume[k];
             ck = d->resume[0] + 8u * (uint32_t)d->in_dropped;
+        } else if (brotli) {
+            ck = d->h_zhdr[0] + 8u * (uint32_t)d->in_dropped;  // a bit offset
         } else {
             ck = d->h_zhdr[0] + (uint32_t)d->in_dropped;
         }
@@ -851,6 +894,44 @@ bool dec_compact(chip_decoder *d)
 {
     if (!d->decoded) return true;
     if (d->k_status != CHIP_NEED_INPUT && d->k_status != CHIP_NEED_OUTPUT) return true;
+    if (d->format == CHIP_FMT_BROTLI) {
+        // the metablock checkpoint (chip_internal.h, BRES_WORDS): input in front of the boundary's byte, output in front of the
+        // window of the boundary that has been handed on
+        uint32_t *zh = d->h_zhdr;
+        if (zh[0] == 0) return true;  // no metablock reached yet
+        bool dirty = false;
+        const size_t drop_in = (((size_t)zh[0] - 1u) >> 3) & ~(size_t)3;
+        if (drop_in >= DEC_DROP_IN) {
+            memmove(d->h_in, d->h_in + drop_in, d->h_in_len - drop_in);
+            d->h_in_len -= drop_in;
+            d->d_in_len = 0;  // the (short) rest is uploaded again
+            zh[0] -= 8u * (uint32_t)drop_in;
+            d->in_dropped += drop_in;
+            d->k_in_used = d->k_in_used > drop_in ? d->k_in_used - (uint32_t)drop_in : 0;
+            dirty = true;
+        }
+        const uint64_t window = (uint64_t)zh[8] | ((uint64_t)zh[9] << 32);
+        const uint64_t dropped = (uint64_t)zh[12] | ((uint64_t)zh[13] << 32);
+        const size_t r1 = zh[1];
+        size_t keep_from = r1 > window ? r1 - (size_t)window : 0;
+        if (keep_from > d->delivered) keep_from = d->delivered;
+        keep_from &= ~(size_t)15;
+        if (keep_from >= DEC_DROP_OUT) {
+            if (!dec_move_down(d, keep_from, d->k_out_len - keep_from)) return false;
+            d->delivered -= keep_from;
+            d->k_out_len -= (uint32_t)keep_from;
+            zh[1] -= (uint32_t)keep_from;
+            const uint64_t nd = dropped + keep_from;
+            zh[12] = (uint32_t)nd;
+            zh[13] = (uint32_t)(nd >> 32);
+            dirty = true;
+        }
+        if (dirty) {
+            if (hipMemcpyAsync(d->d_zres, zh, ZRES_HDR * 4, hipMemcpyHostToDevice, d->stream) != hipSuccess) return false;
+            if (hipStreamSynchronize(d->stream) != hipSuccess) return false;
+        }
+        return true;
+    }
     if (d->format == CHIP_FMT_ZSTD) {
         uint32_t *zh = d->h_zhdr;
         if (zh[0] == 0) return true;  // no block done yet
@@ -916,6 +997,20 @@ bool dec_compact(chip_decoder *d)
     return true;
 }
 
+// Decoded bytes a call may hand on.  A brotli stream that ended in an error hands on what libbrotlidec would have flushed before
+// reaching it: its ring buffer goes out whole (the checkpoint's [10] is its size where the run stopped), and what earlier calls
+// handed on stays handed on.
+size_t dec_out_limit(const chip_decoder *d)
+{
+    if (d->format != CHIP_FMT_BROTLI || d->k_status >= 0) return d->k_out_len;
+    const uint64_t rsz = d->h_zhdr[10];
+    const uint64_t dropped = (uint64_t)d->h_zhdr[12] | ((uint64_t)d->h_zhdr[13] << 32);
+    const uint64_t flushed = rsz ? (dropped + d->k_out_len) / rsz * rsz : 0;
+    size_t lim = flushed > dropped ? (size_t)(flushed - dropped) : 0;
+    if (lim > d->k_out_len) lim = d->k_out_len;
+    return lim > d->delivered ? lim : d->delivered;
+}
+
 void dec_clear(chip_decoder *d)
 {
     d->h_in_len = 0;
@@ -942,7 +1037,7 @@ extern "C" {
 chip_decoder *chip_decoder_new(int format, const chip_decoder_opts *opts)
 {
     if (format != CHIP_FMT_DEFLATE && format != CHIP_FMT_ZLIB && format != CHIP_FMT_GZIP && format != CHIP_FMT_AUTO &&
-        format != CHIP_FMT_ZSTD)
+        format != CHIP_FMT_ZSTD && format != CHIP_FMT_BROTLI)
         return nullptr;
     if (!device_ok()) return nullptr;  // no CPU codec behind this backend
     int device = opts ? opts->device : -1;
@@ -1006,7 +1101,7 @@ chip_decode_result chip_decode(chip_decoder *d, const uint8_t *in, size_t in_len
     size_t n_total = 0;
     for (;;) {
         if (!d->decoded && !dec_run(d)) return fail(-4);
-        const size_t avail = d->k_out_len - d->delivered;
+        const size_t avail = dec_out_limit(d) - d->delivered;
         const size_t n = avail < out_len - n_total ? avail : out_len - n_total;
         if (n) {
             if (hipMemcpyAsync(out + n_total, d->d_out + d->delivered, n, hipMemcpyDeviceToHost, d->stream) != hipSuccess ||
@@ -1017,7 +1112,7 @@ chip_decode_result chip_decode(chip_decoder *d, const uint8_t *in, size_t in_len
         }
         // everything decoded so far is handed on but the device buffer was the limit: make room and decode on
         if (d->delivered == d->k_out_len && d->k_status == CHIP_NEED_OUTPUT && n_total < out_len) {
-            const bool zs = d->format == CHIP_FMT_ZSTD;
+            const bool zs = d->format == CHIP_FMT_ZSTD || d->format == CHIP_FMT_BROTLI;
             const uint32_t before = zs ? d->h_zhdr[1] : d->resume[1];
             if (!dec_compact(d)) return fail(-4);
             if ((zs ? d->h_zhdr[1] : d->resume[1]) == before && d->d_out_cap >= DEC_OUT_LIMIT) break;  // nothing could be dropped and nothing can grow
@@ -1036,6 +1131,27 @@ chip_decode_result chip_decode(chip_decoder *d, const uint8_t *in, size_t in_len
         d->h_in_len -= giveback;
     }
     r.input_remain = (in_len - taken) + giveback;
+    if (d->format == CHIP_FMT_BROTLI) {
+        // BrotliDecoderDecompressStream's result, src/decoder/brotli_c.rs:43-60: Success once the stream is done and its output
+        // handed on, NeedsMoreOutput while decoded bytes wait, an error once what libbrotlidec flushes in front of it
+        // (dec_out_limit) is handed on -- in the call that hands on its last byte -- else NeedsMoreInput
+        if (d->k_status < 0) {
+            if (d->delivered < dec_out_limit(d)) {
+                r.status = CHIP_NEED_OUTPUT;
+            } else {
+                r.status = -1;
+                r.err = d->k_status;
+            }
+        } else if (d->k_status == CHIP_FINISHED && d->delivered == d->k_out_len) {
+            d->done = true;
+            r.status = CHIP_FINISHED;
+        } else if (d->delivered < d->k_out_len || d->k_status == CHIP_NEED_OUTPUT) {
+            r.status = CHIP_NEED_OUTPUT;
+        } else {
+            r.status = CHIP_NEED_INPUT;
+        }
+        return r;
+    }
     if (d->format == CHIP_FMT_ZSTD) {
         // src/decoder/zstd.rs:113-135: 0 -> Finished (frame done AND flushed); else a full output buffer -> NeedOutput,
         // whatever else happened; else no error -> NeedInput; else the error
@@ -1080,7 +1196,15 @@ chip_decode_result chip_decode(chip_decoder *d, const uint8_t *in, size_t in_len
 void chip_decoder_footprint(const chip_decoder *d, size_t *pinned_bytes, size_t *device_bytes)
 {
     if (pinned_bytes) *pinned_bytes = d ? d->h_in_cap + sizeof(Meta) + ZRES_HDR * 4 : 0;
-    if (device_bytes) *device_bytes = d ? d->d_in_cap + d->d_out_cap + sizeof(Meta) + (d->d_zres ? ZRES_BYTES : 0) : 0;
+    if (!device_bytes) return;
+    *device_bytes = 0;
+    if (!d) return;
+    const bool brotli = d->format == CHIP_FMT_BROTLI;
+    *device_bytes = d->d_in_cap + d->d_out_cap + sizeof(Meta) + (d->d_zres ? (brotli ? ZRES_HDR * 4 : ZRES_BYTES) : 0);
+    if (brotli) {  // the kernel's table slots for this decoder's stream (one 128 KiB slot, one worst-case slot)
+        DeviceGuard guard(d->device);
+        *device_bytes += chip::brotli_scratch_bytes_of(d->stream);
+    }
 }
 
 chip_decoder *chip_decoder_reset(chip_decoder *d)
@@ -1098,6 +1222,7 @@ void chip_decoder_free(chip_decoder *d)
     DeviceGuard guard(d->device);
     if (d->stream) {
         chip::release_inflate_scratch_of(d->stream);  // the stream's token scratch goes with it
+        chip::release_brotli_scratch_of(d->stream);
         (void)hipStreamDestroy(d->stream);
     }
     chip_pinned_free(d->h_in);

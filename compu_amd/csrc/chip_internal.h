@@ -97,6 +97,20 @@ hipError_t launch_zstd_encode(const BatchArgs &a, int level, int strategy, uint3
 hipError_t release_zstd_enc_scratch();                 // the zstd encoder's per-wave scratch of the current device (after a sync)
 void release_zstd_enc_scratch_of(hipStream_t stream);  // the same for one (drained) stream
 
+// brotli decoder (brotli.hip): a persistent launch with a 128 KiB table slot per wave, then an always-enqueued launch on 64 waves
+// with worst-case slots for the units whose metablock tables did not fit (an overflow list on the device).
+// BatchArgs::resume (streaming only): the checkpoint written at every metablock boundary -- [0] 1 + bit offset of the boundary in
+// the unit's input (0 = start of the stream), [1] output bytes up to it, [2..5] the distance ring, oldest first, [6] WBITS,
+// [7] libbrotlidec's ring buffer size at the boundary, [8,9] the window (2^WBITS bytes), [10] the ring buffer size where the run
+// stopped, [12,13] output bytes the HOST has dropped in front of the output range (host-written).  The host allocates
+// ZRES_HDR words for it (the header size the streaming code copies for zstd as well).
+constexpr uint32_t BRES_WORDS = 16;
+static_assert(BRES_WORDS <= ZRES_HDR, "the brotli checkpoint fits the header the streaming code copies");
+hipError_t launch_brotli_decode(const BatchArgs &a, hipStream_t stream);
+hipError_t release_brotli_scratch();                 // per-wave table slots of the current device (after a device sync)
+void release_brotli_scratch_of(hipStream_t stream);  // the same for one (drained) stream
+size_t brotli_scratch_bytes_of(hipStream_t stream);  // device bytes those slots hold for `stream` (streaming footprint)
+
 // Detection::detect (src/decoder/mod.rs:28-114) on device: first 2-4 bytes of a unit -> CHIP_DETECT_*.
 // The FLG table of mod.rs:44-55 is packed one word per CINFO; the 0x68 row never matches in the
 // reference (mod.rs:80-82 lacks the `return`) and is kept that way.

@@ -162,6 +162,14 @@ struct Interface {
         if (!h) return std::nullopt;
         return Decoder(h, CHIP_FMT_ZSTD);
     }
+    // Interface::brotli_c(), src/decoder/brotli_c.rs:17-27
+    static std::optional<Decoder> brotli_hip(int device = -1)
+    {
+        chip_decoder_opts o{0, device};
+        chip_decoder *h = chip_decoder_new(CHIP_FMT_BROTLI, &o);
+        if (!h) return std::nullopt;
+        return Decoder(h, CHIP_FMT_BROTLI);
+    }
 };
 
 }  // namespace decoder

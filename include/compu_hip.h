@@ -43,6 +43,10 @@ enum {
     CHIP_FMT_GZIP = 31,
     CHIP_FMT_AUTO = 47, /* decoder only: zlib or gzip, src/decoder/zlib_common.rs:11-14 */
     CHIP_FMT_ZSTD = 100,
+    /* decoder only: RFC 7932 brotli (Interface::brotli_c, src/decoder/brotli_c.rs) -- no large-window streams (a WINDOW_BITS
+     * error, as for compu, which never sets BROTLI_DECODER_PARAM_LARGE_WINDOW), no shared dictionaries; not part of
+     * CHIP_FMT_DETECT routing (compu cannot detect brotli) */
+    CHIP_FMT_BROTLI = 101,
     /* chip_decode_batch only: route every unit by Detection::detect (src/decoder/mod.rs:28-114) to the
      * zlib/gzip or the zstd decoder -- the mixed gzip+zstd batch of BASELINE.json configs[4] */
     CHIP_FMT_DETECT = 0
@@ -96,7 +100,10 @@ int chip_memcpy_d2h(void *dst_host, const void *src_dev, size_t size, void *stre
 int chip_stream_sync(void *stream);
 /* The inflate kernel keeps a token scratch per (device, stream) it has been launched on: one 64 KiB slot per
  * resident wave, about 270 MB on an MI355X, allocated at the first launch and reused.  chip_trim() waits for the
- * current device and gives that memory back (the next launch allocates again).  No reference counterpart:
+ * current device and gives that memory back (the next launch allocates again).  The brotli decoder keeps a table slot per wave in
+ * the same way: 128 KiB per resident wave (at most 16 per CU, about 512 MiB on an MI355X) plus 64 worst-case slots of about
+ * 1.4 MB for the units whose metablock tables do not fit the small one (min(n, 64) of them; a streaming decoder keeps one of
+ * each, freed with it); chip_trim() releases them too.  No reference counterpart:
  * zlib-ng's inflate state is ~40 KiB of host memory per decoder (src/decoder/zlib_ng.rs:29-55). */
 int chip_trim(void);
 
@@ -129,7 +136,9 @@ void chip_decoder_free(chip_decoder *d);
  * reference's state is ~40 KiB per decoder, src/decoder/zlib_ng.rs:29-55).  A zstd stream keeps O(frame window + piece)
  * the same way (ZSTD_decompressStream's own buffers, src/decoder/zstd.rs:98-136): the block checkpoint carries the running
  * XXH64, output behind the window is dropped; a single-segment frame's window is its content size.  The inflate kernel's
- * token scratch (64 KiB per streaming decoder) is not included. */
+ * token scratch (64 KiB per streaming decoder) is not included.  A brotli stream keeps O(window + piece) the same way (checkpoint
+ * at every metablock boundary); its count includes the kernel's table slots of the decoder's stream, one 128 KiB slot and one
+ * worst-case slot of about 1.4 MB, which chip_decoder_free() releases. */
 void chip_decoder_footprint(const chip_decoder *d, size_t *pinned_bytes, size_t *device_bytes);
 /* describe_error_fn: src/decoder/zlib_ng.rs:118-123 (zError), src/decoder/zstd.rs:159-164
  * (ZSTD_getErrorName).  Never NULL for code 0 (tests/decoder.rs:74-76). */
@@ -153,6 +162,12 @@ const char *chip_decoder_strerror(int format, int32_t code);
  * its own) would report instead; with room for the frame the verdicts are the same.  A match offset beyond the
  * frame's Window_Size is -20 even where the bytes exist (RFC 8878 3.1.1.1.2): the verdict never depends on
  * how much history a streaming caller's decoder still holds.
+ * For CHIP_FMT_BROTLI: status[i] is CHIP_FINISHED, CHIP_NEED_INPUT (truncated), CHIP_NEED_OUTPUT, or a negative
+ * BrotliDecoderErrorCode (compu's DecodeError(code), src/decoder/brotli_c.rs:50-59).  On CHIP_NEED_OUTPUT out_len[i] ==
+ * out_cap[i] and those are the stream's first out_cap[i] bytes.  With room for the output the verdict, the output and the code
+ * are libbrotlidec's; on an error out_len[i] counts the bytes decoded in front of it (libbrotlidec flushes fewer).  Exceptions:
+ * a unit that runs 2^24 commands of a single block type in one metablock without output is -31 (UNREACHABLE) where
+ * libbrotlidec keeps going; a unit longer than 512 MiB - 64 reads as truncated.  CHIP_F_COMPU_STATUS changes nothing for brotli.
  * in_base must be 4-byte aligned and its allocation padded to a multiple of 4 bytes.
  * `format` is one CHIP_FMT_* for the whole batch.  `stream` is a hipStream_t (NULL = default
  * stream); the call only enqueues work.  Returns CHIP_OK or a CHIP_E_* code.

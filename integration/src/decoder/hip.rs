@@ -1,4 +1,4 @@
-//! `hip` interface implementation: zlib / gzip / raw deflate and zstd decoding on an MI355X through `libcompu_hip.so`.
+//! `hip` interface implementation: zlib / gzip / raw deflate, zstd and brotli decoding on an MI355X through `libcompu_hip.so`.
 //!
 //! Same shape as `zlib_ng.rs`: one static vtable per format family, the state pointer is the backend's opaque
 //! decoder object, created by the constructor and freed exactly once by `drop_fn`.
@@ -24,6 +24,13 @@ static HIP_ZSTD: Interface = Interface {
     reset_fn,
     decode_fn,
     describe_error_fn: describe_zstd_error_fn,
+};
+
+static HIP_BROTLI: Interface = Interface {
+    drop_fn,
+    reset_fn,
+    decode_fn,
+    describe_error_fn: describe_brotli_error_fn,
 };
 
 impl Interface {
@@ -55,6 +62,19 @@ impl Interface {
         let instance = unsafe { sys::chip_decoder_new(sys::CHIP_FMT_ZSTD, &opts) };
         ptr::NonNull::new(instance as *mut u8).map(|instance| HIP_ZSTD.inner_decoder(instance))
     }
+
+    ///Creates decoder with `hip` interface for brotli (the counterpart of `brotli_c`).
+    ///
+    ///Returns `None` if unable to initialize it (no usable GPU, or lack of memory)
+    pub fn brotli_hip() -> Option<Decoder> {
+        crate::mem::hip_install_allocator();
+        let opts = sys::chip_decoder_opts {
+            window_log_max: 0,
+            device: -1,
+        };
+        let instance = unsafe { sys::chip_decoder_new(sys::CHIP_FMT_BROTLI, &opts) };
+        ptr::NonNull::new(instance as *mut u8).map(|instance| HIP_BROTLI.inner_decoder(instance))
+    }
 }
 
 #[inline]
@@ -69,7 +89,7 @@ unsafe fn decode_fn(state: ptr::NonNull<u8>, input: *const u8, input_remain: usi
                 1 => DecodeStatus::NeedOutput,
                 _ => DecodeStatus::Finished,
             }),
-            //same codes as the CPU backends: zlib's negative return values, -(ZSTD_ErrorCode)
+            //same codes as the CPU backends: zlib's negative return values, -(ZSTD_ErrorCode), BrotliDecoderErrorCode
             code => Err(DecodeError(code)),
         },
     }
@@ -97,6 +117,13 @@ fn describe_zlib_error_fn(code: i32) -> Option<&'static str> {
 #[inline]
 fn describe_zstd_error_fn(code: i32) -> Option<&'static str> {
     let result = unsafe { sys::chip_decoder_strerror(sys::CHIP_FMT_ZSTD, code) };
+    crate::utils::convert_c_str(result)
+}
+
+#[inline]
+fn describe_brotli_error_fn(code: i32) -> Option<&'static str> {
+    //BrotliDecoderErrorString's names, src/decoder/brotli_c.rs (describe_error_fn)
+    let result = unsafe { sys::chip_decoder_strerror(sys::CHIP_FMT_BROTLI, code) };
     crate::utils::convert_c_str(result)
 }
 
@@ -140,6 +167,8 @@ pub enum BatchFormat {
     Zlib(ZlibMode),
     ///zstd frames
     Zstd,
+    ///brotli streams (not part of `Detect`: compu cannot detect brotli)
+    Brotli,
     ///gzip, zlib and zstd units mixed: each unit goes where `Detection::detect` sends it (src/decoder/mod.rs:28-114)
     Detect,
 }
@@ -149,6 +178,7 @@ impl core::fmt::Debug for BatchFormat {
         match self {
             BatchFormat::Zlib(mode) => write!(f, "Zlib({})", mode.max_bits()),
             BatchFormat::Zstd => f.write_str("Zstd"),
+            BatchFormat::Brotli => f.write_str("Brotli"),
             BatchFormat::Detect => f.write_str("Detect"),
         }
     }
@@ -159,6 +189,7 @@ impl BatchFormat {
         match self {
             BatchFormat::Zlib(mode) => mode.max_bits() as _,
             BatchFormat::Zstd => sys::CHIP_FMT_ZSTD,
+            BatchFormat::Brotli => sys::CHIP_FMT_BROTLI,
             BatchFormat::Detect => sys::CHIP_FMT_DETECT,
         }
     }

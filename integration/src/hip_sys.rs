@@ -53,6 +53,7 @@ pub struct chip_zstd_encoder_opts {
 }
 
 pub const CHIP_FMT_ZSTD: c_int = 100;
+pub const CHIP_FMT_BROTLI: c_int = 101;
 ///route every unit of a batch by `Detection::detect` (src/decoder/mod.rs:28-114)
 pub const CHIP_FMT_DETECT: c_int = 0;
 
