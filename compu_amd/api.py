@@ -38,6 +38,10 @@ class _ZstdEncoderOpts(C.Structure):
     _fields_ = [("level", C.c_int32), ("strategy", C.c_int32), ("window_log", C.c_int32), ("device", C.c_int32)]
 
 
+class _BrotliEncoderOpts(C.Structure):
+    _fields_ = [("quality", C.c_int32), ("mode", C.c_int32), ("lgwin", C.c_int32), ("device", C.c_int32)]
+
+
 _lib = None
 
 
@@ -105,6 +109,8 @@ def lib():
     L.chip_encoder_new.argtypes = [C.POINTER(_EncoderOpts)]
     L.chip_encoder_new_zstd.restype = vp
     L.chip_encoder_new_zstd.argtypes = [C.POINTER(_ZstdEncoderOpts)]
+    L.chip_encoder_new_brotli.restype = vp
+    L.chip_encoder_new_brotli.argtypes = [C.POINTER(_BrotliEncoderOpts)]
     L.chip_encode.restype = _EncodeResult
     L.chip_encode.argtypes = [vp, vp, sz, vp, sz, C.c_int]
     L.chip_encoder_reset.restype = vp
@@ -182,7 +188,7 @@ class ZlibMode(enum.IntEnum):
 
 
 FMT_ZSTD = 100
-FMT_BROTLI = 101  # decoder only (Interface::brotli_c)
+FMT_BROTLI = 101  # Interface::brotli_c decoder and encoder
 
 
 class ZstdOptions:
@@ -274,6 +280,33 @@ class ZstdEncoderOptions:
     def window_log(self, window_log):
         assert 10 <= window_log <= 31  # ZSTD_WINDOWLOG_MIN .. ZSTD_WINDOWLOG_MAX_64, zstd.rs:96-101
         self._window_log = window_log
+        return self
+
+
+class BrotliEncoderMode(enum.IntEnum):
+    """src/encoder/brotli_common.rs: compu's raw mode byte, handed to BROTLI_PARAM_MODE unchanged"""
+
+    Generic = 1
+    Text = 2
+    Font = 3
+
+
+class BrotliOptions:
+    """The encoder's BrotliOptions, src/encoder/brotli_common.rs (defaults: quality and mode unset, i.e. libbrotlienc's quality
+    11).  The GPU encoder accepts and records the mode; it has no mode-dependent modelling."""
+
+    def __init__(self):
+        self._quality = 0
+        self._mode = 0
+
+    def quality(self, quality):
+        assert quality > 0
+        assert quality <= 11
+        self._quality = quality
+        return self
+
+    def mode(self, mode):
+        self._mode = int(mode)
         return self
 
 
@@ -606,6 +639,15 @@ class encoder_interface:
         h = lib().chip_encoder_new_zstd(C.byref(o))
         return Encoder(h) if h else None
 
+    @staticmethod
+    def brotli_hip(opts=None, device=-1, lgwin=22):
+        """Interface::brotli_c(opts), src/encoder/brotli_c.rs:38-50 (lgwin: libbrotlienc's default 22, which compu never
+        changes); None on failure."""
+        opts = opts or BrotliOptions()
+        o = _BrotliEncoderOpts(int(opts._quality), int(opts._mode), int(lgwin), device)
+        h = lib().chip_encoder_new_brotli(C.byref(o))
+        return Encoder(h) if h else None
+
 
 # ---- Buffer<N>, src/buffer.rs ---------------------------------------------------------------
 
@@ -893,7 +935,7 @@ def encode_bound(fmt, in_len):
 
 def encode_batch(fmt, level, in_buf, in_off, in_len, out_buf, out_off, out_cap, out_len=None, status=None, stream=None, strategy=0):
     """chip_encode_batch_ex over device tensors: level 0 stored, 1 fixed Huffman, 2..9 (-1 = 6) dynamic Huffman blocks; FMT_ZSTD:
-    zstd levels and ZstdStrategy values."""
+    zstd levels and ZstdStrategy values; FMT_BROTLI: level = quality 0..11 (0 = 11), strategy = mode 0..3, lgwin 22."""
     import torch
 
     n = in_len.numel()

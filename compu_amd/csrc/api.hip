@@ -119,6 +119,7 @@ int chip_trim(void)
     pipes_trim();  // cached host-batch pipelines of the current device (streams, staging and device buffers)
     bool ok = chip::release_inflate_scratch() == hipSuccess;
     ok = chip::release_zstd_enc_scratch() == hipSuccess && ok;
+    ok = chip::release_brotli_enc_scratch() == hipSuccess && ok;
     ok = chip::release_brotli_scratch() == hipSuccess && ok;
     return chip::release_deflate_scratch() == hipSuccess && ok ? CHIP_OK : CHIP_E_LAUNCH;
 }
@@ -1245,6 +1246,9 @@ size_t chip_encode_bound(int format, size_t in_len)
 {
     // zstd: raw blocks of 128 KiB (3-byte headers), the largest frame header (18 bytes) and the checksum
     if (format == CHIP_FMT_ZSTD) return in_len + 3 * (in_len ? (in_len + (128u << 10) - 1) / (128u << 10) : 1) + 18 + 4;
+    // brotli: uncompressed metablocks of 128 KiB (the first header shares its bytes with the WBITS field: at most 4 bytes, then 3
+    // each), the closing empty last metablock (1 byte) -- 4 bytes per metablock and 2 more are a safe margin
+    if (format == CHIP_FMT_BROTLI) return in_len + 4 * (in_len ? (in_len + (128u << 10) - 1) / (128u << 10) : 1) + 2;
     size_t blocks = in_len ? (in_len + 65534) / 65535 : 1;
     size_t wrap = format == CHIP_FMT_GZIP ? 18 : format == CHIP_FMT_ZLIB ? 6 : 0;
     // dynamic levels: a block holds at least 65472 tokens and costs at most 6 bytes more than its stored form
@@ -1287,6 +1291,29 @@ int chip_encode_batch_ex(int format, int level, int strategy, size_t n, const vo
 #endif
         const uint32_t wl = zenc::MAX_DIST_LOG;  // the batch frames use zstd's default window_log (27)
         hipError_t e = launch_zstd_encode(a, level, strategy, wl, wl, ZF_FIRST | ZF_LAST | ZF_ONESHOT, nullptr, (hipStream_t)stream);
+        return e == hipSuccess ? CHIP_OK : CHIP_E_LAUNCH;
+    }
+    if (format == CHIP_FMT_BROTLI) {
+        // level = quality 0..11 (0 = libbrotlienc's default 11), strategy = compu's mode byte 0..3 (recorded only)
+        if (n > 0x7fffffffull || !in_base || !in_off || !in_len || !out_base || !out_off || !out_cap || !out_len || !status ||
+            level < 0 || level > 11 || strategy < 0 || strategy > 3)
+            return CHIP_E_INVALID;
+        if (!device_ok()) return CHIP_E_NO_DEVICE;
+        BatchArgs a;
+        a.in_base = (const uint8_t *)in_base;
+        a.in_off = in_off;
+        a.in_len = in_len;
+        a.out_base = (uint8_t *)out_base;
+        a.out_off = out_off;
+        a.out_cap = out_cap;
+        a.out_len = out_len;
+        a.in_used = nullptr;
+        a.status = status;
+        a.n = (uint32_t)n;
+        a.format = format;
+        a.stats = nullptr;
+        a.resume = nullptr;
+        hipError_t e = launch_brotli_encode(a, level, 22, ZF_FIRST | ZF_LAST, nullptr, (hipStream_t)stream);
         return e == hipSuccess ? CHIP_OK : CHIP_E_LAUNCH;
     }
     if (level == -1) level = 6;  // zlib's Z_DEFAULT_COMPRESSION
@@ -1345,9 +1372,11 @@ struct chip_encoder {
     bool started, finished;
     uint32_t check;
     uint64_t total_in;
-    // zstd (mode == CHIP_FMT_ZSTD): window_log of the options, and the repeat offsets + XXH64 state carried between segments
+    // zstd (mode == CHIP_FMT_ZSTD): window_log of the options, and the repeat offsets + XXH64 state carried between segments;
+    // brotli (mode == CHIP_FMT_BROTLI): lgwin of the options (level = quality, strategy = mode), and the distance ring
     int wlog;
     ZEncStream *d_zs;
+    BEncStream *d_bs;
 };
 
 namespace {
@@ -1379,7 +1408,7 @@ void enc_clear(chip_encoder *e)
 bool enc_segment(chip_encoder *e, bool final)
 {
     const size_t n = e->h_in_len;
-    const bool zstd = e->mode == CHIP_FMT_ZSTD;
+    const bool zstd = e->mode == CHIP_FMT_ZSTD, brotli = e->mode == CHIP_FMT_BROTLI;
     // zstd: with a small window_log the blocks are smaller than the 128 KiB chip_encode_bound counts with
     const size_t zblock = e->wlog < 17 ? (size_t)1 << e->wlog : (size_t)128 << 10;
     const size_t bound = zstd ? n + 3 * (n / zblock + 1) + 22 + 16 : chip_encode_bound(e->mode, n) + 16;
@@ -1422,6 +1451,10 @@ bool enc_segment(chip_encoder *e, bool final)
         const uint32_t flags = (e->started ? 0u : ZF_FIRST) | (final ? ZF_LAST : 0u) | (!e->started && final ? ZF_ONESHOT : 0u);
         const uint32_t wl_single = e->wlog < 27 ? (uint32_t)e->wlog : 27u, wl_window = e->wlog < 20 ? (uint32_t)e->wlog : 20u;
         if (launch_zstd_encode(a, e->level, e->strategy, wl_single, wl_window, flags, e->d_zs, e->stream) != hipSuccess) return false;
+    } else if (brotli) {
+        // every segment but the last ends byte-aligned (Flush's empty metadata metablock); the ring goes on to the next one
+        const uint32_t flags = (e->started ? 0u : ZF_FIRST) | (final ? ZF_LAST : 0u);
+        if (launch_brotli_encode(a, e->level, e->wlog, flags, e->d_bs, e->stream) != hipSuccess) return false;
     } else {
         const uint32_t flags = (e->started ? 0u : 1u) | (final ? 2u | 4u : 0u) | ((uint32_t)e->strategy << 8);
         if (launch_deflate_l1(a, e->level, flags, e->check, e->total_in, &e->d_meta->check, e->stream) != hipSuccess) return false;
@@ -1526,6 +1559,42 @@ chip_encoder *chip_encoder_new_zstd(const chip_zstd_encoder_opts *opts)
     return e;
 }
 
+chip_encoder *chip_encoder_new_brotli(const chip_brotli_encoder_opts *opts)
+{
+    // BrotliOptions::new(), src/encoder/brotli_common.rs: quality and mode unset (libbrotlienc's quality 11), lgwin 22
+    const int quality = opts ? opts->quality : 0, mode = opts ? opts->mode : 0, lgwin = opts ? opts->lgwin : 22;
+    if (quality < 0 || quality > 11 || mode < 0 || mode > 3 || lgwin < 10 || lgwin > 24) return nullptr;
+    if (!device_ok()) return nullptr;
+    int device = opts ? opts->device : -1;
+    if (device < 0 && hipGetDevice(&device) != hipSuccess) return nullptr;
+    DeviceGuard guard(device);
+    if (!guard.ok) return nullptr;
+    const Hooks hooks = current_hooks();
+    chip_encoder *e = (chip_encoder *)hooks.alloc(sizeof(chip_encoder));
+    if (!e) return nullptr;
+    memset(e, 0, sizeof *e);
+    e->hooks = hooks;
+    e->mode = CHIP_FMT_BROTLI;
+    e->level = quality ? quality : 11;
+    e->strategy = mode;
+    e->wlog = lgwin;
+    e->device = device;
+    if (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess) {
+        hooks.release(e);
+        return nullptr;
+    }
+    e->d_meta = (chip_encoder::EMeta *)chip_device_alloc(sizeof(chip_encoder::EMeta));
+    e->h_meta = (chip_encoder::EMeta *)chip_pinned_alloc(sizeof(chip_encoder::EMeta));
+    e->d_bs = (BEncStream *)chip_device_alloc(sizeof(BEncStream));
+    if (!e->d_meta || !e->h_meta || !e->d_bs || !enc_reserve(&e->h_in, &e->h_in_cap, 0, 65536) ||
+        !enc_reserve(&e->h_out, &e->h_out_cap, 0, 65536)) {
+        chip_encoder_free(e);
+        return nullptr;
+    }
+    enc_clear(e);
+    return e;
+}
+
 chip_encode_result chip_encode(chip_encoder *e, const uint8_t *in, size_t in_len, uint8_t *out, size_t out_len, int op)
 {
     chip_encode_result r = {in_len, out_len, CHIP_ENC_ERROR};
@@ -1557,6 +1626,13 @@ chip_encode_result chip_encode(chip_encoder *e, const uint8_t *in, size_t in_len
     if (e->delivered == e->h_out_len) e->h_out_len = e->delivered = 0;
     r.input_remain = in_len - taken;
     r.output_remain = out_len - k;
+    if (e->mode == CHIP_FMT_BROTLI) {
+        // src/encoder/brotli_c.rs:63-84: NeedOutput while compressed bytes wait (BrotliEncoderHasMoreOutput), otherwise Finished
+        // for Finish and Continue for Process and Flush (a failure returned Error above)
+        if (e->h_out_len != 0) r.status = CHIP_ENC_NEED_OUTPUT;
+        else r.status = op == CHIP_OP_FINISH ? CHIP_ENC_FINISHED : CHIP_ENC_CONTINUE;
+        return r;
+    }
     if (e->mode == CHIP_FMT_ZSTD) {
         // ZSTD_compressStream2's return value -> EncodeStatus, src/encoder/zstd.rs:174-197.  It is 0 when no compressed byte
         // waits for delivery, and for Flush also nothing is buffered, for Finish also the frame is closed; 0 is Finished for
@@ -1589,6 +1665,7 @@ void chip_encoder_free(chip_encoder *e)
         (void)hipStreamSynchronize(e->stream);
         chip::release_deflate_scratch_of(e->stream);  // the stream's token scratch goes with it
         chip::release_zstd_enc_scratch_of(e->stream);
+        chip::release_brotli_enc_scratch_of(e->stream);
         (void)hipStreamDestroy(e->stream);
     }
     chip_pinned_free(e->h_in);
@@ -1598,6 +1675,7 @@ void chip_encoder_free(chip_encoder *e)
     chip_device_free(e->d_out);
     chip_device_free(e->d_meta);
     chip_device_free(e->d_zs);
+    chip_device_free(e->d_bs);
     const Hooks hooks = e->hooks;
     hooks.release(e);
 }

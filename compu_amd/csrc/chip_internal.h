@@ -97,6 +97,15 @@ hipError_t launch_zstd_encode(const BatchArgs &a, int level, int strategy, uint3
 hipError_t release_zstd_enc_scratch();                 // the zstd encoder's per-wave scratch of the current device (after a sync)
 void release_zstd_enc_scratch_of(hipStream_t stream);  // the same for one (drained) stream
 
+// brotli encoder (brotli_enc.hip).  Flags: ZF_FIRST writes the WBITS field and starts the distance ring, ZF_LAST closes the stream
+// (otherwise the segment ends byte-aligned).  quality 0..11 (0 = 11), lgwin 10..24.
+struct BEncStream {
+    uint32_t ring[4];  // the distance ring carried from one segment to the next, last distance first
+};
+hipError_t launch_brotli_encode(const BatchArgs &a, int quality, int lgwin, uint32_t flags, BEncStream *stream_state, hipStream_t stream);
+hipError_t release_brotli_enc_scratch();                 // the brotli encoder's per-wave scratch of the current device (after a sync)
+void release_brotli_enc_scratch_of(hipStream_t stream);  // the same for one (drained) stream
+
 // brotli decoder (brotli.hip): a persistent launch with a 128 KiB table slot per wave, then an always-enqueued launch on 64 waves
 // with worst-case slots for the units whose metablock tables did not fit (an overflow list on the device).
 // BatchArgs::resume (streaming only): the checkpoint written at every metablock boundary -- [0] 1 + bit offset of the boundary in

@@ -11,6 +11,7 @@
 // maintainer would add to the crate itself is in INTEGRATION.md.
 #pragma once
 
+#include <cassert>
 #include <cstddef>
 #include <cstdint>
 #include <optional>
@@ -219,6 +220,28 @@ struct ZstdOptions {
     }
 };
 
+// src/encoder/brotli_common.rs: compu's raw mode byte (handed to BROTLI_PARAM_MODE unchanged; recorded only on the GPU)
+enum class BrotliEncoderMode { Generic = 1, Text = 2, Font = 3 };
+
+// the encoder's BrotliOptions, src/encoder/brotli_common.rs (defaults: quality and mode unset = libbrotlienc's quality 11)
+struct BrotliOptions {
+    int32_t quality_ = 0;
+    int32_t mode_ = 0;
+    BrotliOptions quality(int32_t v) const
+    {
+        assert(v > 0 && v <= 11);
+        BrotliOptions o = *this;
+        o.quality_ = v;
+        return o;
+    }
+    BrotliOptions mode(BrotliEncoderMode m) const
+    {
+        BrotliOptions o = *this;
+        o.mode_ = static_cast<int32_t>(m);
+        return o;
+    }
+};
+
 // src/encoder/zlib_common.rs:47-103 (defaults: Gzip, Default strategy, mem_level 8, compression 9, :59-66)
 struct ZlibOptions {
     ZlibMode mode_ = ZlibMode::Gzip;
@@ -334,6 +357,14 @@ struct Interface {
     {
         chip_zstd_encoder_opts o{opts.level_, static_cast<int32_t>(opts.strategy_), opts.window_log_, device};
         chip_encoder *h = chip_encoder_new_zstd(&o);
+        if (!h) return std::nullopt;
+        return Encoder(h);
+    }
+    // Interface::brotli_c(opts), src/encoder/brotli_c.rs:38-50 (lgwin 22, libbrotlienc's default)
+    static std::optional<Encoder> brotli_hip(BrotliOptions opts = {}, int device = -1)
+    {
+        chip_brotli_encoder_opts o{opts.quality_, opts.mode_, 22, device};
+        chip_encoder *h = chip_encoder_new_brotli(&o);
         if (!h) return std::nullopt;
         return Encoder(h);
     }

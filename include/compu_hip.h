@@ -43,9 +43,10 @@ enum {
     CHIP_FMT_GZIP = 31,
     CHIP_FMT_AUTO = 47, /* decoder only: zlib or gzip, src/decoder/zlib_common.rs:11-14 */
     CHIP_FMT_ZSTD = 100,
-    /* decoder only: RFC 7932 brotli (Interface::brotli_c, src/decoder/brotli_c.rs) -- no large-window streams (a WINDOW_BITS
-     * error, as for compu, which never sets BROTLI_DECODER_PARAM_LARGE_WINDOW), no shared dictionaries; not part of
-     * CHIP_FMT_DETECT routing (compu cannot detect brotli) */
+    /* RFC 7932 brotli (decoder: Interface::brotli_c, src/decoder/brotli_c.rs; encoder: chip_encoder_new_brotli and the batch
+     * calls) -- no large-window streams (a WINDOW_BITS error, as for compu, which never sets
+     * BROTLI_DECODER_PARAM_LARGE_WINDOW), no shared dictionaries; not part of CHIP_FMT_DETECT routing (compu cannot detect
+     * brotli) */
     CHIP_FMT_BROTLI = 101,
     /* chip_decode_batch only: route every unit by Detection::detect (src/decoder/mod.rs:28-114) to the
      * zlib/gzip or the zstd decoder -- the mixed gzip+zstd batch of BASELINE.json configs[4] */
@@ -267,15 +268,16 @@ chip_encoder *chip_encoder_reset(chip_encoder *e);
 /* drop_fn src/encoder/zlib_ng.rs:107-111 */
 void chip_encoder_free(chip_encoder *e);
 
-/* chip_encode_batch with a strategy (CHIP_STRATEGY_*, or CHIP_ZSTD_STRATEGY_* for CHIP_FMT_ZSTD); chip_encode_batch is strategy
- * Default. */
+/* chip_encode_batch with a strategy (CHIP_STRATEGY_*, CHIP_ZSTD_STRATEGY_* for CHIP_FMT_ZSTD, or the brotli mode 0..3 for
+ * CHIP_FMT_BROTLI); chip_encode_batch is strategy Default (mode 0). */
 int chip_encode_batch_ex(int format, int level, int strategy, size_t n, const void *in_base, const uint64_t *in_off,
                          const uint32_t *in_len, void *out_base, const uint64_t *out_off, const uint32_t *out_cap,
                          uint32_t *out_len, int32_t *status, void *stream);
 
 /* Batched encode of n independent units (device pointers, one wavefront per unit).  CHIP_FMT_ZSTD: level as in
  * chip_zstd_encoder_opts, window_log 27; each unit becomes one zstd frame with the content checksum (single segment with
- * Frame_Content_Size up to 2^27 bytes, a 2^27 window above).
+ * Frame_Content_Size up to 2^27 bytes, a 2^27 window above).  CHIP_FMT_BROTLI: level = quality 0..11 (0 = 11, -1 is
+ * CHIP_E_INVALID), strategy = mode 0..3; each unit becomes one brotli stream with lgwin 22.
  * out_len[i] = compressed size; status[i] = CHIP_ENC_FINISHED or CHIP_ENC_NEED_OUTPUT.  Each unit becomes
  * one complete stream of `format` (wrapper, one fixed-Huffman or stored deflate body, trailer).  The
  * range out_off[i] .. +out_cap[i] may be used as scratch beyond out_len[i]. */
@@ -322,6 +324,25 @@ typedef struct {
  * The encoder is driven by chip_encode / chip_encoder_reset / chip_encoder_free.  Every frame carries the content checksum
  * (libzstd's default is without it).  chip_encode's status follows src/encoder/zstd.rs:174-197. */
 chip_encoder *chip_encoder_new_zstd(const chip_zstd_encoder_opts *opts);
+
+/* ---- brotli encoder: encoder::Interface::brotli_c / brotli_rust, src/encoder/brotli_c.rs, brotli_common.rs ------------------ */
+
+/* BrotliOptions src/encoder/brotli_common.rs.  The GPU encoder has four quality groups: quality 1 greedy
+ * with a skip over runs without matches, 2..4 greedy with a last-distance probe, 5..9 lazy, 10..11 lazy with two positions per
+ * hash slot.  `mode` is compu's raw byte (BrotliEncoderMode: Generic = 1, Text = 2, Font = 3; 0 = unset), which compu hands
+ * to BROTLI_PARAM_MODE unchanged; the GPU encoder has no mode-dependent modelling, so it is accepted and recorded only. */
+typedef struct {
+    int32_t quality; /* 0..11, 0 = unset = libbrotlienc's default 11 */
+    int32_t mode;    /* 0..3 */
+    int32_t lgwin;   /* 10..24, default 22: the WBITS field; matches reach at most min(2^lgwin - 16, 65536) bytes */
+    int32_t device;  /* HIP device ordinal, -1 = current */
+} chip_brotli_encoder_opts;
+
+/* Interface::brotli_c(opts) src/encoder/brotli_c.rs:38-50.  NULL opts = BrotliOptions::new() (quality 0 = 11, mode 0, lgwin
+ * 22); NULL on quality > 11, mode > 3 or lgwin outside 10..24.  Driven by chip_encode / chip_encoder_reset / chip_encoder_free:
+ * Flush byte-aligns the stream with an empty metadata metablock as libbrotlienc's FLUSH does; chip_encode's status follows
+ * src/encoder/brotli_c.rs:63-84. */
+chip_encoder *chip_encoder_new_brotli(const chip_brotli_encoder_opts *opts);
 
 #ifdef __cplusplus
 }

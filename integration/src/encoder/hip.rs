@@ -1,10 +1,10 @@
-//! `hip` module: zlib / gzip / raw deflate and zstd encoding on an MI355X through `libcompu_hip.so`.
+//! `hip` module: zlib / gzip / raw deflate, zstd and brotli encoding on an MI355X through `libcompu_hip.so`.
 
 extern crate alloc;
 
 use core::ptr;
 
-use super::{Encode, EncodeOp, EncodeStatus, Encoder, Interface, ZlibOptions, ZlibStrategy, ZstdOptions};
+use super::{BrotliOptions, Encode, EncodeOp, EncodeStatus, Encoder, Interface, ZlibOptions, ZlibStrategy, ZstdOptions};
 use crate::hip_sys as sys;
 
 static HIP_ZLIB: Interface = Interface {
@@ -16,6 +16,13 @@ static HIP_ZLIB: Interface = Interface {
 //The zstd encoder is driven by the same three entry points; chip_encode picks the status rules of the encoder's kind
 //(src/encoder/zstd.rs:174-197 for zstd), so encode_fn passes the C status on unchanged.
 static HIP_ZSTD: Interface = Interface {
+    drop_fn,
+    reset_fn,
+    encode_fn,
+};
+
+//The brotli encoder likewise (src/encoder/brotli_c.rs:63-84 for its status rules).
+static HIP_BROTLI: Interface = Interface {
     drop_fn,
     reset_fn,
     encode_fn,
@@ -64,6 +71,24 @@ impl Interface {
         };
         let instance = unsafe { sys::chip_encoder_new_zstd(&opts) };
         ptr::NonNull::new(instance as *mut u8).map(|instance| HIP_ZSTD.inner_encoder(instance, [0; 2]))
+    }
+
+    #[inline]
+    ///Creates encoder with `hip` interface for brotli (the counterpart of `brotli_c`)
+    ///
+    ///Returns `None` if unable to initialize it (no usable GPU, or lack of memory).  The mode byte is accepted and recorded: the
+    ///GPU encoder has no mode-dependent modelling.
+    pub fn brotli_hip(opts: BrotliOptions) -> Option<Encoder> {
+        crate::mem::hip_install_allocator();
+        //`inner` is crate-visible: [quality (0 = unset = 11), mode (compu's raw byte, 0 = unset)], src/encoder/brotli_common.rs
+        let opts = sys::chip_brotli_encoder_opts {
+            quality: opts.inner[0] as _,
+            mode: opts.inner[1] as _,
+            lgwin: 22,
+            device: -1,
+        };
+        let instance = unsafe { sys::chip_encoder_new_brotli(&opts) };
+        ptr::NonNull::new(instance as *mut u8).map(|instance| HIP_BROTLI.inner_encoder(instance, [0; 2]))
     }
 }
 

@@ -52,6 +52,15 @@ pub struct chip_zstd_encoder_opts {
     pub device: i32,
 }
 
+///`chip_brotli_encoder_opts`: the encoder's `BrotliOptions` (src/encoder/brotli_common.rs) and the window
+#[repr(C)]
+pub struct chip_brotli_encoder_opts {
+    pub quality: i32,
+    pub mode: i32,
+    pub lgwin: i32,
+    pub device: i32,
+}
+
 pub const CHIP_FMT_ZSTD: c_int = 100;
 pub const CHIP_FMT_BROTLI: c_int = 101;
 ///route every unit of a batch by `Detection::detect` (src/decoder/mod.rs:28-114)
@@ -107,6 +116,7 @@ extern "C" {
 
     pub fn chip_encoder_new(opts: *const chip_encoder_opts) -> *mut chip_encoder;
     pub fn chip_encoder_new_zstd(opts: *const chip_zstd_encoder_opts) -> *mut chip_encoder;
+    pub fn chip_encoder_new_brotli(opts: *const chip_brotli_encoder_opts) -> *mut chip_encoder;
     pub fn chip_encode(e: *mut chip_encoder, input: *const u8, input_len: usize, output: *mut u8, output_len: usize, op: c_int) -> chip_encode_result;
     pub fn chip_encoder_reset(e: *mut chip_encoder) -> *mut chip_encoder;
     pub fn chip_encoder_free(e: *mut chip_encoder);
