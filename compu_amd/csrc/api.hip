@@ -1156,6 +1156,10 @@ chip_decode_result chip_decode(chip_decoder *d, const uint8_t *in, size_t in_len
     if (d->format == CHIP_FMT_ZSTD) {
         // src/decoder/zstd.rs:113-135: 0 -> Finished (frame done AND flushed); else a full output buffer -> NeedOutput,
         // whatever else happened; else no error -> NeedInput; else the error
+        // A call that returns an error leaves input.pos where the caller set it (compu's decode_fn reports input.size - input.pos,
+        // src/decoder/zstd.rs): the whole input of the call is reported as remaining, also when an empty output range turns the
+        // error into NeedOutput.
+        if (d->k_status < 0 && d->delivered == d->k_out_len) r.input_remain = in_len;
         if (d->k_status == CHIP_FINISHED && d->delivered == d->k_out_len) {
             d->done = true;
             r.status = CHIP_FINISHED;

@@ -999,6 +999,7 @@ __global__ __launch_bounds__(64, CHIP_ZSTD_WAVES) void zstd_kernel(BatchArgs a, 
     int32_t status = ST_RUNNING;
     uint32_t ip = B0;  // absolute byte cursor
     uint32_t opos = 0;  // output cursor
+    uint32_t rewind_to = ~0u;  // inside a compressed block: the output cursor at its start (a block that fails hands on nothing)
     uint32_t rep0 = 1, rep1 = 4, rep2 = 8;
     bool has_checksum = false, has_fcs = false;
     uint64_t fcs = 0, window = 0, out_limit = ~0ULL;
@@ -1163,7 +1164,8 @@ __global__ __launch_bounds__(64, CHIP_ZSTD_WAVES) void zstd_kernel(BatchArgs a, 
             if (END - ip < 3 + bsz) ZNEED_INPUT();
             // ---- compressed block ----------------------------------------------------------------
             const uint32_t bp = ip + 3, bend = bp + bsz;
-            if (bsz < 1) ZFAIL(ZSTD_E_CORRUPTION);
+            rewind_to = opos;
+            if (bsz < 3) ZFAIL(ZSTD_E_CORRUPTION);  // libzstd's MIN_CBLOCK_SIZE (oracle_zstd.c): no two-byte empty block
             const uint32_t b0 = byte_at(b, bp), ltype = b0 & 3u, sf = (b0 >> 2) & 3u;
             uint32_t hl, regen, comp = 0, streams = 1;
             if (ltype < 2) {
@@ -1875,6 +1877,7 @@ __global__ __launch_bounds__(64, CHIP_ZSTD_WAVES) void zstd_kernel(BatchArgs a, 
             copy_literals(restl);
             opos += restl;
             ip = bend;
+            rewind_to = ~0u;
         }
         if (last) {
             if (has_fcs && dropped + opos != fcs) ZFAIL(ZSTD_E_CORRUPTION);
@@ -1903,6 +1906,9 @@ __global__ __launch_bounds__(64, CHIP_ZSTD_WAVES) void zstd_kernel(BatchArgs a, 
     }
     status = CHIP_FINISHED;
 done:
+    // libzstd decodes a block whole before it hands any of it on: the sequences of a failing block already placed are not output
+    // (the oracle drops them too; a streaming caller would otherwise be handed them in front of the error)
+    if (status < 0 && rewind_to != ~0u) opos = rewind_to;
     if ((a.flags & F_COMPU_STATUS) && status != CHIP_FINISHED) {
         // compu looks at the output first (src/decoder/zstd.rs:121-133): output.pos == output.size is NeedOutput whatever
         // ZSTD_decompressStream returned.  An error return leaves output.pos as compu set it, 0 -- libzstd decodes a block only once the one

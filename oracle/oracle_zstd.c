@@ -336,7 +336,9 @@ static int grow(uint8_t **buf, size_t *cap, size_t need)
 /* one compressed block: src[0..n) -> appended to s->out.  Returns 0 or a ZSTD error code. */
 static int decode_compressed_block(orc_zstd *s, const uint8_t *src, size_t n)
 {
-    if (n < 1) return CORRUPT();
+    /* libzstd's MIN_CBLOCK_SIZE: a literals header, one literal byte (raw or RLE) and the sequence count -- so the two-byte block
+     * RFC 8878 allows (no literals, no sequences) is corruption to it (pinned against the system's libzstd, tests/zstd_cases.py) */
+    if (n < 3) return CORRUPT();
     /* ---- literals section (sec. 3.1.1.3.1) ---- */
     unsigned b0 = src[0], type = b0 & 3, sf = (b0 >> 2) & 3;
     size_t hl, regen, comp = 0;
@@ -626,6 +628,9 @@ orc_decode_t orc_zstd_decode(orc_zstd *s, const uint8_t *in, size_t in_len, uint
         s->in_len -= giveback;
     }
     r.input_remain = (in_len - taken) + giveback;
+    /* an error return leaves input->pos as the caller set it, and compu reports input.size - input.pos (src/decoder/zstd.rs): the
+     * call that gets to the damage reports its whole input as remaining (also when an empty output range makes it NeedOutput) */
+    if (err_now) r.input_remain = in_len;
     /* ZSTD_decompressStream's return value: 0 = frame done and flushed, error, or a positive hint */
     int done = s->stage == 3 && s->delivered == s->out_len;
     int is_err = err_now; /* the good bytes of earlier calls have been handed on; those of this call are not */

@@ -91,3 +91,50 @@ def craft_offset_frame(raw_blocks, block_len, offset, window_desc=0x00, fill=Non
     body = bytes([0x00, 0x01, 0x54, 0x00, code, 0x00]) + stream  # raw literals of size 0; one sequence; RLE x 3: LL code 0, OF code, ML code 0
     out += ((len(body) << 3) | (2 << 1) | 1).to_bytes(3, "little") + body
     return bytes(out), data
+
+
+def drive(call, frame, cuts, room, max_calls=200000):
+    """compu's decode loop (src/decoder/mod.rs:323-335) over one decoder: the input arrives in pieces that end at `cuts` (the last
+    piece ends at the frame's end); each call gets what the calls before left of the pieces so far and `room` bytes of output, and a
+    call that reports NeedInput brings the next piece.  `call(input, room)` -> (status or None, err, output bytes, input_remain,
+    output_remain).  Returns the list of those per call, up to Finished, an error, or NeedInput at the end of the input."""
+    frame = bytes(frame)
+    ends = sorted(set(c for c in cuts if 0 < c < len(frame))) + [len(frame)]
+    calls, pos, k = [], 0, 0
+    for _ in range(max_calls):
+        r = call(frame[pos:ends[k]], room)
+        calls.append(r)
+        pos = ends[k] - r[3]
+        if r[0] is None or r[0] == 2:
+            break
+        if r[0] == 0:
+            if k + 1 == len(ends):
+                break
+            k += 1
+    return calls
+
+
+def stream_calls(z, frame, cuts, room, max_calls=200000):
+    """drive() over one ZSTD_DStream of the system libzstd, each call mapped as stream_decode_once maps it"""
+    ds = z.ZSTD_createDStream()
+    dst = C.create_string_buffer(max(room, 1))
+
+    def call(chunk, room):
+        src = C.create_string_buffer(chunk, len(chunk) + 1)
+        ib = _Buf(C.cast(src, C.c_void_p), len(chunk), 0)
+        ob = _Buf(C.cast(dst, C.c_void_p), room, 0)
+        ret = z.ZSTD_decompressStream(ds, C.byref(ob), C.byref(ib))
+        if ret == 0:
+            st, err = 2, 0
+        elif ob.pos == ob.size:
+            st, err = 1, 0
+        elif not z.ZSTD_isError(ret):
+            st, err = 0, 0
+        else:
+            st, err = None, -z.ZSTD_getErrorCode(ret)
+        return st, err, dst.raw[: ob.pos], len(chunk) - ib.pos, room - ob.pos
+
+    try:
+        return drive(call, frame, cuts, room, max_calls)
+    finally:
+        z.ZSTD_freeDStream(ds)
