@@ -1040,16 +1040,17 @@ __device__ CHIP_PHASE_FN bool flush_tokens(WaveLds &L, const uint32_t *grow_, ui
         STAT_ACC(18);
         opos += run - mis;
         opos_ = opos;
-        if (opos > cap) {
-            opos_ = cap;
-            status = CHIP_NEED_OUTPUT;
-            ovf[0] = cstart;
-            ovf[1] = mis;
-            ovf[2] = xcap;
-            return false;
-        }
-        if (too_far) {
-            status = Z_DATA_ERROR;
+        // zlib tests a match's distance only once there is room for its first byte: a match that reaches too far back while the
+        // output is exactly full is "no room", not an error
+        const bool no_room = opos > cap || (too_far && opos == cap);
+        if (no_room || too_far) {
+            if (no_room) {
+                opos_ = cap;
+                ovf[0] = cstart;
+                ovf[1] = mis;
+                ovf[2] = xcap;
+            }
+            status = no_room ? CHIP_NEED_OUTPUT : Z_DATA_ERROR;
             return false;
         }
         if (c0 >= ntok) return true;

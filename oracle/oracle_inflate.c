@@ -368,13 +368,19 @@ static int inflate_step(orc_inflate *s, const uint8_t *in, size_t in_len, uint8_
                     uint8_t h4[4] = {0x1f, 0x8b, 8, (uint8_t)(s->gz_flags >> 8)};
                     s->hcrc = orc_crc32(0, h4, 4);
                 }
+                if (s->gz_idx == 2) {
+                    /* zlib takes CM and FLG together (NEEDBITS(16)) before it looks at either */
+                    NEED(16);
+                    b = PEEK(16);
+                    if ((b & 0xff) != 8) FAIL("unknown compression method");
+                    if (b & 0xe000) FAIL("unknown header flags set");
+                    s->gz_flags = b & 0xff00; /* zlib keeps FLG in bits 8..15 */
+                    DROP(16);
+                    s->gz_idx = 4;
+                    continue;
+                }
                 NEED(8);
                 b = PEEK(8);
-                if (s->gz_idx == 2 && b != 8) FAIL("unknown compression method");
-                if (s->gz_idx == 3) {
-                    if (b & 0xe0) FAIL("unknown header flags set");
-                    s->gz_flags = b << 8; /* zlib keeps FLG in bits 8..15 */
-                }
                 DROP(8);
                 if (s->gz_idx >= 4 && (s->gz_flags & 0x0200)) { uint8_t b_ = (uint8_t)b; s->hcrc = orc_crc32(s->hcrc, &b_, 1); }
                 s->gz_idx++;
@@ -541,6 +547,9 @@ static int inflate_step(orc_inflate *s, const uint8_t *in, size_t in_len, uint8_
                 if (s->pend_len) {
                     if (op == oe) goto leave;
                     unsigned dist = s->pend_dist;
+                    /* zlib checks the distance in its MATCH state, behind the test for output room: a match that reaches
+                     * too far back while the output is full is Z_OK (the token's bits consumed), the error comes next call */
+                    if ((uint64_t)dist > s->total_out + (uint64_t)(op - out)) FAIL("invalid distance too far back");
                     while (s->pend_len && op < oe) {
                         size_t produced = (size_t)(op - out);
                         if (dist > produced) { /* source predates this call: take it from the window */
@@ -589,7 +598,6 @@ static int inflate_step(orc_inflate *s, const uint8_t *in, size_t in_len, uint8_
                 }
                 unsigned dist = E_BASE(e2) + ((unsigned)(h >> cl2) & ((1u << eb2) - 1));
                 DROP(n1 + cl2 + eb2);
-                if ((uint64_t)dist > s->total_out + (uint64_t)(op - out)) FAIL("invalid distance too far back");
                 s->pend_len = len;
                 s->pend_dist = dist;
             }
