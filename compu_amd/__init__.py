@@ -34,6 +34,7 @@ from .api import (  # noqa: F401
     ZstdStrategy,
     decode_batch,
     decode_batch_host,
+    decode_batch_sizes,
     decode_batch_multi,
     encode_batch_host,
     trim,

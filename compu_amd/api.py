@@ -101,6 +101,8 @@ def lib():
     L.chip_decode_batch.argtypes = [C.c_int, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.chip_decode_batch_ex.restype = C.c_int
     L.chip_decode_batch_ex.argtypes = [C.c_int, C.c_uint32, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.chip_decode_batch_sizes.restype = C.c_int
+    L.chip_decode_batch_sizes.argtypes = [C.c_int, C.c_uint32, sz, vp, vp, vp, vp, vp, vp, vp]
     L.chip_detect.restype = C.c_int
     L.chip_detect.argtypes = [vp, sz]
     L.chip_detect_batch.restype = C.c_int
@@ -845,6 +847,30 @@ def decode_batch(fmt, in_buf, in_off, in_len, out_buf, out_off, out_cap, out_len
     if rc != 0:
         raise RuntimeError(f"chip_decode_batch failed: {rc}")
     return out_len, in_used, status
+
+
+def decode_batch_sizes(fmt, in_buf, in_off, in_len, out_size=None, in_used=None, status=None, stream=None, flags=0):
+    """chip_decode_batch_sizes on device tensors: the decoded length of every unit without decoding it (no output buffer).
+    in_buf uint8, in_off int64 (read as u64), in_len / in_used int32 (read as u32), out_size int64 (read as u64), status int32.
+    Only enqueues.  Returns (out_size, in_used, status)."""
+    import torch
+
+    n = in_len.numel()
+    dev = in_buf.device
+    if out_size is None:
+        out_size = torch.empty(n, dtype=torch.int64, device=dev)
+    if in_used is None:
+        in_used = torch.empty(n, dtype=torch.int32, device=dev)
+    if status is None:
+        status = torch.empty(n, dtype=torch.int32, device=dev)
+    _check_tensors(((in_buf, torch.uint8), (in_off, torch.int64), (in_len, torch.int32), (out_size, torch.int64), (in_used, torch.int32),
+                    (status, torch.int32)))
+    with torch.cuda.device(dev):
+        rc = lib().chip_decode_batch_sizes(int(fmt), int(flags), n, _dp(in_buf), _dp(in_off), _dp(in_len), _dp(out_size), _dp(in_used),
+                                           _dp(status), _stream_ptr(stream))
+    if rc != 0:
+        raise RuntimeError(f"chip_decode_batch_sizes failed: {rc}")
+    return out_size, in_used, status
 
 
 def decode_batch_host(fmt, in_buf, in_off, in_len, out_buf, out_off, out_cap, device=-1, slice_bytes=0):

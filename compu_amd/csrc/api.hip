@@ -181,6 +181,51 @@ int chip_decode_batch_ex(int format, uint32_t flags, size_t n, const void *in_ba
     return e == hipSuccess ? CHIP_OK : CHIP_E_LAUNCH;
 }
 
+int chip_decode_batch_sizes(int format, uint32_t flags, size_t n, const void *in_base, const uint64_t *in_off, const uint32_t *in_len,
+                            uint64_t *out_size, uint32_t *in_used, int32_t *status, void *stream)
+{
+    // arguments first, the device second (as chip_decode_batch_ex): a refusal needs no GPU
+    if (flags != 0) return CHIP_E_INVALID;
+    switch (format) {
+    case CHIP_FMT_DEFLATE:
+    case CHIP_FMT_ZLIB:
+    case CHIP_FMT_GZIP:
+    case CHIP_FMT_AUTO:
+    case CHIP_FMT_ZSTD:
+    case CHIP_FMT_DETECT: break;
+    default: return CHIP_E_INVALID;  // brotli: a size pass would be a full decode (header)
+    }
+    if (n == 0) return CHIP_OK;
+    if (n > 0x7fffffffull || !in_base || !in_off || !in_len || !out_size || !in_used || !status || ((uintptr_t)in_base & 3u))
+        return CHIP_E_INVALID;
+    if (!device_ok()) return CHIP_E_NO_DEVICE;
+    BatchArgs a;
+    a.in_base = (const uint8_t *)in_base;
+    a.in_off = in_off;
+    a.in_len = in_len;
+    a.out_base = nullptr;
+    a.out_off = nullptr;
+    a.out_cap = nullptr;
+    a.out_len = nullptr;
+    a.in_used = in_used;
+    a.status = status;
+    a.n = (uint32_t)n;
+    a.format = format;
+    a.stats = nullptr;
+    a.resume = nullptr;
+    a.sel = nullptr;
+    a.sel_n = nullptr;
+    a.flags = 0;
+#ifdef CHIP_STATS
+    a.stats = getenv("CHIP_STATS_PTR") ? (unsigned long long *)strtoull(getenv("CHIP_STATS_PTR"), nullptr, 0) : nullptr;
+#endif
+    hipError_t e;
+    if (format == CHIP_FMT_ZSTD) e = launch_zstd_sizes(a, out_size, 0, (hipStream_t)stream);
+    else if (format == CHIP_FMT_DETECT) e = launch_routed_sizes(a, out_size, (hipStream_t)stream);  // routed as launch_routed routes a decode batch
+    else e = launch_inflate_sizes(a, out_size, (hipStream_t)stream);
+    return e == hipSuccess ? CHIP_OK : CHIP_E_LAUNCH;
+}
+
 }  // extern "C"
 
 namespace {

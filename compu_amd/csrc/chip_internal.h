@@ -67,6 +67,16 @@ constexpr uint32_t F_COMPU_STATUS = 1u;  // = CHIP_F_COMPU_STATUS
 
 // launchers (each only enqueues on `stream`)
 hipError_t launch_inflate(const BatchArgs &a, hipStream_t stream);
+// the size pass (chip_decode_batch_sizes): a.out_base / out_off / out_cap / out_len are not read; the decoded length of unit i goes to
+// out_size[i].  Shares the (device, stream) slot of launch_inflate.
+hipError_t launch_inflate_sizes(const BatchArgs &a, uint64_t *out_size, hipStream_t stream);
+// zstd_sizes.hip: the zstd size pass; the routed size pass (CHIP_FMT_DETECT): router + both size kernels under one lock of the slot,
+// as launch_routed
+hipError_t launch_zstd_sizes(const BatchArgs &a, uint64_t *out_size, int window_log_max, hipStream_t stream);
+hipError_t launch_route_sizes(const BatchArgs &a, uint64_t *out_size, uint32_t *sel_inflate, uint32_t *sel_zstd, uint32_t *counts, hipStream_t stream);
+hipError_t launch_routed_sizes(const BatchArgs &a, uint64_t *out_size, hipStream_t stream);
+// (inflate_sizes.hip: the launch itself, for launch_inflate_sizes, which holds the slot)
+hipError_t enqueue_inflate_sizes(const BatchArgs &a, uint64_t *out_size, uint32_t *scratch, uint32_t *counter, uint32_t blocks, hipStream_t stream);
 hipError_t release_inflate_scratch();  // frees the cached token scratch of the current device (after a device sync)
 void release_inflate_scratch_of(hipStream_t stream);
 hipError_t release_deflate_scratch();  // the encoder's token scratch (dynamic levels), same rules

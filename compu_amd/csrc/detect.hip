@@ -13,7 +13,8 @@ __global__ void detect_kernel(uint32_t n, const uint8_t *in_base, const uint64_t
 
 // One lane per unit: route by Detection::detect.  Units that are neither gzip/zlib nor zstd are answered here, as the
 // decoders would: too short to tell -> NeedInput (detect() == None), anything else -> CHIP_UNKNOWN_FORMAT.
-__global__ void route_kernel(BatchArgs a, uint32_t *sel_inflate, uint32_t *sel_zstd, uint32_t *counts)
+// (out_size: the size pass's 64-bit length array, which then stands for a.out_len; nullptr for a decode batch)
+__device__ __forceinline__ void route_unit(const BatchArgs &a, uint64_t *out_size, uint32_t *sel_inflate, uint32_t *sel_zstd, uint32_t *counts)
 {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= a.n) return;
@@ -23,10 +24,19 @@ __global__ void route_kernel(BatchArgs a, uint32_t *sel_inflate, uint32_t *sel_z
     } else if (kind == CHIP_DETECT_ZSTD) {
         sel_zstd[atomicAdd(&counts[1], 1u)] = i;
     } else {
-        a.out_len[i] = 0;
+        if (out_size) out_size[i] = 0;
+        else a.out_len[i] = 0;
         a.in_used[i] = 0;
         a.status[i] = kind == CHIP_DETECT_NONE ? CHIP_NEED_INPUT : CHIP_UNKNOWN_FORMAT;
     }
+}
+__global__ void route_kernel(BatchArgs a, uint32_t *sel_inflate, uint32_t *sel_zstd, uint32_t *counts)
+{
+    route_unit(a, nullptr, sel_inflate, sel_zstd, counts);
+}
+__global__ void route_sizes_kernel(BatchArgs a, uint64_t *out_size, uint32_t *sel_inflate, uint32_t *sel_zstd, uint32_t *counts)
+{
+    route_unit(a, out_size, sel_inflate, sel_zstd, counts);
 }
 
 hipError_t launch_route(const BatchArgs &a, uint32_t *sel_inflate, uint32_t *sel_zstd, uint32_t *counts, hipStream_t stream)
@@ -36,6 +46,16 @@ hipError_t launch_route(const BatchArgs &a, uint32_t *sel_inflate, uint32_t *sel
     if (e != hipSuccess) return e;
     uint32_t blocks = (a.n + 255u) / 256u;
     hipLaunchKernelGGL(route_kernel, dim3(blocks), dim3(256), 0, stream, a, sel_inflate, sel_zstd, counts);
+    return hipGetLastError();
+}
+
+hipError_t launch_route_sizes(const BatchArgs &a, uint64_t *out_size, uint32_t *sel_inflate, uint32_t *sel_zstd, uint32_t *counts, hipStream_t stream)
+{
+    if (a.n == 0) return hipSuccess;
+    hipError_t e = hipMemsetAsync(counts, 0, 8, stream);
+    if (e != hipSuccess) return e;
+    uint32_t blocks = (a.n + 255u) / 256u;
+    hipLaunchKernelGGL(route_sizes_kernel, dim3(blocks), dim3(256), 0, stream, a, out_size, sel_inflate, sel_zstd, counts);
     return hipGetLastError();
 }
 

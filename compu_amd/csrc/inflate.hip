@@ -156,6 +156,7 @@ constexpr uint32_t HDR_IN_DW = 192;    // input window of the block-header parse
 // store instruction of the walk fills whole lines (lane l, row token k = 4q + j -> word rowbase(l) + 32 q + j with
 // rowbase(l) = (l / 8) * 8 * ROW_TOKENS + (l % 8) * 4).
 constexpr size_t ROWS_WORDS = (size_t)64 * ROW_TOKENS;
+static_assert(64ull * ROW_TOKENS * 258 < (1ull << 32), "count_tokens() sums a super-round's output lengths in 32 bits");
 __device__ __forceinline__ uint32_t row_base(uint32_t l) { return (l >> 3) * (8u * ROW_TOKENS) + (l & 7u) * 4u; }
 __device__ __forceinline__ uint32_t row_word(uint32_t k) { return k + (k >> 2) * 28u; }  // 32 * (k / 4) + k % 4
 
@@ -1245,12 +1246,73 @@ __device__ CHIP_PHASE_FN uint32_t walk_round(WaveLds &L, const InWin &w, const u
     return (uint32_t)__popcll(nonempty);
 }
 
+// ---- the size pass: what the true stream of a super-round adds to the unit's decoded length ----------------------
+// Stands where flush_tokens() stands in the decoder and needs the tokens' lengths only: no LZ77 execution, no window, no output.
+// The path resolve left the stream's pieces in stream order in L.fl.pk; lane k owns piece k, whose tokens are neighbours in one
+// scratch row, so the lane reads them four at a time (the 16-byte groups the walk stored) and sums literal ? 1 : length.  One wave
+// prefix sum gives every piece its start position.  Only while the unit's length is below 32 768 can a distance reach in front of
+// the first byte (a distance is at most 32 768): until then a second sweep over the same tokens, now with a running position,
+// makes the decoder's "invalid distance too far back" check; the first offending token in stream order decides, and the length
+// counted in front of it is what the decoder would have written.  `osize` is wave-uniform.  Returns false on that error.
+__device__ CHIP_PHASE_FN bool count_tokens(WaveLds &L, const uint32_t *grow_, uint32_t ntok_, uint32_t npieces_, uint64_t &osize, int32_t &status)
+{
+    const uint32_t lane = lane_id();
+    GAS const uint32_t *const grow = rdfirst_gptr(grow_);
+    const uint32_t ntok = rdfirst(ntok_), npieces = rdfirst(npieces_);
+    if (ntok == 0) return true;
+    const bool have = lane < npieces;
+    const uint32_t pfirst = have ? L.fl.pk[2u * lane] : ntok;
+    const uint32_t pdelta = have ? L.fl.pk[2u * lane + 1u] : 0u;
+    const uint32_t pnext = lane + 1u < npieces ? L.fl.pk[2u * lane + 2u] : ntok;  // the piece ends where the next one starts
+    const uint32_t k0 = (pfirst + pdelta) & 0xffffu;                               // the piece's first token in its row
+    const uint32_t kend = k0 + (have ? pnext - pfirst : 0u);
+    GAS const uint32_t *const row = grow + (pdelta >> 16);
+    uint32_t sum = 0;
+    for (uint32_t kq = k0 & ~3u; __any(kq < kend); kq += 4u) {
+        if (kq < kend) {
+            const u32x4 t = *(GAS const u32x4 *)(row + 8u * kq);  // kq is a multiple of 4: row_word(kq)
+            const uint32_t t4[4] = {t.x, t.y, t.z, t.w};
+#pragma unroll
+            for (uint32_t j = 0; j < 4; j++)
+                if (kq + j >= k0 && kq + j < kend) sum += (t4[j] & 512u) ? t4[j] & 0x1ffu : 1u;
+        }
+    }
+    const uint32_t incl = wave_incl_scan(sum);  // (a round's tokens give less than 64 * 256 * 258 bytes)
+    const uint32_t olo = rdfirst((uint32_t)osize), ohi = rdfirst((uint32_t)(osize >> 32));
+    if (ohi == 0 && olo < 32768u) {
+        uint32_t at = olo + incl - sum, badat = 0xffffffffu;
+        for (uint32_t kq = k0 & ~3u; __any(kq < kend); kq += 4u) {
+            if (kq < kend) {
+                const u32x4 t = *(GAS const u32x4 *)(row + 8u * kq);
+                const uint32_t t4[4] = {t.x, t.y, t.z, t.w};
+#pragma unroll
+                for (uint32_t j = 0; j < 4; j++)
+                    if (kq + j >= k0 && kq + j < kend) {
+                        const bool ismatch = (t4[j] & 512u) != 0;
+                        if (ismatch && __builtin_amdgcn_ubfe(t4[j], 10, 16) + 1u > at && badat == 0xffffffffu) badat = at;
+                        at += ismatch ? t4[j] & 0x1ffu : 1u;
+                    }
+            }
+        }
+        const uint64_t badm = __ballot(badat != 0xffffffffu);
+        if (badm) {
+            osize = rdlane(badat, (uint32_t)__ffsll((long long)badm) - 1u);
+            status = Z_DATA_ERROR;
+            return false;
+        }
+    }
+    osize = (((uint64_t)ohi << 32) | olo) + rdlane(incl, 63u);
+    return true;
+}
+
 // ---- a block's tokens: super-rounds of walk, path resolve, execution ------------------------------------
 // Decode the tokens of one deflate block from bit `pos` on (tables are in LDS), executing them into gout.  On return `pos` is
 // behind the end-of-block code (status stays ST_RUNNING) or status holds the reason decoding stopped.
+// SIZES (the size pass): the tokens are counted into `osize` instead; gout, opos and cap are not used.
+template <bool SIZES>
 __device__ CHIP_PHASE_FN void decode_block(WaveLds &L, InWin &w, uint32_t &pos, const uint32_t end_bit, uint8_t *gout, uint32_t &opos,
                                            const uint32_t cap, int32_t &status, uint32_t *rows, const uint32_t xt_bits, const uint32_t eob_len,
-                                           const uint32_t flags STAT_PARAM)
+                                           const uint32_t flags, uint64_t &osize STAT_PARAM)
 {
     pos = rdfirst(pos);
     opos = rdfirst(opos);
@@ -1268,14 +1330,18 @@ __device__ CHIP_PHASE_FN void decode_block(WaveLds &L, InWin &w, uint32_t &pos, 
 #ifdef CHIP_EXP_NO_FLUSH  // ablation (no output): the walk alone -- header, tables, walk, path resolve, token rows
         asm volatile("" ::"s"(npk), "s"(ntok));
 #else
-        if (npk) flushed = flush_tokens(L, rows, ntok, npk, gout, opos, cap, st2, ovf STAT_ARG);
+        if constexpr (SIZES) {
+            if (npk) flushed = count_tokens(L, rows, ntok, npk, osize, st2);
+        } else {
+            if (npk) flushed = flush_tokens(L, rows, ntok, npk, gout, opos, cap, st2, ovf STAT_ARG);
+        }
 #endif
         w.win0 = 0xffffffffu;  // the phases used the header window's place
         STAT_ACC(20);
         if (!flushed) {
             status = st2;
             // CHIP_F_COMPU_STATUS: zlib's position when the output filled (else the position stays at the round's start)
-            if ((flags & F_COMPU_STATUS) && st2 == CHIP_NEED_OUTPUT) pos = overflow_bit(L, w, rows, ntok, npk, ovf[0], ovf[1], ovf[2], pos);
+            if (!SIZES && (flags & F_COMPU_STATUS) && st2 == CHIP_NEED_OUTPUT) pos = overflow_bit(L, w, rows, ntok, npk, ovf[0], ovf[1], ovf[2], pos);
             return;
         }
         if (why == R_NEED_INPUT) {
@@ -1298,14 +1364,23 @@ __device__ CHIP_PHASE_FN void decode_block(WaveLds &L, InWin &w, uint32_t &pos, 
 #define CHIP_WAVES_PER_SIMD 5  // (18 waves per CU: two SIMDs hold five; 96 lane registers)
 #endif
 // one unit, start to finish, by the calling wave; scratch = the wave's token rows in HBM
-__device__ __attribute__((always_inline)) void inflate_unit(const BatchArgs &a, const uint32_t u, WaveLds &L, uint32_t *scratch)
+// SIZES (the size pass, chip_decode_batch_sizes): the same unit loop, wrapper, block headers, table builds and walk, but nothing is
+// written: the decoded length is counted in 64 bits and goes to out_size[u]; the unit's output description is never read.
+template <bool SIZES>
+__device__ __attribute__((always_inline)) void inflate_unit(const BatchArgs &a, const uint32_t u, WaveLds &L, uint32_t *scratch, uint64_t *out_size)
 {
     const uint32_t lane = lane_id();
 
     const uint8_t *gin = a.in_base + a.in_off[u];
     const uint32_t in_len = a.in_len[u];
-    uint8_t *gout = a.out_base + a.out_off[u];
-    const uint32_t cap = a.out_cap[u];
+    uint8_t *gout = nullptr;
+    uint32_t cap_ = 0xffffffffu;
+    if constexpr (!SIZES) {
+        gout = a.out_base + a.out_off[u];
+        cap_ = a.out_cap[u];
+    }
+    const uint32_t cap = cap_;
+    uint64_t osize = 0;  // SIZES: the decoded length so far
 
     InWin w;
     const uint32_t mis = (uint32_t)((uintptr_t)gin & 3u);
@@ -1329,7 +1404,7 @@ __device__ __attribute__((always_inline)) void inflate_unit(const BatchArgs &a, 
     uint32_t ck_bit = 0, ck_opos = 0;  // last block boundary reached (streaming decoder: where the next call resumes)
     bool resumed = false;
     uint32_t run_check = 0, run_cov = 0, out_dropped = 0;  // running trailer check: value, stream bytes covered; bytes dropped in front
-    if (a.resume) {
+    if (!SIZES && a.resume) {
         const uint32_t *rs = a.resume + RESUME_WORDS * u;
         const uint32_t r0 = rs[0], r1 = rs[1], r2 = rs[2];
         if (r0 != 0 && r0 <= in_len * 8u && r1 <= cap) {
@@ -1387,11 +1462,15 @@ __device__ __attribute__((always_inline)) void inflate_unit(const BatchArgs &a, 
             }
             pos += 32;
             uint32_t avail = (end_bit - pos) >> 3;
-            uint32_t room = cap - opos;
             uint32_t ncopy = blen < avail ? blen : avail;
-            if (ncopy > room) ncopy = room;
-            wave_copy_stored(gout + opos, w.g32, w.total_dw, pos >> 3, ncopy);
-            opos += ncopy;
+            if constexpr (SIZES) {
+                osize += ncopy;  // LEN bytes are skipped
+            } else {
+                uint32_t room = cap - opos;
+                if (ncopy > room) ncopy = room;
+                wave_copy_stored(gout + opos, w.g32, w.total_dw, pos >> 3, ncopy);
+                opos += ncopy;
+            }
             pos += ncopy * 8u;
             if (ncopy < blen) {
                 // zlib reports Z_OK here; compu calls it NeedInput when no input is left (mod.rs:476-479)
@@ -1533,13 +1612,32 @@ __device__ __attribute__((always_inline)) void inflate_unit(const BatchArgs &a, 
         }
         STAT_ACC(0);
         __builtin_amdgcn_s_setprio(0);
-        decode_block(L, w, pos, end_bit, gout, opos, cap, status, scratch, tables == 1 ? XT_BITS_FIXED : XT_BITS, eob_len, a.flags STAT_ARG);
+        decode_block<SIZES>(L, w, pos, end_bit, gout, opos, cap, status, scratch, tables == 1 ? XT_BITS_FIXED : XT_BITS, eob_len, a.flags, osize STAT_ARG);
         __builtin_amdgcn_s_setprio(2);  // block headers and table builds are short dependent chains: ahead of the other waves' bulk work
         STAT_T0();
     }
     __builtin_amdgcn_s_setprio(0);
     STAT_ACC(0);
-    if (status == CHIP_FINISHED && wrap) {
+    if (SIZES && status == CHIP_FINISHED && wrap) {
+        // trailer, without the check that needs the decoded bytes (Adler-32 / CRC-32): its presence, and gzip's ISIZE against
+        // the counted length.  The decoder's order is 4 bytes present, CRC, 8 bytes present, ISIZE; without the CRC step the two
+        // presence checks are one, so a gzip unit with a wrong CRC AND a cut or wrong ISIZE reads CHIP_NEED_INPUT / length error
+        // here where the decoder reports the data check first (rule 2's exemption)
+        uint32_t k = (pos - start_bit + 7u) >> 3;
+        if (wrap == 1) {
+            if (in_len - k < 4) status = CHIP_NEED_INPUT;
+            k += 4;
+        } else {
+            if (in_len - k < 8) status = CHIP_NEED_INPUT;
+            else {
+                uint32_t isize = gin[k + 4] | ((uint32_t)gin[k + 5] << 8) | ((uint32_t)gin[k + 6] << 16) | ((uint32_t)gin[k + 7] << 24);
+                if (rdfirst(isize) != (uint32_t)osize) status = Z_DATA_ERROR;  // incorrect length check
+            }
+            k += 8;
+        }
+        pos = start_bit + k * 8u;
+    }
+    if (!SIZES && status == CHIP_FINISHED && wrap) {
         // trailer: gzip CRC-32 + ISIZE (little endian), zlib Adler-32 (big endian)
         uint32_t k = (pos - start_bit + 7u) >> 3;
         uint32_t need = wrap == 2 ? 8u : 4u;
@@ -1570,7 +1668,7 @@ __device__ __attribute__((always_inline)) void inflate_unit(const BatchArgs &a, 
     if (a.stats && lane == 0)
         for (int k = 0; k < 24; k++) a.stats[(size_t)u * 24 + k] = st_[k];
 #endif
-    if (a.resume) {
+    if (!SIZES && a.resume) {
         // the stream goes on in a later call: bring the running check up to the boundary it will resume from (the bytes in
         // front of it are final; the caller may drop them once it has handed them on)
         const bool cont = status == CHIP_NEED_INPUT || status == CHIP_NEED_OUTPUT;
@@ -1592,19 +1690,21 @@ __device__ __attribute__((always_inline)) void inflate_unit(const BatchArgs &a, 
     }
     uint32_t used = (pos - start_bit + 7u) >> 3;
     if (used > in_len) used = in_len;
-    if (a.flags & F_COMPU_STATUS) {
+    if (!SIZES && (a.flags & F_COMPU_STATUS)) {
         // compu's reading of zlib's return code, src/decoder/mod.rs:475-483: Z_OK with avail_in == 0 is NeedInput whatever
         // else ran out, and a call that could not move (no input at all: Z_BUF_ERROR) is NeedOutput
         if (status == CHIP_NEED_OUTPUT && used == in_len) status = CHIP_NEED_INPUT;
         else if (status == CHIP_NEED_INPUT && in_len == 0) status = CHIP_NEED_OUTPUT;
     }
     if (lane == 0) {
-        a.out_len[u] = opos;
+        if constexpr (SIZES) out_size[u] = osize;
+        else a.out_len[u] = opos;
         a.in_used[u] = status == CHIP_NEED_INPUT ? in_len : used;
         a.status[u] = status;
     }
 }
 
+#ifndef CHIP_INFLATE_SIZES_TU
 // Persistent grid: each wave takes the next unit from *next_unit until the batch is exhausted.
 __global__ __launch_bounds__(64, CHIP_WAVES_PER_SIMD) void inflate_kernel(BatchArgs a, uint32_t *scratch, uint32_t *next_unit)
 {
@@ -1617,10 +1717,38 @@ __global__ __launch_bounds__(64, CHIP_WAVES_PER_SIMD) void inflate_kernel(BatchA
         i = rdfirst(i);
         if (i >= limit) break;
         const uint32_t u = a.sel ? rdfirst(a.sel[i]) : i;
-        inflate_unit(a, u, L, grow);
+        inflate_unit<false>(a, u, L, grow, nullptr);
         WSYNC();  // the next unit reuses the LDS
     }
 }
+#else
+// The size pass (chip_decode_batch_sizes): the same persistent grid over the same scratch slot, no output.  It is compiled in a
+// translation unit of its own (inflate_sizes.hip includes this file): a second kernel next to inflate_kernel changes the
+// compiler's inlining of the functions both call, and with it inflate_kernel's registers.
+__global__ __launch_bounds__(64, CHIP_WAVES_PER_SIMD) void inflate_sizes_kernel(BatchArgs a, uint64_t *out_size, uint32_t *scratch, uint32_t *next_unit)
+{
+    __shared__ WaveLds L;
+    uint32_t *grow = scratch + (size_t)blockIdx.x * SCRATCH_WORDS;
+    const uint32_t limit = a.sel_n ? *a.sel_n : a.n;
+    for (;;) {
+        uint32_t i = 0;
+        if (lane_id() == 0) i = atomicAdd(next_unit, 1u);
+        i = rdfirst(i);
+        if (i >= limit) break;
+        const uint32_t u = a.sel ? rdfirst(a.sel[i]) : i;
+        inflate_unit<true>(a, u, L, grow, out_size);
+        WSYNC();  // the next unit reuses the LDS
+    }
+}
+
+hipError_t enqueue_inflate_sizes(const BatchArgs &a, uint64_t *out_size, uint32_t *scratch, uint32_t *counter, uint32_t blocks, hipStream_t stream)
+{
+    hipLaunchKernelGGL(inflate_sizes_kernel, dim3(blocks), dim3(64), 0, stream, a, out_size, scratch, counter);
+    return hipGetLastError();
+}
+#endif  // CHIP_INFLATE_SIZES_TU
+
+#ifndef CHIP_INFLATE_SIZES_TU
 
 namespace {
 // Token scratch and the unit counter of a launch, cached per (device, stream): launches on one stream
@@ -1776,6 +1904,50 @@ hipError_t launch_inflate(const BatchArgs &a, hipStream_t stream)
     return launch_inflate_locked(a, stream);
 }
 
+// The size pass shares the decoder's slot of (device, stream): launches on a stream run in order, so the token scratch serves both
+// (the sizes kernel needs no more LDS or registers than inflate_kernel: the slot's resident-wave count holds for it too).
+namespace {
+hipError_t launch_inflate_sizes_locked(const BatchArgs &a, uint64_t *out_size, hipStream_t stream);
+}
+hipError_t launch_inflate_sizes(const BatchArgs &a, uint64_t *out_size, hipStream_t stream)
+{
+    if (a.n == 0) return hipSuccess;
+    std::lock_guard<std::mutex> lk(g_slot_mu);
+    return launch_inflate_sizes_locked(a, out_size, stream);
+}
+
+// The routed size pass: launch_routed()'s critical section with the size kernels behind the router.
+hipError_t launch_routed_sizes(const BatchArgs &a, uint64_t *out_size, hipStream_t stream)
+{
+    if (a.n == 0) return hipSuccess;
+    std::lock_guard<std::mutex> lk(g_slot_mu);
+    uint32_t *sel_i = nullptr, *sel_z = nullptr, *counts = nullptr;
+    hipError_t e = route_scratch_locked(stream, a.n, &sel_i, &sel_z, &counts);
+    if (e == hipSuccess) e = launch_route_sizes(a, out_size, sel_i, sel_z, counts, stream);
+    BatchArgs ai = a, az = a;
+    ai.format = CHIP_FMT_AUTO;
+    ai.sel = sel_i;
+    ai.sel_n = counts;
+    az.format = CHIP_FMT_ZSTD;
+    az.sel = sel_z;
+    az.sel_n = counts + 1;
+    if (e == hipSuccess) e = launch_inflate_sizes_locked(ai, out_size, stream);
+    if (e == hipSuccess) e = launch_zstd_sizes(az, out_size, 0, stream);
+    return e;
+}
+
+namespace {
+hipError_t launch_inflate_sizes_locked(const BatchArgs &a, uint64_t *out_size, hipStream_t stream)
+{
+    LaunchSlot sl;
+    hipError_t e = slot_for(stream, a.n, sl);
+    if (e != hipSuccess) return e;
+    const uint32_t blocks = a.n < (uint32_t)sl.blocks ? a.n : (uint32_t)sl.blocks;
+    if ((e = hipMemsetAsync(sl.counter, 0, 4, stream)) != hipSuccess) return e;
+    return enqueue_inflate_sizes(a, out_size, sl.scratch, sl.counter, blocks, stream);
+}
+}  // namespace
+
 namespace {
 hipError_t launch_inflate_locked(const BatchArgs &a, hipStream_t stream)
 {
@@ -1794,5 +1966,7 @@ hipError_t launch_inflate_locked(const BatchArgs &a, hipStream_t stream)
     return hipGetLastError();
 }
 }  // namespace
+
+#endif  // CHIP_INFLATE_SIZES_TU
 
 }  // namespace chip

@@ -973,16 +973,30 @@ __device__ void wave_match_copy(uint8_t *dst, uint32_t offset, uint32_t n)
 #ifndef CHIP_ZSTD_WAVES
 #define CHIP_ZSTD_WAVES 3  // waves per SIMD the register budget is set for (157 VGPRs); at 4 the LDS (11.2 KB) would allow 14 waves per CU, but 34 registers spill: 5.15 against 4.98 ms
 #endif
+// The kernel's body is compiled twice, with SIZES as a compile-time constant: as zstd_kernel here, and as zstd_sizes_kernel (the size
+// pass, chip_decode_batch_sizes) in the translation unit zstd_sizes.hip, which includes this file -- a second kernel in this translation
+// unit would change the compiler's inlining of the functions both call, and zstd_kernel must come out of the build as it was.
+// SIZES: frame and block headers, literals section header (a Huffman tree description is read, so that a treeless block knows whether it
+// has a table; the streams are skipped by their stated size), sequence header, table descriptions and builds, the FSE state chain, the
+// offsets with the repeat history, and every placement check run as they do in the decoder; nothing is regenerated, copied or hashed.
+// The position is 64-bit: `dropped` counts the completed blocks' bytes and opos the current block's.
+#ifndef CHIP_ZSTD_SIZES_TU
+#define CHIP_ZSTD_SIZES 0
 __global__ __launch_bounds__(64, CHIP_ZSTD_WAVES) void zstd_kernel(BatchArgs a, int wlog_max)
+#else
+#define CHIP_ZSTD_SIZES 1
+__global__ __launch_bounds__(64, CHIP_ZSTD_WAVES) void zstd_sizes_kernel(BatchArgs a, int wlog_max, uint64_t *out_size)
+#endif
 {
+    constexpr bool SIZES = CHIP_ZSTD_SIZES != 0;
     __shared__ ZLds L;
     if (blockIdx.x >= (a.sel_n ? *a.sel_n : a.n)) return;
     const uint32_t u = a.sel ? a.sel[blockIdx.x] : blockIdx.x;
     const uint32_t lane = lane_id();
     const uint8_t *gin = a.in_base + a.in_off[u];
     const uint32_t in_len = a.in_len[u];
-    uint8_t *gout = a.out_base + a.out_off[u];
-    const uint32_t cap = a.out_cap[u];
+    uint8_t *gout = SIZES ? nullptr : a.out_base + a.out_off[u];
+    const uint32_t cap = SIZES ? 0xffffffffu : a.out_cap[u];
 #ifdef CHIP_STATS
     unsigned long long zst_[24] = {};
     unsigned long long *const zst = zst_;
@@ -1014,11 +1028,11 @@ __global__ __launch_bounds__(64, CHIP_ZSTD_WAVES) void zstd_kernel(BatchArgs a, 
 #define ZFAIL(code) do { status = -(code); goto done; } while (0)
 #define ZNEED_INPUT() do { status = CHIP_NEED_INPUT; goto done; } while (0)
 
-    uint32_t *const rs = a.resume;  // streaming decoder: checkpoint blob of this (single) unit, else nullptr
+    uint32_t *const rs = SIZES ? nullptr : a.resume;  // streaming decoder: checkpoint blob of this (single) unit, else nullptr
     bool resumed = false, blocks_done = false;
     // output bytes of this frame that the host has dropped in front of gout (streaming only): positions compared with the
     // frame's content size or output limit count them, offsets can only reach what is still there
-    const uint64_t dropped = rs ? (uint64_t)rs[12] | ((uint64_t)rs[13] << 32) : 0ull;
+    uint64_t dropped = rs ? (uint64_t)rs[12] | ((uint64_t)rs[13] << 32) : 0ull;  // (SIZES: the bytes of the blocks in front of this one)
     if (rs && rs[0] != 0 && rs[0] - 1u <= in_len && rs[1] <= cap) {
         resumed = true;
         ip = B0 + rs[0] - 1u;
@@ -1145,7 +1159,7 @@ __global__ __launch_bounds__(64, CHIP_ZSTD_WAVES) void zstd_kernel(BatchArgs a, 
                 status = CHIP_NEED_OUTPUT;
                 goto done;
             }
-            wave_copy_bytes(gout + opos, (const uint8_t *)b.g32 + ip, k);
+            if (!SIZES) wave_copy_bytes(gout + opos, (const uint8_t *)b.g32 + ip, k);
             opos += k;
             ip += k;
             if (k < bsz) ZNEED_INPUT();
@@ -1156,8 +1170,10 @@ __global__ __launch_bounds__(64, CHIP_ZSTD_WAVES) void zstd_kernel(BatchArgs a, 
                 status = CHIP_NEED_OUTPUT;
                 goto done;
             }
-            const uint8_t v = (uint8_t)byte_at(b, ip + 3);
-            for (uint32_t j = lane; j < bsz; j += 64) gout[opos + j] = v;
+            if (!SIZES) {
+                const uint8_t v = (uint8_t)byte_at(b, ip + 3);
+                for (uint32_t j = lane; j < bsz; j += 64) gout[opos + j] = v;
+            }
             opos += bsz;
             ip += 4;
         } else {
@@ -1250,7 +1266,9 @@ __global__ __launch_bounds__(64, CHIP_ZSTD_WAVES) void zstd_kernel(BatchArgs a, 
                     st0 = lp + 6;
                 }
                 bool sbad = false;
-                if (streams == 4) {
+                if (SIZES) {
+                    // the streams' contents are not looked at: they are skipped by their stated size
+                } else if (streams == 4) {
                     // 16 lanes per stream (see huf_decode4)
                     const uint32_t g = lane >> 4;
                     uint32_t myoff = st0, myout = lit_out;
@@ -1708,7 +1726,7 @@ __global__ __launch_bounds__(64, CHIP_ZSTD_WAVES) void zstd_kernel(BatchArgs a, 
                         if (dropped + ostart + tot > out_limit || (uint64_t)(ostart - block_out0) + tot > BLOCK_MAX) fail = 1;
                         else if (lit_incl > regen - lpos) fail = 2;
                         else if ((uint64_t)ostart + tot > cap) fail = 3;
-                        else if (off > mstart || off > window) fail = 4;  // beyond the frame's start, or beyond its window: the verdict must not
+                        else if ((SIZES ? (uint64_t)off > dropped + mstart : off > mstart) || off > window) fail = 4;  // beyond the frame's start, or beyond its window: the verdict must not
                                                                           // depend on how much history a streaming caller has let go (api.hip, dec_compact)
                     }
                     const uint64_t failm = __ballot(fail != 0);
@@ -1728,7 +1746,7 @@ __global__ __launch_bounds__(64, CHIP_ZSTD_WAVES) void zstd_kernel(BatchArgs a, 
                     // ---- phase A: all literal bytes of the chunk (their sources never depend on this chunk) ----
                     ZT_BEGIN(zt5);
 #ifndef CHIP_EXP_NOEXEC
-                    if (LB) {
+                    if (!SIZES && LB) {
                         LSYNC();
                         L.xpar[2 * lane] = ostart;
                         L.xpar[2 * lane + 1] = lit_before;
@@ -1776,7 +1794,7 @@ __global__ __launch_bounds__(64, CHIP_ZSTD_WAVES) void zstd_kernel(BatchArgs a, 
                     ZT_END(5, zt5);
                     // ---- phase B: matches, several per step as long as none reads what the step writes ----------
                     ZT_BEGIN(zt6);
-                    {
+                    if (!SIZES) {
                         const uint32_t mbi = wave_incl_scan(ml), mbx = mbi - ml;
                         const uint32_t srcend = mstart - off + (ml < off ? ml : off);
                         uint64_t mm = __ballot(ml != 0);
@@ -1874,10 +1892,14 @@ __global__ __launch_bounds__(64, CHIP_ZSTD_WAVES) void zstd_kernel(BatchArgs a, 
                 status = CHIP_NEED_OUTPUT;
                 goto done;
             }
-            copy_literals(restl);
+            if (!SIZES) copy_literals(restl);
             opos += restl;
             ip = bend;
             rewind_to = ~0u;
+        }
+        if (SIZES) {  // the block is counted: the 32-bit cursor starts over
+            dropped += opos;
+            opos = 0;
         }
         if (last) {
             if (has_fcs && dropped + opos != fcs) ZFAIL(ZSTD_E_CORRUPTION);
@@ -1890,7 +1912,8 @@ __global__ __launch_bounds__(64, CHIP_ZSTD_WAVES) void zstd_kernel(BatchArgs a, 
         uint32_t want = rd32_at(b, ip * 8u);
 #ifndef CHIP_EXP_NOXXH
         uint32_t got;
-        if (rs) {  // streaming: the state carried from block to block, then the bytes behind its last stripe
+        if (SIZES) got = want;  // (the checksum's presence is checked, its value needs the bytes)
+        else if (rs) {  // streaming: the state carried from block to block, then the bytes behind its last stripe
             uint64_t acc;
             uint32_t rel;
             hash_upto_opos((uint64_t *)L.huf, 128, acc, rel);
@@ -1909,7 +1932,7 @@ done:
     // libzstd decodes a block whole before it hands any of it on: the sequences of a failing block already placed are not output
     // (the oracle drops them too; a streaming caller would otherwise be handed them in front of the error)
     if (status < 0 && rewind_to != ~0u) opos = rewind_to;
-    if ((a.flags & F_COMPU_STATUS) && status != CHIP_FINISHED) {
+    if (!SIZES && (a.flags & F_COMPU_STATUS) && status != CHIP_FINISHED) {
         // compu looks at the output first (src/decoder/zstd.rs:121-133): output.pos == output.size is NeedOutput whatever
         // ZSTD_decompressStream returned.  An error return leaves output.pos as compu set it, 0 -- libzstd decodes a block only once the one
         // in front has been flushed whole, and returns from inside its loop -- so an error stays an error (also behind blocks that fill
@@ -1923,7 +1946,11 @@ done:
     }
     if (rs && lane == 0 && status != CHIP_NEED_INPUT && status != CHIP_NEED_OUTPUT) rs[0] = 0;  // nothing to continue
     if (lane == 0) {
+#if CHIP_ZSTD_SIZES
+        out_size[u] = dropped + opos;
+#else
         a.out_len[u] = opos;
+#endif
         a.in_used[u] = status == CHIP_NEED_INPUT ? in_len : ip - B0;
         a.status[u] = status;
 #ifdef CHIP_STATS
@@ -1939,11 +1966,20 @@ done:
 
 }  // namespace
 
+#ifndef CHIP_ZSTD_SIZES_TU
 hipError_t launch_zstd_decode(const BatchArgs &a, int window_log_max, hipStream_t stream)
 {
     if (a.n == 0) return hipSuccess;
     hipLaunchKernelGGL(zstd_kernel, dim3(a.n), dim3(64), 0, stream, a, window_log_max ? window_log_max : 27);
     return hipGetLastError();
 }
+#else
+hipError_t launch_zstd_sizes(const BatchArgs &a, uint64_t *out_size, int window_log_max, hipStream_t stream)
+{
+    if (a.n == 0) return hipSuccess;
+    hipLaunchKernelGGL(zstd_sizes_kernel, dim3(a.n), dim3(64), 0, stream, a, window_log_max ? window_log_max : 27, out_size);
+    return hipGetLastError();
+}
+#endif
 
 }  // namespace chip

@@ -498,6 +498,13 @@ public:
         if (rc == CHIP_OK) cursor_ += span;
         return rc;
     }
+    // chip_decode_batch_sizes over a batch held in `in`: the decoded length (64-bit), input consumed and status of every unit
+    // (device arrays), without an output buffer -- what a caller needs to give decode_batch() an out_cap[i].  Only enqueues.
+    static int decode_batch_sizes(int format, size_t n, const DeviceBuffer &in, const uint64_t *in_off, const uint32_t *in_len, uint64_t *out_size,
+                                  uint32_t *in_used, int32_t *status, void *stream = nullptr)
+    {
+        return chip_decode_batch_sizes(format, 0, n, in.data(), in_off, in_len, out_size, in_used, status, stream);
+    }
 
 private:
     uint8_t *buf_;

@@ -197,6 +197,46 @@ int chip_decode_batch_ex(int format, uint32_t flags, size_t n, const void *in_ba
                          uint32_t *in_used, int32_t *status, void *stream);
 
 /*
+ * The size pass: the decoded length of every unit, without decoding it.  chip_decode_batch wants an out_cap[i] and an output
+ * range per unit, and the formats do not say how much a unit decodes to (raw deflate and zlib carry no length, gzip's ISIZE is
+ * modulo 2^32 and sits behind the data).  This call takes the same input description (DEVICE pointers, in_base 4-byte aligned
+ * and padded as for chip_decode_batch, enqueue-only on `stream`), no output buffer at all, and answers per unit
+ *   out_size[i]  decoded length in bytes, 64-bit: a unit may decode to more than an out_cap can express
+ *   in_used[i]   bytes of input consumed, as chip_decode_batch
+ *   status[i]    as chip_decode_batch; never CHIP_NEED_OUTPUT
+ * `flags` must be 0 (anything else: CHIP_E_INVALID); it is there so that options need no third entry point.
+ * `format`: CHIP_FMT_DEFLATE, CHIP_FMT_ZLIB, CHIP_FMT_GZIP, CHIP_FMT_AUTO, CHIP_FMT_ZSTD (window_log_max: the default, as
+ * chip_decode_batch), and CHIP_FMT_DETECT, routed exactly as a CHIP_FMT_DETECT decode batch is (units that are neither get
+ * CHIP_UNKNOWN_FORMAT / CHIP_NEED_INPUT).  CHIP_FMT_BROTLI is CHIP_E_INVALID: brotli's literal context is the two previous
+ * BYTES, so a brotli size pass is a full decode (it would decode into a ring) -- a different design.  Arguments are checked
+ * before the device is looked for (as chip_decode_batch_ex does).
+ * The contract:
+ *  1. Exact on valid streams.  If chip_decode_batch with enough room answers CHIP_FINISHED for a unit, so does the size pass,
+ *     with out_size[i] = that decode's out_len[i] and in_used[i] = its in_used[i].
+ *  2. The same verdict wherever the verdict does not need decoded bytes.  Every check the decoder makes is made -- wrapper header
+ *     fields, code-length verdicts in zlib's order, invalid codes, "invalid distance too far back" (positions in front of the
+ *     unit's first byte included), stored LEN / NLEN, CHIP_NEED_DICT, truncation (CHIP_NEED_INPUT), gzip's ISIZE against the
+ *     counted length -- except the Adler-32 / CRC-32 comparison (a gzip unit whose CRC is wrong AND whose ISIZE is cut or wrong
+ *     therefore reads CHIP_NEED_INPUT / a length error here, where the decoder meets the CRC first).  zstd: frame and block
+ *     headers, literals and sequence section headers, Huffman tree and FSE table descriptions, the sequence bitstream, offsets
+ *     against window and position, Frame_Content_Size against the counted length, window_log_max -- except the CONTENTS of
+ *     Huffman-coded literal streams (skipped by their stated size; a stream of stated size 0 or with a zero last byte is
+ *     content too, and not seen) and the XXH64 comparison.  A frame with Frame_Content_Size
+ *     is still walked: the header is not trusted.  On an error or CHIP_NEED_INPUT out_size[i] is the length
+ *     counted in front of it (as out_len is) and in_used[i] is what chip_decode_batch (flags 0) reports with ample room.
+ *  3. Enough room.  Decoding a unit with out_cap[i] = out_size[i] never answers CHIP_NEED_OUTPUT when the size pass said
+ *     CHIP_FINISHED, damaged payload or not.
+ *  4. A unit whose only fault is one the size pass cannot see (a wrong check value, a damaged Huffman literal stream) is CHIP_FINISHED here and an error
+ *     in the decode that follows: the price of not producing the bytes.
+ * No per-unit device memory: the pass uses the inflate kernel's token scratch of (device, stream) -- one slot per resident wave,
+ * shared with chip_decode_batch on that stream, released by chip_trim() -- and, routed, that slot's index lists; zstd needs none.
+ * No reference counterpart: compu's decode_vec grows a Vec as it goes (src/decoder/mod.rs:323-335); this replaces the
+ * guess / CHIP_NEED_OUTPUT / decode-again loop a batch caller would write around it.
+ */
+int chip_decode_batch_sizes(int format, uint32_t flags, size_t n, const void *in_base, const uint64_t *in_off,
+                            const uint32_t *in_len, uint64_t *out_size, uint32_t *in_used, int32_t *status, void *stream);
+
+/*
  * The same for data that starts and ends in HOST memory (SURVEY.md sec. 8b "pinned-host variant", 8e): every
  * pointer is a host pointer (hipHostMalloc / chip_pinned_alloc memory lets the copies run asynchronously; pageable
  * memory works but serialises them).  The units are cut into slices (about `slice_bytes` of input + output each,

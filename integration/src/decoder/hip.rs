@@ -289,6 +289,26 @@ pub unsafe fn decode_batch_device(format: BatchFormat, compu_status: bool, n: us
     if rc == sys::CHIP_OK { Ok(()) } else { Err(rc) }
 }
 
+///The size pass (`chip_decode_batch_sizes`): the decoded length of every unit of a device-resident batch without decoding it --
+///`out_size[i]` (u64), `in_used[i]`, `status[i]` -- so that `decode_batch_device` can be given an `out_cap[i]` that is enough.
+///No counterpart in this crate: it replaces the grow-and-retry loop a batch caller would write around `decode_vec`
+///(`src/decoder/mod.rs:323-335`).  Every `BatchFormat` but `Brotli` (`Err(-101)`).
+///
+///# Safety
+///
+///As `decode_batch_device`.
+pub unsafe fn decode_batch_sizes_device(format: BatchFormat, n: usize, input: &crate::buffer::DeviceBuffer, in_off: &crate::buffer::DeviceBuffer,
+                                        in_len: &crate::buffer::DeviceBuffer, out_size: &mut crate::buffer::DeviceBuffer,
+                                        in_used: &mut crate::buffer::DeviceBuffer, status: &mut crate::buffer::DeviceBuffer,
+                                        stream: *mut core::ffi::c_void) -> Result<(), i32> {
+    if in_off.capacity() < 8 * n || in_len.capacity() < 4 * n || out_size.capacity() < 8 * n || in_used.capacity() < 4 * n || status.capacity() < 4 * n {
+        return Err(-101);
+    }
+    let rc = sys::chip_decode_batch_sizes(format.tag(), 0, n, input.as_ptr() as *const _, in_off.as_ptr() as *const u64, in_len.as_ptr() as *const u32,
+                                          out_size.as_mut_ptr() as *mut u64, in_used.as_mut_ptr() as *mut u32, status.as_mut_ptr() as *mut i32, stream);
+    if rc == sys::CHIP_OK { Ok(()) } else { Err(rc) }
+}
+
 ///`Detection::detect` for every unit of a device-resident batch (`kind[i]` gets the backend's CHIP_DETECT_* value).
 ///
 ///# Safety

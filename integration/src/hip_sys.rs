@@ -104,6 +104,9 @@ extern "C" {
     ///`src/decoder/zstd.rs:121-133`) where the default names the cause
     pub fn chip_decode_batch_ex(format: c_int, flags: u32, n: usize, in_base: *const c_void, in_off: *const u64, in_len: *const u32, out_base: *mut c_void,
                                 out_off: *const u64, out_cap: *const u32, out_len: *mut u32, in_used: *mut u32, status: *mut i32, stream: *mut c_void) -> c_int;
+    ///the size pass: decoded length (64-bit), input consumed and status of every unit, no output buffer; `flags` must be 0
+    pub fn chip_decode_batch_sizes(format: c_int, flags: u32, n: usize, in_base: *const c_void, in_off: *const u64, in_len: *const u32, out_size: *mut u64,
+                                   in_used: *mut u32, status: *mut i32, stream: *mut c_void) -> c_int;
     pub fn chip_decode_batch_host(format: c_int, n: usize, in_base: *const c_void, in_off: *const u64, in_len: *const u32, out_base: *mut c_void,
                                   out_off: *const u64, out_cap: *const u32, out_len: *mut u32, in_used: *mut u32, status: *mut i32, device: c_int,
                                   slice_bytes: usize) -> c_int;
