@@ -183,7 +183,7 @@ constexpr uint32_t IMG_WORDS = CHUNK_BYTES / 4 + 8;  // + room for the 16-byte r
 constexpr uint32_t TOK_RING = 4;   // token groups on their way from the scratch rows into LDS (LDS-DMA: no registers held)
 static_assert(CHUNK_BYTES % 4 == 0 && CHUNK_BYTES >= 1024 && COPY_LANE_MAX % 16 == 0 && IMG_WORDS % 2 == 0, "geometry");
 
-constexpr uint32_t FLUSH_BYTES = 4 * (IMG_WORDS + 2 * MQ_CAP + 64 * TOK_RING + 128);
+constexpr uint32_t FLUSH_BYTES = 4 * (IMG_WORDS + 2 * MQ_CAP + 64 * TOK_RING + 128 + 4);
 constexpr uint32_t HDR_BYTES = 4 * HDR_IN_DW + 4 * (1 << CL_ROOT) + 80 + sizeof(HuffMeta) + 64 + 320 + 2 * 288 + 2 * 32 + 2 * sizeof(HuffMeta);
 constexpr uint32_t PHASE_BYTES = 8 * WIN_DW > FLUSH_BYTES ? (8 * WIN_DW > HDR_BYTES ? 8 * WIN_DW : HDR_BYTES) : (FLUSH_BYTES > HDR_BYTES ? FLUSH_BYTES : HDR_BYTES);
 #ifndef CHIP_LDS_BYTES
@@ -214,6 +214,7 @@ struct alignas(16) WaveLds {
             uint2 mq[MQ_CAP];                // queued match: .x offset of its first output byte, .y length | distance << 16
             uint32_t tok[64 * TOK_RING];     // token groups, written by global_load_lds_dword
             uint32_t pk[128];                // k-th piece of a batch: [2k] its first stream index, [2k+1] [15:0] (row token - stream index) mod 2^16, [31:16] row base
+            uint32_t trash[4];               // where the stores of lanes that have nothing to store go (never read)
         } fl;
         uint32_t phase_words_[PHASE_BYTES / 4];
     };
@@ -660,6 +661,7 @@ struct ChunkLds {
     uint32_t *out;  // [IMG_WORDS] the chunk's output bytes by offset (offset 0 = the dword-aligned address below the chunk)
     uint2 *mq;      // [MQ_CAP] queued match: .x offset of its first output byte, .y length | distance << 16
     uint32_t *tok;  // [64 * TOK_RING] token groups, written by global_load_lds_dword
+    lds_u8 *trash;  // 16 bytes nobody reads: a lane with nothing to store stores there (a select, not a branch around the store)
 };
 
 __device__ __forceinline__ ChunkLds chunk_lds(WaveLds &L)
@@ -668,24 +670,24 @@ __device__ __forceinline__ ChunkLds chunk_lds(WaveLds &L)
     c.out = L.fl.out;
     c.mq = L.fl.mq;
     c.tok = L.fl.tok;
+    c.trash = (lds_u8 *)L.fl.trash;
     return c;
 }
 
-// exactly n (1..16) bytes of v to the LDS address d
-__device__ __forceinline__ void lds_put(lds_u8 *d, const U128u &v, uint32_t n)
+// exactly n (0..16) bytes of v to the LDS address d.  No branches: a store that n does not reach goes to `trash` (16 bytes that
+// nobody reads) through a select of its address -- a compare and a select per store where an exec-mask region costs five or six
+// instructions, most of them scalar, whether or not a lane is left in it.
+__device__ __forceinline__ void lds_put(lds_u8 *d, lds_u8 *trash, const U128u &v, uint32_t n)
 {
-    if (n >= 4) ((LDS_AS U32u *)d)->v = v.x;
-    if (n >= 8) ((LDS_AS U32u *)(d + 4))->v = v.y;
-    if (n >= 12) ((LDS_AS U32u *)(d + 8))->v = v.z;
-    if (n >= 16) ((LDS_AS U32u *)(d + 12))->v = v.w;
-    uint32_t w = n < 4 ? v.x : n < 8 ? v.y : n < 12 ? v.z : v.w;
-    lds_u8 *t = d + (n & 12u);
-    if (n < 16 && (n & 2u)) {
-        ((LDS_AS U16u *)t)->v = (uint16_t)w;
-        w >>= 16;
-        t += 2;
-    }
-    if (n < 16 && (n & 1u)) *t = (uint8_t)w;
+    ((LDS_AS U32u *)(n >= 4 ? d : trash))->v = v.x;
+    ((LDS_AS U32u *)((n >= 8 ? d : trash) + 4))->v = v.y;
+    ((LDS_AS U32u *)((n >= 12 ? d : trash) + 8))->v = v.z;
+    ((LDS_AS U32u *)((n >= 16 ? d : trash) + 12))->v = v.w;
+    const uint32_t w = n < 4 ? v.x : n < 8 ? v.y : n < 12 ? v.z : v.w;  // (n = 16: nothing below reads it)
+    lds_u8 *const t = d + (n & 12u);
+    const bool two = (n & 2u) != 0, one = (n & 1u) != 0;
+    ((LDS_AS U16u *)(two ? t : trash))->v = (uint16_t)w;
+    *(one ? (two ? t + 2 : t) : trash) = (uint8_t)(two ? w >> 16 : w);
 }
 
 // One queued match, copied by the whole wave (any distance, any length, source anywhere below it).
@@ -777,11 +779,9 @@ __device__ __forceinline__ void round_finish(const Round &r, const ChunkLds &C, 
                 v.z = ((const LDS_AS U32u *)(sp + 8))->v;
                 v.w = ((const LDS_AS U32u *)(sp + 12))->v;
             }
-            if (rem) {
-                const uint32_t n = rem < 16u ? rem : 16u;
-                lds_put(img + r.x + 16u * it, v, n);
-                rem -= n;
-            }
+            const uint32_t n = rem < 16u ? rem : 16u;  // (0 in a lane that is not copying: its stores go to the trash)
+            lds_put(img + r.x + 16u * it, C.trash, v, n);
+            rem -= n;
         }
         LSYNC();
         pend &= ~rm;
@@ -868,39 +868,36 @@ __device__ CHIP_PHASE_FN bool flush_tokens(WaveLds &L, const uint32_t *grow_, ui
     // piece `lane`: first stream index, and what to add to a stream index to get the token's word in the scratch rows
     const uint32_t pfirst = lane < npieces ? L.fl.pk[2u * lane] : 0xffffffffu;
     const uint32_t pdelta = lane < npieces ? L.fl.pk[2u * lane + 1u] : 0u;
-    // Token g + lane of the stream (lanes behind the end re-read the last token: no branch around the load).  The piece a
-    // token lies in = pieces that start at or before it, minus one: `before` pieces start in front of the group (kept
-    // up to date by the caller), those inside it are found through a 64-bit mask of their start positions, put together
-    // with scalar instructions; a DPP-free count of the mask bits below each lane and one cross-lane read finish it.
-    uint32_t before = 0;  // pieces that start before stream index gnext
-    uint32_t gnext = 0;   // stream index the next fetch() asks for
-    uint32_t slot_w = 0;  // ring slot the next fetch() fills
+    // Token g + lane of the stream (lanes behind the end re-read the last token: no branch around the load).  The pieces are in
+    // stream order, so a scalar cursor walks them: `before` pieces start in front of the group, `nfirst` is where the next one
+    // starts and `dcur` is the delta of the piece the group begins in.  A group that lies inside one piece (most do: a piece
+    // is a lane's whole run of tokens) takes `dcur` as it stands; every piece that starts inside the group costs two lane
+    // reads and one select.  No mask of piece starts, no bit count, no cross-lane gather.
+    uint32_t before = 0;       // pieces that start before stream index gnext
+    uint32_t nfirst = 0;       // first stream index of piece `before` (0xffffffff: there is none; piece 0 starts at 0)
+    uint32_t dcur = 0;         // pdelta of piece before - 1
+    uint32_t gnext = 0;        // stream index the next fetch() asks for
+    uint32_t slot_w = 0;       // ring slot the next fetch() fills
     const uint32_t tok_lds = rdfirst((uint32_t)(uintptr_t)(LDS_AS uint32_t *)C.tok);  // LDS byte address of the ring
     // The load goes straight into LDS (global_load_lds_dword: LDS address = M0 + 4 * lane): no register is held while it
     // is in flight, and the compiler does not wait for it -- issue() and the explicit vmcnt wait in front of a slot's
     // first read keep the count: a slot's load is complete once at most TOK_RING - 1 younger loads are outstanding.
     auto fetch = [&]() {
         const uint32_t g = gnext;
-        const uint32_t rel = pfirst - g;
-        uint64_t bm = __ballot(rel < 64u), m = 0;
-        const uint32_t inside = (uint32_t)__popcll(bm);
-        while (bm) {
-            const uint32_t k = (uint32_t)__ffsll((long long)bm) - 1u;
-            m |= 1ull << rdlane(rel, k);
-            bm &= bm - 1ull;
+        uint32_t d = dcur;
+        while (nfirst - g < 64u) {  // (nfirst >= g; "none" is far above any g)
+            dcur = rdlane(pdelta, before);
+            d = lane >= nfirst - g ? dcur : d;
+            before++;
+            const uint32_t nx = rdlane(pfirst, before & 63u);
+            nfirst = before < npieces ? nx : 0xffffffffu;
         }
-        // pieces starting at or before lane t of the group: before + bits 0..t of m = before + (m & 1) + bits below t of m >> 1
-        const uint32_t base = before + (uint32_t)(m & 1ull) - 1u;
-        const uint64_t m1 = m >> 1;
-        const uint32_t k = __builtin_amdgcn_mbcnt_hi((uint32_t)(m1 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m1, base));
-        const uint32_t d = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(k << 2), (int)pdelta);
         const uint32_t t = min(g + lane, ntok - 1u);  // (lanes behind the batch's end read its last token again)
-        before += inside;
         gnext = g + 64u;
         const uint32_t krow = (t + d) & 0xffffu;  // the token's index in its lane's row
         const uint32_t *src = grow + ((d >> 16) + row_word(krow));
         const uint32_t dst = tok_lds + 256u * slot_w;
-        uint32_t keep;
+        uint32_t keep;  // (M0 is a reserved register: it cannot be named as clobbered, so it is put back)
         asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
                      : "=&s"(keep)
                      : "v"(src), "s"(dst)
@@ -949,13 +946,15 @@ __device__ CHIP_PHASE_FN bool flush_tokens(WaveLds &L, const uint32_t *grow_, ui
         bool ending, too_far = false;
         // The common group: 64 tokens that all fit the chunk, no distance reaching in front of the output's first byte.
         // (a distance cannot reach in front of the output once 32 KiB of it exist)
-        if (left >= 64u && run + total <= CHUNK_BYTES && (prod0 >= 32768u || !__any(len != 0 && val > prod0 + start))) {
+        // (the distance test is one compare in every lane, masked by the match lanes: a literal's `val` is below 256.  It is
+        // skipped by the chunk's first output position, not by prod0: prod0 = opos - mis wraps below zero for a unit whose first
+        // byte is not dword aligned, and the sum prod0 + start is right all the same)
+        if (left >= 64u && run + total <= CHUNK_BYTES && (opos >= 32768u || (__ballot(val > prod0 + start) & lenm) == 0)) {
             asm volatile("; the common group" ::: "memory");  // (keeps the compiler from folding this path into the general one below)
-            if (len == 0) img[start] = (uint8_t)val;
-            else {
-                const uint32_t qi = __builtin_amdgcn_mbcnt_hi((uint32_t)(lenm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)lenm, nq)) & (MQ_CAP - 1u);
-                C.mq[qi] = make_uint2(start, len | (val << 16));
-            }
+            // every lane makes both stores, one of them to the trash: two selects instead of two exec-mask regions
+            const uint32_t qi = __builtin_amdgcn_mbcnt_hi((uint32_t)(lenm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)lenm, nq)) & (MQ_CAP - 1u);
+            *(len == 0 ? img + start : C.trash) = (uint8_t)val;
+            *(len != 0 ? &C.mq[qi] : (uint2 *)(uint8_t *)C.trash) = make_uint2(start, len | (val << 16));
             nq += (uint32_t)__popcll(lenm);
             c0 += 64u;
             run += total;
@@ -1015,7 +1014,12 @@ __device__ CHIP_PHASE_FN bool flush_tokens(WaveLds &L, const uint32_t *grow_, ui
             slot_r = (slot_r + 1u) & (TOK_RING - 1u);
         } else if (nacc != 0 && c0 < ntok) {  // a partly taken group: the stream moves by less than a group, the ring starts over
             gnext = c0;
-            before = (uint32_t)__popcll(__ballot(pfirst < c0));
+            before = (uint32_t)__popcll(__ballot(pfirst < c0));  // (at least one: piece 0 starts at 0 and c0 is not 0 here)
+            dcur = rdlane(pdelta, before - 1u);
+            {
+                const uint32_t nx = rdlane(pfirst, before & 63u);
+                nfirst = before < npieces ? nx : 0xffffffffu;
+            }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // no load of the old ring is left to land on the new one
             slot_r = slot_w = 0;
 #pragma unroll
