@@ -59,6 +59,30 @@ struct Meta {
     uint32_t resume[RESUME_WORDS];  // inflate streaming: see BatchArgs::resume
 };
 
+// The arguments of a batch launch over n units of device memory; callers set resume, flags and sel where they use them.
+BatchArgs batch_args(int format, size_t n, const void *in_base, const uint64_t *in_off, const uint32_t *in_len, void *out_base,
+                     const uint64_t *out_off, const uint32_t *out_cap, uint32_t *out_len, uint32_t *in_used, int32_t *status)
+{
+    BatchArgs a;
+    a.in_base = (const uint8_t *)in_base;
+    a.in_off = in_off;
+    a.in_len = in_len;
+    a.out_base = (uint8_t *)out_base;
+    a.out_off = out_off;
+    a.out_cap = out_cap;
+    a.out_len = out_len;
+    a.in_used = in_used;
+    a.status = status;
+    a.n = (uint32_t)n;
+    a.format = format;
+    a.stats = nullptr;
+    a.resume = nullptr;
+#ifdef CHIP_STATS
+    a.stats = getenv("CHIP_STATS_PTR") ? (unsigned long long *)strtoull(getenv("CHIP_STATS_PTR"), nullptr, 0) : nullptr;
+#endif
+    return a;
+}
+
 void pipes_trim();  // defined with the host-batch pipelines below
 
 }  // namespace
@@ -117,11 +141,7 @@ int chip_stream_sync(void *stream) { return hipStreamSynchronize((hipStream_t)st
 int chip_trim(void)
 {
     pipes_trim();  // cached host-batch pipelines of the current device (streams, staging and device buffers)
-    bool ok = chip::release_inflate_scratch() == hipSuccess;
-    ok = chip::release_zstd_enc_scratch() == hipSuccess && ok;
-    ok = chip::release_brotli_enc_scratch() == hipSuccess && ok;
-    ok = chip::release_brotli_scratch() == hipSuccess && ok;
-    return chip::release_deflate_scratch() == hipSuccess && ok ? CHIP_OK : CHIP_E_LAUNCH;
+    return chip::release_scratch() == hipSuccess ? CHIP_OK : CHIP_E_LAUNCH;  // the launch slots of every codec
 }
 
 // ---- batched decode ------------------------------------------------------------------------
@@ -143,26 +163,8 @@ int chip_decode_batch_ex(int format, uint32_t flags, size_t n, const void *in_ba
         !status || ((uintptr_t)in_base & 3u))
         return CHIP_E_INVALID;
     if (!device_ok()) return CHIP_E_NO_DEVICE;
-    BatchArgs a;
-    a.in_base = (const uint8_t *)in_base;
-    a.in_off = in_off;
-    a.in_len = in_len;
-    a.out_base = (uint8_t *)out_base;
-    a.out_off = out_off;
-    a.out_cap = out_cap;
-    a.out_len = out_len;
-    a.in_used = in_used;
-    a.status = status;
-    a.n = (uint32_t)n;
-    a.format = format;
-    a.stats = nullptr;
-    a.resume = nullptr;
-    a.sel = nullptr;
-    a.sel_n = nullptr;
+    BatchArgs a = batch_args(format, n, in_base, in_off, in_len, out_base, out_off, out_cap, out_len, in_used, status);
     a.flags = flags;
-#ifdef CHIP_STATS
-    a.stats = (unsigned long long *)getenv("CHIP_STATS_PTR") ? (unsigned long long *)strtoull(getenv("CHIP_STATS_PTR"), nullptr, 0) : nullptr;
-#endif
     hipError_t e;
     switch (format) {
     case CHIP_FMT_DEFLATE:
@@ -199,26 +201,7 @@ int chip_decode_batch_sizes(int format, uint32_t flags, size_t n, const void *in
     if (n > 0x7fffffffull || !in_base || !in_off || !in_len || !out_size || !in_used || !status || ((uintptr_t)in_base & 3u))
         return CHIP_E_INVALID;
     if (!device_ok()) return CHIP_E_NO_DEVICE;
-    BatchArgs a;
-    a.in_base = (const uint8_t *)in_base;
-    a.in_off = in_off;
-    a.in_len = in_len;
-    a.out_base = nullptr;
-    a.out_off = nullptr;
-    a.out_cap = nullptr;
-    a.out_len = nullptr;
-    a.in_used = in_used;
-    a.status = status;
-    a.n = (uint32_t)n;
-    a.format = format;
-    a.stats = nullptr;
-    a.resume = nullptr;
-    a.sel = nullptr;
-    a.sel_n = nullptr;
-    a.flags = 0;
-#ifdef CHIP_STATS
-    a.stats = getenv("CHIP_STATS_PTR") ? (unsigned long long *)strtoull(getenv("CHIP_STATS_PTR"), nullptr, 0) : nullptr;
-#endif
+    const BatchArgs a = batch_args(format, n, in_base, in_off, in_len, nullptr, nullptr, nullptr, nullptr, in_used, status);
     hipError_t e;
     if (format == CHIP_FMT_ZSTD) e = launch_zstd_sizes(a, out_size, 0, (hipStream_t)stream);
     else if (format == CHIP_FMT_DETECT) e = launch_routed_sizes(a, out_size, (hipStream_t)stream);  // routed as launch_routed routes a decode batch
@@ -303,8 +286,7 @@ void pipe_destroy(Pipe *p)  // the caller has made p->device current
 {
     if (p->stream) {
         (void)hipStreamSynchronize(p->stream);
-        chip::release_inflate_scratch_of(p->stream);
-        chip::release_deflate_scratch_of(p->stream);
+        chip::release_scratch_of(p->stream);
         (void)hipStreamDestroy(p->stream);
     }
     chip_device_free(p->d_in);
@@ -335,19 +317,32 @@ void pipes_trim()
     for (Pipe *p : mine) pipe_destroy(p);
 }
 
-bool grow_dev(uint8_t *&ptr, size_t &cap, size_t need)
+bool grow_buf(uint8_t *&ptr, size_t &cap, size_t need, bool pinned)
 {
     if (need <= cap) return true;
-    chip_device_free(ptr);
+    if (pinned) chip_pinned_free(ptr);
+    else chip_device_free(ptr);
     cap = need + (need >> 2) + 4096;
-    return (ptr = (uint8_t *)chip_device_alloc(cap)) != nullptr || (cap = 0, false);
+    ptr = (uint8_t *)(pinned ? chip_pinned_alloc(cap) : chip_device_alloc(cap));
+    if (!ptr) cap = 0;
+    return ptr != nullptr;
 }
-bool grow_pinned(uint8_t *&ptr, size_t &cap, size_t need)
+bool grow_dev(uint8_t *&ptr, size_t &cap, size_t need) { return grow_buf(ptr, cap, need, false); }
+bool grow_pinned(uint8_t *&ptr, size_t &cap, size_t need) { return grow_buf(ptr, cap, need, true); }
+
+// A pinned buffer that keeps its first `len` bytes when it grows (doubling, from 64 KiB): the streaming objects' input and output.
+bool reserve_pinned(uint8_t **buf, size_t *cap, size_t len, size_t need)
 {
-    if (need <= cap) return true;
-    chip_pinned_free(ptr);
-    cap = need + (need >> 2) + 4096;
-    return (ptr = (uint8_t *)chip_pinned_alloc(cap)) != nullptr || (cap = 0, false);
+    if (need <= *cap) return true;
+    size_t c = *cap ? *cap : 65536;
+    while (c < need) c *= 2;
+    uint8_t *p = (uint8_t *)chip_pinned_alloc(c);
+    if (!p) return false;
+    if (len) memcpy(p, *buf, len);
+    chip_pinned_free(*buf);
+    *buf = p;
+    *cap = c;
+    return true;
 }
 
 struct HostBatch {
@@ -803,20 +798,6 @@ struct chip_decoder {
 
 namespace {
 
-bool dec_reserve_in(chip_decoder *d, size_t need)
-{
-    if (need <= d->h_in_cap) return true;
-    size_t cap = d->h_in_cap ? d->h_in_cap : 65536;
-    while (cap < need) cap *= 2;
-    uint8_t *p = (uint8_t *)chip_pinned_alloc(cap);
-    if (!p) return false;
-    if (d->h_in_len) memcpy(p, d->h_in, d->h_in_len);
-    chip_pinned_free(d->h_in);
-    d->h_in = p;
-    d->h_in_cap = cap;
-    return true;
-}
-
 // Limits of a streaming object: the kernels address a unit's input by 32-bit bit offsets and its output
 // by 32-bit byte offsets.  What is BUFFERED stays far below them (input in front of the last block boundary and output
 // that has been handed on are dropped), so only a single deflate block or zstd frame of that size can run into them.
@@ -872,20 +853,9 @@ bool dec_run(chip_decoder *d)
         for (uint32_t k = 0; k < RESUME_WORDS; k++) m.resume[k] = d->resume[k];
         *d->h_meta = m;
         if (hipMemcpyAsync(d->d_meta, d->h_meta, sizeof(Meta), hipMemcpyHostToDevice, d->stream) != hipSuccess) return false;
-        BatchArgs a;
-        a.in_base = d->d_in;
-        a.in_off = &d->d_meta->in_off;
-        a.in_len = &d->d_meta->in_len;
-        a.out_base = d->d_out;
-        a.out_off = &d->d_meta->out_off;
-        a.out_cap = &d->d_meta->out_cap;
-        a.out_len = &d->d_meta->out_len;
-        a.in_used = &d->d_meta->in_used;
-        a.status = &d->d_meta->status;
-        a.n = 1;
-        a.format = d->format;
-        a.stats = nullptr;
-        a.resume = inflate ? d->d_meta->resume : d->d_zres;
+        Meta *dm = d->d_meta;
+        BatchArgs a = batch_args(d->format, 1, d->d_in, &dm->in_off, &dm->in_len, d->d_out, &dm->out_off, &dm->out_cap, &dm->out_len, &dm->in_used, &dm->status);
+        a.resume = inflate ? dm->resume : d->d_zres;
         hipError_t e = inflate  ? launch_inflate(a, d->stream)
                        : brotli ? launch_brotli_decode(a, d->stream)
                                 : launch_zstd_decode(a, d->window_log_max, d->stream);
@@ -940,18 +910,21 @@ bool dec_compact(chip_decoder *d)
 {
     if (!d->decoded) return true;
     if (d->k_status != CHIP_NEED_INPUT && d->k_status != CHIP_NEED_OUTPUT) return true;
-    if (d->format == CHIP_FMT_BROTLI) {
-        // the metablock checkpoint (chip_internal.h, BRES_WORDS): input in front of the boundary's byte, output in front of the
-        // window of the boundary that has been handed on
+    if (d->format == CHIP_FMT_BROTLI || d->format == CHIP_FMT_ZSTD) {
+        // the checkpoint header (zstd.hip; brotli's metablock checkpoint: chip_internal.h, BRES_WORDS): input in front of the
+        // boundary's byte, output in front of the window of the boundary that has been handed on.  zh[0] is 1 + the boundary's
+        // offset in the input, in bits for brotli and in bytes for zstd.
+        const bool brotli = d->format == CHIP_FMT_BROTLI;
+        const uint32_t in_unit = brotli ? 8u : 1u;
         uint32_t *zh = d->h_zhdr;
-        if (zh[0] == 0) return true;  // no metablock reached yet
+        if (zh[0] == 0) return true;  // no metablock / block done yet
         bool dirty = false;
-        const size_t drop_in = (((size_t)zh[0] - 1u) >> 3) & ~(size_t)3;
+        const size_t drop_in = (((size_t)zh[0] - 1u) / in_unit) & ~(size_t)3;  // the boundary's byte, dword aligned down
         if (drop_in >= DEC_DROP_IN) {
             memmove(d->h_in, d->h_in + drop_in, d->h_in_len - drop_in);
             d->h_in_len -= drop_in;
             d->d_in_len = 0;  // the (short) rest is uploaded again
-            zh[0] -= 8u * (uint32_t)drop_in;
+            zh[0] -= in_unit * (uint32_t)drop_in;
             d->in_dropped += drop_in;
             d->k_in_used = d->k_in_used > drop_in ? d->k_in_used - (uint32_t)drop_in : 0;
             dirty = true;
@@ -961,43 +934,7 @@ bool dec_compact(chip_decoder *d)
         const size_t r1 = zh[1];
         size_t keep_from = r1 > window ? r1 - (size_t)window : 0;
         if (keep_from > d->delivered) keep_from = d->delivered;
-        keep_from &= ~(size_t)15;
-        if (keep_from >= DEC_DROP_OUT) {
-            if (!dec_move_down(d, keep_from, d->k_out_len - keep_from)) return false;
-            d->delivered -= keep_from;
-            d->k_out_len -= (uint32_t)keep_from;
-            zh[1] -= (uint32_t)keep_from;
-            const uint64_t nd = dropped + keep_from;
-            zh[12] = (uint32_t)nd;
-            zh[13] = (uint32_t)(nd >> 32);
-            dirty = true;
-        }
-        if (dirty) {
-            if (hipMemcpyAsync(d->d_zres, zh, ZRES_HDR * 4, hipMemcpyHostToDevice, d->stream) != hipSuccess) return false;
-            if (hipStreamSynchronize(d->stream) != hipSuccess) return false;
-        }
-        return true;
-    }
-    if (d->format == CHIP_FMT_ZSTD) {
-        uint32_t *zh = d->h_zhdr;
-        if (zh[0] == 0) return true;  // no block done yet
-        bool dirty = false;
-        const size_t drop_in = ((size_t)zh[0] - 1u) & ~(size_t)3;  // the boundary's byte, dword aligned down
-        if (drop_in >= DEC_DROP_IN) {
-            memmove(d->h_in, d->h_in + drop_in, d->h_in_len - drop_in);
-            d->h_in_len -= drop_in;
-            d->d_in_len = 0;  // the (short) rest is uploaded again
-            zh[0] -= (uint32_t)drop_in;
-            d->in_dropped += drop_in;
-            d->k_in_used = d->k_in_used > drop_in ? d->k_in_used - (uint32_t)drop_in : 0;
-            dirty = true;
-        }
-        const uint64_t window = (uint64_t)zh[8] | ((uint64_t)zh[9] << 32);
-        const uint64_t dropped = (uint64_t)zh[12] | ((uint64_t)zh[13] << 32);
-        const size_t r1 = zh[1];
-        size_t keep_from = r1 > window ? r1 - (size_t)window : 0;
-        if (keep_from > d->delivered) keep_from = d->delivered;
-        if (zh[5] & 1u) {  // content checksum: bytes the running hash has not taken yet stay
+        if (!brotli && (zh[5] & 1u)) {  // zstd's content checksum: bytes the running hash has not taken yet stay
             const uint64_t hashed = (uint64_t)zh[14] | ((uint64_t)zh[15] << 32);
             const size_t hrel = (size_t)(hashed - dropped);
             if (keep_from > hrel) keep_from = hrel;
@@ -1105,7 +1042,7 @@ chip_decoder *chip_decoder_new(int format, const chip_decoder_opts *opts)
     d->d_meta = (Meta *)chip_device_alloc(sizeof(Meta));
     d->h_meta = (Meta *)chip_pinned_alloc(sizeof(Meta) + ZRES_HDR * 4);
     d->h_zhdr = d->h_meta ? (uint32_t *)(d->h_meta + 1) : nullptr;
-    if (!d->d_meta || !d->h_meta || !dec_reserve_in(d, 65536)) {
+    if (!d->d_meta || !d->h_meta || !reserve_pinned(&d->h_in, &d->h_in_cap, 0, 65536)) {
         chip_decoder_free(d);
         return nullptr;
     }
@@ -1138,7 +1075,7 @@ chip_decode_result chip_decode(chip_decoder *d, const uint8_t *in, size_t in_len
     if (!stream_end_known && in_len) {
         if (!dec_compact(d)) return fail(-4);
         if (d->h_in_len + in_len > DEC_IN_LIMIT) return fail(-4);  // Z_MEM_ERROR: more buffered input than a unit can address
-        if (!dec_reserve_in(d, d->h_in_len + in_len)) return fail(-4);
+        if (!reserve_pinned(&d->h_in, &d->h_in_cap, d->h_in_len, d->h_in_len + in_len)) return fail(-4);
         memcpy(d->h_in + d->h_in_len, in, in_len);
         d->h_in_len += in_len;
         taken = in_len;
@@ -1271,8 +1208,7 @@ void chip_decoder_free(chip_decoder *d)
     if (!d) return;
     DeviceGuard guard(d->device);
     if (d->stream) {
-        chip::release_inflate_scratch_of(d->stream);  // the stream's token scratch goes with it
-        chip::release_brotli_scratch_of(d->stream);
+        chip::release_scratch_of(d->stream);  // the stream's launch slots go with it
         (void)hipStreamDestroy(d->stream);
     }
     chip_pinned_free(d->h_in);
@@ -1315,82 +1251,31 @@ int chip_encode_batch_ex(int format, int level, int strategy, size_t n, const vo
                          void *out_base, const uint64_t *out_off, const uint32_t *out_cap, uint32_t *out_len, int32_t *status,
                          void *stream)
 {
+    // arguments first, the device second: a refusal needs no GPU
     if (n == 0) return CHIP_OK;
-    if (format == CHIP_FMT_ZSTD) {
-        if (n > 0x7fffffffull || !in_base || !in_off || !in_len || !out_base || !out_off || !out_cap || !out_len || !status ||
-            level < -131072 || level > 131072 || strategy < CHIP_ZSTD_STRATEGY_DEFAULT || strategy > CHIP_ZSTD_STRATEGY_BTULTRA2)
-            return CHIP_E_INVALID;
-        if (!device_ok()) return CHIP_E_NO_DEVICE;
-        BatchArgs a;
-        a.in_base = (const uint8_t *)in_base;
-        a.in_off = in_off;
-        a.in_len = in_len;
-        a.out_base = (uint8_t *)out_base;
-        a.out_off = out_off;
-        a.out_cap = out_cap;
-        a.out_len = out_len;
-        a.in_used = nullptr;
-        a.status = status;
-        a.n = (uint32_t)n;
-        a.format = format;
-        a.stats = nullptr;
-        a.resume = nullptr;
-#ifdef CHIP_STATS
-        a.stats = getenv("CHIP_STATS_PTR") ? (unsigned long long *)strtoull(getenv("CHIP_STATS_PTR"), nullptr, 0) : nullptr;
-#endif
-        const uint32_t wl = zenc::MAX_DIST_LOG;  // the batch frames use zstd's default window_log (27)
-        hipError_t e = launch_zstd_encode(a, level, strategy, wl, wl, ZF_FIRST | ZF_LAST | ZF_ONESHOT, nullptr, (hipStream_t)stream);
-        return e == hipSuccess ? CHIP_OK : CHIP_E_LAUNCH;
+    if (!host_args_ok(n, in_base, in_off, in_len, out_base, out_off, out_cap, out_len, status)) return CHIP_E_INVALID;
+    switch (format) {
+    case CHIP_FMT_ZSTD:
+        if (level < -131072 || level > 131072 || strategy < CHIP_ZSTD_STRATEGY_DEFAULT || strategy > CHIP_ZSTD_STRATEGY_BTULTRA2) return CHIP_E_INVALID;
+        break;
+    case CHIP_FMT_BROTLI:  // level = quality 0..11 (0 = libbrotlienc's default 11), strategy = compu's mode byte 0..3 (recorded only)
+        if (level < 0 || level > 11 || strategy < 0 || strategy > 3) return CHIP_E_INVALID;
+        break;
+    case CHIP_FMT_DEFLATE:
+    case CHIP_FMT_ZLIB:
+    case CHIP_FMT_GZIP:
+        if (level == -1) level = 6;  // zlib's Z_DEFAULT_COMPRESSION
+        if (level < 0 || level > 9 || strategy < CHIP_STRATEGY_DEFAULT || strategy > CHIP_STRATEGY_FIXED) return CHIP_E_INVALID;
+        break;
+    default: return CHIP_E_INVALID;
     }
-    if (format == CHIP_FMT_BROTLI) {
-        // level = quality 0..11 (0 = libbrotlienc's default 11), strategy = compu's mode byte 0..3 (recorded only)
-        if (n > 0x7fffffffull || !in_base || !in_off || !in_len || !out_base || !out_off || !out_cap || !out_len || !status ||
-            level < 0 || level > 11 || strategy < 0 || strategy > 3)
-            return CHIP_E_INVALID;
-        if (!device_ok()) return CHIP_E_NO_DEVICE;
-        BatchArgs a;
-        a.in_base = (const uint8_t *)in_base;
-        a.in_off = in_off;
-        a.in_len = in_len;
-        a.out_base = (uint8_t *)out_base;
-        a.out_off = out_off;
-        a.out_cap = out_cap;
-        a.out_len = out_len;
-        a.in_used = nullptr;
-        a.status = status;
-        a.n = (uint32_t)n;
-        a.format = format;
-        a.stats = nullptr;
-        a.resume = nullptr;
-        hipError_t e = launch_brotli_encode(a, level, 22, ZF_FIRST | ZF_LAST, nullptr, (hipStream_t)stream);
-        return e == hipSuccess ? CHIP_OK : CHIP_E_LAUNCH;
-    }
-    if (level == -1) level = 6;  // zlib's Z_DEFAULT_COMPRESSION
-    if (n > 0x7fffffffull || !in_base || !in_off || !in_len || !out_base || !out_off || !out_cap || !out_len || !status ||
-        level < 0 || level > 9 || strategy < CHIP_STRATEGY_DEFAULT || strategy > CHIP_STRATEGY_FIXED ||
-        (format != CHIP_FMT_DEFLATE && format != CHIP_FMT_ZLIB && format != CHIP_FMT_GZIP))
-        return CHIP_E_INVALID;
     if (!device_ok()) return CHIP_E_NO_DEVICE;
-    BatchArgs a;
-    a.in_base = (const uint8_t *)in_base;
-    a.in_off = in_off;
-    a.in_len = in_len;
-    a.out_base = (uint8_t *)out_base;
-    a.out_off = out_off;
-    a.out_cap = out_cap;
-    a.out_len = out_len;
-    a.in_used = nullptr;
-    a.status = status;
-    a.n = (uint32_t)n;
-    a.format = format;
-    a.stats = nullptr;
-    a.resume = nullptr;
-    a.sel = nullptr;
-    a.sel_n = nullptr;
-#ifdef CHIP_STATS
-    a.stats = (unsigned long long *)getenv("CHIP_STATS_PTR") ? (unsigned long long *)strtoull(getenv("CHIP_STATS_PTR"), nullptr, 0) : nullptr;
-#endif
-    hipError_t e = launch_deflate_l1(a, level, 7u | ((uint32_t)strategy << 8), format == CHIP_FMT_ZLIB ? 1u : 0u, 0, nullptr, (hipStream_t)stream);
+    const BatchArgs a = batch_args(format, n, in_base, in_off, in_len, out_base, out_off, out_cap, out_len, nullptr, status);
+    const uint32_t wl = zenc::MAX_DIST_LOG;  // the batch frames use zstd's default window_log (27)
+    hipError_t e;
+    if (format == CHIP_FMT_ZSTD) e = launch_zstd_encode(a, level, strategy, wl, wl, ZF_FIRST | ZF_LAST | ZF_ONESHOT, nullptr, (hipStream_t)stream);
+    else if (format == CHIP_FMT_BROTLI) e = launch_brotli_encode(a, level, 22, ZF_FIRST | ZF_LAST, nullptr, (hipStream_t)stream);
+    else e = launch_deflate_l1(a, level, 7u | ((uint32_t)strategy << 8), format == CHIP_FMT_ZLIB ? 1u : 0u, 0, nullptr, (hipStream_t)stream);
     return e == hipSuccess ? CHIP_OK : CHIP_E_LAUNCH;
 }
 
@@ -1430,20 +1315,6 @@ struct chip_encoder {
 
 namespace {
 
-bool enc_reserve(uint8_t **buf, size_t *cap, size_t len, size_t need)
-{
-    if (need <= *cap) return true;
-    size_t c = *cap ? *cap : 65536;
-    while (c < need) c *= 2;
-    uint8_t *p = (uint8_t *)chip_pinned_alloc(c);
-    if (!p) return false;
-    if (len) memcpy(p, *buf, len);
-    chip_pinned_free(*buf);
-    *buf = p;
-    *cap = c;
-    return true;
-}
-
 void enc_clear(chip_encoder *e)
 {
     e->h_in_len = 0;
@@ -1477,22 +1348,8 @@ bool enc_segment(chip_encoder *e, bool final)
     chip_encoder::EMeta m = {0, 0, (uint32_t)n, (uint32_t)bound, 0, 0, 0, 0};
     *e->h_meta = m;
     if (hipMemcpyAsync(e->d_meta, e->h_meta, sizeof m, hipMemcpyHostToDevice, e->stream) != hipSuccess) return false;
-    BatchArgs a;
-    a.in_base = e->d_in;
-    a.in_off = &e->d_meta->in_off;
-    a.in_len = &e->d_meta->in_len;
-    a.out_base = e->d_out;
-    a.out_off = &e->d_meta->out_off;
-    a.out_cap = &e->d_meta->out_cap;
-    a.out_len = &e->d_meta->out_len;
-    a.in_used = nullptr;
-    a.status = &e->d_meta->status;
-    a.n = 1;
-    a.format = e->mode;
-    a.stats = nullptr;
-    a.resume = nullptr;
-    a.sel = nullptr;
-    a.sel_n = nullptr;
+    chip_encoder::EMeta *dm = e->d_meta;
+    const BatchArgs a = batch_args(e->mode, 1, e->d_in, &dm->in_off, &dm->in_len, e->d_out, &dm->out_off, &dm->out_cap, &dm->out_len, nullptr, &dm->status);
     if (zstd) {
         // a frame compressed in one call (Finish with the whole input buffered) is single-segment with Frame_Content_Size, as
         // libzstd's one-call ZSTD_e_end; otherwise the header declares a window: the segments are at most 1 MiB and no match
@@ -1512,7 +1369,7 @@ bool enc_segment(chip_encoder *e, bool final)
     if (hipStreamSynchronize(e->stream) != hipSuccess) return false;
     if (e->h_meta->status != CHIP_ENC_FINISHED) return false;
     const size_t got = e->h_meta->out_len;
-    if (!enc_reserve(&e->h_out, &e->h_out_cap, e->h_out_len, e->h_out_len + got)) return false;
+    if (!reserve_pinned(&e->h_out, &e->h_out_cap, e->h_out_len, e->h_out_len + got)) return false;
     if (got && (hipMemcpyAsync(e->h_out + e->h_out_len, e->d_out, got, hipMemcpyDeviceToHost, e->stream) != hipSuccess ||
                 hipStreamSynchronize(e->stream) != hipSuccess))
         return false;
@@ -1523,6 +1380,42 @@ bool enc_segment(chip_encoder *e, bool final)
     e->started = true;
     if (final) e->finished = true;
     return true;
+}
+
+// What the three public constructors share once the options are parsed and found valid.  state_bytes: the device block a
+// zstd or brotli encoder carries from one segment to the next (d_zs / d_bs), 0 for none.
+chip_encoder *encoder_new_common(int mode, int level, int strategy, int wlog, int device, size_t state_bytes)
+{
+    if (!device_ok()) return nullptr;  // no CPU codec behind this backend
+    if (device < 0 && hipGetDevice(&device) != hipSuccess) return nullptr;
+    DeviceGuard guard(device);
+    if (!guard.ok) return nullptr;
+    const Hooks hooks = current_hooks();
+    chip_encoder *e = (chip_encoder *)hooks.alloc(sizeof(chip_encoder));
+    if (!e) return nullptr;
+    memset(e, 0, sizeof *e);
+    e->hooks = hooks;
+    e->mode = mode;
+    e->level = level;
+    e->strategy = strategy;
+    e->wlog = wlog;
+    e->device = device;
+    if (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess) {
+        hooks.release(e);
+        return nullptr;
+    }
+    e->d_meta = (chip_encoder::EMeta *)chip_device_alloc(sizeof(chip_encoder::EMeta));
+    e->h_meta = (chip_encoder::EMeta *)chip_pinned_alloc(sizeof(chip_encoder::EMeta));
+    void *state = state_bytes ? chip_device_alloc(state_bytes) : nullptr;
+    if (mode == CHIP_FMT_ZSTD) e->d_zs = (ZEncStream *)state;
+    else e->d_bs = (BEncStream *)state;
+    if (!e->d_meta || !e->h_meta || (state_bytes && !state) || !reserve_pinned(&e->h_in, &e->h_in_cap, 0, 65536) ||
+        !reserve_pinned(&e->h_out, &e->h_out_cap, 0, 65536)) {
+        chip_encoder_free(e);
+        return nullptr;
+    }
+    enc_clear(e);
+    return e;
 }
 
 }  // namespace
@@ -1538,32 +1431,7 @@ chip_encoder *chip_encoder_new(const chip_encoder_opts *opts)
     if ((mode != CHIP_FMT_DEFLATE && mode != CHIP_FMT_ZLIB && mode != CHIP_FMT_GZIP) || level < 0 || level > 9) return nullptr;
     // what deflateInit2_ refuses (Z_STREAM_ERROR -> None, src/encoder/zlib_ng.rs:81-86): memLevel outside 1..9, unknown strategy
     if (strategy < CHIP_STRATEGY_DEFAULT || strategy > CHIP_STRATEGY_FIXED || mem_level < 0 || mem_level > 9) return nullptr;
-    if (!device_ok()) return nullptr;  // no CPU codec behind this backend
-    int device = opts ? opts->device : -1;
-    if (device < 0 && hipGetDevice(&device) != hipSuccess) return nullptr;
-    DeviceGuard guard(device);
-    if (!guard.ok) return nullptr;
-    const Hooks hooks = current_hooks();
-    chip_encoder *e = (chip_encoder *)hooks.alloc(sizeof(chip_encoder));
-    if (!e) return nullptr;
-    memset(e, 0, sizeof *e);
-    e->hooks = hooks;
-    e->mode = mode;
-    e->level = level;
-    e->strategy = strategy;
-    e->device = device;
-    if (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess) {
-        hooks.release(e);
-        return nullptr;
-    }
-    e->d_meta = (chip_encoder::EMeta *)chip_device_alloc(sizeof(chip_encoder::EMeta));
-    e->h_meta = (chip_encoder::EMeta *)chip_pinned_alloc(sizeof(chip_encoder::EMeta));
-    if (!e->d_meta || !e->h_meta || !enc_reserve(&e->h_in, &e->h_in_cap, 0, 65536) || !enc_reserve(&e->h_out, &e->h_out_cap, 0, 65536)) {
-        chip_encoder_free(e);
-        return nullptr;
-    }
-    enc_clear(e);
-    return e;
+    return encoder_new_common(mode, level, strategy, 0, opts ? opts->device : -1, 0);
 }
 
 chip_encoder *chip_encoder_new_zstd(const chip_zstd_encoder_opts *opts)
@@ -1577,35 +1445,7 @@ chip_encoder *chip_encoder_new_zstd(const chip_zstd_encoder_opts *opts)
         return nullptr;
     if (level == 0) level = 3;
     if (level > 22) level = 22;
-    if (!device_ok()) return nullptr;
-    int device = opts ? opts->device : -1;
-    if (device < 0 && hipGetDevice(&device) != hipSuccess) return nullptr;
-    DeviceGuard guard(device);
-    if (!guard.ok) return nullptr;
-    const Hooks hooks = current_hooks();
-    chip_encoder *e = (chip_encoder *)hooks.alloc(sizeof(chip_encoder));
-    if (!e) return nullptr;
-    memset(e, 0, sizeof *e);
-    e->hooks = hooks;
-    e->mode = CHIP_FMT_ZSTD;
-    e->level = level;
-    e->strategy = strategy;
-    e->wlog = wlog;
-    e->device = device;
-    if (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess) {
-        hooks.release(e);
-        return nullptr;
-    }
-    e->d_meta = (chip_encoder::EMeta *)chip_device_alloc(sizeof(chip_encoder::EMeta));
-    e->h_meta = (chip_encoder::EMeta *)chip_pinned_alloc(sizeof(chip_encoder::EMeta));
-    e->d_zs = (ZEncStream *)chip_device_alloc(sizeof(ZEncStream));
-    if (!e->d_meta || !e->h_meta || !e->d_zs || !enc_reserve(&e->h_in, &e->h_in_cap, 0, 65536) ||
-        !enc_reserve(&e->h_out, &e->h_out_cap, 0, 65536)) {
-        chip_encoder_free(e);
-        return nullptr;
-    }
-    enc_clear(e);
-    return e;
+    return encoder_new_common(CHIP_FMT_ZSTD, level, strategy, wlog, opts ? opts->device : -1, sizeof(ZEncStream));
 }
 
 chip_encoder *chip_encoder_new_brotli(const chip_brotli_encoder_opts *opts)
@@ -1613,35 +1453,7 @@ chip_encoder *chip_encoder_new_brotli(const chip_brotli_encoder_opts *opts)
     // BrotliOptions::new(), src/encoder/brotli_common.rs: quality and mode unset (libbrotlienc's quality 11), lgwin 22
     const int quality = opts ? opts->quality : 0, mode = opts ? opts->mode : 0, lgwin = opts ? opts->lgwin : 22;
     if (quality < 0 || quality > 11 || mode < 0 || mode > 3 || lgwin < 10 || lgwin > 24) return nullptr;
-    if (!device_ok()) return nullptr;
-    int device = opts ? opts->device : -1;
-    if (device < 0 && hipGetDevice(&device) != hipSuccess) return nullptr;
-    DeviceGuard guard(device);
-    if (!guard.ok) return nullptr;
-    const Hooks hooks = current_hooks();
-    chip_encoder *e = (chip_encoder *)hooks.alloc(sizeof(chip_encoder));
-    if (!e) return nullptr;
-    memset(e, 0, sizeof *e);
-    e->hooks = hooks;
-    e->mode = CHIP_FMT_BROTLI;
-    e->level = quality ? quality : 11;
-    e->strategy = mode;
-    e->wlog = lgwin;
-    e->device = device;
-    if (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess) {
-        hooks.release(e);
-        return nullptr;
-    }
-    e->d_meta = (chip_encoder::EMeta *)chip_device_alloc(sizeof(chip_encoder::EMeta));
-    e->h_meta = (chip_encoder::EMeta *)chip_pinned_alloc(sizeof(chip_encoder::EMeta));
-    e->d_bs = (BEncStream *)chip_device_alloc(sizeof(BEncStream));
-    if (!e->d_meta || !e->h_meta || !e->d_bs || !enc_reserve(&e->h_in, &e->h_in_cap, 0, 65536) ||
-        !enc_reserve(&e->h_out, &e->h_out_cap, 0, 65536)) {
-        chip_encoder_free(e);
-        return nullptr;
-    }
-    enc_clear(e);
-    return e;
+    return encoder_new_common(CHIP_FMT_BROTLI, quality ? quality : 11, mode, lgwin, opts ? opts->device : -1, sizeof(BEncStream));
 }
 
 chip_encode_result chip_encode(chip_encoder *e, const uint8_t *in, size_t in_len, uint8_t *out, size_t out_len, int op)
@@ -1658,7 +1470,7 @@ chip_encode_result chip_encode(chip_encoder *e, const uint8_t *in, size_t in_len
     while (!e->finished && taken < in_len && e->h_out_len - e->delivered <= ENC_BACKLOG) {
         const size_t room = ENC_SEGMENT - (e->h_in_len < ENC_SEGMENT ? e->h_in_len : ENC_SEGMENT);
         const size_t k = in_len - taken < room ? in_len - taken : room;
-        if (!enc_reserve(&e->h_in, &e->h_in_cap, e->h_in_len, e->h_in_len + k)) return r;
+        if (!reserve_pinned(&e->h_in, &e->h_in_cap, e->h_in_len, e->h_in_len + k)) return r;
         memcpy(e->h_in + e->h_in_len, in + taken, k);
         e->h_in_len += k;
         taken += k;
@@ -1712,9 +1524,7 @@ void chip_encoder_free(chip_encoder *e)
     DeviceGuard guard(e->device);
     if (e->stream) {
         (void)hipStreamSynchronize(e->stream);
-        chip::release_deflate_scratch_of(e->stream);  // the stream's token scratch goes with it
-        chip::release_zstd_enc_scratch_of(e->stream);
-        chip::release_brotli_enc_scratch_of(e->stream);
+        chip::release_scratch_of(e->stream);  // the stream's launch slots go with it
         (void)hipStreamDestroy(e->stream);
     }
     chip_pinned_free(e->h_in);

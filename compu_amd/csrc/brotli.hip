@@ -11,10 +11,10 @@
 // every wave SLOT_SMALL bytes.  A unit whose metablock does not fit is appended to an overflow list and left; a second launch
 // of the same kernel, always enqueued behind the first, takes that list on a small grid with SLOT_LARGE bytes per wave and
 // decodes those units again from their start (or from their streaming checkpoint).
-#include <map>
 #include <mutex>
 
 #include "chip_internal.h"
+#include "launch_slots.h"
 #define BROTLI_TAB_SPACE __device__
 #include "brotli_tables.h"
 
@@ -863,7 +863,7 @@ __global__ __launch_bounds__(64, 3) void brotli_kernel(BatchArgs a, uint8_t *scr
     }
 }
 
-// per-wave slots, the overflow list and the counters, cached per (device, stream) like the zstd encoder's
+// per-wave slots, the overflow list and the counters: a launch slot ("Launch slots")
 struct BSlot {
     uint8_t *small = nullptr;
     uint8_t *large = nullptr;
@@ -871,37 +871,31 @@ struct BSlot {
     int blocks = 0;
     uint32_t large_blocks = 0;
     size_t list_n = 0;
-};
-std::mutex g_br_mu;
-std::map<std::pair<int, hipStream_t>, BSlot> g_br_slots;
-
-// (caller holds g_br_mu)
-hipError_t bslot_for(hipStream_t stream, uint32_t n, BSlot &out)
-{
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    BSlot &sl = g_br_slots[{dev, stream}];
-    static int max_blocks[64] = {0};
-    const int di = dev < 64 ? dev : 63;
-    if (!max_blocks[di]) {
-        int per_cu = 0, cus = 0;
-        if ((e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, brotli_kernel, 64, 0)) != hipSuccess) return e;
-        if ((e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess) return e;
-        if (per_cu < 1) per_cu = 1;
-        if (per_cu > 16) per_cu = 16;  // bounds the small slots at 16 * CUs * 128 KiB
-        max_blocks[di] = per_cu * cus;
+    void free()
+    {
+        (void)hipFree(small);
+        (void)hipFree(large);
+        (void)hipFree(ctr);
     }
-    const int want = n < (uint32_t)max_blocks[di] ? (int)n : max_blocks[di];
+    size_t bytes() const { return (size_t)blocks * SLOT_SMALL + (size_t)large_blocks * SLOT_LARGE + (4 + list_n) * sizeof(uint32_t); }
+};
+SlotCache<BSlot> g_br_cache;
+ResidentWaves g_br_resident;
+
+// (caller holds g_br_cache.mu) room for a batch of n units
+hipError_t bslot_reserve(BSlot &sl, hipStream_t stream, uint32_t n)
+{
+    int max_blocks = 0;
+    hipError_t e = g_br_resident.get((const void *)brotli_kernel, max_blocks, 16);  // bounds the small slots at 16 * CUs * 128 KiB
+    if (e != hipSuccess) return e;
+    const int want = n < (uint32_t)max_blocks ? (int)n : max_blocks;
     const uint32_t want_large = n < LARGE_BLOCKS ? n : LARGE_BLOCKS;  // a streaming decoder (n = 1) keeps one large slot
     if (sl.blocks < want || sl.list_n < n || sl.large_blocks < want_large) {
         if ((sl.small || sl.large) && (e = hipStreamSynchronize(stream)) != hipSuccess) return e;  // launches on the stream still use them
-        (void)hipFree(sl.small);
-        (void)hipFree(sl.large);
-        (void)hipFree(sl.ctr);
+        sl.free();
         const uint32_t old_large = sl.large_blocks;
         sl = BSlot{};
-        const int blocks = want <= 1 ? 1 : (want + want / 4 < max_blocks[di] ? want + want / 4 : max_blocks[di]);
+        const int blocks = grown_blocks(want, max_blocks);
         const size_t list_n = n < 1024 ? 1024 : (size_t)n;
         if ((e = hipMalloc((void **)&sl.small, (size_t)blocks * SLOT_SMALL)) != hipSuccess) return e;
         const uint32_t large_blocks = want_large > old_large ? want_large : old_large;
@@ -911,7 +905,6 @@ hipError_t bslot_for(hipStream_t stream, uint32_t n, BSlot &out)
         sl.large_blocks = large_blocks;
         sl.list_n = list_n;
     }
-    out = sl;
     return hipSuccess;
 }
 
@@ -920,62 +913,20 @@ hipError_t bslot_for(hipStream_t stream, uint32_t n, BSlot &out)
 hipError_t launch_brotli_decode(const BatchArgs &a, hipStream_t stream)
 {
     if (a.n == 0) return hipSuccess;
-    std::lock_guard<std::mutex> lk(g_br_mu);
-    BSlot sl;
-    hipError_t e = bslot_for(stream, a.n, sl);
+    std::lock_guard<std::mutex> lk(g_br_cache.mu);  // from the slot's lookup to the last launch
+    BSlot *sl = nullptr;
+    hipError_t e = g_br_cache.at(stream, sl);
+    if (e == hipSuccess) e = bslot_reserve(*sl, stream, a.n);
     if (e != hipSuccess) return e;
-    if ((e = hipMemsetAsync(sl.ctr, 0, 16, stream)) != hipSuccess) return e;
-    const uint32_t blocks = a.n < (uint32_t)sl.blocks ? a.n : (uint32_t)sl.blocks;
-    hipLaunchKernelGGL(brotli_kernel, dim3(blocks), dim3(64), 0, stream, a, sl.small, SLOT_SMALL, sl.ctr, sl.ctr + 4, 0u);
+    if ((e = hipMemsetAsync(sl->ctr, 0, 16, stream)) != hipSuccess) return e;
+    const uint32_t blocks = a.n < (uint32_t)sl->blocks ? a.n : (uint32_t)sl->blocks;
+    hipLaunchKernelGGL(brotli_kernel, dim3(blocks), dim3(64), 0, stream, a, sl->small, SLOT_SMALL, sl->ctr, sl->ctr + 4, 0u);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    const uint32_t lb = a.n < sl.large_blocks ? a.n : sl.large_blocks;
-    hipLaunchKernelGGL(brotli_kernel, dim3(lb), dim3(64), 0, stream, a, sl.large, SLOT_LARGE, sl.ctr, sl.ctr + 4, 1u);
+    const uint32_t lb = a.n < sl->large_blocks ? a.n : sl->large_blocks;
+    hipLaunchKernelGGL(brotli_kernel, dim3(lb), dim3(64), 0, stream, a, sl->large, SLOT_LARGE, sl->ctr, sl->ctr + 4, 1u);
     return hipGetLastError();
 }
 
-hipError_t release_brotli_scratch()
-{
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    if ((e = hipDeviceSynchronize()) != hipSuccess) return e;
-    std::lock_guard<std::mutex> lk(g_br_mu);
-    for (auto it = g_br_slots.begin(); it != g_br_slots.end();) {
-        if (it->first.first == dev) {
-            (void)hipFree(it->second.small);
-            (void)hipFree(it->second.large);
-            (void)hipFree(it->second.ctr);
-            it = g_br_slots.erase(it);
-        } else {
-            ++it;
-        }
-    }
-    return hipSuccess;
-}
-
-size_t brotli_scratch_bytes_of(hipStream_t stream)
-{
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 0;
-    std::lock_guard<std::mutex> lk(g_br_mu);
-    auto it = g_br_slots.find({dev, stream});
-    if (it == g_br_slots.end()) return 0;
-    const BSlot &sl = it->second;
-    return (size_t)sl.blocks * SLOT_SMALL + (size_t)sl.large_blocks * SLOT_LARGE + (4 + sl.list_n) * sizeof(uint32_t);
-}
-
-void release_brotli_scratch_of(hipStream_t stream)
-{
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return;
-    std::lock_guard<std::mutex> lk(g_br_mu);
-    auto it = g_br_slots.find({dev, stream});
-    if (it != g_br_slots.end()) {
-        (void)hipFree(it->second.small);
-        (void)hipFree(it->second.large);
-        (void)hipFree(it->second.ctr);
-        g_br_slots.erase(it);
-    }
-}
+size_t brotli_scratch_bytes_of(hipStream_t stream) { return g_br_cache.bytes_of(stream); }
 
 }  // namespace chip

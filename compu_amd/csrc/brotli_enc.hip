@@ -5,10 +5,10 @@
 // code lengths (rank sort, pointer jumping), the sizes, the bit emission (per-item bit counts, a wave scan, ORs into an LDS bit
 // buffer) and the copies of uncompressed metablocks.  Lane 0 keeps what is serial: the distance ring chain, the Huffman merge and
 // length limit, the code descriptions and headers.
-#include <map>
 #include <mutex>
 
 #include "chip_internal.h"
+#include "launch_slots.h"
 #include "brotli_enc_core.h"
 
 namespace chip {
@@ -397,79 +397,11 @@ __global__ __launch_bounds__(64) void brotli_enc_kernel(BEncArgs a, uint8_t *scr
     }
 }
 
-// per-wave scratch and the unit counter, cached per (device, stream) like the zstd encoder's (zstd_enc.hip zslot_for)
-struct BSlot {
-    uint8_t *scratch = nullptr;
-    uint32_t *counter = nullptr;
-    int blocks = 0;
-};
-std::mutex g_benc_mu;
-std::map<std::pair<int, hipStream_t>, BSlot> g_benc_slots;
-
-// (caller holds g_benc_mu)
-hipError_t bslot_for(hipStream_t stream, uint32_t n, BSlot &out)
-{
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    BSlot &sl = g_benc_slots[{dev, stream}];
-    static int max_blocks[64] = {0};
-    const int di = dev < 64 ? dev : 63;
-    if (!max_blocks[di]) {
-        int per_cu = 0, cus = 0;
-        if ((e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, brotli_enc_kernel, 64, 0)) != hipSuccess) return e;
-        if ((e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess) return e;
-        if (per_cu < 1) per_cu = 1;
-        max_blocks[di] = per_cu * cus;
-    }
-    const int want = n < (uint32_t)max_blocks[di] ? (int)n : max_blocks[di];
-    if (sl.blocks < want) {
-        if (sl.scratch && (e = hipStreamSynchronize(stream)) != hipSuccess) return e;  // launches on the stream still use it
-        (void)hipFree(sl.scratch);
-        sl.scratch = nullptr;
-        sl.blocks = 0;
-        const int blocks = want <= 1 ? 1 : (want + want / 4 < max_blocks[di] ? want + want / 4 : max_blocks[di]);
-        uint8_t *p = nullptr;
-        if ((e = hipMalloc((void **)&p, (size_t)blocks * WAVE_SCRATCH + 256)) != hipSuccess) return e;
-        sl.scratch = p;
-        sl.counter = (uint32_t *)(p + (size_t)blocks * WAVE_SCRATCH);
-        sl.blocks = blocks;
-    }
-    out = sl;
-    return hipSuccess;
-}
+// per-wave scratch and the unit counter: a launch slot ("Launch slots")
+SlotCache<WaveScratch> g_benc_cache;
+ResidentWaves g_benc_resident;
 
 }  // namespace
-
-hipError_t release_brotli_enc_scratch()
-{
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    if ((e = hipDeviceSynchronize()) != hipSuccess) return e;
-    std::lock_guard<std::mutex> lk(g_benc_mu);
-    for (auto it = g_benc_slots.begin(); it != g_benc_slots.end();) {
-        if (it->first.first == dev) {
-            (void)hipFree(it->second.scratch);
-            it = g_benc_slots.erase(it);
-        } else {
-            ++it;
-        }
-    }
-    return hipSuccess;
-}
-
-void release_brotli_enc_scratch_of(hipStream_t stream)
-{
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return;
-    std::lock_guard<std::mutex> lk(g_benc_mu);
-    auto it = g_benc_slots.find({dev, stream});
-    if (it != g_benc_slots.end()) {
-        (void)hipFree(it->second.scratch);
-        g_benc_slots.erase(it);
-    }
-}
 
 hipError_t launch_brotli_encode(const BatchArgs &b, int quality, int lgwin, uint32_t flags, BEncStream *stream_state, hipStream_t stream)
 {
@@ -480,13 +412,16 @@ hipError_t launch_brotli_encode(const BatchArgs &b, int quality, int lgwin, uint
     a.lgwin = (uint32_t)lgwin;
     a.flags = flags;
     a.stream = stream_state;
-    std::lock_guard<std::mutex> lk(g_benc_mu);
-    BSlot sl;
-    hipError_t e = bslot_for(stream, b.n, sl);
+    std::lock_guard<std::mutex> lk(g_benc_cache.mu);  // from the slot's lookup to the launch
+    WaveScratch *sl = nullptr;
+    int max_blocks = 0;
+    hipError_t e = g_benc_cache.at(stream, sl);
+    if (e == hipSuccess) e = g_benc_resident.get((const void *)brotli_enc_kernel, max_blocks);
+    if (e == hipSuccess) e = sl->reserve(stream, b.n, max_blocks, WAVE_SCRATCH);
     if (e != hipSuccess) return e;
-    if ((e = hipMemsetAsync(sl.counter, 0, 4, stream)) != hipSuccess) return e;
-    const uint32_t blocks = b.n < (uint32_t)sl.blocks ? b.n : (uint32_t)sl.blocks;
-    hipLaunchKernelGGL(brotli_enc_kernel, dim3(blocks), dim3(64), 0, stream, a, sl.scratch, sl.counter);
+    if ((e = hipMemsetAsync(sl->counter, 0, 4, stream)) != hipSuccess) return e;
+    const uint32_t blocks = b.n < (uint32_t)sl->blocks ? b.n : (uint32_t)sl->blocks;
+    hipLaunchKernelGGL(brotli_enc_kernel, dim3(blocks), dim3(64), 0, stream, a, sl->scratch, sl->counter);
     return hipGetLastError();
 }
 

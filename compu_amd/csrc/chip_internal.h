@@ -77,10 +77,9 @@ hipError_t launch_route_sizes(const BatchArgs &a, uint64_t *out_size, uint32_t *
 hipError_t launch_routed_sizes(const BatchArgs &a, uint64_t *out_size, hipStream_t stream);
 // (inflate_sizes.hip: the launch itself, for launch_inflate_sizes, which holds the slot)
 hipError_t enqueue_inflate_sizes(const BatchArgs &a, uint64_t *out_size, uint32_t *scratch, uint32_t *counter, uint32_t blocks, hipStream_t stream);
-hipError_t release_inflate_scratch();  // frees the cached token scratch of the current device (after a device sync)
-void release_inflate_scratch_of(hipStream_t stream);
-hipError_t release_deflate_scratch();  // the encoder's token scratch (dynamic levels), same rules
-void release_deflate_scratch_of(hipStream_t stream);  // the same for one (drained) stream of the current device
+// launch_slots.hip: the cached launch scratch of every codec ("Launch slots")
+hipError_t release_scratch();                 // every slot of the current device, after a device sync
+void release_scratch_of(hipStream_t stream);  // the slots of one (drained) stream of the current device
 hipError_t launch_zstd_decode(const BatchArgs &a, int window_log_max, hipStream_t stream);
 // Detection-driven router of a mixed batch: appends the index of every gzip / zlib unit to sel_inflate and of every zstd
 // frame to sel_zstd (counts[0], counts[1], zeroed by the call) and answers units that are neither at once.
@@ -104,8 +103,6 @@ struct ZEncStream {
 };
 hipError_t launch_zstd_encode(const BatchArgs &a, int level, int strategy, uint32_t wlog_single, uint32_t wlog_window, uint32_t flags,
                               ZEncStream *stream_state, hipStream_t stream);
-hipError_t release_zstd_enc_scratch();                 // the zstd encoder's per-wave scratch of the current device (after a sync)
-void release_zstd_enc_scratch_of(hipStream_t stream);  // the same for one (drained) stream
 
 // brotli encoder (brotli_enc.hip).  Flags: ZF_FIRST writes the WBITS field and starts the distance ring, ZF_LAST closes the stream
 // (otherwise the segment ends byte-aligned).  quality 0..11 (0 = 11), lgwin 10..24.
@@ -113,8 +110,6 @@ struct BEncStream {
     uint32_t ring[4];  // the distance ring carried from one segment to the next, last distance first
 };
 hipError_t launch_brotli_encode(const BatchArgs &a, int quality, int lgwin, uint32_t flags, BEncStream *stream_state, hipStream_t stream);
-hipError_t release_brotli_enc_scratch();                 // the brotli encoder's per-wave scratch of the current device (after a sync)
-void release_brotli_enc_scratch_of(hipStream_t stream);  // the same for one (drained) stream
 
 // brotli decoder (brotli.hip): a persistent launch with a 128 KiB table slot per wave, then an always-enqueued launch on 64 waves
 // with worst-case slots for the units whose metablock tables did not fit (an overflow list on the device).
@@ -126,9 +121,7 @@ void release_brotli_enc_scratch_of(hipStream_t stream);  // the same for one (dr
 constexpr uint32_t BRES_WORDS = 16;
 static_assert(BRES_WORDS <= ZRES_HDR, "the brotli checkpoint fits the header the streaming code copies");
 hipError_t launch_brotli_decode(const BatchArgs &a, hipStream_t stream);
-hipError_t release_brotli_scratch();                 // per-wave table slots of the current device (after a device sync)
-void release_brotli_scratch_of(hipStream_t stream);  // the same for one (drained) stream
-size_t brotli_scratch_bytes_of(hipStream_t stream);  // device bytes those slots hold for `stream` (streaming footprint)
+size_t brotli_scratch_bytes_of(hipStream_t stream);  // device bytes its per-wave table slots hold for `stream` (streaming footprint)
 
 // Detection::detect (src/decoder/mod.rs:28-114) on device: first 2-4 bytes of a unit -> CHIP_DETECT_*.
 // The FLG table of mod.rs:44-55 is packed one word per CINFO; the 0x68 row never matches in the

@@ -16,8 +16,9 @@
 #include "chip_internal.h"
 #include "wave_checksums.h"
 
-#include <map>
 #include <mutex>
+
+#include "launch_slots.h"
 
 namespace chip {
 
@@ -1057,80 +1058,11 @@ __global__ __launch_bounds__(64) void deflate_dyn2_kernel(EncArgs a, uint32_t *s
     dyn_grid(a, L, scratch, next_unit);
 }
 
-// Token scratch and the unit counter of the dynamic-level launches, cached per (device, stream) like the
-// inflate kernel's (inflate.hip slot_for): sized for min(n, resident waves) waves.
-struct EncSlot {
-    uint32_t *scratch = nullptr;
-    uint32_t *counter = nullptr;
-    int blocks = 0;
-};
-std::mutex g_enc_mu;
-std::map<std::pair<int, hipStream_t>, EncSlot> g_enc_slots;
-
-// (caller holds g_enc_mu)
-hipError_t enc_slot_for(hipStream_t stream, uint32_t n, EncSlot &out)
-{
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    EncSlot &sl = g_enc_slots[{dev, stream}];
-    static int max_blocks[64] = {0};
-    const int di = dev < 64 ? dev : 63;
-    if (!max_blocks[di]) {
-        int per_cu = 0, cus = 0;
-        if ((e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, deflate_dyn_kernel, 64, 0)) != hipSuccess) return e;
-        if ((e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess) return e;
-        if (per_cu < 1) per_cu = 1;
-        max_blocks[di] = per_cu * cus;
-    }
-    const int want = n < (uint32_t)max_blocks[di] ? (int)n : max_blocks[di];
-    if (sl.blocks < want) {
-        if (sl.scratch && (e = hipStreamSynchronize(stream)) != hipSuccess) return e;  // launches on the stream still use it
-        (void)hipFree(sl.scratch);
-        sl.scratch = nullptr;
-        sl.blocks = 0;
-        const int blocks = want <= 1 ? 1 : (want + want / 4 < max_blocks[di] ? want + want / 4 : max_blocks[di]);
-        uint32_t *p = nullptr;
-        if ((e = hipMalloc((void **)&p, (size_t)blocks * TOK_BLOCK * 4 + 256)) != hipSuccess) return e;
-        sl.scratch = p;
-        sl.counter = p + (size_t)blocks * TOK_BLOCK;
-        sl.blocks = blocks;
-    }
-    out = sl;
-    return hipSuccess;
-}
+// Token scratch and the unit counter of the dynamic-level launches: a launch slot ("Launch slots")
+SlotCache<WaveScratch> g_enc_cache;
+ResidentWaves g_enc_resident;  // of deflate_dyn_kernel, for both dynamic kernels
 
 }  // namespace
-
-hipError_t release_deflate_scratch()
-{
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    if ((e = hipDeviceSynchronize()) != hipSuccess) return e;
-    std::lock_guard<std::mutex> lk(g_enc_mu);
-    for (auto it = g_enc_slots.begin(); it != g_enc_slots.end();) {
-        if (it->first.first == dev) {
-            (void)hipFree(it->second.scratch);
-            it = g_enc_slots.erase(it);
-        } else {
-            ++it;
-        }
-    }
-    return hipSuccess;
-}
-
-void release_deflate_scratch_of(hipStream_t stream)
-{
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return;
-    std::lock_guard<std::mutex> lk(g_enc_mu);
-    auto it = g_enc_slots.find({dev, stream});
-    if (it != g_enc_slots.end()) {
-        (void)hipFree(it->second.scratch);
-        g_enc_slots.erase(it);
-    }
-}
 
 hipError_t launch_deflate_l1(const BatchArgs &b, int level, uint32_t flags, uint32_t check_seed, uint64_t total_before,
                              uint32_t *check_out, hipStream_t stream)
@@ -1145,16 +1077,17 @@ hipError_t launch_deflate_l1(const BatchArgs &b, int level, uint32_t flags, uint
     a.check_out = check_out;
     const uint32_t strategy = (flags >> 8) & 7u;
     if (level >= 2 && strategy != CHIP_STRATEGY_FIXED) {
-        // One lock from the slot's lookup to the launch (as launch_inflate): another host thread launching a larger batch on the same
-        // stream may free and reallocate the scratch in enc_slot_for(); the counter reset and the kernel reach the stream back to back.
-        std::lock_guard<std::mutex> lk(g_enc_mu);
-        EncSlot sl;
-        hipError_t e = enc_slot_for(stream, b.n, sl);
+        std::lock_guard<std::mutex> lk(g_enc_cache.mu);  // from the slot's lookup to the launch
+        WaveScratch *sl = nullptr;
+        int max_blocks = 0;
+        hipError_t e = g_enc_cache.at(stream, sl);
+        if (e == hipSuccess) e = g_enc_resident.get((const void *)deflate_dyn_kernel, max_blocks);
+        if (e == hipSuccess) e = sl->reserve(stream, b.n, max_blocks, (size_t)TOK_BLOCK * 4);
         if (e != hipSuccess) return e;
-        if ((e = hipMemsetAsync(sl.counter, 0, 4, stream)) != hipSuccess) return e;
-        const uint32_t blocks = b.n < (uint32_t)sl.blocks ? b.n : (uint32_t)sl.blocks;
-        if (level >= 6) hipLaunchKernelGGL(deflate_dyn2_kernel, dim3(blocks), dim3(64), 0, stream, a, sl.scratch, sl.counter);
-        else hipLaunchKernelGGL(deflate_dyn_kernel, dim3(blocks), dim3(64), 0, stream, a, sl.scratch, sl.counter);
+        if ((e = hipMemsetAsync(sl->counter, 0, 4, stream)) != hipSuccess) return e;
+        const uint32_t blocks = b.n < (uint32_t)sl->blocks ? b.n : (uint32_t)sl->blocks;
+        if (level >= 6) hipLaunchKernelGGL(deflate_dyn2_kernel, dim3(blocks), dim3(64), 0, stream, a, (uint32_t *)sl->scratch, sl->counter);
+        else hipLaunchKernelGGL(deflate_dyn_kernel, dim3(blocks), dim3(64), 0, stream, a, (uint32_t *)sl->scratch, sl->counter);
         return hipGetLastError();
     }
     hipLaunchKernelGGL(deflate_kernel, dim3(b.n), dim3(64), 0, stream, a);

@@ -19,11 +19,10 @@
 #include <cstddef>
 #include <cstdio>
 #include <cstdlib>
-#include <map>
 #include <mutex>
-#include <utility>
 
 #include "chip_internal.h"
+#include "launch_slots.h"
 #include "wave_checksums.h"
 
 namespace chip {
@@ -1755,69 +1754,46 @@ hipError_t enqueue_inflate_sizes(const BatchArgs &a, uint64_t *out_size, uint32_
 #ifndef CHIP_INFLATE_SIZES_TU
 
 namespace {
-// Token scratch and the unit counter of a launch, cached per (device, stream): launches on one stream
-// run in order, so they can share a slot; different streams get their own.
-struct LaunchSlot {
-    uint32_t *scratch = nullptr;
-    uint32_t *counter = nullptr;
-    int blocks = 0;
+// Token scratch and the unit counter of a launch, and the lists of a routed batch: a launch slot ("Launch slots").
+// A streaming decoder (batches of one) holds one 64 KiB slot, not the 270 MB a full grid needs.
+struct LaunchSlot : WaveScratch {
     uint32_t *route = nullptr;  // routed batches: [0,1] list lengths, then two index lists of route_cap entries
     size_t route_cap = 0;
+    void free()
+    {
+        WaveScratch::free();
+        (void)hipFree(route);
+    }
 };
-std::mutex g_slot_mu;
-std::map<std::pair<int, hipStream_t>, LaunchSlot> g_slots;
+SlotCache<LaunchSlot> g_slots;
+ResidentWaves g_resident;
 
-// The slot of (current device, stream), with token scratch for min(n, resident waves) waves: a streaming decoder
-// (batches of one) holds one 64 KiB slot, not the 270 MB a full grid needs; the scratch grows when a larger batch arrives.
-// (caller holds g_slot_mu)
-hipError_t slot_for(hipStream_t stream, uint32_t n, LaunchSlot &out)
+// (caller holds g_slots.mu) the slot of (current device, stream) with token scratch for min(n, resident waves) waves
+hipError_t slot_for(hipStream_t stream, uint32_t n, LaunchSlot *&sl)
 {
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
+#ifdef CHIP_EXP_PER_CU  // occupancy probe: a smaller persistent grid (at most this many waves per CU)
+    const int per_cu_cap = CHIP_EXP_PER_CU;
+#else
+    const int per_cu_cap = 0;
+#endif
+    int max_blocks = 0, per_cu = 0;
+    hipError_t e = g_slots.at(stream, sl);
+    if (e == hipSuccess) e = g_resident.get((const void *)inflate_kernel, max_blocks, per_cu_cap, &per_cu);
     if (e != hipSuccess) return e;
-    LaunchSlot &sl = g_slots[{dev, stream}];
-    static int max_blocks[64] = {0};  // resident waves of a full grid, per device
-    const int di = dev < 64 ? dev : 63;
-    if (!max_blocks[di]) {
-        int per_cu = 0, cus = 0;
-        if ((e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, inflate_kernel, 64, 0)) != hipSuccess) return e;
-        if ((e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess) return e;
-        if (per_cu < 1) per_cu = 1;
-#ifdef CHIP_EXP_PER_CU  // occupancy probe: a smaller persistent grid (waves per CU)
-        per_cu = CHIP_EXP_PER_CU;
-#endif
-        max_blocks[di] = per_cu * cus;
 #ifdef CHIP_STATS
-        if (getenv("CHIP_DEBUG_GRID")) fprintf(stderr, "[chip] inflate_kernel: %d waves per CU x %d CUs resident (LDS %zu B per wave)\n", per_cu, cus, sizeof(WaveLds));
+    if (per_cu && getenv("CHIP_DEBUG_GRID"))
+        fprintf(stderr, "[chip] inflate_kernel: %d waves per CU x %d CUs resident (LDS %zu B per wave)\n", per_cu, max_blocks / per_cu, sizeof(WaveLds));
 #endif
-    }
-    const int want = n < (uint32_t)max_blocks[di] ? (int)n : max_blocks[di];
-    if (sl.blocks < want) {
-        if (sl.scratch && (e = hipStreamSynchronize(stream)) != hipSuccess) return e;  // launches on the stream still use it
-        (void)hipFree(sl.scratch);
-        sl.scratch = nullptr;
-        sl.blocks = 0;
-        // a little headroom for batches that grow slowly (streaming objects stay at one wave)
-        const int blocks = want <= 1 ? 1 : (want + want / 4 < max_blocks[di] ? want + want / 4 : max_blocks[di]);
-        uint32_t *p = nullptr;
-        if ((e = hipMalloc((void **)&p, (size_t)blocks * SCRATCH_WORDS * 4 + 256)) != hipSuccess) return e;
-        sl.scratch = p;
-        sl.counter = p + (size_t)blocks * SCRATCH_WORDS;
-        sl.blocks = blocks;
-    }
-    out = sl;
-    return hipSuccess;
+    return sl->reserve(stream, n, max_blocks, (size_t)SCRATCH_WORDS * 4);
 }
-}  // namespace
 
-namespace {
-// (caller holds g_slot_mu)
+// (caller holds g_slots.mu)
 hipError_t route_scratch_locked(hipStream_t stream, size_t n, uint32_t **sel_inflate, uint32_t **sel_zstd, uint32_t **counts)
 {
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
+    LaunchSlot *slp = nullptr;
+    hipError_t e = g_slots.at(stream, slp);
     if (e != hipSuccess) return e;
-    LaunchSlot &sl = g_slots[{dev, stream}];
+    LaunchSlot &sl = *slp;
     if (n > sl.route_cap) {
         // work queued on the stream may still read the old lists: let it finish before they go
         if (sl.route && (e = hipStreamSynchronize(stream)) != hipSuccess) return e;
@@ -1838,7 +1814,7 @@ hipError_t launch_inflate_locked(const BatchArgs &a, hipStream_t stream);
 
 hipError_t route_scratch(hipStream_t stream, size_t n, uint32_t **sel_inflate, uint32_t **sel_zstd, uint32_t **counts)
 {
-    std::lock_guard<std::mutex> lk(g_slot_mu);
+    std::lock_guard<std::mutex> lk(g_slots.mu);
     return route_scratch_locked(stream, n, sel_inflate, sel_zstd, counts);
 }
 
@@ -1849,7 +1825,7 @@ hipError_t route_scratch(hipStream_t stream, size_t n, uint32_t **sel_inflate, u
 hipError_t launch_routed(const BatchArgs &a, hipStream_t stream)
 {
     if (a.n == 0) return hipSuccess;
-    std::lock_guard<std::mutex> lk(g_slot_mu);
+    std::lock_guard<std::mutex> lk(g_slots.mu);
     uint32_t *sel_i = nullptr, *sel_z = nullptr, *counts = nullptr;
     hipError_t e = route_scratch_locked(stream, a.n, &sel_i, &sel_z, &counts);
     if (e == hipSuccess) e = launch_route(a, sel_i, sel_z, counts, stream);
@@ -1865,38 +1841,6 @@ hipError_t launch_routed(const BatchArgs &a, hipStream_t stream)
     return e;
 }
 
-hipError_t release_inflate_scratch()
-{
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    if ((e = hipDeviceSynchronize()) != hipSuccess) return e;
-    std::lock_guard<std::mutex> lk(g_slot_mu);
-    for (auto it = g_slots.begin(); it != g_slots.end();) {
-        if (it->first.first == dev) {
-            (void)hipFree(it->second.scratch);
-            (void)hipFree(it->second.route);
-            it = g_slots.erase(it);
-        } else {
-            ++it;
-        }
-    }
-    return hipSuccess;
-}
-
-void release_inflate_scratch_of(hipStream_t stream)
-{
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return;
-    std::lock_guard<std::mutex> lk(g_slot_mu);
-    auto it = g_slots.find({dev, stream});
-    if (it != g_slots.end()) {
-        (void)hipFree(it->second.scratch);
-        (void)hipFree(it->second.route);
-        g_slots.erase(it);
-    }
-}
-
 hipError_t launch_inflate(const BatchArgs &a, hipStream_t stream)
 {
     if (a.n == 0) return hipSuccess;
@@ -1904,7 +1848,7 @@ hipError_t launch_inflate(const BatchArgs &a, hipStream_t stream)
     // free and reallocate the scratch in slot_for(); it must not do so between this thread's lookup and its launch (the
     // stream synchronisation in slot_for() only covers work that is already queued).  The counter reset and the kernel also
     // have to reach the stream back to back.
-    std::lock_guard<std::mutex> lk(g_slot_mu);
+    std::lock_guard<std::mutex> lk(g_slots.mu);
     return launch_inflate_locked(a, stream);
 }
 
@@ -1916,7 +1860,7 @@ hipError_t launch_inflate_sizes_locked(const BatchArgs &a, uint64_t *out_size, h
 hipError_t launch_inflate_sizes(const BatchArgs &a, uint64_t *out_size, hipStream_t stream)
 {
     if (a.n == 0) return hipSuccess;
-    std::lock_guard<std::mutex> lk(g_slot_mu);
+    std::lock_guard<std::mutex> lk(g_slots.mu);
     return launch_inflate_sizes_locked(a, out_size, stream);
 }
 
@@ -1924,7 +1868,7 @@ hipError_t launch_inflate_sizes(const BatchArgs &a, uint64_t *out_size, hipStrea
 hipError_t launch_routed_sizes(const BatchArgs &a, uint64_t *out_size, hipStream_t stream)
 {
     if (a.n == 0) return hipSuccess;
-    std::lock_guard<std::mutex> lk(g_slot_mu);
+    std::lock_guard<std::mutex> lk(g_slots.mu);
     uint32_t *sel_i = nullptr, *sel_z = nullptr, *counts = nullptr;
     hipError_t e = route_scratch_locked(stream, a.n, &sel_i, &sel_z, &counts);
     if (e == hipSuccess) e = launch_route_sizes(a, out_size, sel_i, sel_z, counts, stream);
@@ -1943,30 +1887,30 @@ hipError_t launch_routed_sizes(const BatchArgs &a, uint64_t *out_size, hipStream
 namespace {
 hipError_t launch_inflate_sizes_locked(const BatchArgs &a, uint64_t *out_size, hipStream_t stream)
 {
-    LaunchSlot sl;
+    LaunchSlot *sl = nullptr;
     hipError_t e = slot_for(stream, a.n, sl);
     if (e != hipSuccess) return e;
-    const uint32_t blocks = a.n < (uint32_t)sl.blocks ? a.n : (uint32_t)sl.blocks;
-    if ((e = hipMemsetAsync(sl.counter, 0, 4, stream)) != hipSuccess) return e;
-    return enqueue_inflate_sizes(a, out_size, sl.scratch, sl.counter, blocks, stream);
+    const uint32_t blocks = a.n < (uint32_t)sl->blocks ? a.n : (uint32_t)sl->blocks;
+    if ((e = hipMemsetAsync(sl->counter, 0, 4, stream)) != hipSuccess) return e;
+    return enqueue_inflate_sizes(a, out_size, (uint32_t *)sl->scratch, sl->counter, blocks, stream);
 }
 }  // namespace
 
 namespace {
 hipError_t launch_inflate_locked(const BatchArgs &a, hipStream_t stream)
 {
-    LaunchSlot sl;
+    LaunchSlot *sl = nullptr;
     hipError_t e = slot_for(stream, a.n, sl);
     if (e != hipSuccess) return e;
-    uint32_t blocks = a.n < (uint32_t)sl.blocks ? a.n : (uint32_t)sl.blocks;
+    uint32_t blocks = a.n < (uint32_t)sl->blocks ? a.n : (uint32_t)sl->blocks;
 #ifdef CHIP_EXP_EVEN_GRID  // probe: as many waves as give every wave the same number of units (no ragged last round)
     if (blocks) {
         const uint32_t per_wave = (a.n + blocks - 1) / blocks;
         blocks = (a.n + per_wave - 1) / per_wave;
     }
 #endif
-    if ((e = hipMemsetAsync(sl.counter, 0, 4, stream)) != hipSuccess) return e;
-    hipLaunchKernelGGL(inflate_kernel, dim3(blocks), dim3(64), 0, stream, a, sl.scratch, sl.counter);
+    if ((e = hipMemsetAsync(sl->counter, 0, 4, stream)) != hipSuccess) return e;
+    hipLaunchKernelGGL(inflate_kernel, dim3(blocks), dim3(64), 0, stream, a, (uint32_t *)sl->scratch, sl->counter);
     return hipGetLastError();
 }
 }  // namespace

@@ -3,10 +3,10 @@
 // literals, Huffman / FSE tables) in a per-wave HBM scratch; the hash table of the match finder lives in LDS.  The lanes share
 // the match finder (64-position chunks, zstd_enc_core.h), the literal copy and histogram, the Huffman stream sizes and the Raw
 // copies; the Huffman code and bit emission, the FSE state chain and the headers run on lane 0.
-#include <map>
 #include <mutex>
 
 #include "chip_internal.h"
+#include "launch_slots.h"
 #include "zstd_enc_core.h"
 
 namespace chip {
@@ -248,79 +248,11 @@ __global__ __launch_bounds__(64) void zstd_enc_kernel(ZEncArgs a, uint8_t *scrat
     }
 }
 
-// per-wave scratch and the unit counter, cached per (device, stream) like the deflate encoder's (deflate.hip enc_slot_for)
-struct ZSlot {
-    uint8_t *scratch = nullptr;
-    uint32_t *counter = nullptr;
-    int blocks = 0;
-};
-std::mutex g_zenc_mu;
-std::map<std::pair<int, hipStream_t>, ZSlot> g_zenc_slots;
-
-// (caller holds g_zenc_mu)
-hipError_t zslot_for(hipStream_t stream, uint32_t n, ZSlot &out)
-{
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    ZSlot &sl = g_zenc_slots[{dev, stream}];
-    static int max_blocks[64] = {0};
-    const int di = dev < 64 ? dev : 63;
-    if (!max_blocks[di]) {
-        int per_cu = 0, cus = 0;
-        if ((e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, zstd_enc_kernel, 64, 0)) != hipSuccess) return e;
-        if ((e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess) return e;
-        if (per_cu < 1) per_cu = 1;
-        max_blocks[di] = per_cu * cus;
-    }
-    const int want = n < (uint32_t)max_blocks[di] ? (int)n : max_blocks[di];
-    if (sl.blocks < want) {
-        if (sl.scratch && (e = hipStreamSynchronize(stream)) != hipSuccess) return e;  // launches on the stream still use it
-        (void)hipFree(sl.scratch);
-        sl.scratch = nullptr;
-        sl.blocks = 0;
-        const int blocks = want <= 1 ? 1 : (want + want / 4 < max_blocks[di] ? want + want / 4 : max_blocks[di]);
-        uint8_t *p = nullptr;
-        if ((e = hipMalloc((void **)&p, (size_t)blocks * WAVE_SCRATCH + 256)) != hipSuccess) return e;
-        sl.scratch = p;
-        sl.counter = (uint32_t *)(p + (size_t)blocks * WAVE_SCRATCH);
-        sl.blocks = blocks;
-    }
-    out = sl;
-    return hipSuccess;
-}
+// per-wave scratch and the unit counter: a launch slot ("Launch slots")
+SlotCache<WaveScratch> g_zenc_cache;
+ResidentWaves g_zenc_resident;
 
 }  // namespace
-
-hipError_t release_zstd_enc_scratch()
-{
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    if ((e = hipDeviceSynchronize()) != hipSuccess) return e;
-    std::lock_guard<std::mutex> lk(g_zenc_mu);
-    for (auto it = g_zenc_slots.begin(); it != g_zenc_slots.end();) {
-        if (it->first.first == dev) {
-            (void)hipFree(it->second.scratch);
-            it = g_zenc_slots.erase(it);
-        } else {
-            ++it;
-        }
-    }
-    return hipSuccess;
-}
-
-void release_zstd_enc_scratch_of(hipStream_t stream)
-{
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return;
-    std::lock_guard<std::mutex> lk(g_zenc_mu);
-    auto it = g_zenc_slots.find({dev, stream});
-    if (it != g_zenc_slots.end()) {
-        (void)hipFree(it->second.scratch);
-        g_zenc_slots.erase(it);
-    }
-}
 
 void zstd_enc_group(int level, int strategy, uint32_t &group, uint32_t &skip_shift)
 {
@@ -353,14 +285,16 @@ hipError_t launch_zstd_encode(const BatchArgs &b, int level, int strategy, uint3
     a.wlog_window = wlog_window;
     a.flags = flags;
     a.stream = stream_state;
-    // one lock from the slot's lookup to the launch (as launch_deflate_l1)
-    std::lock_guard<std::mutex> lk(g_zenc_mu);
-    ZSlot sl;
-    hipError_t e = zslot_for(stream, b.n, sl);
+    std::lock_guard<std::mutex> lk(g_zenc_cache.mu);  // from the slot's lookup to the launch
+    WaveScratch *sl = nullptr;
+    int max_blocks = 0;
+    hipError_t e = g_zenc_cache.at(stream, sl);
+    if (e == hipSuccess) e = g_zenc_resident.get((const void *)zstd_enc_kernel, max_blocks);
+    if (e == hipSuccess) e = sl->reserve(stream, b.n, max_blocks, WAVE_SCRATCH);
     if (e != hipSuccess) return e;
-    if ((e = hipMemsetAsync(sl.counter, 0, 4, stream)) != hipSuccess) return e;
-    const uint32_t blocks = b.n < (uint32_t)sl.blocks ? b.n : (uint32_t)sl.blocks;
-    hipLaunchKernelGGL(zstd_enc_kernel, dim3(blocks), dim3(64), 0, stream, a, sl.scratch, sl.counter);
+    if ((e = hipMemsetAsync(sl->counter, 0, 4, stream)) != hipSuccess) return e;
+    const uint32_t blocks = b.n < (uint32_t)sl->blocks ? b.n : (uint32_t)sl->blocks;
+    hipLaunchKernelGGL(zstd_enc_kernel, dim3(blocks), dim3(64), 0, stream, a, sl->scratch, sl->counter);
     return hipGetLastError();
 }
 
