@@ -23,6 +23,10 @@ if [ "${CHIP_BUILD_STATS:-0}" = "1" ]; then
     "$HIPCC" --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -Wall -DCHIP_STATS \
         -o "$here/../libcompu_hip_stats.so" "$here"/*.hip
     echo "built $here/../libcompu_hip_stats.so (diagnostic)"
+    # the same with literal pairing compiled out of the inflate walk: the yardstick of tests/test_inflate_pairs_gpu.py's super-round count
+    "$HIPCC" --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -Wall -DCHIP_STATS -DCHIP_EXP_NO_PAIR \
+        -o "$here/../libcompu_hip_stats_nopair.so" "$here"/*.hip
+    echo "built $here/../libcompu_hip_stats_nopair.so (diagnostic)"
 fi
 # C++ replay of the reference's integration tests over the C ABI (runs on the GPU box only)
 g++ -O1 -std=c++17 -Wall -o "$here/../../tests/cpp/test_reference" "$here/../../tests/cpp/test_reference.cpp" \

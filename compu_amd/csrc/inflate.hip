@@ -160,7 +160,11 @@ __device__ __forceinline__ uint32_t row_base(uint32_t l) { return (l >> 3) * (8u
 __device__ __forceinline__ uint32_t row_word(uint32_t k) { return k + (k >> 2) * 28u; }  // 32 * (k / 4) + k % 4
 
 // token: [8:0] literal byte, or match length 3..258; [9] match; [25:10] match distance - 1 (a piece's entry token in a joined lane's
-// row is found from the popcount of the owner's boundary marks, not from the tokens)
+// row is found from the popcount of the owner's boundary marks, not from the tokens).  A literal token may carry the literal behind
+// it as well (a pair): [31] set, [23:16] the second byte (where a byte store of the register's high half reads it); a match has
+// bit 31 clear.  tok_olen() is a token's output length for the code that reads tokens from the rows one by one (count_tokens(),
+// overflow_bit()); flush_tokens() forms the same value from the fields it has already taken apart.
+__device__ __forceinline__ uint32_t tok_olen(uint32_t t) { return (t & 512u) ? t & 0x1ffu : 1u + (t >> 31); }
 
 struct HuffMeta {
     uint32_t limit15[16];  // [l] = end (exclusive) of the 15-bit-aligned code space of lengths <= l; [0] = 0
@@ -797,7 +801,8 @@ __device__ __forceinline__ uint32_t lane_gather(uint32_t x, uint32_t src)
 // zlib leaves with every bit of the token consumed during which (or, when the output was exactly full, in front of which) it ran
 // out of room, and holds fewer than eight unused bits: its avail_in follows from the bit position behind that token.
 // End of the token that starts at bit p (never an end-of-block code), read from memory with the block's tables.
-__device__ uint32_t token_end(const WaveLds &L, const InWin &w, uint32_t p)
+// (second: the token is a literal pair and the code of its second literal counts too)
+__device__ uint32_t token_end(const WaveLds &L, const InWin &w, uint32_t p, bool second)
 {
     const uint16_t *const pool16 = (const uint16_t *)L.pool;
     const uint32_t i = p >> 5;
@@ -806,8 +811,12 @@ __device__ uint32_t token_end(const WaveLds &L, const InWin &w, uint32_t p)
     const uint32_t r = L.lit_root[lo & ((1u << LIT_ROOT) - 1u)];
     const uint32_t e = L.pool[(r >> 5) + __builtin_amdgcn_ubfe(lo, LIT_ROOT, r)];
     const uint32_t n1 = __builtin_amdgcn_ubfe(e, 10, 5);
-    if (!(e & F_LEN)) return p + n1;
     const uint32_t w2 = __builtin_amdgcn_alignbit(hi, lo, n1);
+    if (!(e & F_LEN)) {
+        if (!second) return p + n1;
+        const uint32_t r2 = L.lit_root[w2 & ((1u << LIT_ROOT) - 1u)];
+        return p + n1 + __builtin_amdgcn_ubfe(L.pool[(r2 >> 5) + __builtin_amdgcn_ubfe(w2, LIT_ROOT, r2)], 10, 5);
+    }
     uint32_t m = L.dist_root[w2 & ((1u << DIST_ROOT) - 1u)];
     if (m & D_LONG) {
         const uint32_t b16 = ((m >> 4) & 127u) | ((m >> 12) << 7);
@@ -832,7 +841,7 @@ __device__ __attribute__((always_inline)) uint32_t overflow_bit(const WaveLds &L
         const uint32_t d = lane_gather(pdelta, k - 1u);
         const uint32_t krow = (t + d) & 0xffffu, rb = d >> 16;
         const uint32_t tok = grow[rb + row_word(krow)];
-        uint32_t olen = (tok & 512u) ? (tok & 0x1ffu) : 1u;
+        uint32_t olen = tok_olen(tok);
         if (g + lane >= ntok) olen = 0;
         const uint32_t incl = wave_incl_scan(olen);
         const uint64_t over = __ballot(olen != 0 && run + incl > xcap);
@@ -840,8 +849,14 @@ __device__ __attribute__((always_inline)) uint32_t overflow_bit(const WaveLds &L
             const uint32_t f = (uint32_t)__ffsll((long long)over) - 1u;
             const uint32_t rbf = rdlane(rb, f), kf = rdlane(krow, f);
             const uint32_t owner = ((rbf / (8u * ROW_TOKENS)) << 3) | ((rbf % (8u * ROW_TOKENS)) >> 2);  // row_base() inverted
+            // zlib reads a literal's code before it looks for room: of a pair that overflows, the second code is consumed only
+            // if the first byte was written
+            const bool both = rdlane(run + incl - 1u, f) <= xcap;
             uint32_t p = B + owner * S_BITS;
-            for (uint32_t j = 0; j <= kf; j++) p = rdfirst(token_end(L, w, p));
+            for (uint32_t j = 0; j <= kf; j++) {
+                const uint32_t tj = rdfirst(grow[rbf + row_word(j)]);
+                p = rdfirst(token_end(L, w, p, (tj >> 31) != 0 && (j < kf || both)));
+            }
             return p;
         }
         run += rdlane(incl, 63u);
@@ -929,13 +944,14 @@ __device__ CHIP_PHASE_FN bool flush_tokens(WaveLds &L, const uint32_t *grow_, ui
         static_assert(TOK_RING == 4, "the wait below counts three younger ring loads");
         asm volatile("s_waitcnt vmcnt(3)" ::: "memory");  // the load into slot_r has landed
         const uint32_t t = C.tok[64u * slot_r + lane];
-        // token: [8:0] literal byte or match length, [9] match, [25:10] distance - 1
+        // token: [8:0] literal byte or match length, [9] match, [25:10] distance - 1; a literal pair: [31], second byte in [23:16]
         // (a literal's byte is the token's low byte as it stands; length and distance are only formed where a match is queued)
         const bool ismatch = (t & 512u) != 0;
         const uint32_t len = ismatch ? t & 0x1ffu : 0u;
         const uint32_t val = ismatch ? __builtin_amdgcn_ubfe(t, 10, 16) + 1u : t;  // distance, or the literal (low byte)
         const uint32_t left = ntok - c0;
-        uint32_t olen = ismatch ? len : 1u;
+        const bool pair = (int32_t)t < 0;
+        uint32_t olen = ismatch ? len : 1u + (t >> 31);
         olen = lane < left ? olen : 0u;  // (only the last group of a batch has lanes behind the end)
         const uint32_t incl = wave_incl_scan(olen);
         const uint32_t start = run + incl - olen;
@@ -953,6 +969,7 @@ __device__ CHIP_PHASE_FN bool flush_tokens(WaveLds &L, const uint32_t *grow_, ui
             // every lane makes both stores, one of them to the trash: two selects instead of two exec-mask regions
             const uint32_t qi = __builtin_amdgcn_mbcnt_hi((uint32_t)(lenm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)lenm, nq)) & (MQ_CAP - 1u);
             *(len == 0 ? img + start : C.trash) = (uint8_t)val;
+            *(pair ? img + start + 1u : C.trash) = (uint8_t)(t >> 16);
             *(len != 0 ? &C.mq[qi] : (uint2 *)(uint8_t *)C.trash) = make_uint2(start, len | (val << 16));
             nq += (uint32_t)__popcll(lenm);
             c0 += 64u;
@@ -972,7 +989,9 @@ __device__ CHIP_PHASE_FN bool flush_tokens(WaveLds &L, const uint32_t *grow_, ui
             // chunk is empty (long matches: 64 tokens can be 16 KB) or the stop is an error
             too_far = stopm != 0 && ((badm & ~nofit) >> nacc) & 1ull;
             if (stopm && !too_far && run != mis) nacc = 0;
+            // (a pair whose second byte does not fit the chunk is a token that does not fit: it goes whole to the next chunk)
             if (lane < nacc && len == 0) img[start] = (uint8_t)val;
+            if (lane < nacc && pair) img[start + 1u] = (uint8_t)(t >> 16);
             const uint64_t mm = lenm & (nacc == 64u ? ~0ull : (1ull << nacc) - 1ull);
             if (lane < nacc && len != 0) {
                 const uint32_t qi = __builtin_amdgcn_mbcnt_hi((uint32_t)(mm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mm, nq)) & (MQ_CAP - 1u);
@@ -1142,14 +1161,32 @@ __device__ CHIP_PHASE_FN uint32_t walk_round(WaveLds &L, const InWin &w, const u
             const uint32_t b16 = ((m >> 4) & 127u) | ((m >> 12) << 7);
             m = pool16[b16 + __builtin_amdgcn_ubfe(w2, DIST_ROOT, m)];
         }
+#ifndef CHIP_EXP_NO_PAIR
+        // A literal takes the literal behind it along as one token (a pair) when there is one, it ends inside the chain's limit, and
+        // its start is no boundary of the segment's owner: a chain that pairs across the owner's boundary walks one literal out of
+        // phase with the owner and cannot join before the run of literals ends.  (Inside its own segment a lane sees no mark in
+        // front of it.)  Whatever else the second code is, the literal goes alone, and that code is met as a token's first.
+        const uint32_t r2 = L.lit_root[w2 & ((1u << LIT_ROOT) - 1u)];
+        const uint32_t e2 = L.pool[(r2 >> 5) + __builtin_amdgcn_ubfe(w2, LIT_ROOT, r2)];
+        const uint32_t p2 = p + n1;
+        const uint32_t mk2 = *(const uint32_t *)((const uint8_t *)L.w.bm + ((p2 >> 3) & ~3u));
+#endif
         const uint32_t cl2 = m & 15u, eb2 = __builtin_amdgcn_ubfe(m, 4, 4);
         const uint32_t dm1 = (__builtin_amdgcn_ubfe(m, 8, 2) << eb2) + __builtin_amdgcn_ubfe(w2, cl2, eb2);
         z = (e & (F_HALT | F_INV)) | (m & D_BAD);
         tl = n1 + cl2 + eb2;
+#ifndef CHIP_EXP_NO_PAIR
+        const uint32_t n2 = __builtin_amdgcn_ubfe(e2, 10, 5);
+        const bool pair = ((e | e2) & (F_LEN | F_HALT)) == 0 && p2 + n2 <= hard_r && ((mk2 >> (p2 & 31u)) & 1u) == 0;
+        tl += pair ? n2 : 0u;
+        const uint32_t pr = pair ? (e2 & 0x00ff0000u) | 0x80000000u : 0u;
+#else
+        const uint32_t pr = 0;
+#endif
         q = p + tl;
         if ((jb | z) != 0 || q > hard_r) return false;
         const uint32_t v = __builtin_amdgcn_ubfe(lo, e, e >> 5) + __builtin_amdgcn_ubfe(e, 16, 9);
-        tok = (((dm1 << 10) | 512u) & msk) | v;
+        tok = (((dm1 << 10) | 512u) & msk) | v | pr;
         nst++;
         return true;
     };
@@ -1277,7 +1314,7 @@ __device__ CHIP_PHASE_FN bool count_tokens(WaveLds &L, const uint32_t *grow_, ui
             const uint32_t t4[4] = {t.x, t.y, t.z, t.w};
 #pragma unroll
             for (uint32_t j = 0; j < 4; j++)
-                if (kq + j >= k0 && kq + j < kend) sum += (t4[j] & 512u) ? t4[j] & 0x1ffu : 1u;
+                if (kq + j >= k0 && kq + j < kend) sum += tok_olen(t4[j]);
         }
     }
     const uint32_t incl = wave_incl_scan(sum);  // (a round's tokens give less than 64 * 256 * 258 bytes)
@@ -1293,7 +1330,7 @@ __device__ CHIP_PHASE_FN bool count_tokens(WaveLds &L, const uint32_t *grow_, ui
                     if (kq + j >= k0 && kq + j < kend) {
                         const bool ismatch = (t4[j] & 512u) != 0;
                         if (ismatch && __builtin_amdgcn_ubfe(t4[j], 10, 16) + 1u > at && badat == 0xffffffffu) badat = at;
-                        at += ismatch ? t4[j] & 0x1ffu : 1u;
+                        at += tok_olen(t4[j]);
                     }
             }
         }

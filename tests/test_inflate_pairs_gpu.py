@@ -1,0 +1,372 @@
+"""Literal pairs in the inflate kernel (compu_amd/csrc/inflate.hip: the walk's `token` step, flush_tokens, count_tokens,
+overflow_bit): a literal token may carry the literal behind it, and nothing a caller sees may change for it.  Streams are built
+with tests/deflate_writer.py and run as raw deflate and as gzip at output misalignments 0-3:
+
+  * literal runs of length 1-5 between matches, with the block's first token at every bit position of a byte;
+  * all-literal blocks of 3 000 / 3 001 (and 6 000 / 6 001) literals: codes of 4-6 bits, and codes of 15 bits only;
+  * a pair or a lone literal in front of the end-of-block code, of a second block, of an invalid code;
+  * input cut at every byte, with the pair's codes at every bit position of a byte (so the cut falls on every bit of a pair);
+  * capacity 0-6 at the stream's start and 2 559 / 2 560 / 2 561 deep inside a run of literals;
+  * literal runs that start at every offset around the first two chunk boundaries of the executor (CHUNK_BYTES = 2 560);
+  * a match of distance 1 and 2 straight behind a pair; fixed-Huffman blocks; a stored block between two dynamic ones.
+
+Bytes, out_len and status are oracle.inflate_units' (same offsets and capacities), status and in_used the oracle decoder's; the
+size pass must name the length the oracle decodes at ample capacity.  The first test needs no GPU: it pins what the oracle (and,
+for valid streams, zlib) says about every case."""
+import os
+import random
+import subprocess
+import sys
+import zlib
+from collections import namedtuple
+
+import numpy as np
+import pytest
+
+import deflate_writer as W
+from oracle import oracle as O
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CHUNK_BYTES = 2560
+POISON = 0xA5
+BAD = -3  # Z_DATA_ERROR
+VALID, INVALID, CUT = "valid", "invalid", "cut"
+
+# kind: VALID (a whole stream: zlib decodes it to `content`), INVALID (`content` is what comes out in front of the bad code),
+# CUT (`data` is a whole stream's first bytes; raw only has a meaning for `body`, gzip gets the header in front and no trailer)
+Case = namedtuple("Case", "name body content kind caps")
+
+# 8 codes of 4 bits, 12 of 5, 8 of 6 (the end-of-block code among them): a complete set
+SHORT_LITS = list(range(97, 97 + 27))
+SHORT_LENS = [0] * 257
+for _i, _s in enumerate(SHORT_LITS):
+    SHORT_LENS[_s] = 4 if _i < 8 else 5 if _i < 20 else 6
+SHORT_LENS[256] = 6
+# end-of-block 1 bit, thirteen unused literals of 2..14 bits, two literals of 15 bits: complete; the data uses the last two only
+LONG_LITS = [200, 201]
+LONG_LENS = [0] * 257
+LONG_LENS[256] = 1
+for _i in range(13):
+    LONG_LENS[_i] = 2 + _i
+LONG_LENS[200] = LONG_LENS[201] = 15
+assert W.kraft(SHORT_LENS) == 32768 and W.kraft(LONG_LENS) == 32768
+
+
+def _lead(d, shift):
+    """non-final fixed blocks in front: empty ones take 10 bits, one with a 9-bit literal 19 -- (2 a + 3 b) mod 8 reaches every shift"""
+    a, b = {0: (0, 0), 1: (0, 3), 2: (1, 0), 3: (0, 1), 4: (2, 0), 5: (1, 1), 6: (3, 0), 7: (2, 1)}[shift]
+    for _ in range(a):
+        d.fixed([])
+    for _ in range(b):
+        d.fixed([200])
+    return d
+
+
+def _prefix(rnd, n):
+    """tokens that give exactly n bytes: forty literals, then long matches, the last one ending at n (a match in front of the run
+    that follows, so that the run's first literal starts a pair)"""
+    toks, pos = [], 0
+    while pos < min(n, 40):
+        toks.append(rnd.choice(SHORT_LITS))
+        pos += 1
+    while pos < n:
+        ln = min(258, n - pos)
+        if n - pos - ln in (1, 2):
+            ln -= 3
+        toks.append(("m", ln, rnd.randrange(1, min(pos, 2000) + 1)))
+        pos += ln
+    return toks
+
+
+def build_cases():
+    rnd = random.Random(20250317)
+    cases = []
+
+    def add(name, d, kind=VALID, caps=(None,), content=None):
+        cases.append(Case(name, d.body(), bytes(d.content) if content is None else content, kind, tuple(caps)))
+
+    def lits(n, alphabet=SHORT_LITS):
+        return [rnd.choice(alphabet) for _ in range(n)]
+
+    # -- short literal runs between matches, the first token at every bit position of a byte
+    for shift in range(8):
+        toks = lits(6)
+        for rep in range(60):
+            for run in (1, 2, 3, 4, 5):
+                toks += lits(run) + [("m", rnd.choice((3, 4, 7, 20)), rnd.randrange(1, 7))]
+        add(f"short_runs_{shift}", _lead(W.Deflate(), shift).dynamic(toks, final=True, ndist=2))
+    # -- all-literal blocks (more than 64 segments of 320 bits: 6 000 short codes, 3 000 long ones)
+    for n in (3000, 3001, 6000, 6001):
+        add(f"all_short_{n}", W.Deflate().dynamic(lits(n), lit_lens=SHORT_LENS, dist_lens=[0], final=True))
+    for n in (3000, 3001):
+        add(f"all_long_{n}", W.Deflate().dynamic(lits(n, LONG_LITS), lit_lens=LONG_LENS, dist_lens=[0], final=True))
+    # -- a pair / a lone literal in front of the end of the block
+    add("tail_pair_eob", W.Deflate().dynamic([97, 98], final=True))
+    add("tail_single_eob", W.Deflate().dynamic([97], final=True))
+    for n in (1, 3, 5, 64, 65):
+        add(f"tail_odd_then_block_{n}", W.Deflate().dynamic(lits(n), lit_lens=SHORT_LENS, dist_lens=[0]).dynamic(lits(4), lit_lens=SHORT_LENS, dist_lens=[0], final=True))
+    # -- ... of an invalid code (the fixed code's symbols 286 and 287; a dynamic block's incomplete set is refused with its header)
+    for n in (1, 2, 3, 4):
+        for bad in (286, 287):
+            d = W.Deflate().fixed([97 + k for k in range(n)] + [("s", bad)], final=True, eob=False).raw_bits(0, 16)
+            add(f"tail_invalid_{n}_{bad}", d, kind=INVALID)
+    # -- input cut at every byte; with the eight shifts the cut falls on every bit of a pair's two codes
+    for shift in range(8):
+        d = _lead(W.Deflate(), shift).dynamic(lits(6, LONG_LITS), lit_lens=LONG_LENS, dist_lens=[0], final=True)
+        body = d.body()
+        for n in range(1, len(body)):  # (no input at all is a call that cannot move: another verdict)
+            cases.append(Case(f"cut_long_{shift}_{n}", body[:n], bytes(d.content), CUT, (None,)))
+        d = _lead(W.Deflate(), shift).dynamic(lits(7), lit_lens=SHORT_LENS, dist_lens=[0], final=True)
+        body = d.body()
+        for n in range(len(body) - 8, len(body)):
+            cases.append(Case(f"cut_short_{shift}_{n}", body[:n], bytes(d.content), CUT, (None,)))
+    # -- capacity: at the stream's start, and on a pair deep inside the unit
+    add("cap_start", W.Deflate().dynamic(lits(5) + [("m", 4, 2)] + lits(3), final=True, ndist=2), caps=(0, 1, 2, 3, 4, 5, 6, None))
+    add("cap_deep_even", W.Deflate().dynamic(lits(3000), lit_lens=SHORT_LENS, dist_lens=[0], final=True), caps=(2559, 2560, 2561, 2999, 3000))
+    add("cap_deep_odd", W.Deflate().dynamic(lits(1) + [("m", 3, 1)] + lits(2995), final=True, ndist=2), caps=(2557, 2558, 2559, 2560, 2561, 2562))
+    # -- literal runs that start (behind a match, so with a pair) at every offset around the first and the second chunk boundary
+    for s in list(range(2552, 2563)) + list(range(5100, 5125)):
+        add(f"chunk_run_{s}", W.Deflate().dynamic(_prefix(rnd, s) + lits(9) + [("m", 5, 3)] + lits(4), final=True, ndist=2))
+    add("chunk_run_lits", W.Deflate().dynamic(lits(2 * CHUNK_BYTES + 40), final=True))
+    # -- a match whose source is the pair in front of it
+    for dist in (1, 2):
+        for ln in (3, 4, 17, 40, 258):
+            add(f"pair_match_{dist}_{ln}", W.Deflate().dynamic([97, ("m", 3, 1), 98, 99, ("m", ln, dist), 100, 101, ("m", ln, dist), 102], final=True, ndist=2))
+        add(f"pair_match_{dist}_many", W.Deflate().dynamic([97] + [98, 99, ("m", 5, dist)] * 150, final=True, ndist=2))
+    # -- other block types
+    toks = []
+    for rep in range(300):
+        toks += lits(rnd.randrange(1, 7), range(97, 200)) + [("m", rnd.choice((3, 5, 30)), rnd.randrange(1, 5))]
+    add("fixed_mixed", W.Deflate().fixed(toks, final=True))
+    add("fixed_all_lits", W.Deflate().fixed(lits(2001, range(120, 170)), final=True))  # 8-bit and 9-bit codes
+    for n in (4, 5):
+        add(f"stored_between_{n}", W.Deflate().dynamic(lits(n)).stored(bytes(lits(7))).dynamic(lits(n), final=True))
+    return cases
+
+
+@pytest.fixture(scope="module")
+def cases():
+    return build_cases()
+
+
+def _units(cases, fmt):
+    """-> [(case, stream, capacity)]"""
+    units = []
+    for c in cases:
+        if fmt == O.MODE_DEFLATE:
+            data = c.body
+        else:
+            data = W.gzip_header() + c.body + (W.gzip_trailer(c.content) if c.kind == VALID else b"")
+        for cap in c.caps:
+            units.append((c, data, len(c.content) + 19 if cap is None else cap))
+    return units
+
+
+def _decoder_verdict(fmt, data, cap):
+    got, ir, orr, st, err = O.InflateDecoder(fmt).decode(data, int(cap))
+    return got, len(data) - ir, (err if err else st)
+
+
+def _layout(units, mis):
+    caps = np.array([u[2] for u in units], dtype=np.int64)
+    ooff = np.zeros(len(units), dtype=np.int64)
+    ooff[1:] = np.cumsum((caps[:-1] + 15 + 16) & ~15)
+    ooff += 16 + mis
+    return ooff, caps, int(ooff[-1] + caps[-1]) + 32
+
+
+def _pack(units):
+    lens = np.array([len(u[1]) for u in units], dtype=np.int64)
+    offs = np.zeros(len(units), dtype=np.int64)
+    offs[1:] = np.cumsum((lens[:-1] + 7) & ~7)
+    buf = np.zeros(int(offs[-1] + lens[-1]) + 8, dtype=np.uint8)
+    for i, u in enumerate(units):
+        buf[offs[i] : offs[i] + lens[i]] = np.frombuffer(u[1], dtype=np.uint8)
+    return buf, offs, lens
+
+
+_ORACLE = {}
+
+
+def _oracle_units(fmt, units, mis):
+    """computed once per (format, misalignment) and shared; nobody changes it"""
+    if (fmt, mis) not in _ORACLE:
+        buf, offs, lens = _pack(units)
+        ooff, caps, total = _layout(units, mis)
+        out = np.full(total, POISON, dtype=np.uint8)
+        out, out_len, status, bad = O.inflate_units(fmt, buf, offs, lens, total, ooff, caps, out=out)
+        for a in (out, out_len, status):
+            a.setflags(write=False)
+        _ORACLE[(fmt, mis)] = (out, out_len, status)
+    return _ORACLE[(fmt, mis)]
+
+
+_VERDICTS = {}
+
+
+def _verdicts(fmt, units):
+    if fmt not in _VERDICTS:
+        _VERDICTS[fmt] = [_decoder_verdict(fmt, data, cap) for _, data, cap in units]
+    return _VERDICTS[fmt]
+
+
+def test_oracle_verdicts(cases):
+    """no GPU: what the oracle says about every case is what the case was built for; zlib agrees on the valid streams"""
+    names = [c.name for c in cases]
+    assert len(set(names)) == len(names)
+    for c in cases:
+        if c.kind == VALID:
+            z = zlib.decompressobj(-15)
+            assert z.decompress(c.body) == c.content and z.eof and z.unused_data == b"", c.name
+    for fmt in (O.MODE_DEFLATE, O.MODE_GZIP):
+        units = _units(cases, fmt)
+        verdicts = _verdicts(fmt, units)
+        for mis in (0, 3):
+            out, out_len, status = _oracle_units(fmt, units, mis)
+            ooff, caps, _ = _layout(units, mis)
+            written = np.zeros(len(out), dtype=bool)
+            for i, (c, data, cap) in enumerate(units):
+                got, used, st = verdicts[i]
+                where = (c.name, fmt, cap, st, used)
+                assert bytes(out[ooff[i] : ooff[i] + out_len[i]]) == got and int(status[i]) == st, where
+                written[ooff[i] : ooff[i] + out_len[i]] = True
+                if c.kind == INVALID:
+                    assert st == BAD and got == c.content, where
+                elif c.kind == CUT:
+                    # the literals whose codes lie whole in front of the cut are out (all of them when only the end-of-block code is cut)
+                    assert st == O.NEED_INPUT and used == len(data) and c.content.startswith(got), where
+                elif cap > len(c.content) or (fmt == O.MODE_DEFLATE and cap == len(c.content)):
+                    assert st == O.FINISHED and got == c.content and used == len(data), where
+                elif cap == len(c.content):
+                    assert st in (O.NEED_OUTPUT, O.FINISHED) and got == c.content, where
+                else:
+                    assert st == O.NEED_OUTPUT and got == c.content[:cap] and used <= len(data), where
+            assert (out[~written] == POISON).all()
+    # the cut cases: between them the cuts leave 0, 1, ... 6 of the six 15-bit literals (a cut inside either code of every pair)
+    by = {c.name: c for c in cases}
+    units = _units(cases, O.MODE_DEFLATE)
+    left = {len(v[0]) for (c, _, _), v in zip(units, _verdicts(O.MODE_DEFLATE, units)) if c.name.startswith("cut_long_")}
+    assert left >= set(range(7))  # (the shifting blocks in front add up to three bytes)
+    # the geometry the cases aim at
+    assert len(by["all_long_3000"].body) * 8 > 64 * 320 and len(by["all_short_6000"].body) * 8 > 64 * 320
+    assert len(by["chunk_run_2560"].content) == 2560 + 9 + 5 + 4 and len(by["cap_deep_even"].content) == 3000
+    assert sum(1 for c in cases if c.kind == INVALID) == 8 and sum(1 for c in cases if c.kind == CUT) > 300
+
+
+def _run_gpu(torch, fmt, units, mis, flags):
+    import compu_amd
+
+    buf, offs, lens = _pack(units)
+    ooff, caps, total = _layout(units, mis)
+    dev = "cuda:0"
+    d_out = torch.full((total,), POISON, dtype=torch.uint8, device=dev)
+    out_len, in_used, status = compu_amd.decode_batch(
+        fmt, torch.from_numpy(buf).to(dev), torch.from_numpy(offs).to(dev), torch.from_numpy(lens.astype(np.int32)).to(dev), d_out,
+        torch.from_numpy(ooff).to(dev), torch.from_numpy(caps.astype(np.int32)).to(dev), flags=flags)
+    torch.cuda.synchronize()
+    return d_out.cpu().numpy(), out_len.cpu().numpy(), in_used.cpu().numpy(), status.cpu().numpy()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("fmt", [O.MODE_DEFLATE, O.MODE_GZIP], ids=["raw", "gzip"])
+@pytest.mark.parametrize("mis", [0, 1, 2, 3])
+def test_pairs_match_the_oracle(gpu, cases, fmt, mis):
+    import compu_amd
+
+    units = _units(cases, fmt)
+    ooff, caps, _ = _layout(units, mis)
+    r_out, r_len, r_st = _oracle_units(fmt, units, mis)
+    verdicts = _verdicts(fmt, units)
+    for flags in (compu_amd.F_COMPU_STATUS, 0):
+        g_out, g_len, g_used, g_st = _run_gpu(gpu, fmt, units, mis, flags)
+        keep = np.ones(len(g_out), dtype=bool)
+        for i, (c, data, cap) in enumerate(units):
+            _, used, st = verdicts[i]
+            where = (c.name, mis, flags, cap, int(g_st[i]), st, int(g_used[i]), used, int(g_len[i]), int(r_len[i]))
+            assert int(g_len[i]) == int(r_len[i]), where
+            lo, hi = int(ooff[i]), int(ooff[i]) + int(r_len[i])
+            assert np.array_equal(g_out[lo:hi], r_out[lo:hi]), where
+            keep[lo:hi] = False
+            if flags & compu_amd.F_COMPU_STATUS:
+                assert int(g_st[i]) == st == int(r_st[i]), where
+                if st in (O.NEED_OUTPUT, O.FINISHED, O.NEED_INPUT):
+                    assert int(g_used[i]) == used, where
+                continue
+            # without the flag, the batch call's two documented deviations (include/compu_hip.h): a unit whose output is exactly
+            # full and whose input is all read reports CHIP_NEED_OUTPUT; in_used is only zlib's count for a finished unit
+            if st == O.NEED_INPUT and int(r_len[i]) == cap and used == len(data) and g_st[i] != O.NEED_INPUT:
+                assert g_st[i] == O.NEED_OUTPUT, where
+                continue
+            assert int(g_st[i]) == st, where
+            if st in (O.FINISHED, O.NEED_INPUT):
+                assert int(g_used[i]) == used, where
+        assert (g_out[keep] == POISON).all(), (mis, flags, np.flatnonzero(g_out[keep] != POISON)[:8])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("fmt", [O.MODE_DEFLATE, O.MODE_GZIP], ids=["raw", "gzip"])
+def test_size_pass_agrees_with_the_decoded_length(gpu, cases, fmt):
+    """the size pass counts a pair as two bytes: its length and status are those of a decode at ample capacity (every case once)"""
+    import compu_amd
+
+    units = [(c, data, len(c.content) + 19) for c, data, cap in _units(cases, fmt) if cap == c.caps[0]]
+    buf, offs, lens = _pack(units)
+    ooff, caps, total = _layout(units, 0)
+    _, r_len, r_st, _ = O.inflate_units(fmt, buf, offs, lens, total, ooff, caps)
+    dev = "cuda:0"
+    d_in, d_off, d_len = gpu.from_numpy(buf).to(dev), gpu.from_numpy(offs).to(dev), gpu.from_numpy(lens.astype(np.int32)).to(dev)
+    size, _, st = compu_amd.decode_batch_sizes(fmt, d_in, d_off, d_len)
+    d_out = gpu.zeros(total, dtype=gpu.uint8, device=dev)
+    g_len, _, g_st = compu_amd.decode_batch(fmt, d_in, d_off, d_len, d_out, gpu.from_numpy(ooff).to(dev), gpu.from_numpy(caps.astype(np.int32)).to(dev))
+    gpu.cuda.synchronize()
+    size, st, g_len, g_st = size.cpu().numpy(), st.cpu().numpy(), g_len.cpu().numpy(), g_st.cpu().numpy()
+    for i, (c, _, _) in enumerate(units):
+        where = (c.name, int(size[i]), int(g_len[i]), int(r_len[i]), int(st[i]), int(g_st[i]), int(r_st[i]))
+        assert int(size[i]) == int(g_len[i]) == int(r_len[i]) and int(st[i]) == int(g_st[i]) == int(r_st[i]), where
+
+
+_STATS_CHILD = r"""
+import os, sys
+import numpy as np, torch
+sys.path.insert(0, sys.argv[1]); sys.path.insert(0, os.path.join(sys.argv[1], "tests"))
+import compu_amd
+import test_inflate_pairs_gpu as T
+cases = [c for c in T.build_cases() if c.name.startswith("all_")]
+units = [(c, c.body, len(c.content) + 19) for c in cases]
+buf, offs, lens = T._pack(units)
+ooff, caps, total = T._layout(units, 0)
+dev = "cuda:0"
+stats = torch.zeros(len(units) * 24, dtype=torch.int64, device=dev)
+os.environ["CHIP_STATS_PTR"] = str(stats.data_ptr())
+out = torch.zeros(total, dtype=torch.uint8, device=dev)
+ol, iu, st = compu_amd.decode_batch(-15, torch.from_numpy(buf).to(dev), torch.from_numpy(offs).to(dev), torch.from_numpy(lens.astype(np.int32)).to(dev), out,
+                                    torch.from_numpy(ooff).to(dev), torch.from_numpy(caps.astype(np.int32)).to(dev))
+torch.cuda.synchronize()
+assert (st.cpu().numpy() == 2).all()
+s = stats.cpu().numpy().reshape(len(units), 24)
+print("ROUNDS", " ".join(f"{c.name}={int(s[i, 8])}:{int(s[i, 10])}" for i, c in enumerate(cases)))
+"""
+
+
+@pytest.mark.gpu
+def test_pairing_does_not_cost_super_rounds(gpu):
+    """The mark rule (no pair across a boundary the segment's owner marked): without it a chain one literal out of phase with
+    the owner never joins inside a run of literals and the super-rounds collapse.  The -DCHIP_STATS build counts super-rounds per
+    unit (slot 8) and tokens (slot 10); the same build with -DCHIP_EXP_NO_PAIR is the yardstick.  One process per library."""
+    libs = [os.path.join(ROOT, "compu_amd", n) for n in ("libcompu_hip_stats.so", "libcompu_hip_stats_nopair.so")]
+    if not all(os.path.exists(p) for p in libs):
+        pytest.skip("the diagnostic builds are not built (CHIP_BUILD_STATS=1 compu_amd/csrc/build.sh makes both): "
+                    "parity of the all-literal blocks is checked by test_pairs_match_the_oracle only")
+    got = []
+    for lib in libs:
+        r = subprocess.run([sys.executable, "-c", _STATS_CHILD, ROOT], env=dict(os.environ, COMPU_HIP_LIB=lib), capture_output=True, text=True, timeout=120)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = [l for l in r.stdout.splitlines() if l.startswith("ROUNDS ")][-1]
+        got.append({k: tuple(int(x) for x in v.split(":")) for k, v in (kv.split("=") for kv in line.split()[1:])})
+    print(got)
+    for name, (rounds, tokens) in got[0].items():
+        rounds0, tokens0 = got[1][name]
+        assert rounds <= rounds0, (name, rounds, rounds0)
+        # a block of literals only: a lane leaves at most two literals of its segment (21 or more) alone, the one in front of the
+        # join and one for parity, so at most 12 tokens stand for 21 literals
+        assert tokens < 0.7 * tokens0, (name, tokens, tokens0)

@@ -51,8 +51,55 @@ static uint64_t g_pairs9, g_pairs10, g_pairs11, g_pairs12, g_lits, g_litpairs_po
 static uint64_t g_dhist[4096]; static uint64_t g_clh[16], g_dclh[16], g_ntokh;
 
 #define MAXSEG 4096
+// ---- current scheme with the "literal pair" policy (pairs = 1) or without (pairs = 0, the same replay as below plus the counts):
+// a literal takes the literal behind it along in the same step when the pair ends inside the lane's limit and the second
+// literal's start is not a boundary the segment's owner has marked (a lane sees no mark in front of it inside its own segment).
+// Only a token's start is marked.  Counts per block: wave-steps, lane-tokens, tokens and pieces of the true stream, super-rounds.
+static double g_pp_steps[2], g_pp_lanetok[2], g_pp_tok[2], g_pp_pieces[2], g_pp_rounds[2];
+static void sim_pairs(Block *b, int S, int XT, int pairs) {
+    uint32_t n = b->end - b->start, B = 0; double steps = 0, lanetok = 0, tok = 0, pieces = 0, rounds = 0;
+    static uint8_t mark[1 << 22]; static uint32_t at[64][260];
+    while (B < n && b->tb[B]) {
+        uint32_t p[64], lim[64]; int act[64]; int nact = 0;
+        memset(mark + B, 0, (size_t)64 * S + 64 < n - B ? (size_t)64 * S + 64 : n - B);
+        for (int l = 0; l < 64; l++) { p[l] = B + l * S; lim[l] = p[l] + S + XT; if (lim[l] > B + 64u * S) lim[l] = B + 64u * S; act[l] = p[l] < n; nact += act[l]; }
+        int st = 0; uint32_t endpos = 0; int joined_to[64]; uint32_t stop[64]; int cnt[64];
+        for (int l = 0; l < 64; l++) { joined_to[l] = -1; stop[l] = 0; cnt[l] = 0; }
+        while (nact) {
+            st++;
+            for (int l = 0; l < 64; l++) if (act[l]) {
+                uint32_t seg = (p[l] - B) / S; if (seg > 63) seg = 63;
+                if ((int)seg == l) mark[p[l]] = 1;
+                else if (mark[p[l]]) { act[l] = 0; nact--; joined_to[l] = seg; stop[l] = p[l]; continue; }
+                int t = p[l] < n ? b->tb[p[l]] : 0;
+                if (!t) { act[l] = 0; nact--; stop[l] = p[l]; continue; }
+                at[l][cnt[l]] = p[l];
+                if (pairs && b->lit[p[l]]) {
+                    uint32_t p2 = p[l] + t; int t2 = p2 < n ? b->tb[p2] : 0;
+                    uint32_t seg2 = (p2 - B) / S; if (seg2 > 63) seg2 = 63;
+                    if (t2 && b->lit[p2] && p2 + t2 <= lim[l] && !((int)seg2 != l && mark[p2])) t += t2;
+                }
+                p[l] += t; cnt[l]++; lanetok++;
+                if (p[l] >= lim[l] || cnt[l] >= 252) { act[l] = 0; nact--; stop[l] = p[l]; }
+            }
+        }
+        steps += st; rounds++;
+        // the true stream: lane 0's chain, then the chain it joined from the join on
+        int l = 0; uint32_t from = B;
+        for (;;) {
+            int k0 = 0; while (k0 < cnt[l] && at[l][k0] < from) k0++;
+            if (cnt[l] > k0) { tok += cnt[l] - k0; pieces++; }  // (a lane that joined took no token at or behind the join)
+            if (joined_to[l] < 0) { endpos = stop[l]; break; }
+            from = stop[l]; l = joined_to[l];
+        }
+        if (endpos <= B) break;
+        B = endpos;
+    }
+    g_pp_steps[pairs] += steps; g_pp_lanetok[pairs] += lanetok; g_pp_tok[pairs] += tok; g_pp_pieces[pairs] += pieces; g_pp_rounds[pairs] += rounds;
+}
 static void sim_block(Block *b, int S, int XT, int ring, int refill_every, int refill_min) {
     uint32_t n = b->end - b->start;
+    sim_pairs(b, S, XT, 0); sim_pairs(b, S, XT, 1);
     // ---- true chain marks
     // ---- current scheme: super-rounds of 64 segments from true position B
     {
@@ -193,16 +240,19 @@ int main(int argc, char **argv) {
             for (;;) { int il = 0, ll = 0; int t = token(&hl, &hd, p, &il, &ll); if (!t) break; g_clh[g_cur_cl]++; g_ntokh++; if (!il) g_dclh[g_cur_dcl]++; if (il) { g_lits++; if (prevlit) { int s = prevlen + ll; g_litpairs_possible++; if (s <= 9) g_pairs9++; if (s <= 10) g_pairs10++; if (s <= 11) g_pairs11++; if (s <= 12) g_pairs12++; } } prevlit = il; prevlen = ll; p += t; ntok++; }
             uint32_t eob = p; { uint32_t q = p; dec(&hl, &q); p = q; }
             Block b; b.start = pos; b.end = eob; b.ntok = ntok; uint32_t n = eob - pos;
-            b.tb = calloc(n + 64, 1);
-            for (uint32_t q = 0; q < n; q++) { int il, ll; int t = token(&hl, &hd, pos + q, &il, &ll); if (pos + q + t > eob + 0 && t) { /* runs past EOB start: allow */ } b.tb[q] = t; }
+            b.tb = calloc(n + 64, 1); b.lit = calloc(n + 64, 1);
+            for (uint32_t q = 0; q < n; q++) { int il = 0, ll; int t = token(&hl, &hd, pos + q, &il, &ll); if (pos + q + t > eob + 0 && t) { /* runs past EOB start: allow */ } b.tb[q] = t; b.lit[q] = t && il; }
             g_tok += ntok;
             sim_block(&b, S, XT, ring, re, rmin);
-            free(b.tb); pos = p;
+            free(b.tb); free(b.lit); pos = p;
         }
         g_units++; free(in);
     }
     printf("units %.0f tokens/unit %.0f | current: steps/unit %.0f lane-tokens/unit %.0f (x%.2f) | rolling(S=%d ring=%d every=%d min=%d): steps/unit %.0f lane-tokens %.0f (x%.2f)\n",
            g_units, g_tok / g_units, g_steps_cur / g_units, g_lanetok_cur / g_units, g_lanetok_cur / g_tok, S, ring, re, rmin, g_steps_roll / g_units, g_lanetok_roll / g_units, g_lanetok_roll / g_tok);
+    for (int k = 0; k < 2; k++)
+        printf("literal pairs %s: wave-steps/unit %.0f lane-tokens/unit %.0f tokens/unit %.0f super-rounds/unit %.2f lanes on the path per super-round %.1f\n", k ? "on " : "off",
+               g_pp_steps[k] / g_units, g_pp_lanetok[k] / g_units, g_pp_tok[k] / g_units, g_pp_rounds[k] / g_units, g_pp_pieces[k] / g_pp_rounds[k]);
     printf("early-cut(active<=%d): steps/unit %.0f lane-tokens %.0f\n", g_cut, g_steps_cut / g_units, g_lanetok_cut / g_units);
     printf("literals/unit %.0f; adjacent literal pairs with total code bits <=9: %.3f <=10: %.3f <=11: %.3f <=12: %.3f (of adjacent lit-lit pairs %.0f/unit)\n", g_lits / g_units,
            (double)g_pairs9 / g_litpairs_possible, (double)g_pairs10 / g_litpairs_possible, (double)g_pairs11 / g_litpairs_possible, (double)g_pairs12 / g_litpairs_possible, g_litpairs_possible / g_units);
