@@ -85,14 +85,19 @@ constexpr int CL_ROOT = 7;
 //   lit_root[next 9 bits] (16 bits) = [4:0] number of further index bits nb, [15:5] index in pool[] of the code's
 //   entry (nb = 0) or of its prefix's sub-table (2^nb entries, indexed by the nb bits behind the root's nine);
 //   pool[] entry (32 bits, "final"): [4:0] code length cl, [9:5] number of extra bits eb, [14:10] cl + eb,
-//   [15] halt (end of block, or with [25]: invalid code), [24:16] value (literal byte, or length base 3..258),
-//   [31] length code.  The fields sit where v_bfe_u32 / v_alignbit_b32 read their 5-bit offset and width operands.
+//   [15] halt (end of block, or with [26]: invalid code), [25:16] value as the token wants it (literal byte, or 512 + length
+//   base 3..258: the token's match bit comes with the base), [31] length code.  The fields sit where v_bfe_u32 /
+//   v_alignbit_b32 read their 5-bit offset and width operands.  A root entry's [15:3] is the byte offset of the pool entry or
+//   sub-table as it stands (nb is below 8, the offset a multiple of 4).
 // Distance codes: dist_root[next 8 bits] (16 bits) is the final entry for codes of up to 8 bits (99 % of matches):
 //   [3:0] code length, [7:4] number of extra bits, [9:8] mantissa (distance - 1 = mantissa << extra bits, plus the extra
-//   bits' value), [10] invalid code, [11] longer code: then [3:0] is the number of further index bits and
-//   {[15:12], [10:4]} the index (in 16-bit units) of a sub-table of such entries at the top of pool[].
-constexpr uint32_t F_HALT = 1u << 15, F_INV = 1u << 25, F_LEN = 1u << 31;
-constexpr uint32_t D_BAD = 1u << 10, D_LONG = 1u << 11;
+//   bits' value), [10] invalid code, [15] longer code: then [3:0] is the number of further index bits and [11:3] the byte
+//   offset of a sub-table of such entries from DIST_SUB_BYTES on (the sub-tables lie in the top 256 16-bit units of pool[],
+//   and each starts at an even unit).
+constexpr uint32_t F_HALT = 1u << 15, F_INV = 1u << 26, F_LEN = 1u << 31;
+constexpr uint32_t D_BAD = 1u << 10, D_LONG = 1u << 15;
+static_assert(15 - LIT_ROOT < 8 && 15 - DIST_ROOT < 8, "a root entry's index bit count leaves its bits [4:3] clear");
+static_assert((2u << (15 - DIST_ROOT)) - 2u < 256u, "the distance sub-tables fit the 256 units that a root entry's offset spans");
 
 __device__ __forceinline__ uint32_t make_final(uint32_t sym, uint32_t len)
 {
@@ -106,7 +111,7 @@ __device__ __forceinline__ uint32_t make_final(uint32_t sym, uint32_t len)
         eb = (s >> 2) - 1;
         base = 3 + ((4 + (s & 3)) << eb);
     }
-    return len | (eb << 5) | ((len + eb) << 10) | (base << 16) | F_LEN;
+    return len | (eb << 5) | ((len + eb) << 10) | ((512u | base) << 16) | F_LEN;
 }
 __device__ __forceinline__ uint32_t make_dist16(uint32_t sym, uint32_t len)
 {
@@ -194,6 +199,7 @@ constexpr uint32_t PHASE_BYTES = 8 * WIN_DW > FLUSH_BYTES ? (8 * WIN_DW > HDR_BY
 #endif
 constexpr uint32_t POOL_WORDS = (CHIP_LDS_BYTES - 2 * 512 - 2 * 256 - PHASE_BYTES) / 4;
 constexpr uint32_t POOL_U16 = 2 * POOL_WORDS;
+constexpr uint32_t DIST_SUB_BYTES = 2 * (POOL_U16 - 256);  // byte offset in pool[] that a long distance code's root entry counts from
 
 struct alignas(16) WaveLds {
     union {  // first: the walk's window reads (ds_read2_b32) take small offsets only
@@ -464,7 +470,7 @@ __device__ CHIP_PHASE_FN int build_dist(WaveLds &L, const uint8_t *lens, int n, 
                     }
                     pool16[base16 + t] = (uint16_t)e;
                 }
-                L.dist_root[__brev(xj >> (15 - DIST_ROOT)) >> (32 - DIST_ROOT)] = (uint16_t)(D_LONG | sb | ((base16 & 127u) << 4) | ((base16 >> 7) << 12));
+                L.dist_root[__brev(xj >> (15 - DIST_ROOT)) >> (32 - DIST_ROOT)] = (uint16_t)(D_LONG | sb | ((2u * base16 - DIST_SUB_BYTES) << 3));
             }
             used16 += total;
         }
@@ -472,6 +478,18 @@ __device__ CHIP_PHASE_FN int build_dist(WaveLds &L, const uint8_t *lens, int n, 
     WSYNC();
     return 0;
 }
+// The pool entry of the literal/length code whose first bits are x's low ones; r = lit_root[x's low LIT_ROOT bits].  The root entry
+// is used as it stands: [15:3] is a byte offset, [4:0] the width of the sub-table index.
+__device__ __forceinline__ uint32_t pool_at(const WaveLds &L, uint32_t r, uint32_t x)
+{
+    return *(const uint32_t *)((const uint8_t *)L.pool + ((r >> 3) + (__builtin_amdgcn_ubfe(x, LIT_ROOT, r) << 2)));
+}
+// The sub-table entry of a distance code of more than DIST_ROOT bits; m = its root entry (D_LONG set), x's low bits the code.
+__device__ __forceinline__ uint32_t dist_sub_at(const WaveLds &L, uint32_t m, uint32_t x)
+{
+    return *(const uint16_t *)((const uint8_t *)L.pool + DIST_SUB_BYTES + (__builtin_amdgcn_ubfe(m, 3, 9) + (__builtin_amdgcn_ubfe(x, DIST_ROOT, m) << 1)));
+}
+
 struct InWin {
     const uint32_t *g32;  // dword-aligned base covering the unit's bytes
     uint32_t total_dw;    // dwords that contain at least one byte of the unit
@@ -804,24 +822,20 @@ __device__ __forceinline__ uint32_t lane_gather(uint32_t x, uint32_t src)
 // (second: the token is a literal pair and the code of its second literal counts too)
 __device__ uint32_t token_end(const WaveLds &L, const InWin &w, uint32_t p, bool second)
 {
-    const uint16_t *const pool16 = (const uint16_t *)L.pool;
     const uint32_t i = p >> 5;
     const uint32_t d0 = i < w.total_dw ? w.g32[i] : 0u, d1 = i + 1u < w.total_dw ? w.g32[i + 1u] : 0u, d2 = i + 2u < w.total_dw ? w.g32[i + 2u] : 0u;
     const uint32_t lo = __builtin_amdgcn_alignbit(d1, d0, p), hi = __builtin_amdgcn_alignbit(d2, d1, p);
     const uint32_t r = L.lit_root[lo & ((1u << LIT_ROOT) - 1u)];
-    const uint32_t e = L.pool[(r >> 5) + __builtin_amdgcn_ubfe(lo, LIT_ROOT, r)];
+    const uint32_t e = pool_at(L, r, lo);
     const uint32_t n1 = __builtin_amdgcn_ubfe(e, 10, 5);
     const uint32_t w2 = __builtin_amdgcn_alignbit(hi, lo, n1);
     if (!(e & F_LEN)) {
         if (!second) return p + n1;
         const uint32_t r2 = L.lit_root[w2 & ((1u << LIT_ROOT) - 1u)];
-        return p + n1 + __builtin_amdgcn_ubfe(L.pool[(r2 >> 5) + __builtin_amdgcn_ubfe(w2, LIT_ROOT, r2)], 10, 5);
+        return p + n1 + __builtin_amdgcn_ubfe(pool_at(L, r2, w2), 10, 5);
     }
     uint32_t m = L.dist_root[w2 & ((1u << DIST_ROOT) - 1u)];
-    if (m & D_LONG) {
-        const uint32_t b16 = ((m >> 4) & 127u) | ((m >> 12) << 7);
-        m = pool16[b16 + __builtin_amdgcn_ubfe(w2, DIST_ROOT, m)];
-    }
+    if (m & D_LONG) m = dist_sub_at(L, m, w2);
     return p + n1 + (m & 15u) + __builtin_amdgcn_ubfe(m, 4, 4);
 }
 
@@ -1048,16 +1062,14 @@ __device__ CHIP_PHASE_FN bool flush_tokens(WaveLds &L, const uint32_t *grow_, ui
         const uint32_t xcap = cap - (opos - mis);
         {
             const uint32_t xe = run < xcap ? run : xcap;
-            for (uint32_t xq = 4u * lane; xq < xe; xq += 256u) {
-                const uint32_t wv = C.out[xq >> 2];
-                if (xq >= mis && xq + 4u <= xe) {
-                    *(GAS uint32_t *)(base + xq) = wv;
-                } else {
-#pragma unroll
-                    for (int k = 0; k < 4; k++)
-                        if (xq + k >= mis && xq + k < xe) ((GAS uint8_t *)base)[xq + k] = (uint8_t)(wv >> (8 * k));
-                }
-            }
+            // The whole 16-byte blocks from image offset 16 on: one LDS read and one global store of four dwords per lane and trip
+            // (the image offset is a multiple of 16, the address dword aligned), 1 KiB per trip.
+            for (uint32_t xq = 16u + 16u * lane; xq + 16u <= xe; xq += 1024u) *(GAS u32x4_a4 *)(base + xq) = *(const LDS_AS u32x4 *)(img + xq);
+            // The first block (what lies below `mis` belongs to the chunk before) and the partial last one, byte-exact: lanes 0..15
+            // hold the first block's bytes, lanes 16..31 those behind the last whole block; one byte store for both.
+            const uint32_t xt = xe < 16u ? 16u : xe & ~15u;
+            const uint32_t xb = lane < 16u ? lane : xt + (lane - 16u);
+            if (lane < 32u && xb >= mis && xb < xe) ((GAS uint8_t *)base)[xb] = img[xb];
         }
         WSYNC();  // the next chunk overwrites the image and may load these bytes from memory
         STAT_ACC(18);
@@ -1097,26 +1109,47 @@ __device__ CHIP_PHASE_FN uint32_t walk_round(WaveLds &L, const InWin &w, const u
     GAS const uint32_t *const g32 = rdfirst_gptr(w.g32);
     const uint32_t total_dw = rdfirst(w.total_dw);
     GAS uint32_t *const myrow = rdfirst_gptr(rows_) + row_base(lane);
-    uint16_t *const pool16 = (uint16_t *)L.pool;
     const uint32_t D0 = B >> 5;
     WSYNC();  // the phase before (header parse, previous flush) is done with the window's place
     {
+        // Four dwords per lane and access: WIN_Q whole quads of input (loaded dword aligned, stored 16-byte aligned: win[] is the
+        // structure's first member) and BM_Q 16-byte aligned quads of zeroed mark bits.  What that leaves goes one dword per lane
+        // in a narrow step of EDGE_LANES lanes: the quad the input ends in (lanes 0..3: no load touches a dword at or beyond
+        // total_dw; the wide store has zeroed the quad, these dwords overwrite it), the window's dwords behind its last whole
+        // quad, and the mark words in front of and behind the aligned quads.  win[] and bm[] are neighbours: one index serves both.
+        constexpr uint32_t WIN_Q = WIN_DW / 4, WIN_R = WIN_DW % 4;
+        constexpr uint32_t BM_A = (WIN_DW + 3u) & ~3u;                // first 16-byte aligned word of bm[], as an index from win[0]
+        constexpr uint32_t BM_Q = (2u * WIN_DW - BM_A) / 4, BM_TAIL = (2u * WIN_DW - BM_A) % 4;
+        constexpr uint32_t EDGE_LO = WIN_R + (BM_A - WIN_DW);         // dwords between the window's last whole quad and BM_A
+        constexpr uint32_t EDGE_LANES = 4u + EDGE_LO + BM_TAIL;
+        constexpr uint32_t PER_LANE = (WIN_Q + 63) / 64;
+        static_assert(offsetof(WaveLds, w.win) == 0 && offsetof(WaveLds, w.bm) == 4 * WIN_DW && BM_Q <= WIN_Q && EDGE_LANES <= 64, "window staging");
+        uint32_t *const ww = L.w.win;
+        const uint32_t rem = total_dw - D0;  // dwords of input from the window's first on (at least one: B lies inside the input)
         // all loads of the window go out before the first LDS store waits for one
-        constexpr uint32_t PER_LANE = (WIN_DW + 63) / 64;
-        uint32_t v[PER_LANE];
-#pragma unroll
-        for (uint32_t j = 0; j < PER_LANE; j++) {
-            const uint32_t i = D0 + 64u * j + lane;
-            v[j] = i < total_dw ? g32[i] : 0u;
+        static_assert(PER_LANE <= 4, "the quads per lane below");  // (named values, not an array: as an array the compiler waits for each load in turn)
+        auto quad = [&](uint32_t j) -> u32x4 {
+            const uint32_t k = 64u * j + lane;
+            if ((64u * j + 63u < WIN_Q || k < WIN_Q) && 4u * k + 4u <= rem) return *(GAS const u32x4_a4 *)(g32 + D0 + 4u * k);
+            return u32x4{0, 0, 0, 0};
+        };
+        const u32x4 v0 = quad(0), v1 = quad(1), v2 = quad(2), v3 = quad(3);  // (a quad index no lane has costs nothing)
+        uint32_t ni = 4u * (rem >> 2) + lane;
+        bool nput = ni < rem && ni < 4u * WIN_Q;
+        if (lane >= 4u) {
+            const uint32_t j = lane - 4u;
+            ni = j < EDGE_LO ? 4u * WIN_Q + j : 2u * WIN_DW - BM_TAIL + (j - EDGE_LO);
+            nput = j < EDGE_LO + BM_TAIL;
         }
+        uint32_t nv = 0;
+        if (nput && ni < rem && ni < WIN_DW) nv = g32[D0 + ni];
 #pragma unroll
         for (uint32_t j = 0; j < PER_LANE; j++) {
             const uint32_t k = 64u * j + lane;
-            if (k < WIN_DW) {
-                L.w.win[k] = v[j];
-                L.w.bm[k] = 0;
-            }
+            if (64u * j + 63u < WIN_Q || k < WIN_Q) *(u32x4 *)(ww + 4u * k) = j == 0 ? v0 : j == 1 ? v1 : j == 2 ? v2 : v3;
+            if (64u * j + 63u < BM_Q || k < BM_Q) *(u32x4 *)(ww + BM_A + 4u * k) = u32x4{0, 0, 0, 0};
         }
+        if (nput) ww[ni] = nv;
     }
     LSYNC();
     STAT_ACC(1);
@@ -1152,27 +1185,25 @@ __device__ CHIP_PHASE_FN uint32_t walk_round(WaveLds &L, const InWin &w, const u
         const uint32_t d0 = wp[0], d1 = wp[1], d2 = wp[2];
         const uint32_t lo = __builtin_amdgcn_alignbit(d1, d0, p), hi = __builtin_amdgcn_alignbit(d2, d1, p);
         const uint32_t r = L.lit_root[lo & ((1u << LIT_ROOT) - 1u)];
-        const uint32_t e = L.pool[(r >> 5) + __builtin_amdgcn_ubfe(lo, LIT_ROOT, r)];
+        const uint32_t e = pool_at(L, r, lo);
         const uint32_t n1 = __builtin_amdgcn_ubfe(e, 10, 5);
         const uint32_t msk = (uint32_t)((int32_t)e >> 31);  // all ones for a length code
         const uint32_t w2 = __builtin_amdgcn_alignbit(hi, lo, n1);
         uint32_t m = L.dist_root[w2 & ((1u << DIST_ROOT) - 1u)] & msk;
-        if (m & D_LONG) {  // a distance code of more than 8 bits (1 % of the matches): through its sub-table
-            const uint32_t b16 = ((m >> 4) & 127u) | ((m >> 12) << 7);
-            m = pool16[b16 + __builtin_amdgcn_ubfe(w2, DIST_ROOT, m)];
-        }
+        if (m & D_LONG) m = dist_sub_at(L, m, w2);  // a distance code of more than 8 bits (1 % of the matches): through its sub-table
 #ifndef CHIP_EXP_NO_PAIR
         // A literal takes the literal behind it along as one token (a pair) when there is one, it ends inside the chain's limit, and
         // its start is no boundary of the segment's owner: a chain that pairs across the owner's boundary walks one literal out of
         // phase with the owner and cannot join before the run of literals ends.  (Inside its own segment a lane sees no mark in
         // front of it.)  Whatever else the second code is, the literal goes alone, and that code is met as a token's first.
         const uint32_t r2 = L.lit_root[w2 & ((1u << LIT_ROOT) - 1u)];
-        const uint32_t e2 = L.pool[(r2 >> 5) + __builtin_amdgcn_ubfe(w2, LIT_ROOT, r2)];
+        const uint32_t e2 = pool_at(L, r2, w2);
         const uint32_t p2 = p + n1;
         const uint32_t mk2 = *(const uint32_t *)((const uint8_t *)L.w.bm + ((p2 >> 3) & ~3u));
 #endif
         const uint32_t cl2 = m & 15u, eb2 = __builtin_amdgcn_ubfe(m, 4, 4);
-        const uint32_t dm1 = (__builtin_amdgcn_ubfe(m, 8, 2) << eb2) + __builtin_amdgcn_ubfe(w2, cl2, eb2);
+        // (only a token that is taken uses dm1: its entry has neither D_BAD nor D_LONG, so what lies above bit 8 is the mantissa)
+        const uint32_t dm1 = ((m >> 8) << eb2) + __builtin_amdgcn_ubfe(w2, cl2, eb2);
         z = (e & (F_HALT | F_INV)) | (m & D_BAD);
         tl = n1 + cl2 + eb2;
 #ifndef CHIP_EXP_NO_PAIR
@@ -1185,9 +1216,8 @@ __device__ CHIP_PHASE_FN uint32_t walk_round(WaveLds &L, const InWin &w, const u
 #endif
         q = p + tl;
         if ((jb | z) != 0 || q > hard_r) return false;
-        const uint32_t v = __builtin_amdgcn_ubfe(lo, e, e >> 5) + __builtin_amdgcn_ubfe(e, 16, 9);
-        tok = (((dm1 << 10) | 512u) & msk) | v | pr;
-        nst++;
+        const uint32_t v = __builtin_amdgcn_ubfe(lo, e, e >> 5) + __builtin_amdgcn_ubfe(e, 16, 10);  // (a length's entry brings the match bit)
+        tok = (dm1 << 10) | v | pr;  // (a literal's m is zero, and so is its dm1)
         return true;
     };
     bool full = false;  // the lane's row is full
@@ -1196,7 +1226,7 @@ __device__ CHIP_PHASE_FN uint32_t walk_round(WaveLds &L, const InWin &w, const u
         uint32_t t4[4];  // (a slot whose token is not taken keeps whatever its registers hold: nothing reads a row behind its lane's count)
 #pragma unroll
         for (int k = 0; k < 4; k++) asm volatile("" : "=v"(t4[k]));
-        const uint32_t ng = nst;
+        uint32_t took = 0;  // tokens the lane takes in this trip: a constant per step, added to the row's count once
         if (run) {
             if (nst + 4u > ROW_TOKENS) {
                 run = false;
@@ -1204,16 +1234,23 @@ __device__ CHIP_PHASE_FN uint32_t walk_round(WaveLds &L, const InWin &w, const u
             } else {
                 bool ok = token(t4[0]);
                 if (ok) {
+                    took = 1;
                     ok = token(t4[1]);
                     if (ok) {
+                        took = 2;
                         ok = token(t4[2]);
-                        if (ok) ok = token(t4[3]);
+                        if (ok) {
+                            took = 3;
+                            ok = token(t4[3]);
+                            if (ok) took = 4;
+                        }
                     }
                 }
                 run = ok;
             }
         }
-        if (nst > ng) *(GAS u32x4 *)(myrow + 8u * ng) = u32x4{t4[0], t4[1], t4[2], t4[3]};  // ng is a multiple of 4: row_word(ng)
+        if (took) *(GAS u32x4 *)(myrow + 8u * nst) = u32x4{t4[0], t4[1], t4[2], t4[3]};  // nst is a multiple of 4 here: row_word(nst)
+        nst += took;
     }
     // back to stream positions: a lane that dropped out stands behind the token it did not take
     const bool dropped = s0 < end_bit && !full;
