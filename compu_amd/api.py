@@ -42,6 +42,10 @@ class _BrotliEncoderOpts(C.Structure):
     _fields_ = [("quality", C.c_int32), ("mode", C.c_int32), ("lgwin", C.c_int32), ("device", C.c_int32)]
 
 
+class _BgzfSummary(C.Structure):
+    _fields_ = [("n_blocks", C.c_uint64), ("total_out", C.c_uint64), ("in_used", C.c_uint64), ("status", C.c_int32), ("eof", C.c_uint32)]
+
+
 _lib = None
 
 
@@ -124,6 +128,12 @@ def lib():
     L.chip_encode_batch_ex.argtypes = [C.c_int, C.c_int, C.c_int, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.chip_encode_bound.restype = sz
     L.chip_encode_bound.argtypes = [C.c_int, sz]
+    L.chip_bgzf_plan_host.restype = C.c_int
+    L.chip_bgzf_plan_host.argtypes = [vp, C.c_uint64, C.c_uint64, vp, vp, vp, vp, C.POINTER(_BgzfSummary)]
+    L.chip_bgzf_plan.restype = C.c_int
+    L.chip_bgzf_plan.argtypes = [vp, C.c_uint64, C.c_uint64, vp, vp, vp, vp, C.POINTER(_BgzfSummary), vp]
+    L.chip_bgzf_eof_block.restype = vp
+    L.chip_bgzf_eof_block.argtypes = [C.POINTER(C.c_size_t)]
     _lib = L
     return L
 
@@ -961,7 +971,8 @@ def encode_bound(fmt, in_len):
 
 def encode_batch(fmt, level, in_buf, in_off, in_len, out_buf, out_off, out_cap, out_len=None, status=None, stream=None, strategy=0):
     """chip_encode_batch_ex over device tensors: level 0 stored, 1 fixed Huffman, 2..9 (-1 = 6) dynamic Huffman blocks; FMT_ZSTD:
-    zstd levels and ZstdStrategy values; FMT_BROTLI: level = quality 0..11 (0 = 11), strategy = mode 0..3, lgwin 22."""
+    zstd levels and ZstdStrategy values; FMT_BROTLI: level = quality 0..11 (0 = 11), strategy = mode 0..3, lgwin 22; FMT_BGZF: levels and
+    strategies as ZlibMode.Gzip, one BGZF block per unit, a unit above 65280 bytes is EncodeStatus.Error with out_len 0."""
     import torch
 
     n = in_len.numel()
@@ -978,3 +989,109 @@ def encode_batch(fmt, level, in_buf, in_off, in_len, out_buf, out_off, out_cap, 
     if rc != 0:
         raise RuntimeError(f"chip_encode_batch failed: {rc}")
     return out_len, status
+
+
+# ---- BGZF: from a file to a batch and back (include/compu_hip.h, "BGZF") ------------------------
+
+FMT_BGZF = 131  # CHIP_FMT_BGZF: encode_batch / encode_batch_host / encode_bound only, one BGZF block per unit
+
+
+class BgzfStatus(enum.IntEnum):
+    Ok = 0
+    Truncated = 1
+    BadHeader = 2
+
+
+class BgzfSummary:
+    """chip_bgzf_summary: n_blocks and total_out of the whole walk, in_used where it stopped, status why, eof = the last block
+    has ISIZE 0."""
+
+    __slots__ = ("n_blocks", "total_out", "in_used", "status", "eof")
+
+    def __init__(self, raw):
+        self.n_blocks, self.total_out, self.in_used = int(raw.n_blocks), int(raw.total_out), int(raw.in_used)
+        self.status, self.eof = BgzfStatus(raw.status), int(raw.eof)
+
+    def as_tuple(self):
+        return (self.n_blocks, self.total_out, self.in_used, int(self.status), self.eof)
+
+    def __repr__(self):
+        return f"BgzfSummary(n_blocks={self.n_blocks}, total_out={self.total_out}, in_used={self.in_used}, status={self.status.name}, eof={self.eof})"
+
+
+def bgzf_eof_block():
+    """htslib's 28-byte EOF marker (chip_bgzf_eof_block)."""
+    n = C.c_size_t(0)
+    p = lib().chip_bgzf_eof_block(C.byref(n))
+    return C.string_at(p, n.value)
+
+
+def bgzf_plan_host(data, max_blocks=None):
+    """chip_bgzf_plan_host over bytes / a uint8 numpy array in host memory: (in_off u64, in_len u32, out_off u64, out_cap u32,
+    summary) of the first min(n_blocks, max_blocks) blocks (None = all of them: one call to count, one to fill)."""
+    import numpy as np
+
+    buf = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8)
+    raw = _BgzfSummary()
+    p = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None  # noqa: E731
+    if max_blocks is None:
+        rc = lib().chip_bgzf_plan_host(p(buf), buf.size, 0, None, None, None, None, C.byref(raw))
+        if rc != 0:
+            raise RuntimeError(f"chip_bgzf_plan_host failed: {rc}")
+        max_blocks = int(raw.n_blocks)
+    m = int(max_blocks)
+    in_off, in_len, out_off, out_cap = np.zeros(m, np.uint64), np.zeros(m, np.uint32), np.zeros(m, np.uint64), np.zeros(m, np.uint32)
+    rc = lib().chip_bgzf_plan_host(p(buf), buf.size, m, p(in_off), p(in_len), p(out_off), p(out_cap), C.byref(raw))
+    if rc != 0:
+        raise RuntimeError(f"chip_bgzf_plan_host failed: {rc}")
+    k = min(m, int(raw.n_blocks))
+    return in_off[:k], in_len[:k], out_off[:k], out_cap[:k], BgzfSummary(raw)
+
+
+def bgzf_plan(in_buf, length, stream=None, max_blocks=None):
+    """chip_bgzf_plan over a uint8 device tensor holding `length` bytes of BGZF (4-byte aligned, padded to a multiple of 4):
+    returns (in_off int64, in_len int32, out_off int64, out_cap int32, summary) -- device tensors of the first
+    min(n_blocks, max_blocks) blocks, ready for decode_batch(ZlibMode.Gzip, ..).  Synchronous on `stream`.  max_blocks None: all
+    of them (one call to count, one to fill)."""
+    import torch
+
+    dev = _check_tensors(((in_buf, torch.uint8),))
+    length = int(length)
+    if length < 0 or length > in_buf.numel():
+        raise ValueError(f"length {length} outside the buffer of {in_buf.numel()} bytes")
+    raw = _BgzfSummary()
+    base, sp = (_dp(in_buf) if length else None), _stream_ptr(stream)
+    with torch.cuda.device(dev):
+        if max_blocks is None:  # count, then fill
+            rc = lib().chip_bgzf_plan(base, length, 0, None, None, None, None, C.byref(raw), sp)
+            if rc != 0:
+                raise RuntimeError(f"chip_bgzf_plan failed: {rc}")
+            max_blocks = int(raw.n_blocks)
+        m = int(max_blocks)
+        in_off, out_off = torch.empty(m, dtype=torch.int64, device=dev), torch.empty(m, dtype=torch.int64, device=dev)
+        in_len, out_cap = torch.empty(m, dtype=torch.int32, device=dev), torch.empty(m, dtype=torch.int32, device=dev)
+        q = lambda t: _dp(t) if m else None  # noqa: E731
+        rc = lib().chip_bgzf_plan(base, length, m, q(in_off), q(in_len), q(out_off), q(out_cap), C.byref(raw), sp)
+    if rc != 0:
+        raise RuntimeError(f"chip_bgzf_plan failed: {rc}")
+    k = min(m, int(raw.n_blocks))
+    return in_off[:k], in_len[:k], out_off[:k], out_cap[:k], BgzfSummary(raw)
+
+
+def bgzf_decode(in_buf, length, stream=None):
+    """Decode a whole BGZF buffer on the device: plan, allocate total_out bytes, decode_batch(ZlibMode.Gzip).  Raises ValueError
+    when the file is no whole BGZF file (the summary says where) and RuntimeError with the first bad block's index and status
+    when a block does not decode to its ISIZE.  Returns the uint8 output tensor.  Waits for the decode."""
+    import torch
+
+    in_off, in_len, out_off, out_cap, summ = bgzf_plan(in_buf, length, stream=stream)
+    if summ.status != BgzfStatus.Ok:
+        raise ValueError(f"not a whole BGZF file: {summ!r}")
+    out = torch.empty(max(summ.total_out, 4), dtype=torch.uint8, device=in_buf.device)
+    if summ.n_blocks:
+        out_len, _, status = decode_batch(ZlibMode.Gzip, in_buf, in_off, in_len, out, out_off, out_cap, stream=stream)
+        bad = ((status != int(DecodeStatus.Finished)) | (out_len != out_cap)).nonzero()
+        if bad.numel():
+            i = int(bad[0])
+            raise RuntimeError(f"BGZF block {i} did not decode: status {int(status[i])}, {int(out_len[i])} of {int(out_cap[i])} bytes")
+    return out[: summ.total_out]

@@ -1235,7 +1235,7 @@ size_t chip_encode_bound(int format, size_t in_len)
     // each), the closing empty last metablock (1 byte) -- 4 bytes per metablock and 2 more are a safe margin
     if (format == CHIP_FMT_BROTLI) return in_len + 4 * (in_len ? (in_len + (128u << 10) - 1) / (128u << 10) : 1) + 2;
     size_t blocks = in_len ? (in_len + 65534) / 65535 : 1;
-    size_t wrap = format == CHIP_FMT_GZIP ? 18 : format == CHIP_FMT_ZLIB ? 6 : 0;
+    size_t wrap = format == CHIP_FMT_BGZF ? 26 : format == CHIP_FMT_GZIP ? 18 : format == CHIP_FMT_ZLIB ? 6 : 0;  // header + trailer
     // dynamic levels: a block holds at least 65472 tokens and costs at most 6 bytes more than its stored form
     return in_len + 5 * blocks + 6 * (in_len / 65472 + 1) + 5 + wrap;
 }
@@ -1264,6 +1264,7 @@ int chip_encode_batch_ex(int format, int level, int strategy, size_t n, const vo
     case CHIP_FMT_DEFLATE:
     case CHIP_FMT_ZLIB:
     case CHIP_FMT_GZIP:
+    case CHIP_FMT_BGZF:  // one BGZF block per unit (deflate.hip's wrapper branch); units above 65280 bytes are CHIP_ENC_ERROR
         if (level == -1) level = 6;  // zlib's Z_DEFAULT_COMPRESSION
         if (level < 0 || level > 9 || strategy < CHIP_STRATEGY_DEFAULT || strategy > CHIP_STRATEGY_FIXED) return CHIP_E_INVALID;
         break;

@@ -425,6 +425,14 @@ __device__ __forceinline__ void encode_unit(const EncArgs &a, const uint32_t u, 
     const bool no_match = strategy == CHIP_STRATEGY_HUFFMAN_ONLY, rle = strategy == CHIP_STRATEGY_RLE;
     const bool lazy = a.level >= 4;  // (dynamic levels only: zlib's lazy matching starts at level 4 too)
     const int fmt = a.b.format;
+    const bool bgzf = fmt == CHIP_FMT_BGZF, gz = fmt == CHIP_FMT_GZIP || bgzf;  // a BGZF block is a gzip member with the BC subfield
+    if (bgzf && n > 65280u) {  // (uniform) htslib's block payload: a larger unit could not promise a block of at most 64 KiB
+        if (lane == 0) {
+            a.b.out_len[u] = 0;
+            a.b.status[u] = CHIP_ENC_ERROR;
+        }
+        return;
+    }
 
     const uint32_t mis = (uint32_t)((uintptr_t)gin & 3u);
     const uint32_t *g32 = (const uint32_t *)(gin - mis);
@@ -452,7 +460,15 @@ __device__ __forceinline__ void encode_unit(const EncArgs &a, const uint32_t u, 
 
     uint32_t obytes = 0, nbits = 0;
     // ---- wrapper header ---------------------------------------------------------------------------
-    if (hdr && fmt == CHIP_FMT_GZIP) {
+    if (hdr && bgzf) {
+        // SAM specification sec. 4.1 as htslib writes it: FLG = FEXTRA, no time, OS ff, XLEN 6, the BC subfield; BSIZE (bytes 16, 17)
+        // is patched in behind the trailer
+        put_uniform(L, nbits, 0x04088b1fu, 32);
+        put_uniform(L, nbits, 0, 32);
+        put_uniform(L, nbits, (a.level == 9 ? 2u : a.level == 1 ? 4u : 0u) | (0xffu << 8) | (6u << 16), 32);
+        put_uniform(L, nbits, 0x00024342u, 32);
+        put_uniform(L, nbits, 0, 16);
+    } else if (hdr && fmt == CHIP_FMT_GZIP) {
         // RFC 1952 sec. 2.3: no name / time; XFL 4 = fastest (level 1), 2 = best (level 9); OS 3 = Unix
         put_uniform(L, nbits, 0x00088b1fu, 32);
         put_uniform(L, nbits, 0, 32);
@@ -998,9 +1014,9 @@ __device__ __forceinline__ void encode_unit(const EncArgs &a, const uint32_t u, 
     }
     // ---- checksum / trailer -----------------------------------------------------------------------
     uint32_t check = a.check_seed;
-    if (fmt == CHIP_FMT_GZIP) check = wave_crc32((LDS_AS uint32_t *)L.table, gin, n, a.check_seed);  // the hash table is dead by now
+    if (gz) check = wave_crc32((LDS_AS uint32_t *)L.table, gin, n, a.check_seed);  // the hash table is dead by now
     else if (fmt == CHIP_FMT_ZLIB) check = wave_adler32(gin, n, a.check_seed);
-    if (trl && fmt == CHIP_FMT_GZIP) {
+    if (trl && gz) {
         const uint32_t isize = (uint32_t)(a.total_before + n);
         if (lane < 8) {
             uint32_t w = lane < 4 ? check : isize;
@@ -1011,6 +1027,7 @@ __device__ __forceinline__ void encode_unit(const EncArgs &a, const uint32_t u, 
         if (lane < 4 && obytes + lane < cap) gout[obytes + lane] = (uint8_t)(check >> (8 * (3 - lane)));
         obytes += 4;
     }
+    if (bgzf && lane < 2 && obytes <= cap) gout[16u + lane] = (uint8_t)((obytes - 1u) >> (8u * lane));  // BSIZE = block size - 1
     if (lane == 0) {
         a.b.out_len[u] = obytes <= cap ? obytes : cap;
         a.b.status[u] = obytes <= cap ? CHIP_ENC_FINISHED : CHIP_ENC_NEED_OUTPUT;

@@ -505,11 +505,28 @@ public:
     {
         return chip_decode_batch_sizes(format, 0, n, in.data(), in_off, in_len, out_size, in_used, status, stream);
     }
+    // chip_bgzf_plan over the BGZF bytes held in `in` (its first `len` bytes): the four DEVICE arrays of the decode_batch(CHIP_FMT_GZIP, ..)
+    // that follows, for the first min(n_blocks, max_blocks) blocks, and the summary of the whole walk.  Synchronous on `stream`.
+    static int bgzf_plan(const DeviceBuffer &in, uint64_t len, uint64_t max_blocks, uint64_t *in_off, uint32_t *in_len, uint64_t *out_off,
+                         uint32_t *out_cap, chip_bgzf_summary &summary, void *stream = nullptr)
+    {
+        if (len > in.len()) return CHIP_E_INVALID;
+        return chip_bgzf_plan(in.data(), len, max_blocks, in_off, in_len, out_off, out_cap, &summary, stream);
+    }
 
 private:
     uint8_t *buf_;
     size_t cap_;
     size_t cursor_ = 0;
 };
+
+// chip_bgzf_plan_host: the BGZF walk over host memory (no device needed); the arrays are what chip_decode_batch_host / _multi take.
+inline int bgzf_plan_host(const uint8_t *in, uint64_t len, uint64_t max_blocks, uint64_t *in_off, uint32_t *in_len, uint64_t *out_off,
+                          uint32_t *out_cap, chip_bgzf_summary &summary)
+{
+    return chip_bgzf_plan_host(in, len, max_blocks, in_off, in_len, out_off, out_cap, &summary);
+}
+// htslib's 28-byte EOF marker, to be written behind the last block of a file made with chip_encode_batch(CHIP_FMT_BGZF, ..)
+inline const uint8_t *bgzf_eof_block(size_t &len) { return chip_bgzf_eof_block(&len); }
 
 }  // namespace compu

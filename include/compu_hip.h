@@ -48,6 +48,9 @@ enum {
      * BROTLI_DECODER_PARAM_LARGE_WINDOW), no shared dictionaries; not part of CHIP_FMT_DETECT routing (compu cannot detect
      * brotli) */
     CHIP_FMT_BROTLI = 101,
+    /* chip_encode_batch / _ex / _host and chip_encode_bound only: every unit becomes one BGZF block (below).  Decoding takes
+     * CHIP_FMT_GZIP with the arrays of chip_bgzf_plan; the streaming chip_encoder_new does not take this tag. */
+    CHIP_FMT_BGZF = 131,
     /* chip_decode_batch only: route every unit by Detection::detect (src/decoder/mod.rs:28-114) to the
      * zlib/gzip or the zstd decoder -- the mixed gzip+zstd batch of BASELINE.json configs[4] */
     CHIP_FMT_DETECT = 0
@@ -278,6 +281,56 @@ int chip_detect(const uint8_t *bytes, size_t len);
 int chip_detect_batch(size_t n, const void *in_base, const uint64_t *in_off, const uint32_t *in_len, int32_t *kind,
                       void *stream);
 
+/* ---- BGZF: from a file to a batch (additive API) ------------------------- */
+
+/*
+ * BGZF (the blocked gzip of BAM, BCF, tabix-indexed VCF and bgzip; SAM specification sec. 4.1) is a concatenation of gzip
+ * members of at most 64 KiB, compressed and decoded, each stating its own compressed size: exactly the batch of independent
+ * units chip_decode_batch wants.  These calls turn a BGZF buffer into that call's four arrays.
+ * A block at byte p has the 18-byte header htslib writes:  1f 8b 08 04 | MTIME (4) XFL OS, any value | 06 00 (XLEN 6) |
+ * 42 43 02 00 ('B' 'C', SLEN 2) | BSIZE (u16 LE).  It is BSIZE + 1 bytes long and ISIZE is the u32 LE in its last 4 bytes.
+ * LIMIT: the BC subfield must be the only one.  A block whose extra field holds other subfields as well is valid by the SAM
+ * specification and CHIP_BGZF_BAD_HEADER here (no known writer emits one).
+ * The plan of `len` bytes is defined by this walk:
+ *   p = 0, n = 0, total = 0
+ *   loop: p == len -> OK;  len - p < 18 -> TRUNCATED;  header bytes wrong -> BAD_HEADER;
+ *         bs = BSIZE + 1;  bs < 28 -> BAD_HEADER (18 + the 2-byte empty deflate stream + 8);  p + bs > len -> TRUNCATED;
+ *         isize = LE32(p + bs - 4);  isize > 65536 -> BAD_HEADER;
+ *         block n: in_off = p, in_len = bs, out_off = total, out_cap = isize;  n++, total += isize, p += bs
+ * summary: n_blocks = n and total_out = total of the WHOLE walk, in_used = p where it stopped, status why, eof = 1 when the last
+ * block has ISIZE 0 (htslib's EOF marker is such a block).  Blocks with ISIZE 0 are units like any other (out_cap 0): indices
+ * are the file's block numbers.  The arrays receive the first min(n_blocks, max_blocks) blocks and nothing behind them is
+ * written: max_blocks = 0 with null arrays counts, a second call fills.  in_off is relative to the buffer and out_off starts at
+ * 0, so the arrays go unchanged to chip_decode_batch(CHIP_FMT_GZIP, n_blocks, in_base, in_off, in_len, out, out_off, out_cap, ..).
+ * CHIP_E_INVALID, checked before the device is looked for: summary NULL, a NULL buffer with len > 0, NULL arrays with
+ * max_blocks > 0 (chip_bgzf_plan: in_base not 4-byte aligned, len > 2^40).  len == 0 is CHIP_OK with an all-zero summary.
+ * No reference counterpart: compu has no container formats.
+ */
+enum { CHIP_BGZF_OK = 0, CHIP_BGZF_TRUNCATED = 1, CHIP_BGZF_BAD_HEADER = 2 };
+typedef struct {
+    uint64_t n_blocks, total_out, in_used;
+    int32_t status;
+    uint32_t eof;
+} chip_bgzf_summary;
+
+/* The walk itself on HOST memory: pure host arithmetic, no device needed (as chip_partition_units).  Its arrays are what
+ * chip_decode_batch_host / chip_decode_batch_multi take. */
+int chip_bgzf_plan_host(const uint8_t *in, uint64_t len, uint64_t max_blocks, uint64_t *in_off, uint32_t *in_len, uint64_t *out_off,
+                        uint32_t *out_cap, chip_bgzf_summary *summary);
+
+/* The same answer for a buffer in DEVICE memory, without one dependent memory round trip per block: in_base and the four arrays
+ * are DEVICE pointers, summary is a HOST pointer.  in_base as for chip_decode_batch (4-byte aligned, allocation padded to a
+ * multiple of 4 bytes); len is arbitrary.  SYNCHRONOUS on `stream` (n_blocks is a host argument of the decode that follows): it
+ * returns when the arrays are in device memory and *summary is filled, and waits once in between to size its scratch by the
+ * number of header candidates.  Scratch per (device, stream), kept between calls and released by chip_trim(): 16 bytes per
+ * 16 KiB of input and 36 + 4 * ceil(log2(candidates + 1)) bytes per candidate (about 7 MB for 65 536 blocks).  More than 2^31 - 1
+ * candidates: CHIP_E_NOMEM.  The calling thread's current device is left as it was. */
+int chip_bgzf_plan(const void *in_base, uint64_t len, uint64_t max_blocks, uint64_t *in_off, uint32_t *in_len, uint64_t *out_off,
+                   uint32_t *out_cap, chip_bgzf_summary *summary, void *stream);
+
+/* htslib's 28-byte EOF marker (an empty BGZF block); *len gets 28 (len may be NULL).  Static storage. */
+const uint8_t *chip_bgzf_eof_block(size_t *len);
+
 /* ---- encoder: mirrors encoder::Interface, src/encoder/mod.rs:52-57 ---------------------------- */
 
 typedef struct chip_encoder chip_encoder;
@@ -320,7 +373,12 @@ int chip_encode_batch_ex(int format, int level, int strategy, size_t n, const vo
  * CHIP_E_INVALID), strategy = mode 0..3; each unit becomes one brotli stream with lgwin 22.
  * out_len[i] = compressed size; status[i] = CHIP_ENC_FINISHED or CHIP_ENC_NEED_OUTPUT.  Each unit becomes
  * one complete stream of `format` (wrapper, one fixed-Huffman or stored deflate body, trailer).  The
- * range out_off[i] .. +out_cap[i] may be used as scratch beyond out_len[i]. */
+ * range out_off[i] .. +out_cap[i] may be used as scratch beyond out_len[i].
+ * CHIP_FMT_BGZF: levels and strategies as CHIP_FMT_GZIP, and the same deflate body; each unit becomes one BGZF block -- the
+ * 18-byte header of chip_bgzf_plan with MTIME 0, XFL as for gzip, OS ff (as htslib writes) and BSIZE = out_len[i] - 1, then
+ * CRC-32 and ISIZE.  A unit with in_len[i] > 65280 (htslib's block payload) is CHIP_ENC_ERROR with out_len[i] = 0; a block never
+ * exceeds 65 536 bytes (incompressible input is stored: 65 280 + 5 + 26; a dynamic-level block costs at most 6 bytes more).
+ * Writing the EOF marker (chip_bgzf_eof_block) and laying the blocks end to end is the caller's job. */
 int chip_encode_batch(int format, int level, size_t n, const void *in_base, const uint64_t *in_off,
                       const uint32_t *in_len, void *out_base, const uint64_t *out_off, const uint32_t *out_cap,
                       uint32_t *out_len, int32_t *status, void *stream);

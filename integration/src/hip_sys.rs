@@ -63,6 +63,8 @@ pub struct chip_brotli_encoder_opts {
 
 pub const CHIP_FMT_ZSTD: c_int = 100;
 pub const CHIP_FMT_BROTLI: c_int = 101;
+///`chip_encode_batch` / `_ex` / `_host` and `chip_encode_bound` only: one BGZF block per unit (at most 65280 input bytes each)
+pub const CHIP_FMT_BGZF: c_int = 131;
 ///route every unit of a batch by `Detection::detect` (src/decoder/mod.rs:28-114)
 pub const CHIP_FMT_DETECT: c_int = 0;
 
@@ -70,6 +72,22 @@ pub const CHIP_FMT_DETECT: c_int = 0;
 pub const CHIP_F_COMPU_STATUS: u32 = 1;
 ///`chip_decode_batch` / `chip_encode_batch` return codes
 pub const CHIP_OK: c_int = 0;
+
+///`chip_bgzf_summary::status`
+pub const CHIP_BGZF_OK: i32 = 0;
+pub const CHIP_BGZF_TRUNCATED: i32 = 1;
+pub const CHIP_BGZF_BAD_HEADER: i32 = 2;
+
+///what the BGZF walk found: blocks and decoded bytes of the whole walk, where it stopped and why, whether the last block is empty
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct chip_bgzf_summary {
+    pub n_blocks: u64,
+    pub total_out: u64,
+    pub in_used: u64,
+    pub status: i32,
+    pub eof: u32,
+}
 
 pub type chip_malloc_fn = unsafe extern "C" fn(opaque: *mut c_void, size: usize) -> *mut c_void;
 pub type chip_free_fn = unsafe extern "C" fn(opaque: *mut c_void, ptr: *mut c_void);
@@ -116,6 +134,16 @@ extern "C" {
     pub fn chip_partition_units(n: usize, in_len: *const u32, out_cap: *const u32, parts: c_int, cuts: *mut usize) -> c_int;
     pub fn chip_detect(bytes: *const u8, len: usize) -> c_int;
     pub fn chip_detect_batch(n: usize, in_base: *const c_void, in_off: *const u64, in_len: *const u32, kind: *mut i32, stream: *mut c_void) -> c_int;
+
+    // ---- BGZF: the four arrays of chip_decode_batch(CHIP_FMT_GZIP, ..) from a BGZF buffer (no reference counterpart)
+    ///the serial walk on host memory; pure host arithmetic, no device needed
+    pub fn chip_bgzf_plan_host(input: *const u8, len: u64, max_blocks: u64, in_off: *mut u64, in_len: *mut u32, out_off: *mut u64, out_cap: *mut u32,
+                               summary: *mut chip_bgzf_summary) -> c_int;
+    ///the same answer for a buffer in device memory (device arrays, host summary); synchronous on `stream`
+    pub fn chip_bgzf_plan(in_base: *const c_void, len: u64, max_blocks: u64, in_off: *mut u64, in_len: *mut u32, out_off: *mut u64, out_cap: *mut u32,
+                          summary: *mut chip_bgzf_summary, stream: *mut c_void) -> c_int;
+    ///htslib's 28-byte EOF marker (static storage)
+    pub fn chip_bgzf_eof_block(len: *mut usize) -> *const u8;
 
     pub fn chip_encoder_new(opts: *const chip_encoder_opts) -> *mut chip_encoder;
     pub fn chip_encoder_new_zstd(opts: *const chip_zstd_encoder_opts) -> *mut chip_encoder;
