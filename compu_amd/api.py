@@ -834,6 +834,7 @@ def _check_tensors(pairs):
 
 
 F_COMPU_STATUS = 1  # CHIP_F_COMPU_STATUS
+F_MEMBERS = 2  # CHIP_F_MEMBERS: a unit is a series of gzip members / zstd frames (gzip, auto, zstd and detect batches; not with F_COMPU_STATUS)
 
 
 def decode_batch(fmt, in_buf, in_off, in_len, out_buf, out_off, out_cap, out_len=None, in_used=None, status=None, stream=None, flags=0):

@@ -153,11 +153,21 @@ int chip_decode_batch(int format, size_t n, const void *in_base, const uint64_t 
     return chip_decode_batch_ex(format, 0, n, in_base, in_off, in_len, out_base, out_off, out_cap, out_len, in_used, status, stream);
 }
 
+// CHIP_F_MEMBERS goes with the formats that have a concatenation convention (RFC 1952 sec. 2.2, RFC 8878 sec. 3.1), and not with
+// CHIP_F_COMPU_STATUS: compu has no multi-member decode whose return values could be mirrored
+static bool members_flag_ok(int format, uint32_t flags)
+{
+    if (!(flags & CHIP_F_MEMBERS)) return true;
+    if (flags & CHIP_F_COMPU_STATUS) return false;
+    return format == CHIP_FMT_GZIP || format == CHIP_FMT_AUTO || format == CHIP_FMT_ZSTD || format == CHIP_FMT_DETECT;
+}
+
 int chip_decode_batch_ex(int format, uint32_t flags, size_t n, const void *in_base, const uint64_t *in_off, const uint32_t *in_len,
                          void *out_base, const uint64_t *out_off, const uint32_t *out_cap, uint32_t *out_len,
                          uint32_t *in_used, int32_t *status, void *stream)
 {
-    if (flags & ~(uint32_t)CHIP_F_COMPU_STATUS) return CHIP_E_INVALID;
+    if (flags & ~(uint32_t)(CHIP_F_COMPU_STATUS | CHIP_F_MEMBERS)) return CHIP_E_INVALID;
+    if (!members_flag_ok(format, flags)) return CHIP_E_INVALID;
     if (n == 0) return CHIP_OK;
     if (n > 0x7fffffffull || !in_base || !in_off || !in_len || !out_base || !out_off || !out_cap || !out_len || !in_used ||
         !status || ((uintptr_t)in_base & 3u))
@@ -187,7 +197,8 @@ int chip_decode_batch_sizes(int format, uint32_t flags, size_t n, const void *in
                             uint64_t *out_size, uint32_t *in_used, int32_t *status, void *stream)
 {
     // arguments first, the device second (as chip_decode_batch_ex): a refusal needs no GPU
-    if (flags != 0) return CHIP_E_INVALID;
+    if (flags & ~(uint32_t)CHIP_F_MEMBERS) return CHIP_E_INVALID;
+    if (!members_flag_ok(format, flags)) return CHIP_E_INVALID;
     switch (format) {
     case CHIP_FMT_DEFLATE:
     case CHIP_FMT_ZLIB:
@@ -201,7 +212,8 @@ int chip_decode_batch_sizes(int format, uint32_t flags, size_t n, const void *in
     if (n > 0x7fffffffull || !in_base || !in_off || !in_len || !out_size || !in_used || !status || ((uintptr_t)in_base & 3u))
         return CHIP_E_INVALID;
     if (!device_ok()) return CHIP_E_NO_DEVICE;
-    const BatchArgs a = batch_args(format, n, in_base, in_off, in_len, nullptr, nullptr, nullptr, nullptr, in_used, status);
+    BatchArgs a = batch_args(format, n, in_base, in_off, in_len, nullptr, nullptr, nullptr, nullptr, in_used, status);
+    a.flags = flags;
     hipError_t e;
     if (format == CHIP_FMT_ZSTD) e = launch_zstd_sizes(a, out_size, 0, (hipStream_t)stream);
     else if (format == CHIP_FMT_DETECT) e = launch_routed_sizes(a, out_size, (hipStream_t)stream);  // routed as launch_routed routes a decode batch

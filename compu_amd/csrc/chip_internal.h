@@ -64,6 +64,7 @@ struct BatchArgs {
     uint32_t flags = 0;  // CHIP_F_* of chip_decode_batch_ex (include/compu_hip.h)
 };
 constexpr uint32_t F_COMPU_STATUS = 1u;  // = CHIP_F_COMPU_STATUS
+constexpr uint32_t F_MEMBERS = 2u;       // = CHIP_F_MEMBERS
 
 // launchers (each only enqueues on `stream`)
 hipError_t launch_inflate(const BatchArgs &a, hipStream_t stream);
@@ -77,6 +78,11 @@ hipError_t launch_route_sizes(const BatchArgs &a, uint64_t *out_size, uint32_t *
 hipError_t launch_routed_sizes(const BatchArgs &a, uint64_t *out_size, hipStream_t stream);
 // (inflate_sizes.hip: the launch itself, for launch_inflate_sizes, which holds the slot)
 hipError_t enqueue_inflate_sizes(const BatchArgs &a, uint64_t *out_size, uint32_t *scratch, uint32_t *counter, uint32_t blocks, hipStream_t stream);
+// (inflate_members.hip: the same for a CHIP_F_MEMBERS batch; out_size != nullptr launches the size pass, else the decoder)
+hipError_t enqueue_inflate_members(const BatchArgs &a, uint64_t *out_size, uint32_t *scratch, uint32_t *counter, uint32_t blocks, hipStream_t stream);
+// (zstd_members.hip, zstd_members_sizes.hip: the CHIP_F_MEMBERS kernels behind launch_zstd_decode / launch_zstd_sizes)
+hipError_t launch_zstd_members(const BatchArgs &a, int window_log_max, hipStream_t stream);
+hipError_t launch_zstd_members_sizes(const BatchArgs &a, uint64_t *out_size, int window_log_max, hipStream_t stream);
 // launch_slots.hip: the cached launch scratch of every codec ("Launch slots")
 hipError_t release_scratch();                 // every slot of the current device, after a device sync
 void release_scratch_of(hipStream_t stream);  // the slots of one (drained) stream of the current device

@@ -1443,6 +1443,14 @@ __device__ CHIP_PHASE_FN void decode_block(WaveLds &L, InWin &w, uint32_t &pos, 
 // one unit, start to finish, by the calling wave; scratch = the wave's token rows in HBM
 // SIZES (the size pass, chip_decode_batch_sizes): the same unit loop, wrapper, block headers, table builds and walk, but nothing is
 // written: the decoded length is counted in 64 bits and goes to out_size[u]; the unit's output description is never read.
+// CHIP_INFLATE_MEMBERS (inflate_members.hip, CHIP_F_MEMBERS): a gzip member that ends with CHIP_FINISHED and has `1f 8b` behind its
+// trailer is followed by the next one (the walk of include/compu_hip.h): the output base and the room move past the member, the
+// member's state (wrapper, tables, block flags, output position) starts over, the input position goes on where it stands.  Every
+// check that is relative to the output base -- a distance "too far back", CRC-32, ISIZE -- thereby becomes the member's own.  The
+// code of the member loop is compiled only there: without the macro this file's tokens are what they were.
+#ifndef CHIP_INFLATE_MEMBERS
+#define CHIP_INFLATE_MEMBERS 0
+#endif
 template <bool SIZES>
 __device__ __attribute__((always_inline)) void inflate_unit(const BatchArgs &a, const uint32_t u, WaveLds &L, uint32_t *scratch, uint64_t *out_size)
 {
@@ -1456,7 +1464,13 @@ __device__ __attribute__((always_inline)) void inflate_unit(const BatchArgs &a, 
         gout = a.out_base + a.out_off[u];
         cap_ = a.out_cap[u];
     }
+#if CHIP_INFLATE_MEMBERS
+    uint32_t cap = cap_;        // room left behind the finished members
+    uint32_t opos_members = 0;  // output bytes of the finished members
+    uint64_t osize_members = 0;
+#else
     const uint32_t cap = cap_;
+#endif
     uint64_t osize = 0;  // SIZES: the decoded length so far
 
     InWin w;
@@ -1496,9 +1510,17 @@ __device__ __attribute__((always_inline)) void inflate_unit(const BatchArgs &a, 
             out_dropped = rs[5];
         }
     }
+#if CHIP_INFLATE_MEMBERS
+next_member:
+#endif
     if (!resumed && format != CHIP_FMT_DEFLATE) {
         uint32_t hdr = 0;
+#if CHIP_INFLATE_MEMBERS
+        const uint32_t k0 = (pos - start_bit) >> 3;  // (a member starts at a byte: 0, or behind a trailer)
+        status = parse_wrapper((LDS_AS uint32_t *)&L, gin + k0, in_len - k0, format, wrap, hdr);
+#else
         status = parse_wrapper((LDS_AS uint32_t *)&L, gin, in_len, format, wrap, hdr);
+#endif
         status = (int32_t)rdfirst((uint32_t)status);
         wrap = rdfirst(wrap);
         pos += rdfirst(hdr) * 8u;
@@ -1740,6 +1762,31 @@ __device__ __attribute__((always_inline)) void inflate_unit(const BatchArgs &a, 
         }
         pos = start_bit + k * 8u;
     }
+#if CHIP_INFLATE_MEMBERS
+    if (status == CHIP_FINISHED && wrap == 2) {
+        const uint32_t k = (pos - start_bit) >> 3;
+        if (in_len - k >= 2 && rdfirst(gin[k]) == 0x1fu && rdfirst(gin[k + 1]) == 0x8bu) {  // another member starts here
+            WSYNC();  // (the checksum's tables took the whole LDS; every lane is done with them)
+            if constexpr (SIZES) {
+                osize_members += osize;
+                osize = 0;
+            } else {
+                gout += opos;
+                cap -= opos;
+                opos_members += opos;
+                opos = 0;
+            }
+            format = CHIP_FMT_GZIP;
+            status = ST_RUNNING;
+            last = false;
+            tables = 0;
+            w.win0 = 0xffffffffu;
+            goto next_member;
+        }
+    }
+    opos += opos_members;  // (nothing below reads the output)
+    osize += osize_members;
+#endif
     STAT_ACC(6);
 #ifdef CHIP_STATS
     if (a.stats && lane == 0)
@@ -1781,7 +1828,48 @@ __device__ __attribute__((always_inline)) void inflate_unit(const BatchArgs &a, 
     }
 }
 
-#ifndef CHIP_INFLATE_SIZES_TU
+#if CHIP_INFLATE_MEMBERS
+// CHIP_F_MEMBERS (inflate_members.hip includes this file): the decoder's and the size pass's persistent grids with the member loop
+// compiled into inflate_unit.  A translation unit of its own for the reason inflate_sizes.hip has one.
+__global__ __launch_bounds__(64, CHIP_WAVES_PER_SIMD) void inflate_members_kernel(BatchArgs a, uint32_t *scratch, uint32_t *next_unit)
+{
+    __shared__ WaveLds L;
+    uint32_t *grow = scratch + (size_t)blockIdx.x * SCRATCH_WORDS;
+    const uint32_t limit = a.sel_n ? *a.sel_n : a.n;
+    for (;;) {
+        uint32_t i = 0;
+        if (lane_id() == 0) i = atomicAdd(next_unit, 1u);
+        i = rdfirst(i);
+        if (i >= limit) break;
+        const uint32_t u = a.sel ? rdfirst(a.sel[i]) : i;
+        inflate_unit<false>(a, u, L, grow, nullptr);
+        WSYNC();  // the next unit reuses the LDS
+    }
+}
+__global__ __launch_bounds__(64, CHIP_WAVES_PER_SIMD) void inflate_members_sizes_kernel(BatchArgs a, uint64_t *out_size, uint32_t *scratch, uint32_t *next_unit)
+{
+    __shared__ WaveLds L;
+    uint32_t *grow = scratch + (size_t)blockIdx.x * SCRATCH_WORDS;
+    const uint32_t limit = a.sel_n ? *a.sel_n : a.n;
+    for (;;) {
+        uint32_t i = 0;
+        if (lane_id() == 0) i = atomicAdd(next_unit, 1u);
+        i = rdfirst(i);
+        if (i >= limit) break;
+        const uint32_t u = a.sel ? rdfirst(a.sel[i]) : i;
+        inflate_unit<true>(a, u, L, grow, out_size);
+        WSYNC();
+    }
+}
+
+// (the caller, launch_inflate_locked() / launch_inflate_sizes_locked() in inflate.hip, holds the slot)
+hipError_t enqueue_inflate_members(const BatchArgs &a, uint64_t *out_size, uint32_t *scratch, uint32_t *counter, uint32_t blocks, hipStream_t stream)
+{
+    if (out_size) hipLaunchKernelGGL(inflate_members_sizes_kernel, dim3(blocks), dim3(64), 0, stream, a, out_size, scratch, counter);
+    else hipLaunchKernelGGL(inflate_members_kernel, dim3(blocks), dim3(64), 0, stream, a, scratch, counter);
+    return hipGetLastError();
+}
+#elif !defined(CHIP_INFLATE_SIZES_TU)
 // Persistent grid: each wave takes the next unit from *next_unit until the batch is exhausted.
 __global__ __launch_bounds__(64, CHIP_WAVES_PER_SIMD) void inflate_kernel(BatchArgs a, uint32_t *scratch, uint32_t *next_unit)
 {
@@ -1825,7 +1913,7 @@ hipError_t enqueue_inflate_sizes(const BatchArgs &a, uint64_t *out_size, uint32_
 }
 #endif  // CHIP_INFLATE_SIZES_TU
 
-#ifndef CHIP_INFLATE_SIZES_TU
+#if !defined(CHIP_INFLATE_SIZES_TU) && !CHIP_INFLATE_MEMBERS
 
 namespace {
 // Token scratch and the unit counter of a launch, and the lists of a routed batch: a launch slot ("Launch slots").
@@ -1966,6 +2054,7 @@ hipError_t launch_inflate_sizes_locked(const BatchArgs &a, uint64_t *out_size, h
     if (e != hipSuccess) return e;
     const uint32_t blocks = a.n < (uint32_t)sl->blocks ? a.n : (uint32_t)sl->blocks;
     if ((e = hipMemsetAsync(sl->counter, 0, 4, stream)) != hipSuccess) return e;
+    if (a.flags & F_MEMBERS) return enqueue_inflate_members(a, out_size, (uint32_t *)sl->scratch, sl->counter, blocks, stream);
     return enqueue_inflate_sizes(a, out_size, (uint32_t *)sl->scratch, sl->counter, blocks, stream);
 }
 }  // namespace
@@ -1984,6 +2073,7 @@ hipError_t launch_inflate_locked(const BatchArgs &a, hipStream_t stream)
     }
 #endif
     if ((e = hipMemsetAsync(sl->counter, 0, 4, stream)) != hipSuccess) return e;
+    if (a.flags & F_MEMBERS) return enqueue_inflate_members(a, nullptr, (uint32_t *)sl->scratch, sl->counter, blocks, stream);
     hipLaunchKernelGGL(inflate_kernel, dim3(blocks), dim3(64), 0, stream, a, (uint32_t *)sl->scratch, sl->counter);
     return hipGetLastError();
 }

@@ -980,12 +980,27 @@ __device__ void wave_match_copy(uint8_t *dst, uint32_t offset, uint32_t n)
 // has a table; the streams are skipped by their stated size), sequence header, table descriptions and builds, the FSE state chain, the
 // offsets with the repeat history, and every placement check run as they do in the decoder; nothing is regenerated, copied or hashed.
 // The position is 64-bit: `dropped` counts the completed blocks' bytes and opos the current block's.
+// CHIP_ZSTD_MEMBERS (zstd_members.hip, zstd_members_sizes.hip; CHIP_F_MEMBERS): a frame that ends with CHIP_FINISHED and has a frame
+// magic number behind it is followed by the next frame (the walk of include/compu_hip.h): the output base and the room move past the
+// frame and the frame's state starts over; the input cursor is the unit's and goes on where it stands.  The code of the frame loop is
+// compiled only there: without the macro this file's tokens are what they were.
+#ifndef CHIP_ZSTD_MEMBERS
+#define CHIP_ZSTD_MEMBERS 0
+#endif
 #ifndef CHIP_ZSTD_SIZES_TU
 #define CHIP_ZSTD_SIZES 0
+#if CHIP_ZSTD_MEMBERS
+__global__ __launch_bounds__(64, CHIP_ZSTD_WAVES) void zstd_members_kernel(BatchArgs a, int wlog_max)
+#else
 __global__ __launch_bounds__(64, CHIP_ZSTD_WAVES) void zstd_kernel(BatchArgs a, int wlog_max)
+#endif
 #else
 #define CHIP_ZSTD_SIZES 1
+#if CHIP_ZSTD_MEMBERS
+__global__ __launch_bounds__(64, CHIP_ZSTD_WAVES) void zstd_members_sizes_kernel(BatchArgs a, int wlog_max, uint64_t *out_size)
+#else
 __global__ __launch_bounds__(64, CHIP_ZSTD_WAVES) void zstd_sizes_kernel(BatchArgs a, int wlog_max, uint64_t *out_size)
+#endif
 #endif
 {
     constexpr bool SIZES = CHIP_ZSTD_SIZES != 0;
@@ -996,7 +1011,12 @@ __global__ __launch_bounds__(64, CHIP_ZSTD_WAVES) void zstd_sizes_kernel(BatchAr
     const uint8_t *gin = a.in_base + a.in_off[u];
     const uint32_t in_len = a.in_len[u];
     uint8_t *gout = SIZES ? nullptr : a.out_base + a.out_off[u];
+#if CHIP_ZSTD_MEMBERS
+    uint32_t cap = SIZES ? 0xffffffffu : a.out_cap[u];  // room left behind the finished frames
+    uint64_t out_frames = 0;                            // output bytes of the finished frames
+#else
     const uint32_t cap = SIZES ? 0xffffffffu : a.out_cap[u];
+#endif
 #ifdef CHIP_STATS
     unsigned long long zst_[24] = {};
     unsigned long long *const zst = zst_;
@@ -1101,6 +1121,9 @@ __global__ __launch_bounds__(64, CHIP_ZSTD_WAVES) void zstd_sizes_kernel(BatchAr
     };
 
     // ---- frame header (sec. 3.1.1.1) ------------------------------------------------------------
+#if CHIP_ZSTD_MEMBERS
+next_frame:
+#endif
     if (!resumed) {
         if (END - ip < 4) ZNEED_INPUT();
         uint32_t magic = rd32_at(b, ip * 8u);
@@ -1932,6 +1955,35 @@ done:
     // libzstd decodes a block whole before it hands any of it on: the sequences of a failing block already placed are not output
     // (the oracle drops them too; a streaming caller would otherwise be handed them in front of the error)
     if (status < 0 && rewind_to != ~0u) opos = rewind_to;
+#if CHIP_ZSTD_MEMBERS
+    if (status == CHIP_FINISHED && END - ip >= 4) {
+        const uint32_t magic = rd32_at(b, ip * 8u);
+        if (magic == 0xFD2FB528u || (magic & 0xFFFFFFF0u) == 0x184D2A50u) {  // another frame starts here
+            out_frames += dropped + opos;
+            if (!SIZES) {
+                gout += opos;
+                cap -= opos;
+            }
+            opos = 0;
+            dropped = 0;
+            rewind_to = ~0u;
+            rep0 = 1;
+            rep1 = 4;
+            rep2 = 8;
+            has_checksum = has_fcs = blocks_done = false;
+            fcs = window = 0;
+            out_limit = ~0ULL;
+            WSYNC();  // (every lane is done with the frame's tables)
+            if (lane == 0) {
+                L.huf_valid = 0;
+                L.ll.valid = L.of.valid = L.ml.valid = 0;
+            }
+            WSYNC();
+            status = ST_RUNNING;
+            goto next_frame;
+        }
+    }
+#endif
     if (!SIZES && (a.flags & F_COMPU_STATUS) && status != CHIP_FINISHED) {
         // compu looks at the output first (src/decoder/zstd.rs:121-133): output.pos == output.size is NeedOutput whatever
         // ZSTD_decompressStream returned.  An error return leaves output.pos as compu set it, 0 -- libzstd decodes a block only once the one
@@ -1946,8 +1998,12 @@ done:
     }
     if (rs && lane == 0 && status != CHIP_NEED_INPUT && status != CHIP_NEED_OUTPUT) rs[0] = 0;  // nothing to continue
     if (lane == 0) {
-#if CHIP_ZSTD_SIZES
+#if CHIP_ZSTD_SIZES && CHIP_ZSTD_MEMBERS
+        out_size[u] = out_frames + dropped + opos;
+#elif CHIP_ZSTD_SIZES
         out_size[u] = dropped + opos;
+#elif CHIP_ZSTD_MEMBERS
+        a.out_len[u] = (uint32_t)out_frames + opos;
 #else
         a.out_len[u] = opos;
 #endif
@@ -1966,10 +2022,23 @@ done:
 
 }  // namespace
 
-#ifndef CHIP_ZSTD_SIZES_TU
+#if CHIP_ZSTD_MEMBERS && !defined(CHIP_ZSTD_SIZES_TU)
+hipError_t launch_zstd_members(const BatchArgs &a, int window_log_max, hipStream_t stream)
+{
+    hipLaunchKernelGGL(zstd_members_kernel, dim3(a.n), dim3(64), 0, stream, a, window_log_max ? window_log_max : 27);
+    return hipGetLastError();
+}
+#elif CHIP_ZSTD_MEMBERS
+hipError_t launch_zstd_members_sizes(const BatchArgs &a, uint64_t *out_size, int window_log_max, hipStream_t stream)
+{
+    hipLaunchKernelGGL(zstd_members_sizes_kernel, dim3(a.n), dim3(64), 0, stream, a, window_log_max ? window_log_max : 27, out_size);
+    return hipGetLastError();
+}
+#elif !defined(CHIP_ZSTD_SIZES_TU)
 hipError_t launch_zstd_decode(const BatchArgs &a, int window_log_max, hipStream_t stream)
 {
     if (a.n == 0) return hipSuccess;
+    if (a.flags & F_MEMBERS) return launch_zstd_members(a, window_log_max, stream);
     hipLaunchKernelGGL(zstd_kernel, dim3(a.n), dim3(64), 0, stream, a, window_log_max ? window_log_max : 27);
     return hipGetLastError();
 }
@@ -1977,6 +2046,7 @@ hipError_t launch_zstd_decode(const BatchArgs &a, int window_log_max, hipStream_
 hipError_t launch_zstd_sizes(const BatchArgs &a, uint64_t *out_size, int window_log_max, hipStream_t stream)
 {
     if (a.n == 0) return hipSuccess;
+    if (a.flags & F_MEMBERS) return launch_zstd_members_sizes(a, out_size, window_log_max, stream);
     hipLaunchKernelGGL(zstd_sizes_kernel, dim3(a.n), dim3(64), 0, stream, a, window_log_max ? window_log_max : 27, out_size);
     return hipGetLastError();
 }

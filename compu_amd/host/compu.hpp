@@ -58,6 +58,8 @@ struct Decode {
 };
 
 // src/decoder/zlib_common.rs:4-29
+// chip_decode_batch_ex / chip_decode_batch_sizes options (DeviceBuffer::decode_batch's `flags`); MEMBERS has no compu counterpart
+constexpr uint32_t F_COMPU_STATUS = CHIP_F_COMPU_STATUS, F_MEMBERS = CHIP_F_MEMBERS;
 enum class ZlibMode : int { Deflate = CHIP_FMT_DEFLATE, Zlib = CHIP_FMT_ZLIB, Gzip = CHIP_FMT_GZIP, Auto = CHIP_FMT_AUTO };
 
 // src/decoder/zstd.rs:22-74
@@ -488,7 +490,8 @@ public:
     }
     // chip_decode_batch[_ex] with this buffer's spare capacity as the output: unit i lands at spare + out_off[i] (device
     // arrays, as in chip_decode_batch); `span` bytes behind the cursor become part of the data.  Only enqueues.
-    // flags: CHIP_F_COMPU_STATUS reports every unit's status exactly as compu's decode_fn would (include/compu_hip.h).
+    // flags: CHIP_F_COMPU_STATUS reports every unit's status exactly as compu's decode_fn would; CHIP_F_MEMBERS decodes a unit
+    // as a series of gzip members / zstd frames (include/compu_hip.h).
     int decode_batch(int format, size_t n, const DeviceBuffer &in, const uint64_t *in_off, const uint32_t *in_len, const uint64_t *out_off,
                      const uint32_t *out_cap, uint32_t *out_len, uint32_t *in_used, int32_t *status, size_t span, void *stream = nullptr,
                      uint32_t flags = 0)

@@ -193,8 +193,49 @@ int chip_decode_batch(int format, size_t n, const void *in_base, const uint64_t 
  *     that fill out_cap[i] exactly (ZSTD_decompressStream returns an error before it writes output.pos, so compu sees 0),
  *     except for an empty output range (0 == 0: NeedOutput).
  * Everything else is identical.  Unknown flag bits: CHIP_E_INVALID.
+ *
+ * CHIP_F_MEMBERS: a unit is a SERIES of gzip members (RFC 1952 sec. 2.2: WARC / Common Crawl records, `cat a.gz b.gz`) or of
+ * zstd frames and skippable frames (RFC 8878 sec. 3.1: pzstd output, seekable files), decoded one behind the other by the wave
+ * that owns the unit, as gzip -d and ZSTD_decompress do.  For CHIP_FMT_GZIP, CHIP_FMT_AUTO, CHIP_FMT_ZSTD and CHIP_FMT_DETECT (routed:
+ * gzip / zlib units and zstd units each go to their member kernel, units that are neither are answered as without the flag).
+ * CHIP_E_INVALID, before the device is looked for, with CHIP_FMT_DEFLATE, CHIP_FMT_ZLIB and CHIP_FMT_BROTLI (no concatenation
+ * convention) and together with CHIP_F_COMPU_STATUS (compu has no multi-member decode to mirror).  No reference counterpart, and
+ * batch only: the streaming decoders do not take it (compu's caller sees Finished, calls reset and goes on), nor do
+ * chip_decode_batch_host / _multi, which have no flags word.
+ * The contract.  decode1(p, room) is what a unit without the flag answers for the input in[p .. len) and `room` bytes of output:
+ * (st, out_len, in_used).  With the flag a unit of `len` bytes and out_cap `cap` answers
+ *
+ *   p = 0; total = 0
+ *   loop:
+ *     (st, ol, iu) = decode1(p, cap - total)          # size pass: no room limit, 64-bit total
+ *     total += ol
+ *     if st != CHIP_FINISHED:
+ *         status = st; out_len = total
+ *         in_used = (st == CHIP_NEED_INPUT) ? len : p + iu
+ *         stop
+ *     p += iu
+ *     if another member starts at p: continue
+ *     status = CHIP_FINISHED; out_len = total; in_used = p; stop
+ *
+ * "Another member starts at p", only behind a unit of the same family --
+ *   gzip: the member just finished was gzip (not zlib under CHIP_FMT_AUTO / CHIP_FMT_DETECT), len - p >= 2 and the bytes at p
+ *     are 1f 8b;
+ *   zstd: len - p >= 4 and the LE32 at p is 0xFD2FB528 or 0x184D2A50 .. 0x184D2A5F.
+ * Anything else behind a finished member is trailing bytes, not counted in in_used, as without the flag: zero padding, a lone
+ * 1f, fewer than 4 bytes behind a zstd frame.  Once a member is started its verdict is the unit's: 1f 8b followed by nothing is
+ * CHIP_NEED_INPUT, 1f 8b 07 ... is -3, a wrong CRC in member 3 is -3 with out_len = members 1 and 2 plus what member 3 decoded
+ * (out_len counts the bytes in front of the error, as ever).  It follows that
+ *   - a match distance never reaches in front of its own member's first byte: gzip -3 ("invalid distance too far back"), zstd
+ *     -20, although the previous member's bytes lie right there in the output;
+ *   - CRC-32 / ISIZE and XXH64 / Frame_Content_Size are checked per member, over that member's bytes only;
+ *   - zstd's "on CHIP_NEED_OUTPUT out_len counts whole blocks only" applies to the frame that ran out of room; earlier frames
+ *     count in full;
+ *   - a unit made only of skippable frames is CHIP_FINISHED with out_len 0;
+ *   - in_len == 0 answers as without the flag, and a single-member unit answers the same with and without it.
+ * The loop ends: a started gzip member consumes at least 18 bytes, a started zstd frame at least 8, or the unit ends.
  */
 enum { CHIP_F_COMPU_STATUS = 1 };
+enum { CHIP_F_MEMBERS = 2 };
 int chip_decode_batch_ex(int format, uint32_t flags, size_t n, const void *in_base, const uint64_t *in_off, const uint32_t *in_len,
                          void *out_base, const uint64_t *out_off, const uint32_t *out_cap, uint32_t *out_len,
                          uint32_t *in_used, int32_t *status, void *stream);
@@ -207,7 +248,9 @@ int chip_decode_batch_ex(int format, uint32_t flags, size_t n, const void *in_ba
  *   out_size[i]  decoded length in bytes, 64-bit: a unit may decode to more than an out_cap can express
  *   in_used[i]   bytes of input consumed, as chip_decode_batch
  *   status[i]    as chip_decode_batch; never CHIP_NEED_OUTPUT
- * `flags` must be 0 (anything else: CHIP_E_INVALID); it is there so that options need no third entry point.
+ * `flags` is 0 or CHIP_F_MEMBERS (anything else, CHIP_F_COMPU_STATUS included: CHIP_E_INVALID).  With CHIP_F_MEMBERS (formats as
+ * for chip_decode_batch_ex) a unit is a series of members and the four rules below hold per unit, measured against the decode
+ * with the same flag; out_size[i] is the series' total and may exceed 2^32.
  * `format`: CHIP_FMT_DEFLATE, CHIP_FMT_ZLIB, CHIP_FMT_GZIP, CHIP_FMT_AUTO, CHIP_FMT_ZSTD (window_log_max: the default, as
  * chip_decode_batch), and CHIP_FMT_DETECT, routed exactly as a CHIP_FMT_DETECT decode batch is (units that are neither get
  * CHIP_UNKNOWN_FORMAT / CHIP_NEED_INPUT).  CHIP_FMT_BROTLI is CHIP_E_INVALID: brotli's literal context is the two previous
@@ -290,7 +333,9 @@ int chip_detect_batch(size_t n, const void *in_base, const uint64_t *in_off, con
  * A block at byte p has the 18-byte header htslib writes:  1f 8b 08 04 | MTIME (4) XFL OS, any value | 06 00 (XLEN 6) |
  * 42 43 02 00 ('B' 'C', SLEN 2) | BSIZE (u16 LE).  It is BSIZE + 1 bytes long and ISIZE is the u32 LE in its last 4 bytes.
  * LIMIT: the BC subfield must be the only one.  A block whose extra field holds other subfields as well is valid by the SAM
- * specification and CHIP_BGZF_BAD_HEADER here (no known writer emits one).
+ * specification and CHIP_BGZF_BAD_HEADER here (no known writer emits one).  Such a file still decodes, without a plan: as ONE
+ * CHIP_FMT_GZIP unit with CHIP_F_MEMBERS (chip_decode_batch_ex), one wave walking its members, within the 512 MiB limit of a
+ * unit's input.
  * The plan of `len` bytes is defined by this walk:
  *   p = 0, n = 0, total = 0
  *   loop: p == len -> OK;  len - p < 18 -> TRUNCATED;  header bytes wrong -> BAD_HEADER;

@@ -70,6 +70,9 @@ pub const CHIP_FMT_DETECT: c_int = 0;
 
 ///`chip_decode_batch_ex` flag: report `DecodeStatus` exactly as compu's `decode_fn` would
 pub const CHIP_F_COMPU_STATUS: u32 = 1;
+///`chip_decode_batch_ex` / `chip_decode_batch_sizes` flag: a unit is a series of gzip members or zstd frames, decoded one behind the
+///other (gzip, auto, zstd and detect batches; not together with `CHIP_F_COMPU_STATUS`).  No compu counterpart.
+pub const CHIP_F_MEMBERS: u32 = 2;
 ///`chip_decode_batch` / `chip_encode_batch` return codes
 pub const CHIP_OK: c_int = 0;
 
