@@ -46,6 +46,11 @@ class _BgzfSummary(C.Structure):
     _fields_ = [("n_blocks", C.c_uint64), ("total_out", C.c_uint64), ("in_used", C.c_uint64), ("status", C.c_int32), ("eof", C.c_uint32)]
 
 
+class _ZstdPlanSummary(C.Structure):
+    _fields_ = [("n_frames", C.c_uint64), ("n_skippable", C.c_uint64), ("n_unsized", C.c_uint64), ("total_out", C.c_uint64),
+                ("in_used", C.c_uint64), ("status", C.c_int32), ("pad", C.c_uint32)]
+
+
 _lib = None
 
 
@@ -134,6 +139,12 @@ def lib():
     L.chip_bgzf_plan.argtypes = [vp, C.c_uint64, C.c_uint64, vp, vp, vp, vp, C.POINTER(_BgzfSummary), vp]
     L.chip_bgzf_eof_block.restype = vp
     L.chip_bgzf_eof_block.argtypes = [C.POINTER(C.c_size_t)]
+    L.chip_zstd_plan_host.restype = C.c_int
+    L.chip_zstd_plan_host.argtypes = [vp, C.c_uint64, C.c_uint64, vp, vp, vp, vp, C.POINTER(_ZstdPlanSummary)]
+    L.chip_zstd_plan.restype = C.c_int
+    L.chip_zstd_plan.argtypes = [vp, C.c_uint64, C.c_uint64, vp, vp, vp, vp, C.POINTER(_ZstdPlanSummary), vp]
+    L.chip_layout_units.restype = C.c_int
+    L.chip_layout_units.argtypes = [sz, vp, vp, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), vp]
     _lib = L
     return L
 
@@ -1096,3 +1107,130 @@ def bgzf_decode(in_buf, length, stream=None):
             i = int(bad[0])
             raise RuntimeError(f"BGZF block {i} did not decode: status {int(status[i])}, {int(out_len[i])} of {int(out_cap[i])} bytes")
     return out[: summ.total_out]
+
+
+# ---- zstd frames: from a file to a batch (include/compu_hip.h, "zstd frames") -------------------
+
+ZPLAN_UNSIZED = 0xFFFFFFFF  # CHIP_ZPLAN_UNSIZED: out_cap of a frame without Frame_Content_Size (-1 in an int32 tensor)
+
+
+class ZstdPlanStatus(enum.IntEnum):
+    Ok = 0
+    Truncated = 1
+    BadHeader = 2
+    TooLarge = 3
+
+
+class ZstdPlanSummary:
+    """chip_zstd_plan_summary: n_frames, n_skippable, n_unsized and total_out of the whole walk, in_used where it stopped (the
+    start of the frame it stopped at), status why."""
+
+    __slots__ = ("n_frames", "n_skippable", "n_unsized", "total_out", "in_used", "status")
+
+    def __init__(self, raw):
+        self.n_frames, self.n_skippable, self.n_unsized = int(raw.n_frames), int(raw.n_skippable), int(raw.n_unsized)
+        self.total_out, self.in_used, self.status = int(raw.total_out), int(raw.in_used), ZstdPlanStatus(raw.status)
+
+    def as_tuple(self):
+        return (self.n_frames, self.n_skippable, self.n_unsized, self.total_out, self.in_used, int(self.status))
+
+    def __repr__(self):
+        return (f"ZstdPlanSummary(n_frames={self.n_frames}, n_skippable={self.n_skippable}, n_unsized={self.n_unsized}, "
+                f"total_out={self.total_out}, in_used={self.in_used}, status={self.status.name})")
+
+
+def zstd_plan_host(data, max_frames=None):
+    """chip_zstd_plan_host over bytes / a uint8 numpy array in host memory: (in_off u64, in_len u32, out_off u64, out_cap u32,
+    summary) of the first min(n_frames, max_frames) frames (None = all of them: one call to count, one to fill)."""
+    import numpy as np
+
+    buf = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8)
+    raw = _ZstdPlanSummary()
+    p = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None  # noqa: E731
+    if max_frames is None:
+        rc = lib().chip_zstd_plan_host(p(buf), buf.size, 0, None, None, None, None, C.byref(raw))
+        if rc != 0:
+            raise RuntimeError(f"chip_zstd_plan_host failed: {rc}")
+        max_frames = int(raw.n_frames)
+    m = int(max_frames)
+    in_off, in_len, out_off, out_cap = np.zeros(m, np.uint64), np.zeros(m, np.uint32), np.zeros(m, np.uint64), np.zeros(m, np.uint32)
+    rc = lib().chip_zstd_plan_host(p(buf), buf.size, m, p(in_off), p(in_len), p(out_off), p(out_cap), C.byref(raw))
+    if rc != 0:
+        raise RuntimeError(f"chip_zstd_plan_host failed: {rc}")
+    k = min(m, int(raw.n_frames))
+    return in_off[:k], in_len[:k], out_off[:k], out_cap[:k], ZstdPlanSummary(raw)
+
+
+def zstd_plan(in_buf, length, stream=None, max_frames=None):
+    """chip_zstd_plan over a uint8 device tensor holding `length` bytes of zstd frames (4-byte aligned, padded to a multiple of
+    4): returns (in_off int64, in_len int32, out_off int64, out_cap int32, summary) -- device tensors of the first
+    min(n_frames, max_frames) frames; with summary.n_unsized == 0 they are ready for decode_batch(FMT_ZSTD, ..).  Synchronous
+    on `stream`.  max_frames None: all of them (one call to count, one to fill)."""
+    import torch
+
+    dev = _check_tensors(((in_buf, torch.uint8),))
+    length = int(length)
+    if length < 0 or length > in_buf.numel():
+        raise ValueError(f"length {length} outside the buffer of {in_buf.numel()} bytes")
+    raw = _ZstdPlanSummary()
+    base, sp = (_dp(in_buf) if length else None), _stream_ptr(stream)
+    with torch.cuda.device(dev):
+        if max_frames is None:  # count, then fill
+            rc = lib().chip_zstd_plan(base, length, 0, None, None, None, None, C.byref(raw), sp)
+            if rc != 0:
+                raise RuntimeError(f"chip_zstd_plan failed: {rc}")
+            max_frames = int(raw.n_frames)
+        m = int(max_frames)
+        in_off, out_off = torch.empty(m, dtype=torch.int64, device=dev), torch.empty(m, dtype=torch.int64, device=dev)
+        in_len, out_cap = torch.empty(m, dtype=torch.int32, device=dev), torch.empty(m, dtype=torch.int32, device=dev)
+        q = lambda t: _dp(t) if m else None  # noqa: E731
+        rc = lib().chip_zstd_plan(base, length, m, q(in_off), q(in_len), q(out_off), q(out_cap), C.byref(raw), sp)
+    if rc != 0:
+        raise RuntimeError(f"chip_zstd_plan failed: {rc}")
+    k = min(m, int(raw.n_frames))
+    return in_off[:k], in_len[:k], out_off[:k], out_cap[:k], ZstdPlanSummary(raw)
+
+
+def layout_units(out_size, stream=None):
+    """chip_layout_units over the int64 device tensor a size pass filled (read as u64): returns (out_off int64, out_cap int32,
+    total, n_over) -- out_off the exclusive sum of the sizes, out_cap the sizes clipped to 0xFFFFFFFF, n_over how many were
+    clipped.  Synchronous on `stream`."""
+    import torch
+
+    dev = _check_tensors(((out_size, torch.int64),))
+    n = out_size.numel()
+    out_off, out_cap = torch.empty(n, dtype=torch.int64, device=dev), torch.empty(n, dtype=torch.int32, device=dev)
+    total, n_over = C.c_uint64(0), C.c_uint64(0)
+    q = lambda t: _dp(t) if n else None  # noqa: E731
+    with torch.cuda.device(dev):
+        rc = lib().chip_layout_units(n, q(out_size), q(out_off), q(out_cap), C.byref(total), C.byref(n_over), _stream_ptr(stream))
+    if rc != 0:
+        raise RuntimeError(f"chip_layout_units failed: {rc}")
+    return out_off, out_cap, int(total.value), int(n_over.value)
+
+
+def zstd_frames_decode(in_buf, length, stream=None):
+    """Decode a whole buffer of zstd frames on the device, one unit per frame: plan; when frames lack Frame_Content_Size, the
+    size pass over the plan's units and layout_units; allocate; decode_batch(FMT_ZSTD).  Raises ValueError when the buffer is
+    no whole series of frames (the summary says where) or a frame decodes to more than a unit can hold, and RuntimeError with
+    the first bad frame's index and status when a frame does not decode to its size.  Returns (the uint8 output tensor,
+    (in_off, in_len, out_off, out_cap) as used for the decode, summary).  Waits for the decode."""
+    import torch
+
+    in_off, in_len, out_off, out_cap, summ = zstd_plan(in_buf, length, stream=stream)
+    if summ.status != ZstdPlanStatus.Ok:
+        raise ValueError(f"not a whole series of zstd frames: {summ!r}")
+    total = summ.total_out
+    if summ.n_unsized:
+        out_size, _, _ = decode_batch_sizes(FMT_ZSTD, in_buf, in_off, in_len, stream=stream)
+        out_off, out_cap, total, n_over = layout_units(out_size, stream=stream)
+        if n_over:
+            raise ValueError(f"{n_over} frames decode to more than 4 GiB - 1: {summ!r}")
+    out = torch.empty(max(total, 4), dtype=torch.uint8, device=in_buf.device)
+    if summ.n_frames:
+        out_len, _, status = decode_batch(FMT_ZSTD, in_buf, in_off, in_len, out, out_off, out_cap, stream=stream)
+        bad = ((status != int(DecodeStatus.Finished)) | (out_len != out_cap)).nonzero()
+        if bad.numel():
+            i = int(bad[0])
+            raise RuntimeError(f"zstd frame {i} did not decode: status {int(status[i])}, {int(out_len[i])} of {int(out_cap[i])} bytes")
+    return out[:total], (in_off, in_len, out_off, out_cap), summ

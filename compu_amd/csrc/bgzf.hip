@@ -5,7 +5,7 @@
 // version gives the same answer without chasing BSIZE through HBM one block after the other:
 //   1. count    every byte position is tested for the gzip magic with FEXTRA (`1f 8b 08 04`) in 16-byte loads, the rare hits for the
 //               other fixed header bytes; one count per 16 KiB tile
-//   2. scan     exclusive scan of the tile counts (reduce-then-scan: bgzf_scan_local_kernel, bgzf_scan_partials_kernel)
+//   2. scan     exclusive scan of the tile counts (reduce-then-scan: plan_scan_local_kernel, plan_scan_partials_kernel)
 //      -- the host reads the candidate count and sizes the candidate scratch --
 //   3. emit     tiles with candidates are read again and their candidates written in ascending order: position, BSIZE and the
 //               per-candidate verdict (block too short / runs past the end / ISIZE too large), ISIZE
@@ -24,6 +24,7 @@
 
 #include "chip_internal.h"
 #include "launch_slots.h"
+#include "plan_common.h"
 
 namespace chip {
 
@@ -32,9 +33,6 @@ namespace {
 constexpr uint32_t BGZF_HDR = 18;               // bytes of the header this library accepts (XLEN 6: the BC subfield alone)
 constexpr uint32_t BGZF_MIN = 28;               // header + empty deflate body (2) + CRC-32 + ISIZE
 constexpr uint32_t BGZF_MAGIC = 0x04088b1fu;    // 1f 8b 08 04, little endian
-constexpr uint32_t TILE_THREADS = 256, TILE_ITERS = 4;
-constexpr uint32_t TILE_CHUNKS = TILE_THREADS * TILE_ITERS;  // 16-byte chunks per workgroup: a 16 KiB tile
-constexpr uint32_t SCAN_THREADS = 1024;
 
 // what the kernels hand to the host (device memory, copied back once the candidates are counted and once at the end)
 struct DevSummary {
@@ -52,106 +50,14 @@ struct Acc {
 };
 __host__ __device__ __forceinline__ Acc operator+(const Acc &a, const Acc &b) { return Acc{a.c + b.c, a.s + b.s}; }
 
-__device__ __forceinline__ uint64_t shfl_up_t(uint64_t v, uint32_t d) { return __shfl_up((unsigned long long)v, d, 64); }
 __device__ __forceinline__ Acc shfl_up_t(const Acc &v, uint32_t d) { return Acc{shfl_up_t(v.c, d), shfl_up_t(v.s, d)}; }
-
-// inclusive scan across the wave (Hillis-Steele over ds_bpermute; the 64-bit sums have no DPP form)
-template <class T>
-__device__ __forceinline__ T wave_incl_scan_t(T v)
-{
-    const uint32_t lane = lane_id();
-#pragma unroll
-    for (uint32_t d = 1; d < 64; d <<= 1) {
-        const T t = shfl_up_t(v, d);
-        if (lane >= d) v = v + t;
-    }
-    return v;
-}
-
-// exclusive scan across a workgroup of SCAN_THREADS; s_wave has SCAN_THREADS / 64 + 1 entries; every thread takes part
-template <class T>
-__device__ __forceinline__ T block_excl_scan(const T v, T *s_wave, T &total)
-{
-    constexpr uint32_t NW = SCAN_THREADS / 64;
-    const uint32_t lane = lane_id(), wave = threadIdx.x >> 6;
-    const T inc = wave_incl_scan_t(v);
-    T exc = shfl_up_t(inc, 1);
-    if (lane == 0) exc = T{};
-    if (lane == 63) s_wave[wave] = inc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        T run{};
-        for (uint32_t w = 0; w < NW; w++) {
-            const T t = s_wave[w];
-            s_wave[w] = run;
-            run = run + t;
-        }
-        s_wave[NW] = run;
-    }
-    __syncthreads();
-    const T r = s_wave[wave] + exc;
-    total = s_wave[NW];
-    __syncthreads();  // s_wave is free again
-    return r;
-}
-
-// out[i] = sum of in[b * SCAN_THREADS .. i) for the workgroup b that holds i; partial[b] = the workgroup's total
-template <class T>
-__global__ __launch_bounds__(SCAN_THREADS) void bgzf_scan_local_kernel(const T *in, T *out, uint64_t n, T *partial)
-{
-    __shared__ T s_wave[SCAN_THREADS / 64 + 1];
-    const uint64_t i = (uint64_t)blockIdx.x * SCAN_THREADS + threadIdx.x;
-    T total;
-    const T r = block_excl_scan(i < n ? in[i] : T{}, s_wave, total);
-    if (i < n) out[i] = r;
-    if (threadIdx.x == 0) partial[blockIdx.x] = total;
-}
-
-// one workgroup: partial[0 .. nb) becomes its exclusive scan, *total the sum
-template <class T>
-__global__ __launch_bounds__(SCAN_THREADS) void bgzf_scan_partials_kernel(T *partial, uint64_t nb, T *total)
-{
-    __shared__ T s_wave[SCAN_THREADS / 64 + 1];
-    T carry{};
-    for (uint64_t b0 = 0; b0 < nb; b0 += SCAN_THREADS) {
-        const uint64_t i = b0 + threadIdx.x;
-        T t;
-        const T r = block_excl_scan(i < nb ? partial[i] : T{}, s_wave, t);
-        if (i < nb) partial[i] = carry + r;
-        carry = carry + t;
-    }
-    if (threadIdx.x == 0) *total = carry;
-}
-
-struct __attribute__((packed, aligned(4))) Chunk16 {
-    uint32_t w[4];
-};
-
-// the 16 bytes of chunk g and the 4 behind them (in_base is 4-byte aligned and padded to len4 = len rounded up to 4; nothing
-// outside [0, len4) is read, what lies beyond reads as 0)
-__device__ __forceinline__ void load_chunk(const uint8_t *base, uint64_t len4, uint64_t g, uint32_t w[5])
-{
-    const uint64_t b = g * 16;
-    if (b + 20 <= len4) {
-        const Chunk16 v = *(const Chunk16 *)(base + b);
-        w[0] = v.w[0], w[1] = v.w[1], w[2] = v.w[2], w[3] = v.w[3];
-        w[4] = *(const uint32_t *)(base + b + 16);
-    } else {
-#pragma unroll
-        for (uint32_t k = 0; k < 5; k++) w[k] = b + 4 * k + 4 <= len4 ? *(const uint32_t *)(base + b + 4 * k) : 0u;
-    }
-}
 
 // bit k: the four bytes at offset k of the chunk are the magic
 __device__ __forceinline__ uint32_t magic_mask(const uint32_t w[5])
 {
     uint32_t m = 0;
 #pragma unroll
-    for (uint32_t k = 0; k < 16; k++) {
-        const uint32_t lo = w[k >> 2], hi = w[(k >> 2) + 1], sh = 8 * (k & 3);
-        const uint32_t v = sh ? (lo >> sh) | (hi << (32 - sh)) : lo;
-        m |= (v == BGZF_MAGIC ? 1u : 0u) << k;
-    }
+    for (uint32_t k = 0; k < 16; k++) m |= (chunk_word(w, k) == BGZF_MAGIC ? 1u : 0u) << k;
     return m;
 }
 
@@ -255,13 +161,7 @@ __global__ __launch_bounds__(256) void bgzf_succ_kernel(const uint64_t *pos, con
     const uint32_t f = info[i];
     if ((f >> 16) == 0) {
         const uint64_t nx = pos[i] + (f & 0xffffu) + 1u;
-        uint32_t lo = i + 1u, hi = n_cand;  // first candidate at or behind nx
-        while (lo < hi) {
-            const uint32_t mid = lo + ((hi - lo) >> 1);
-            if (pos[mid] < nx) lo = mid + 1u;
-            else hi = mid;
-        }
-        if (lo < n_cand && pos[lo] == nx) j = lo;
+        j = candidate_at(pos, i + 1u, n_cand, nx);
     }
     jump[i] = j;
     marked[i] = (i == 0 && pos[0] == 0) ? 1u : 0u;
@@ -270,24 +170,6 @@ __global__ __launch_bounds__(256) void bgzf_succ_kernel(const uint64_t *pos, con
         ds->status = len < BGZF_HDR ? CHIP_BGZF_TRUNCATED : CHIP_BGZF_BAD_HEADER;
         ds->eof = 0;
     }
-}
-
-__global__ __launch_bounds__(256) void bgzf_double_kernel(const uint32_t *jump, uint32_t *jump2, uint32_t n_cand)
-{
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= n_cand) return;
-    const uint32_t j = jump[i];
-    jump2[i] = j < n_cand ? (jump[j] < n_cand ? jump[j] : n_cand) : n_cand;
-}
-
-// One level of the top-down marking.  A candidate marked by another thread of this very launch may or may not hand its mark
-// on at once: either way only candidates on the chain from 0 get one, and those marked before the launch all hand it on.
-__global__ __launch_bounds__(256) void bgzf_mark_kernel(const uint32_t *jump, uint32_t *marked, uint32_t n_cand)
-{
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= n_cand || !marked[i]) return;
-    const uint32_t j = jump[i];
-    if (j < n_cand) marked[j] = 1u;
 }
 
 __global__ __launch_bounds__(256) void bgzf_flags_kernel(const uint32_t *info, const uint32_t *isz, const uint32_t *marked, uint32_t n_cand, Acc *acc)
@@ -335,18 +217,6 @@ struct BgzfSlot {
     size_t tiles_cap = 0, cand_cap = 0;
     DevSummary *d_sum = nullptr, *h_sum = nullptr;
 
-    // (the call that used a buffer last has waited for the stream, under the cache's lock: nothing in flight reads it)
-    static hipError_t grow(uint8_t *&p, size_t &cap, size_t want)
-    {
-        if (cap >= want) return hipSuccess;
-        (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        const size_t take = want + want / 4;
-        const hipError_t e = hipMalloc((void **)&p, take);
-        if (e == hipSuccess) cap = take;
-        return e;
-    }
     hipError_t summary()
     {
         hipError_t e = hipSuccess;
@@ -364,8 +234,6 @@ struct BgzfSlot {
 };
 SlotCache<BgzfSlot> g_bgzf_cache;
 
-inline size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
-
 // Enqueues everything, waits twice (candidate count, summary).  The caller holds the cache's lock.
 hipError_t plan_locked(BgzfSlot &sl, const uint8_t *base, uint64_t len, uint64_t max_blocks, uint64_t *in_off, uint32_t *in_len,
                        uint64_t *out_off, uint32_t *out_cap, chip_bgzf_summary *summary, hipStream_t stream, bool &too_many)
@@ -374,13 +242,13 @@ hipError_t plan_locked(BgzfSlot &sl, const uint8_t *base, uint64_t len, uint64_t
     if (e != hipSuccess) return e;
     const uint64_t n_chunks = (len + 15) / 16, n_tiles = (n_chunks + TILE_CHUNKS - 1) / TILE_CHUNKS;
     const uint64_t tile_parts = (n_tiles + SCAN_THREADS - 1) / SCAN_THREADS;
-    if ((e = BgzfSlot::grow(sl.tiles, sl.tiles_cap, (size_t)(2 * n_tiles + tile_parts) * 8)) != hipSuccess) return e;
+    if ((e = grow_buffer(sl.tiles, sl.tiles_cap, (size_t)(2 * n_tiles + tile_parts) * 8)) != hipSuccess) return e;
     uint64_t *tile_cnt = (uint64_t *)sl.tiles, *tile_excl = tile_cnt + n_tiles, *tile_part = tile_excl + n_tiles;
     if ((e = hipMemsetAsync(sl.d_sum, 0, sizeof(DevSummary), stream)) != hipSuccess) return e;
     hipLaunchKernelGGL(bgzf_count_kernel, dim3((uint32_t)n_tiles), dim3(TILE_THREADS), 0, stream, base, len, n_chunks, tile_cnt);
-    hipLaunchKernelGGL(bgzf_scan_local_kernel<uint64_t>, dim3((uint32_t)tile_parts), dim3(SCAN_THREADS), 0, stream, (const uint64_t *)tile_cnt,
+    hipLaunchKernelGGL(plan_scan_local_kernel<uint64_t>, dim3((uint32_t)tile_parts), dim3(SCAN_THREADS), 0, stream, (const uint64_t *)tile_cnt,
                        tile_excl, n_tiles, tile_part);
-    hipLaunchKernelGGL(bgzf_scan_partials_kernel<uint64_t>, dim3(1), dim3(SCAN_THREADS), 0, stream, tile_part, tile_parts, &sl.d_sum->cand);
+    hipLaunchKernelGGL(plan_scan_partials_kernel<uint64_t>, dim3(1), dim3(SCAN_THREADS), 0, stream, tile_part, tile_parts, &sl.d_sum->cand);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     if ((e = hipMemcpyAsync(sl.h_sum, sl.d_sum, sizeof(DevSummary), hipMemcpyDeviceToHost, stream)) != hipSuccess) return e;
     if ((e = hipStreamSynchronize(stream)) != hipSuccess) return e;
@@ -394,13 +262,12 @@ hipError_t plan_locked(BgzfSlot &sl, const uint8_t *base, uint64_t len, uint64_t
         return hipSuccess;
     }
     const uint32_t n_cand = (uint32_t)cand64;
-    uint32_t levels = 1;  // 2^levels > n_cand: every distance on the chain has its bits below `levels`
-    while (levels < 32 && (1ull << levels) <= n_cand) levels++;
+    const uint32_t levels = jump_levels(n_cand);
     const size_t cand_parts = ((size_t)n_cand + SCAN_THREADS - 1) / SCAN_THREADS;
     const size_t o_acc = 0, o_part = o_acc + (size_t)n_cand * sizeof(Acc), o_pos = o_part + cand_parts * sizeof(Acc);
     const size_t o_info = o_pos + (size_t)n_cand * 8, o_isz = up16(o_info + (size_t)n_cand * 4), o_mark = up16(o_isz + (size_t)n_cand * 4);
     const size_t o_jump = up16(o_mark + (size_t)n_cand * 4), jump_stride = up16((size_t)n_cand * 4);
-    if ((e = BgzfSlot::grow(sl.cand, sl.cand_cap, o_jump + jump_stride * levels)) != hipSuccess) return e;
+    if ((e = grow_buffer(sl.cand, sl.cand_cap, o_jump + jump_stride * levels)) != hipSuccess) return e;
     Acc *acc = (Acc *)(sl.cand + o_acc), *acc_part = (Acc *)(sl.cand + o_part);
     uint64_t *pos = (uint64_t *)(sl.cand + o_pos);
     uint32_t *info = (uint32_t *)(sl.cand + o_info), *isz = (uint32_t *)(sl.cand + o_isz), *marked = (uint32_t *)(sl.cand + o_mark);
@@ -412,13 +279,13 @@ hipError_t plan_locked(BgzfSlot &sl, const uint8_t *base, uint64_t len, uint64_t
     hipLaunchKernelGGL(bgzf_succ_kernel, cgrid, dim3(256), 0, stream, (const uint64_t *)pos, (const uint32_t *)info, n_cand, len, jump(0), marked,
                        sl.d_sum);
     for (uint32_t k = 0; k + 1 < levels; k++)
-        hipLaunchKernelGGL(bgzf_double_kernel, cgrid, dim3(256), 0, stream, (const uint32_t *)jump(k), jump(k + 1), n_cand);
-    for (uint32_t k = levels; k-- > 0;) hipLaunchKernelGGL(bgzf_mark_kernel, cgrid, dim3(256), 0, stream, (const uint32_t *)jump(k), marked, n_cand);
+        hipLaunchKernelGGL(plan_double_kernel, cgrid, dim3(256), 0, stream, (const uint32_t *)jump(k), jump(k + 1), n_cand);
+    for (uint32_t k = levels; k-- > 0;) hipLaunchKernelGGL(plan_mark_kernel, cgrid, dim3(256), 0, stream, (const uint32_t *)jump(k), marked, n_cand);
     hipLaunchKernelGGL(bgzf_flags_kernel, cgrid, dim3(256), 0, stream, (const uint32_t *)info, (const uint32_t *)isz, (const uint32_t *)marked, n_cand,
                        acc);
-    hipLaunchKernelGGL(bgzf_scan_local_kernel<Acc>, dim3((uint32_t)cand_parts), dim3(SCAN_THREADS), 0, stream, (const Acc *)acc, acc, (uint64_t)n_cand,
+    hipLaunchKernelGGL(plan_scan_local_kernel<Acc>, dim3((uint32_t)cand_parts), dim3(SCAN_THREADS), 0, stream, (const Acc *)acc, acc, (uint64_t)n_cand,
                        acc_part);
-    hipLaunchKernelGGL(bgzf_scan_partials_kernel<Acc>, dim3(1), dim3(SCAN_THREADS), 0, stream, acc_part, (uint64_t)cand_parts, (Acc *)sl.d_sum);
+    hipLaunchKernelGGL(plan_scan_partials_kernel<Acc>, dim3(1), dim3(SCAN_THREADS), 0, stream, acc_part, (uint64_t)cand_parts, (Acc *)sl.d_sum);
     hipLaunchKernelGGL(bgzf_output_kernel, cgrid, dim3(256), 0, stream, (const uint64_t *)pos, (const uint32_t *)info, (const uint32_t *)isz,
                        (const uint32_t *)marked, (const uint32_t *)jump(0), (const Acc *)acc, (const Acc *)acc_part, n_cand, len, max_blocks, in_off,
                        in_len, out_off, out_cap, sl.d_sum);

@@ -516,6 +516,21 @@ public:
         if (len > in.len()) return CHIP_E_INVALID;
         return chip_bgzf_plan(in.data(), len, max_blocks, in_off, in_len, out_off, out_cap, &summary, stream);
     }
+    // chip_zstd_plan over the zstd frames held in `in` (its first `len` bytes): the four DEVICE arrays of the decode_batch(CHIP_FMT_ZSTD, ..)
+    // that follows, for the first min(n_frames, max_frames) frames, and the summary of the whole walk.  Synchronous on `stream`.
+    static int zstd_plan(const DeviceBuffer &in, uint64_t len, uint64_t max_frames, uint64_t *in_off, uint32_t *in_len, uint64_t *out_off,
+                         uint32_t *out_cap, chip_zstd_plan_summary &summary, void *stream = nullptr)
+    {
+        if (len > in.len()) return CHIP_E_INVALID;
+        return chip_zstd_plan(in.data(), len, max_frames, in_off, in_len, out_off, out_cap, &summary, stream);
+    }
+    // chip_layout_units: from the out_size of decode_batch_sizes() to the out_off / out_cap of decode_batch() (DEVICE arrays); `total` is
+    // what to allocate, `n_over` counts the units above 4 GiB - 1.  Synchronous on `stream`.
+    static int layout_units(size_t n, const uint64_t *out_size, uint64_t *out_off, uint32_t *out_cap, uint64_t &total, uint64_t &n_over,
+                            void *stream = nullptr)
+    {
+        return chip_layout_units(n, out_size, out_off, out_cap, &total, &n_over, stream);
+    }
 
 private:
     uint8_t *buf_;
@@ -528,6 +543,12 @@ inline int bgzf_plan_host(const uint8_t *in, uint64_t len, uint64_t max_blocks, 
                           uint32_t *out_cap, chip_bgzf_summary &summary)
 {
     return chip_bgzf_plan_host(in, len, max_blocks, in_off, in_len, out_off, out_cap, &summary);
+}
+// chip_zstd_plan_host: the zstd frame walk over host memory (no device needed); the arrays are what chip_decode_batch_host / _multi take.
+inline int zstd_plan_host(const uint8_t *in, uint64_t len, uint64_t max_frames, uint64_t *in_off, uint32_t *in_len, uint64_t *out_off,
+                          uint32_t *out_cap, chip_zstd_plan_summary &summary)
+{
+    return chip_zstd_plan_host(in, len, max_frames, in_off, in_len, out_off, out_cap, &summary);
 }
 // htslib's 28-byte EOF marker, to be written behind the last block of a file made with chip_encode_batch(CHIP_FMT_BGZF, ..)
 inline const uint8_t *bgzf_eof_block(size_t &len) { return chip_bgzf_eof_block(&len); }

@@ -376,6 +376,89 @@ int chip_bgzf_plan(const void *in_base, uint64_t len, uint64_t max_blocks, uint6
 /* htslib's 28-byte EOF marker (an empty BGZF block); *len gets 28 (len may be NULL).  Static storage. */
 const uint8_t *chip_bgzf_eof_block(size_t *len);
 
+/* ---- zstd frames: from a file to a batch (additive API) ------------------- */
+
+/*
+ * A zstd file may hold many frames (RFC 8878 sec. 3.1: pzstd output, the seekable format, one frame per chunk, `cat a.zst b.zst`),
+ * with skippable frames among them.  Where a frame ends is found without decoding anything: from its header and the 3-byte header
+ * of each block; with Frame_Content_Size the frame also states how much room it needs.  These calls turn such a buffer into the
+ * four arrays of chip_decode_batch(CHIP_FMT_ZSTD, ..), one unit and so one wave per frame, where the same buffer as ONE unit with
+ * CHIP_F_MEMBERS is decoded by a single wave.  All integers are little endian.
+ * The plan of `len` bytes is defined by this walk:
+ *   p = 0; n = 0; skipped = 0; unsized = 0; total = 0
+ *   loop:
+ *     p == len            -> OK
+ *     len - p < 4         -> TRUNCATED
+ *     m = LE32(p)
+ *     m in 0x184D2A50 .. 0x184D2A5F (skippable frame):
+ *         len - p < 8 -> TRUNCATED;  s = LE32(p + 4);  s > len - p - 8 -> TRUNCATED
+ *         skipped++;  p += 8 + s;  continue                 (no unit: indices count data frames only)
+ *     m != 0xFD2FB528     -> BAD_HEADER
+ *     len - p < 5         -> TRUNCATED
+ *     fhd = byte(p + 4);  f = fhd >> 6;  ss = (fhd >> 5) & 1;  d = fhd & 3
+ *     hs = 5 + (ss ? 0 : 1) + {0,1,2,4}[d] + (f == 0 ? ss : {-,2,4,8}[f])
+ *     len - p < hs        -> TRUNCATED
+ *     fcs = absent when f == 0 and ss == 0, else the field's value (the 2-byte form + 256)
+ *     q = p + hs;  blocks = 0
+ *     per block:  len - q < 3 -> TRUNCATED;  h = LE24(q);  type = (h >> 1) & 3;  type == 3 -> BAD_HEADER
+ *                 ++blocks > CHIP_ZPLAN_MAX_BLOCKS -> TOO_LARGE
+ *                 body = (type == 1) ? 1 : h >> 3;  body > len - q - 3 -> TRUNCATED
+ *                 q += 3 + body;  stop after the block with h & 1
+ *     fhd & 4 (checksum):  len - q < 4 -> TRUNCATED;  q += 4
+ *     q - p > 2^32 - 1, or fcs present and fcs >= 0xFFFFFFFF  -> TOO_LARGE
+ *     frame n:  in_off = p, in_len = q - p, out_off = total,
+ *               out_cap = fcs, or CHIP_ZPLAN_UNSIZED (adds 0 to total, unsized++)
+ *     n++;  total += fcs or 0;  p = q
+ * summary: n_frames = n, n_skippable = skipped, n_unsized = unsized and total_out = total of the WHOLE walk, status why it
+ * stopped, in_used = the p of the frame (or skippable frame) where it stopped -- not q: a frame that is cut or refused is not
+ * consumed.  The plan judges only what it needs to find lengths.  The reserved bit of the frame header descriptor, the window
+ * descriptor, the dictionary ID, Block_Maximum_Size, the content of the blocks and Frame_Content_Size against what the blocks
+ * decode to are the business of the decode that follows, as they are today.  The block cap belongs to the definition (host and
+ * device): a frame of legal empty raw blocks would otherwise keep a single GPU lane hopping for minutes, and at the block sizes
+ * libzstd writes 2^20 blocks are far beyond the 4 GiB in_len can express.
+ * The arrays receive the first min(n_frames, max_frames) frames and nothing behind them is written: max_frames = 0 with null
+ * arrays counts, a second call fills.  in_off is relative to the buffer and out_off starts at 0, so with n_unsized == 0 the
+ * arrays go unchanged to chip_decode_batch(CHIP_FMT_ZSTD, n_frames, in_base, in_off, in_len, out, out_off, out_cap, ..).  With
+ * unsized frames: chip_decode_batch_sizes over in_off / in_len, then chip_layout_units, then the decode.
+ * CHIP_E_INVALID, checked before the device is looked for: summary NULL, a NULL buffer with len > 0, NULL arrays with
+ * max_frames > 0 (chip_zstd_plan: in_base not 4-byte aligned, len > 2^40).  len == 0 is CHIP_OK with an all-zero summary.
+ * No reference counterpart: compu has no container formats.
+ */
+enum { CHIP_ZPLAN_OK = 0, CHIP_ZPLAN_TRUNCATED = 1, CHIP_ZPLAN_BAD_HEADER = 2, CHIP_ZPLAN_TOO_LARGE = 3 };
+#define CHIP_ZPLAN_UNSIZED 0xFFFFFFFFu   /* out_cap of a frame without Frame_Content_Size */
+#define CHIP_ZPLAN_MAX_BLOCKS (1u << 20) /* blocks per frame the walk follows */
+typedef struct {
+    uint64_t n_frames, n_skippable, n_unsized, total_out, in_used;
+    int32_t status;
+    uint32_t pad;
+} chip_zstd_plan_summary;
+
+/* The walk itself on HOST memory: pure host arithmetic, no device needed.  Its arrays are what chip_decode_batch_host /
+ * chip_decode_batch_multi take. */
+int chip_zstd_plan_host(const uint8_t *in, uint64_t len, uint64_t max_frames, uint64_t *in_off, uint32_t *in_len, uint64_t *out_off,
+                        uint32_t *out_cap, chip_zstd_plan_summary *summary);
+
+/* The same answer for a buffer in DEVICE memory, with the conventions of chip_bgzf_plan: in_base and the four arrays are DEVICE
+ * pointers, summary is a HOST pointer; in_base 4-byte aligned, its allocation padded to a multiple of 4 bytes; len is arbitrary.
+ * SYNCHRONOUS on `stream`: it returns when the arrays are in device memory and *summary is filled, and waits once in between to
+ * size its scratch by the number of magic-number candidates.  Scratch per (device, stream), a launch slot of its own, kept between
+ * calls and released by chip_trim(): 16 bytes per 16 KiB of input and 60 + 4 * ceil(log2(candidates + 1)) bytes per candidate.
+ * More than 2^31 - 1 candidates: CHIP_E_NOMEM.  Input that changes during the call: CHIP_E_LAUNCH, nothing is written out of
+ * range.  The calling thread's current device is left as it was. */
+int chip_zstd_plan(const void *in_base, uint64_t len, uint64_t max_frames, uint64_t *in_off, uint32_t *in_len, uint64_t *out_off,
+                   uint32_t *out_cap, chip_zstd_plan_summary *summary, void *stream);
+
+/* The step between chip_decode_batch_sizes and chip_decode_batch, on the device: out_size (the size pass's answer), out_off and
+ * out_cap are DEVICE arrays of n entries; out_off[i] = the exclusive 64-bit sum of out_size[0 .. i), out_cap[i] =
+ * min(out_size[i], 0xFFFFFFFF).  total and n_over are HOST pointers: the sum of all sizes, and the number of units with
+ * out_size > 0xFFFFFFFF (too large for one unit; their out_cap is clipped).  SYNCHRONOUS on `stream` (the caller allocates
+ * `total` bytes next).  out_size and out_off must not be the same array.  n == 0 writes *total = *n_over = 0 without touching the
+ * device.  CHIP_E_INVALID before the device is looked for: total or n_over NULL, a NULL array with n > 0, n > 2^32 - 1.  Scratch:
+ * 8 bytes per 1024 units in the slot of chip_zstd_plan.  Without it a caller holding frames with no Frame_Content_Size, or gzip
+ * units after a size pass, copies n sizes to the host and n offsets back.  No reference counterpart. */
+int chip_layout_units(size_t n, const uint64_t *out_size, uint64_t *out_off, uint32_t *out_cap, uint64_t *total, uint64_t *n_over,
+                      void *stream);
+
 /* ---- encoder: mirrors encoder::Interface, src/encoder/mod.rs:52-57 ---------------------------- */
 
 typedef struct chip_encoder chip_encoder;

@@ -333,3 +333,60 @@ pub fn partition_units(in_len: &[u32], out_cap: &[u32], parts: usize) -> Option<
     let rc = unsafe { sys::chip_partition_units(in_len.len(), in_len.as_ptr(), out_cap.as_ptr(), parts as _, cuts.as_mut_ptr()) };
     if rc == sys::CHIP_OK { Some(cuts) } else { None }
 }
+
+///The frame index of a buffer of zstd frames in host memory (`chip_zstd_plan_host`): `(in_off, in_len, out_off, out_cap)` of every
+///data frame -- what `decode_batch_host` / `decode_batch_multi` take with `BatchFormat::Zstd` once no `out_cap` is
+///`CHIP_ZPLAN_UNSIZED` -- and the summary of the walk.  Pure host arithmetic.  No counterpart in this crate.
+#[allow(clippy::type_complexity)]
+pub fn zstd_plan_host(input: &[u8]) -> Result<(alloc::vec::Vec<u64>, alloc::vec::Vec<u32>, alloc::vec::Vec<u64>, alloc::vec::Vec<u32>, sys::chip_zstd_plan_summary), i32> {
+    let mut summary = sys::chip_zstd_plan_summary::default();
+    let rc = unsafe { sys::chip_zstd_plan_host(input.as_ptr(), input.len() as u64, 0, ptr::null_mut(), ptr::null_mut(), ptr::null_mut(), ptr::null_mut(), &mut summary) };
+    if rc != sys::CHIP_OK {
+        return Err(rc);
+    }
+    let n = summary.n_frames as usize;
+    let (mut in_off, mut in_len, mut out_off, mut out_cap) = (alloc::vec![0u64; n], alloc::vec![0u32; n], alloc::vec![0u64; n], alloc::vec![0u32; n]);
+    let rc = unsafe {
+        sys::chip_zstd_plan_host(input.as_ptr(), input.len() as u64, n as u64, in_off.as_mut_ptr(), in_len.as_mut_ptr(), out_off.as_mut_ptr(),
+                                 out_cap.as_mut_ptr(), &mut summary)
+    };
+    if rc == sys::CHIP_OK { Ok((in_off, in_len, out_off, out_cap, summary)) } else { Err(rc) }
+}
+
+///`chip_zstd_plan` over the first `len` bytes of a device-resident buffer: fills the four device arrays for the first
+///`max_frames` frames and returns the summary of the whole walk (`max_frames` 0 counts).  Synchronous on `stream`.
+///
+///# Safety
+///
+///As `decode_batch_device`; `input` must be 4-byte aligned and padded to a multiple of 4 bytes.
+pub unsafe fn zstd_plan_device(input: &crate::buffer::DeviceBuffer, len: usize, max_frames: usize, in_off: &mut crate::buffer::DeviceBuffer,
+                               in_len: &mut crate::buffer::DeviceBuffer, out_off: &mut crate::buffer::DeviceBuffer, out_cap: &mut crate::buffer::DeviceBuffer,
+                               stream: *mut core::ffi::c_void) -> Result<sys::chip_zstd_plan_summary, i32> {
+    if len > input.capacity() || in_off.capacity() < 8 * max_frames || out_off.capacity() < 8 * max_frames || in_len.capacity() < 4 * max_frames
+        || out_cap.capacity() < 4 * max_frames
+    {
+        return Err(-101);
+    }
+    let mut summary = sys::chip_zstd_plan_summary::default();
+    let rc = sys::chip_zstd_plan(input.as_ptr() as *const _, len as u64, max_frames as u64, in_off.as_mut_ptr() as *mut u64, in_len.as_mut_ptr() as *mut u32,
+                                 out_off.as_mut_ptr() as *mut u64, out_cap.as_mut_ptr() as *mut u32, &mut summary, stream);
+    if rc == sys::CHIP_OK { Ok(summary) } else { Err(rc) }
+}
+
+///`chip_layout_units`: from the `out_size` of `decode_batch_sizes_device` to the `out_off` / `out_cap` of `decode_batch_device`
+///without a host round trip per unit.  Returns `(total, n_over)`: the bytes to allocate and the units above 4 GiB - 1.
+///Synchronous on `stream`.
+///
+///# Safety
+///
+///As `decode_batch_device`.
+pub unsafe fn layout_units_device(n: usize, out_size: &crate::buffer::DeviceBuffer, out_off: &mut crate::buffer::DeviceBuffer,
+                                  out_cap: &mut crate::buffer::DeviceBuffer, stream: *mut core::ffi::c_void) -> Result<(u64, u64), i32> {
+    if out_size.capacity() < 8 * n || out_off.capacity() < 8 * n || out_cap.capacity() < 4 * n {
+        return Err(-101);
+    }
+    let (mut total, mut n_over) = (0u64, 0u64);
+    let rc = sys::chip_layout_units(n, out_size.as_ptr() as *const u64, out_off.as_mut_ptr() as *mut u64, out_cap.as_mut_ptr() as *mut u32, &mut total,
+                                    &mut n_over, stream);
+    if rc == sys::CHIP_OK { Ok((total, n_over)) } else { Err(rc) }
+}

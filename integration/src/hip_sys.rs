@@ -92,6 +92,30 @@ pub struct chip_bgzf_summary {
     pub eof: u32,
 }
 
+///`chip_zstd_plan_summary::status`
+pub const CHIP_ZPLAN_OK: i32 = 0;
+pub const CHIP_ZPLAN_TRUNCATED: i32 = 1;
+pub const CHIP_ZPLAN_BAD_HEADER: i32 = 2;
+pub const CHIP_ZPLAN_TOO_LARGE: i32 = 3;
+///`out_cap` of a frame without `Frame_Content_Size`
+pub const CHIP_ZPLAN_UNSIZED: u32 = 0xFFFF_FFFF;
+///blocks per frame the walk follows
+pub const CHIP_ZPLAN_MAX_BLOCKS: u32 = 1 << 20;
+
+///what the zstd frame walk found: frames, skippable frames, frames without a content size and stated content bytes of the whole
+///walk, the start of the frame where it stopped and why
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct chip_zstd_plan_summary {
+    pub n_frames: u64,
+    pub n_skippable: u64,
+    pub n_unsized: u64,
+    pub total_out: u64,
+    pub in_used: u64,
+    pub status: i32,
+    pub pad: u32,
+}
+
 pub type chip_malloc_fn = unsafe extern "C" fn(opaque: *mut c_void, size: usize) -> *mut c_void;
 pub type chip_free_fn = unsafe extern "C" fn(opaque: *mut c_void, ptr: *mut c_void);
 
@@ -147,6 +171,17 @@ extern "C" {
                           summary: *mut chip_bgzf_summary, stream: *mut c_void) -> c_int;
     ///htslib's 28-byte EOF marker (static storage)
     pub fn chip_bgzf_eof_block(len: *mut usize) -> *const u8;
+
+    // ---- zstd frames: the four arrays of chip_decode_batch(CHIP_FMT_ZSTD, ..) from a buffer of frames (no reference counterpart)
+    ///the serial walk on host memory; pure host arithmetic, no device needed
+    pub fn chip_zstd_plan_host(input: *const u8, len: u64, max_frames: u64, in_off: *mut u64, in_len: *mut u32, out_off: *mut u64, out_cap: *mut u32,
+                               summary: *mut chip_zstd_plan_summary) -> c_int;
+    ///the same answer for a buffer in device memory (device arrays, host summary); synchronous on `stream`
+    pub fn chip_zstd_plan(in_base: *const c_void, len: u64, max_frames: u64, in_off: *mut u64, in_len: *mut u32, out_off: *mut u64, out_cap: *mut u32,
+                          summary: *mut chip_zstd_plan_summary, stream: *mut c_void) -> c_int;
+    ///from a size pass to a decode on the device: offsets (exclusive sum) and clipped capacities of `out_size`; host `total` / `n_over`
+    pub fn chip_layout_units(n: usize, out_size: *const u64, out_off: *mut u64, out_cap: *mut u32, total: *mut u64, n_over: *mut u64,
+                             stream: *mut c_void) -> c_int;
 
     pub fn chip_encoder_new(opts: *const chip_encoder_opts) -> *mut chip_encoder;
     pub fn chip_encoder_new_zstd(opts: *const chip_zstd_encoder_opts) -> *mut chip_encoder;
