@@ -51,6 +51,10 @@ class _ZstdPlanSummary(C.Structure):
                 ("in_used", C.c_uint64), ("status", C.c_int32), ("pad", C.c_uint32)]
 
 
+class _FileSummary(C.Structure):
+    _fields_ = [("n_units", C.c_uint64), ("out_len", C.c_uint64), ("table_off", C.c_uint64), ("status", C.c_int32), ("pad", C.c_uint32)]
+
+
 _lib = None
 
 
@@ -145,6 +149,12 @@ def lib():
     L.chip_zstd_plan.argtypes = [vp, C.c_uint64, C.c_uint64, vp, vp, vp, vp, C.POINTER(_ZstdPlanSummary), vp]
     L.chip_layout_units.restype = C.c_int
     L.chip_layout_units.argtypes = [sz, vp, vp, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), vp]
+    L.chip_pack_units.restype = C.c_int
+    L.chip_pack_units.argtypes = [sz, vp, vp, vp, vp, C.c_uint64, vp, C.POINTER(C.c_uint64), vp]
+    L.chip_encode_file.restype = C.c_int
+    L.chip_encode_file.argtypes = [C.c_int, C.c_int, C.c_uint32, C.c_uint32, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(_FileSummary), vp]
+    L.chip_encode_file_bound.restype = C.c_uint64
+    L.chip_encode_file_bound.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint64]
     _lib = L
     return L
 
@@ -1234,3 +1244,100 @@ def zstd_frames_decode(in_buf, length, stream=None):
             i = int(bad[0])
             raise RuntimeError(f"zstd frame {i} did not decode: status {int(status[i])}, {int(out_len[i])} of {int(out_cap[i])} bytes")
     return out[:total], (in_off, in_len, out_off, out_cap), summ
+
+
+# ---- writing files: from a batch to a file (include/compu_hip.h, "writing files") ---------------
+
+W_SEEK_TABLE = 1  # CHIP_W_SEEK_TABLE: the seek table of zstd's seekable format behind the last frame (FMT_ZSTD only)
+
+
+class FileStatus(enum.IntEnum):
+    Ok = 0
+    NeedOutput = 1
+
+
+class FileSummary:
+    """chip_file_summary: n_units encoded, out_len the file's length (the exact size needed on NeedOutput), table_off where the
+    seek table starts (out_len without one), status."""
+
+    __slots__ = ("n_units", "out_len", "table_off", "status")
+
+    def __init__(self, raw):
+        self.n_units, self.out_len, self.table_off = int(raw.n_units), int(raw.out_len), int(raw.table_off)
+        self.status = FileStatus(raw.status)
+
+    def as_tuple(self):
+        return (self.n_units, self.out_len, self.table_off, int(self.status))
+
+    def __repr__(self):
+        return f"FileSummary(n_units={self.n_units}, out_len={self.out_len}, table_off={self.table_off}, status={self.status.name})"
+
+
+def pack_units(src, src_off, src_len, dst=None, stream=None):
+    """chip_pack_units over device tensors: the ranges src[src_off[i] .. + src_len[i]) (src uint8, src_off int64 read as u64,
+    src_len int32 read as u32) end to end.  dst None: a tensor of exactly `total` bytes is allocated (one call to size it, one to
+    fill).  With a dst that is too small nothing is written; compare the returned total with dst.numel().  Returns (dst, dst_off
+    int64, total).  Synchronous on `stream`."""
+    import torch
+
+    pairs = [(src, torch.uint8), (src_off, torch.int64), (src_len, torch.int32)] + ([(dst, torch.uint8)] if dst is not None else [])
+    dev = _check_tensors(pairs)
+    n = src_len.numel()
+    if src_off.numel() != n:
+        raise ValueError(f"{src_off.numel()} offsets for {n} lengths")
+    dst_off = torch.empty(n, dtype=torch.int64, device=dev)
+    total = C.c_uint64(0)
+    q = lambda t: _dp(t) if t is not None and t.numel() else None  # noqa: E731
+    sp = _stream_ptr(stream)
+
+    def call(d):
+        rc = lib().chip_pack_units(n, q(src) if n else None, q(src_off), q(src_len), q(d), d.numel() if d is not None else 0, q(dst_off),
+                                   C.byref(total), sp)
+        if rc != 0:
+            raise RuntimeError(f"chip_pack_units failed: {rc}")
+
+    with torch.cuda.device(dev):
+        call(dst)
+        if dst is None:
+            dst = torch.empty(int(total.value), dtype=torch.uint8, device=dev)
+            if total.value:
+                call(dst)
+    return dst, dst_off, int(total.value)
+
+
+def encode_file_bound(fmt, length, unit_bytes=0, flags=0):
+    """chip_encode_file_bound: the output size that is always enough; 0 for arguments encode_file refuses."""
+    return int(lib().chip_encode_file_bound(int(fmt), int(unit_bytes), int(flags), int(length)))
+
+
+def encode_file(fmt, level, in_buf, length, unit_bytes=0, flags=0, stream=None, out=None):
+    """chip_encode_file over a uint8 device tensor holding `length` bytes (4-byte aligned, padded to a multiple of 4): cut into
+    units of unit_bytes (0: 65280 for FMT_BGZF, 262144 for ZlibMode.Gzip and FMT_ZSTD), encoded, packed, trailer appended -- a
+    BGZF file, a file of gzip members, a file of zstd frames (flags W_SEEK_TABLE: with the seekable format's seek table).
+    out None: a tensor of encode_file_bound bytes is allocated and the result is a view of its first out_len bytes.  With an
+    `out` that is too small the summary says NeedOutput with the exact out_len and nothing is written.  Returns (the uint8
+    output tensor trimmed to out_len -- None on NeedOutput --, summary).  Synchronous on `stream`."""
+    import torch
+
+    dev = _check_tensors(((in_buf, torch.uint8),) + (((out, torch.uint8),) if out is not None else ()))
+    length = int(length)
+    if length < 0 or length > in_buf.numel():
+        raise ValueError(f"length {length} outside the buffer of {in_buf.numel()} bytes")
+    if out is None:
+        bound = encode_file_bound(fmt, length, unit_bytes, flags)
+        if bound == 0:
+            raise ValueError(f"encode_file refuses format {int(fmt)}, unit_bytes {unit_bytes}, flags {flags}, length {length}")
+        out = torch.empty(bound, dtype=torch.uint8, device=dev)
+    raw = _FileSummary()
+    with torch.cuda.device(dev):
+        rc = lib().chip_encode_file(int(fmt), int(level), int(unit_bytes), int(flags), _dp(in_buf) if length else None, length,
+                                    _dp(out) if out.numel() else None, out.numel(), C.byref(raw), _stream_ptr(stream))
+    if rc != 0:
+        raise RuntimeError(f"chip_encode_file failed: {rc}")
+    summ = FileSummary(raw)
+    return (out[: summ.out_len] if summ.status == FileStatus.Ok else None), summ
+
+
+def bgzf_write(in_buf, length, level=6, stream=None):
+    """A whole BGZF file of the first `length` bytes of in_buf: encode_file(FMT_BGZF, level, ..) with htslib's block payload."""
+    return encode_file(FMT_BGZF, level, in_buf, length, stream=stream)

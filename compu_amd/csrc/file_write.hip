@@ -1,0 +1,386 @@
+// The write side of the container formats: chip_pack_units lays ranges of device memory end to end, chip_encode_file cuts a buffer
+// into units, encodes them with the batch encoder, packs the results and appends the format's trailer (htslib's EOF block, the
+// seek table of zstd's seekable format).  DESIGN.md sec. 4.13.
+//
+//   1. widen    the 32-bit lengths become 64-bit sums-to-be (chip_encode_file: a unit that is not CHIP_ENC_FINISHED is counted)
+//   2. scan     exclusive 64-bit scan (plan_common.h), the total goes to the summary
+//      -- the host reads the total and compares it with the room --
+//   3. copy     destination-driven: one wave per PACK_TILE bytes of destination, cut at absolute addresses that are multiples of
+//               16.  The wave finds the unit that holds the tile's first byte with a binary search over the offsets, then walks the
+//               units that intersect the tile, their offsets and lengths loaded 64 units at a time; each intersection is byte
+//               stores up to the first 16-byte aligned destination address, aligned 16-byte stores fed by unaligned 16-byte
+//               loads, byte stores for the rest.
+//   4. trailer  (chip_encode_file) 28 bytes of EOF block, or 17 + 8n bytes of seek table from the device arrays
+// Order between the phases comes from kernel boundaries on the stream only.  A destination byte belongs to exactly one tile and
+// is written once, by that tile's wave; no store is wider than its bytes, so no wave ever touches a 16-byte granule's bytes that
+// belong to another.  The copy writes dst[0 .. total) only, whatever the arrays hold by then: every store is clipped to its tile,
+// and the tiles end at the total the host compared with the room.
+#include <string.h>
+
+#include <mutex>
+
+#include "chip_internal.h"
+#include "launch_slots.h"
+#include "plan_common.h"
+
+namespace chip {
+
+namespace {
+
+typedef uint32_t pk_u32x4 __attribute__((ext_vector_type(4)));
+typedef pk_u32x4 pk_u32x4_u __attribute__((aligned(1)));  // 16 bytes at any address (gfx950 does unaligned global loads)
+
+// Destination bytes per wave: 4 rounds of 64 lanes x 16 bytes, all four loads of a lane issued before its first store.  With
+// 16 waves resident per CU that is 64 KiB of loads in flight per CU, the amount that hides most of an HBM miss on this chip;
+// a larger tile adds nothing to that and makes the many-small-units case walk more units per wave.
+constexpr uint32_t PACK_TILE = 4096;
+constexpr uint32_t PACK_ROUNDS = PACK_TILE / (64 * 16);
+constexpr uint32_t PACK_WAVES = 4;  // waves (tiles) per workgroup
+
+// what the kernels hand to the host (device memory, copied back once the scan is done)
+struct DevSummary {
+    uint64_t total;  // sum of all lengths
+    uint32_t bad;    // chip_encode_file: units whose status is not CHIP_ENC_FINISHED
+    uint32_t pad;
+};
+
+__global__ __launch_bounds__(256) void pack_widen_kernel(const uint32_t *len, const int32_t *status, uint64_t n, uint64_t *wide, DevSummary *ds)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    wide[i] = len[i];
+    if (status && status[i] != CHIP_ENC_FINISHED) atomicAdd(&ds->bad, 1u);  // (never, with slots of chip_encode_bound bytes)
+}
+
+// behind the two scan kernels: off[i] gets its workgroup's offset; the caller's array, if there is one, a copy
+__global__ __launch_bounds__(256) void pack_offsets_kernel(uint64_t *off, const uint64_t *part, uint64_t n, uint64_t *user_off)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t o = off[i] + part[i / SCAN_THREADS];
+    off[i] = o;
+    if (user_off) user_off[i] = o;
+}
+
+__device__ __forceinline__ uint64_t rdfirst64(uint64_t v) { return ((uint64_t)rdfirst((uint32_t)(v >> 32)) << 32) | rdfirst((uint32_t)v); }
+
+// `chunks` >= 1 aligned 16-byte stores at db fed by unaligned 16-byte loads at sb, R rounds of 64 lanes.  No load sits under an exec
+// mask (a lane behind the last chunk loads that chunk again), so all of a lane's loads are in flight before its first store.
+template <uint32_t R>
+__device__ __forceinline__ void copy_chunks(const uint8_t *sb, uint8_t *db, uint32_t chunks, uint32_t lane)
+{
+    pk_u32x4 v[R];
+#pragma unroll
+    for (uint32_t k = 0; k < R; k++) {
+        const uint32_t c = lane + 64u * k;
+        v[k] = *(const pk_u32x4_u *)(sb + 16u * (c < chunks ? c : chunks - 1u));
+    }
+#pragma unroll
+    for (uint32_t k = 0; k < R; k++) {
+        const uint32_t c = lane + 64u * k;
+        if (c < chunks) *(pk_u32x4 *)(db + 16u * c) = v[k];
+    }
+}
+
+// cnt <= PACK_TILE bytes from src to dst, by the whole wave; src, dst and cnt are wave-uniform
+__device__ __forceinline__ void copy_span(const uint8_t *src, uint8_t *dst, uint32_t cnt, uint32_t lane)
+{
+    uint32_t head = (16u - (uint32_t)((uintptr_t)dst & 15u)) & 15u;
+    head = head < cnt ? head : cnt;
+    const uint8_t *sb = src + head;
+    uint8_t *db = dst + head;  // 16-byte aligned (or cnt == head)
+    const uint32_t chunks = (cnt - head) >> 4, tail = (cnt - head) & 15u;
+    // head and tail: lanes 0..14 the bytes in front of the first chunk, lanes 16..30 those behind the last
+    const uint32_t edge = lane < 16u ? lane : head + 16u * chunks + (lane - 16u);
+    const bool on_edge = lane < 16u ? lane < head : lane - 16u < tail;
+    uint8_t eb = 0;
+    if (on_edge) eb = src[edge];
+    if (chunks > 64u) copy_chunks<PACK_ROUNDS>(sb, db, chunks, lane);  // (uniform)
+    else if (chunks) copy_chunks<1>(sb, db, chunks, lane);
+    if (on_edge) dst[edge] = eb;
+}
+
+__global__ __launch_bounds__(64 * PACK_WAVES) void pack_copy_kernel(const uint8_t *src_base, const uint64_t *src_off, const uint32_t *src_len,
+                                                                    uint8_t *dst_base, const uint64_t *__restrict__ dst_off, uint32_t n, uint64_t total)
+{
+    const uint32_t lane = lane_id();
+    const uint64_t t = (uint64_t)blockIdx.x * PACK_WAVES + rdfirst(threadIdx.x >> 6);
+    // tile t in destination offsets: absolute addresses [A + t * PACK_TILE, + PACK_TILE) with A = dst_base rounded down to 16
+    const uint32_t mis = (uint32_t)((uintptr_t)dst_base & 15u);
+    const uint64_t lo = t ? t * PACK_TILE - mis : 0;
+    uint64_t hi = (t + 1) * PACK_TILE - mis;
+    hi = hi < total ? hi : total;
+    if (lo >= total) return;  // (uniform) the last workgroup's spare waves
+    // the last unit that starts at or in front of lo: the one that holds byte lo (empty units at lo sit in front of it)
+    uint32_t u = 0, b = n;  // dst_off[u] <= lo, and dst_off[b] > lo or b == n
+    while (b - u > 1u) {
+        const uint32_t mid = u + ((b - u) >> 1);
+        if (rdfirst64(dst_off[mid]) <= lo) u = mid;
+        else b = mid;
+    }
+    // the units that intersect the tile, 64 at a time: lane j holds unit u + j, one round trip for all of them
+    for (uint64_t first = u;; first += 64u) {  // (64-bit: n may be 2^32 - 1)
+        const uint64_t uj = first + lane;
+        uint64_t d_v = ~0ull, so_v = 0;
+        uint32_t len_v = 0;
+        if (uj < n) d_v = dst_off[uj], so_v = src_off[uj], len_v = src_len[uj];
+        const uint32_t here = (uint32_t)__popcll(__ballot(d_v < hi));  // (the offsets ascend: a prefix of the lanes)
+        for (uint32_t j = 0; j < here; j++) {
+            const uint64_t d = ((uint64_t)rdlane((uint32_t)(d_v >> 32), j) << 32) | rdlane((uint32_t)d_v, j);
+            const uint64_t so = ((uint64_t)rdlane((uint32_t)(so_v >> 32), j) << 32) | rdlane((uint32_t)so_v, j);
+            const uint64_t s = d > lo ? d : lo, end = d + rdlane(len_v, j), e = end < hi ? end : hi;
+            if (e > s) copy_span(src_base + so + (s - d), dst_base + s, (uint32_t)(e - s), lane);
+        }
+        if (here < 64u) break;
+    }
+}
+
+// chip_encode_file: the arrays of the encode batch, unit i = [i * unit, min(len, (i + 1) * unit)) into slot i
+__global__ __launch_bounds__(256) void file_units_kernel(uint64_t *in_off, uint32_t *in_len, uint64_t *out_off, uint32_t *out_cap, uint32_t n,
+                                                         uint32_t unit, uint64_t len, uint32_t slot)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t at = (uint64_t)i * unit, left = len - at;  // (len == 0: the one unit of empty content)
+    in_off[i] = at;
+    in_len[i] = left < unit ? (uint32_t)left : unit;
+    out_off[i] = (uint64_t)i * slot;
+    out_cap[i] = slot;
+}
+
+struct EofWords {
+    uint32_t w[7];  // htslib's EOF block
+};
+
+__global__ __launch_bounds__(64) void file_eof_kernel(uint8_t *at, EofWords eof)
+{
+    const uint32_t lane = threadIdx.x;
+    uint32_t w = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < 7; k++) w = (lane >> 2) == k ? eof.w[k] : w;
+    if (lane < 28) at[lane] = (uint8_t)(w >> (8 * (lane & 3u)));
+}
+
+__device__ __forceinline__ void put_le32(uint8_t *p, uint32_t v)
+{
+    p[0] = (uint8_t)v, p[1] = (uint8_t)(v >> 8), p[2] = (uint8_t)(v >> 16), p[3] = (uint8_t)(v >> 24);
+}
+
+// the seek table of zstd's seekable format (contrib/seekable_format, no per-frame checksums) at `at`, any alignment: 17 + 8n bytes
+__global__ __launch_bounds__(256) void file_seek_table_kernel(uint8_t *at, const uint32_t *c_len, const uint32_t *d_len, uint32_t n)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    if (i == 0) {
+        put_le32(at, 0x184D2A5Eu);
+        put_le32(at + 4, 8u * n + 9u);
+    }
+    uint8_t *e = at + 8 + 8ull * i;
+    put_le32(e, c_len[i]);
+    put_le32(e + 4, d_len[i]);
+    if (i == n - 1u) {
+        put_le32(e + 8, n);
+        e[12] = 0;  // Seek_Table_Descriptor: no checksums
+        put_le32(e + 13, 0x8F92EAB1u);
+    }
+}
+
+// The scratch of one (device, stream): the per-unit arrays with the scan's partials behind them, chip_encode_file's slot area,
+// the summary on the device and its pinned copy.  A launch slot.
+struct FileSlot {
+    uint8_t *arrays = nullptr, *area = nullptr;
+    size_t arrays_cap = 0, area_cap = 0;
+    DevSummary *d_sum = nullptr, *h_sum = nullptr;
+
+    hipError_t summary()
+    {
+        hipError_t e = hipSuccess;
+        if (!d_sum) e = hipMalloc((void **)&d_sum, sizeof(DevSummary));
+        if (e == hipSuccess && !h_sum) e = hipHostMalloc((void **)&h_sum, sizeof(DevSummary), hipHostMallocDefault);
+        return e;
+    }
+    void free()
+    {
+        (void)hipFree(arrays);
+        (void)hipFree(area);
+        (void)hipFree(d_sum);
+        if (h_sum) (void)hipHostFree(h_sum);
+    }
+};
+SlotCache<FileSlot> g_file_cache;
+
+// lengths -> offsets in `off` (n entries, `part` behind them) and the caller's array; waits for the total
+hipError_t offsets_locked(FileSlot &sl, uint64_t n, const uint32_t *len, const int32_t *status, uint64_t *off, uint64_t *part, uint64_t *user_off,
+                          hipStream_t stream)
+{
+    const uint64_t parts = (n + SCAN_THREADS - 1) / SCAN_THREADS;
+    const dim3 grid((uint32_t)((n + 255) / 256));
+    hipError_t e = hipMemsetAsync(sl.d_sum, 0, sizeof(DevSummary), stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(pack_widen_kernel, grid, dim3(256), 0, stream, len, status, n, off, sl.d_sum);
+    hipLaunchKernelGGL(plan_scan_local_kernel<uint64_t>, dim3((uint32_t)parts), dim3(SCAN_THREADS), 0, stream, (const uint64_t *)off, off, n, part);
+    hipLaunchKernelGGL(plan_scan_partials_kernel<uint64_t>, dim3(1), dim3(SCAN_THREADS), 0, stream, part, parts, &sl.d_sum->total);
+    hipLaunchKernelGGL(pack_offsets_kernel, grid, dim3(256), 0, stream, off, (const uint64_t *)part, n, user_off);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if ((e = hipMemcpyAsync(sl.h_sum, sl.d_sum, sizeof(DevSummary), hipMemcpyDeviceToHost, stream)) != hipSuccess) return e;
+    return hipStreamSynchronize(stream);
+}
+
+// only enqueues; total > 0 and total <= the room behind dst_base
+void enqueue_copy(uint64_t n, const uint8_t *src_base, const uint64_t *src_off, const uint32_t *src_len, uint8_t *dst_base, const uint64_t *off,
+                  uint64_t total, hipStream_t stream)
+{
+    const uint64_t tiles = (total + ((uintptr_t)dst_base & 15u) + PACK_TILE - 1) / PACK_TILE;
+    hipLaunchKernelGGL(pack_copy_kernel, dim3((uint32_t)((tiles + PACK_WAVES - 1) / PACK_WAVES)), dim3(64 * PACK_WAVES), 0, stream, src_base, src_off,
+                       src_len, dst_base, off, (uint32_t)n, total);
+}
+
+hipError_t pack_locked(FileSlot &sl, uint64_t n, const uint8_t *src_base, const uint64_t *src_off, const uint32_t *src_len, uint8_t *dst_base,
+                       uint64_t dst_cap, uint64_t *dst_off, uint64_t *total, hipStream_t stream)
+{
+    hipError_t e = sl.summary();
+    if (e != hipSuccess) return e;
+    const uint64_t parts = (n + SCAN_THREADS - 1) / SCAN_THREADS;
+    if ((e = grow_buffer(sl.arrays, sl.arrays_cap, (size_t)(n + parts) * 8)) != hipSuccess) return e;
+    uint64_t *off = (uint64_t *)sl.arrays, *part = off + n;
+    if ((e = offsets_locked(sl, n, src_len, nullptr, off, part, dst_off, stream)) != hipSuccess) return e;
+    *total = sl.h_sum->total;
+    if (*total == 0 || *total > dst_cap) return hipSuccess;
+    enqueue_copy(n, src_base, src_off, src_len, dst_base, off, *total, stream);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    return hipStreamSynchronize(stream);  // the slot's offsets are read until the copy is done
+}
+
+// What chip_encode_file makes of its arguments (all but the level and the pointers): false = CHIP_E_INVALID.
+struct FileShape {
+    uint32_t unit;     // bytes per unit
+    uint64_t n;        // units encoded: ceil(len / unit), one unit of empty content for an empty gzip / zstd input
+    uint64_t trailer;  // bytes behind the last unit
+};
+bool file_shape(int format, uint32_t unit_bytes, uint32_t flags, uint64_t len, FileShape &s)
+{
+    if (format != CHIP_FMT_BGZF && format != CHIP_FMT_GZIP && format != CHIP_FMT_ZSTD) return false;
+    if ((flags & ~(uint32_t)CHIP_W_SEEK_TABLE) || (flags && format != CHIP_FMT_ZSTD)) return false;
+    const bool bgzf = format == CHIP_FMT_BGZF;
+    s.unit = unit_bytes ? unit_bytes : bgzf ? 65280u : 262144u;
+    if (s.unit > (bgzf ? 65280u : 0x40000000u) || len > ((uint64_t)1 << 40)) return false;
+    s.n = (len + s.unit - 1) / s.unit;
+    if (s.n == 0 && !bgzf) s.n = 1;
+    if (s.n > 0x7fffffffull || (flags && s.n > 0x8000000ull)) return false;
+    s.trailer = bgzf ? 28 : flags ? 17 + 8 * s.n : 0;
+    return true;
+}
+
+bool level_ok(int format, int level) { return format == CHIP_FMT_ZSTD ? level >= -131072 && level <= 131072 : level >= -1 && level <= 9; }
+
+// Enqueues everything, waits twice (total, end).  The caller holds the cache's lock.
+hipError_t encode_file_locked(FileSlot &sl, int format, int level, const FileShape &s, uint32_t flags, const uint8_t *in_base, uint64_t len,
+                              uint8_t *out_base, uint64_t out_cap, chip_file_summary *summary, hipStream_t stream, bool &encoder_failed)
+{
+    hipError_t e = sl.summary();
+    if (e != hipSuccess) return e;
+    const uint32_t n = (uint32_t)s.n;
+    const size_t slot = up16(chip_encode_bound(format, s.unit)), parts = ((size_t)n + SCAN_THREADS - 1) / SCAN_THREADS;
+    uint64_t total = 0;
+    // in_off (the packed offsets once the encode is done) | out_off | in_len | out_cap | out_len | status | partials
+    if ((e = grow_buffer(sl.arrays, sl.arrays_cap, (size_t)n * 32 + parts * 8)) != hipSuccess) return e;
+    if ((e = grow_buffer(sl.area, sl.area_cap, (size_t)n * slot)) != hipSuccess) return e;
+    uint64_t *in_off = (uint64_t *)sl.arrays, *out_off = in_off + n;
+    uint32_t *in_len = (uint32_t *)(out_off + n), *cap = in_len + n, *out_len = cap + n;
+    int32_t *status = (int32_t *)(out_len + n);
+    uint64_t *part = (uint64_t *)(status + n);
+    if (n) {  // (an empty BGZF file has no unit)
+        hipLaunchKernelGGL(file_units_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, in_off, in_len, out_off, cap, n, s.unit, len, (uint32_t)slot);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        // (an empty input has no buffer: the one unit of length 0 reads nothing, the batch call wants a pointer)
+        if (chip_encode_batch(format, level, n, in_base ? in_base : sl.area, in_off, in_len, sl.area, out_off, cap, out_len, status, stream) != CHIP_OK) {
+            encoder_failed = true;
+            return hipSuccess;
+        }
+        if ((e = offsets_locked(sl, n, out_len, status, in_off, part, nullptr, stream)) != hipSuccess) return e;
+        if (sl.h_sum->bad) {
+            encoder_failed = true;
+            return hipSuccess;
+        }
+        total = sl.h_sum->total;
+    }
+    summary->n_units = n;
+    summary->table_off = flags ? total : total + s.trailer;
+    summary->out_len = total + s.trailer;
+    summary->status = summary->out_len > out_cap ? CHIP_FILE_NEED_OUTPUT : CHIP_FILE_OK;
+    if (summary->status != CHIP_FILE_OK) return hipSuccess;
+    if (total) enqueue_copy(n, sl.area, out_off, out_len, out_base, in_off, total, stream);
+    if (format == CHIP_FMT_BGZF) {
+        EofWords eof;
+        memcpy(eof.w, chip_bgzf_eof_block(nullptr), sizeof(eof.w));
+        hipLaunchKernelGGL(file_eof_kernel, dim3(1), dim3(64), 0, stream, out_base + total, eof);
+    } else if (flags) {
+        hipLaunchKernelGGL(file_seek_table_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, out_base + total, (const uint32_t *)out_len,
+                           (const uint32_t *)in_len, n);
+    }
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    return hipStreamSynchronize(stream);  // the slot is handed on only with nothing in flight
+}
+
+}  // namespace
+
+}  // namespace chip
+
+using namespace chip;
+
+extern "C" {
+
+int chip_pack_units(size_t n, const void *src_base, const uint64_t *src_off, const uint32_t *src_len, void *dst_base, uint64_t dst_cap,
+                    uint64_t *dst_off, uint64_t *total, void *stream)
+{
+    // arguments first, the device second: a refusal needs no GPU
+    if (!total || (n && (!src_base || !src_off || !src_len)) || (dst_cap && !dst_base) || (uint64_t)n > 0xFFFFFFFFull) return CHIP_E_INVALID;
+    *total = 0;
+    if (n == 0) return CHIP_OK;
+    int devices = 0;
+    if (hipGetDeviceCount(&devices) != hipSuccess || devices <= 0) return CHIP_E_NO_DEVICE;
+    std::lock_guard<std::mutex> lk(g_file_cache.mu);  // from the slot's lookup to the last launch (and the wait behind it)
+    FileSlot *sl = nullptr;
+    if (g_file_cache.at((hipStream_t)stream, sl) != hipSuccess) return CHIP_E_LAUNCH;
+    const hipError_t e = pack_locked(*sl, n, (const uint8_t *)src_base, src_off, src_len, (uint8_t *)dst_base, dst_cap, dst_off, total, (hipStream_t)stream);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize((hipStream_t)stream);  // the slot is handed on only with nothing in flight
+        *total = 0;
+        return e == hipErrorOutOfMemory ? CHIP_E_NOMEM : CHIP_E_LAUNCH;
+    }
+    return CHIP_OK;
+}
+
+uint64_t chip_encode_file_bound(int format, uint32_t unit_bytes, uint32_t flags, uint64_t len)
+{
+    FileShape s;
+    if (!file_shape(format, unit_bytes, flags, len, s)) return 0;
+    if (s.n == 0) return s.trailer;
+    return (s.n - 1) * chip_encode_bound(format, s.unit) + chip_encode_bound(format, (size_t)(len - (s.n - 1) * s.unit)) + s.trailer;
+}
+
+int chip_encode_file(int format, int level, uint32_t unit_bytes, uint32_t flags, const void *in_base, uint64_t len, void *out_base,
+                     uint64_t out_cap, chip_file_summary *summary, void *stream)
+{
+    FileShape s;
+    if (!summary || (len && !in_base) || ((uintptr_t)in_base & 3u) || (out_cap && !out_base) || !file_shape(format, unit_bytes, flags, len, s) ||
+        !level_ok(format, level))
+        return CHIP_E_INVALID;
+    *summary = chip_file_summary{0, 0, 0, CHIP_FILE_OK, 0};
+    int devices = 0;
+    if (hipGetDeviceCount(&devices) != hipSuccess || devices <= 0) return CHIP_E_NO_DEVICE;
+    std::lock_guard<std::mutex> lk(g_file_cache.mu);
+    FileSlot *sl = nullptr;
+    if (g_file_cache.at((hipStream_t)stream, sl) != hipSuccess) return CHIP_E_LAUNCH;
+    bool encoder_failed = false;
+    const hipError_t e = encode_file_locked(*sl, format, level, s, flags, (const uint8_t *)in_base, len, (uint8_t *)out_base, out_cap, summary,
+                                            (hipStream_t)stream, encoder_failed);
+    if (e != hipSuccess || encoder_failed) {
+        (void)hipStreamSynchronize((hipStream_t)stream);
+        *summary = chip_file_summary{0, 0, 0, CHIP_FILE_OK, 0};
+        return e == hipErrorOutOfMemory ? CHIP_E_NOMEM : CHIP_E_LAUNCH;
+    }
+    return CHIP_OK;
+}
+
+}  // extern "C"

@@ -1,7 +1,8 @@
 // What the container plans (bgzf.hip, zstd_plan.hip) have in common: the tile geometry of the
 // candidate search, the chunk loader, the reduce-then-scan kernels, the doubling and marking kernels over a successor table,
-// and the growing device buffer of their slots.  Everything sits in an anonymous namespace, as it did inside bgzf.hip: each of
-// the two translation units gets kernels of its own, and nothing here is seen from outside them.
+// and the growing device buffer of their slots.  The file writer (file_write.hip, sec. 4.13) takes the scans and the buffer.
+// Everything sits in an anonymous namespace, as it did inside bgzf.hip: each translation unit gets kernels of its own, and
+// nothing here is seen from outside them.
 #pragma once
 #include "chip_internal.h"
 
@@ -110,8 +111,8 @@ __device__ __forceinline__ uint32_t chunk_word(const uint32_t w[5], uint32_t k)
     return sh ? (lo >> sh) | (hi << (32 - sh)) : lo;
 }
 
-// jump table k + 1 = jump table k applied twice; n_cand is the sink
-__global__ __launch_bounds__(256) void plan_double_kernel(const uint32_t *jump, uint32_t *jump2, uint32_t n_cand)
+// jump table k + 1 = jump table k applied twice; n_cand is the sink  ([[maybe_unused]]: file_write.hip takes the scans only)
+[[maybe_unused]] __global__ __launch_bounds__(256) void plan_double_kernel(const uint32_t *jump, uint32_t *jump2, uint32_t n_cand)
 {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n_cand) return;
@@ -121,7 +122,7 @@ __global__ __launch_bounds__(256) void plan_double_kernel(const uint32_t *jump, 
 
 // One level of the top-down marking.  A candidate marked by another thread of this very launch may or may not hand its mark
 // on at once: either way only candidates on the chain from 0 get one, and those marked before the launch all hand it on.
-__global__ __launch_bounds__(256) void plan_mark_kernel(const uint32_t *jump, uint32_t *marked, uint32_t n_cand)
+[[maybe_unused]] __global__ __launch_bounds__(256) void plan_mark_kernel(const uint32_t *jump, uint32_t *marked, uint32_t n_cand)
 {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n_cand || !marked[i]) return;

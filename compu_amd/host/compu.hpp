@@ -531,6 +531,32 @@ public:
     {
         return chip_layout_units(n, out_size, out_off, out_cap, &total, &n_over, stream);
     }
+    // chip_pack_units into this buffer's spare capacity: the ranges src[src_off[i] .. + src_len[i]) (DEVICE arrays) end to end behind
+    // the cursor, which moves by `total` when they fit; when they do not, nothing is written and `total` says how much room is needed.
+    // dst_off (DEVICE, may be nullptr) receives the n offsets.  Synchronous on `stream`.
+    int pack_units(size_t n, const DeviceBuffer &src, const uint64_t *src_off, const uint32_t *src_len, uint64_t *dst_off, uint64_t &total,
+                   void *stream = nullptr)
+    {
+        const int rc = chip_pack_units(n, src.data(), src_off, src_len, buf_ + cursor_, cap_ - cursor_, dst_off, &total, stream);
+        if (rc == CHIP_OK && total <= cap_ - cursor_) cursor_ += total;
+        return rc;
+    }
+    // chip_encode_file into this buffer's spare capacity: the first `len` bytes of `in` as a BGZF file, a file of gzip members or a file of
+    // zstd frames (flags CHIP_W_SEEK_TABLE: with the seek table) behind the cursor, which moves by summary.out_len on CHIP_FILE_OK.
+    // chip_encode_file_bound(format, unit_bytes, flags, len) of spare capacity is always enough.  Synchronous on `stream`.
+    int encode_file(int format, int level, uint32_t unit_bytes, uint32_t flags, const DeviceBuffer &in, uint64_t len, chip_file_summary &summary,
+                    void *stream = nullptr)
+    {
+        if (len > in.len()) return CHIP_E_INVALID;
+        const int rc = chip_encode_file(format, level, unit_bytes, flags, in.data(), len, buf_ + cursor_, cap_ - cursor_, &summary, stream);
+        if (rc == CHIP_OK && summary.status == CHIP_FILE_OK) cursor_ += summary.out_len;
+        return rc;
+    }
+    // a whole BGZF file of htslib's block payload
+    int bgzf_write(int level, const DeviceBuffer &in, uint64_t len, chip_file_summary &summary, void *stream = nullptr)
+    {
+        return encode_file(CHIP_FMT_BGZF, level, 0, 0, in, len, summary, stream);
+    }
 
 private:
     uint8_t *buf_;
@@ -550,7 +576,8 @@ inline int zstd_plan_host(const uint8_t *in, uint64_t len, uint64_t max_frames, 
 {
     return chip_zstd_plan_host(in, len, max_frames, in_off, in_len, out_off, out_cap, &summary);
 }
-// htslib's 28-byte EOF marker, to be written behind the last block of a file made with chip_encode_batch(CHIP_FMT_BGZF, ..)
+// htslib's 28-byte EOF marker, to be written behind the last block of a file made with chip_encode_batch(CHIP_FMT_BGZF, ..) (DeviceBuffer::
+// bgzf_write does all of it)
 inline const uint8_t *bgzf_eof_block(size_t &len) { return chip_bgzf_eof_block(&len); }
 
 }  // namespace compu

@@ -506,7 +506,8 @@ int chip_encode_batch_ex(int format, int level, int strategy, size_t n, const vo
  * 18-byte header of chip_bgzf_plan with MTIME 0, XFL as for gzip, OS ff (as htslib writes) and BSIZE = out_len[i] - 1, then
  * CRC-32 and ISIZE.  A unit with in_len[i] > 65280 (htslib's block payload) is CHIP_ENC_ERROR with out_len[i] = 0; a block never
  * exceeds 65 536 bytes (incompressible input is stored: 65 280 + 5 + 26; a dynamic-level block costs at most 6 bytes more).
- * Writing the EOF marker (chip_bgzf_eof_block) and laying the blocks end to end is the caller's job. */
+ * The blocks stay in their slots: chip_pack_units lays them end to end, and chip_encode_file does all of it -- cut, encode, pack,
+ * EOF marker (chip_bgzf_eof_block) -- in one call (below, "writing files"). */
 int chip_encode_batch(int format, int level, size_t n, const void *in_base, const uint64_t *in_off,
                       const uint32_t *in_len, void *out_base, const uint64_t *out_off, const uint32_t *out_cap,
                       uint32_t *out_len, int32_t *status, void *stream);
@@ -518,6 +519,77 @@ size_t chip_encode_bound(int format, size_t in_len);
 int chip_encode_batch_host(int format, int level, size_t n, const void *in_base, const uint64_t *in_off, const uint32_t *in_len,
                            void *out_base, const uint64_t *out_off, const uint32_t *out_cap, uint32_t *out_len, int32_t *status,
                            int device, size_t slice_bytes);
+
+/* ---- writing files: from a batch to a file (additive API) ---------------- */
+
+/*
+ * chip_encode_batch leaves every unit in a slot of its own; a file is those units end to end.  chip_pack_units is that step on
+ * the device.  src_base, src_off, src_len, dst_base and dst_off are DEVICE pointers, total is a HOST pointer.
+ *   dst_off[i] = the exclusive 64-bit sum of src_len[0 .. i)             (dst_off may be NULL: not wanted)
+ *   *total     = the sum of all lengths
+ *   *total <= dst_cap:  the bytes src_base[src_off[i] .. + src_len[i]) land at dst_base[dst_off[i] ..)
+ *   *total >  dst_cap:  no byte of dst_base is written; the call is still CHIP_OK and *total and dst_off are answered -- the caller
+ *                       compares, allocates and calls again
+ * The contract.  src_base and dst_base may have any alignment.  Source ranges may lie in any order, with gaps, and may overlap
+ * each other; the destination must not overlap any of them.  Nothing outside [src_off[i], src_off[i] + src_len[i]) is read and
+ * nothing outside dst_base[0 .. total) is written; every destination byte is written exactly once, with a store that covers
+ * only bytes of the range (the byte behind `total` keeps its value, whatever the alignment).
+ * SYNCHRONOUS on `stream`, as chip_layout_units (the caller allocates or writes `total` bytes next).  n == 0 writes *total = 0
+ * without touching the device.  CHIP_E_INVALID before the device is looked for: total NULL, src_base / src_off / src_len NULL
+ * with n > 0, dst_base NULL with dst_cap > 0, n > 2^32 - 1.  Scratch: 8 bytes per unit (the offsets) and 8 bytes per 1024 units in
+ * the slot of chip_encode_file.  The calling thread's current device is left as it was.
+ * No reference counterpart: compu has no container formats.  Without it a caller copies out_len[] to the host, sums it and
+ * issues one copy per unit.
+ */
+int chip_pack_units(size_t n, const void *src_base, const uint64_t *src_off, const uint32_t *src_len, void *dst_base, uint64_t dst_cap,
+                    uint64_t *dst_off, uint64_t *total, void *stream);
+
+/*
+ * From a buffer to a file, both in DEVICE memory: the file chip_bgzf_plan, CHIP_F_MEMBERS or chip_zstd_plan reads back.  The
+ * input is cut into n = ceil(len / unit_bytes) units, unit i = [i * unit_bytes, min(len, (i + 1) * unit_bytes)); every unit is
+ * encoded by chip_encode_batch(format, level, ..) -- the same kernels, the same bytes -- into a scratch slot of
+ * chip_encode_bound(format, unit_bytes) bytes rounded up to 16; the encoded units are packed end to end into out_base
+ * (chip_pack_units' kernel) and the format's trailer follows.
+ *   CHIP_FMT_BGZF  unit_bytes 0 (= 65 280, htslib's payload) or 1 .. 65 280; one BGZF block per unit, then htslib's 28-byte EOF
+ *                  block.  len == 0: the EOF block alone (n_units = 0), as bgzip writes for empty input.
+ *   CHIP_FMT_GZIP  unit_bytes 0 (= 262 144) or 1 .. 2^30; one gzip member per unit: the series gzip -d and CHIP_F_MEMBERS read.
+ *                  len == 0: one member of empty content (a file of no bytes is not gzip).
+ *   CHIP_FMT_ZSTD  unit_bytes as for gzip; one frame per unit, with content checksum and Frame_Content_Size as the batch
+ *                  encoder writes them.  len == 0: one frame of empty content.  With CHIP_W_SEEK_TABLE the seek table of zstd's
+ *                  seekable format (contrib/seekable_format, without per-frame checksums) follows the last frame:
+ *                    LE32 0x184D2A5E | LE32 8 * n + 9 | n x { LE32 compressed size, LE32 content size } | LE32 n | u8 0 |
+ *                    LE32 0x8F92EAB1                                                  -- 17 + 8 * n bytes, a skippable frame
+ * level: as chip_encode_batch (strategy Default).  The 262 144 is a convention (the frame size DESIGN.md sec. 4.12 was measured
+ * at), not a tuned number.
+ * summary (HOST): n_units = units encoded; out_len = the file's length; table_off = where the seek table starts (out_len without
+ * one); status = CHIP_FILE_OK, or CHIP_FILE_NEED_OUTPUT when out_len > out_cap: out_len is then the exact size to come back with
+ * and no byte of out_base has been written.  chip_encode_file_bound is the size that is always enough:
+ * (n - 1) * chip_encode_bound(unit_bytes) + chip_encode_bound(last unit) + trailer; pure host arithmetic, 0 for arguments
+ * chip_encode_file refuses.
+ * in_base is 4-byte aligned and its allocation padded to a multiple of 4 bytes, as for chip_encode_batch.  SYNCHRONOUS on
+ * `stream`: it waits once for the packed size and once for the file.
+ * CHIP_E_INVALID, before the device is looked for: summary NULL; in_base NULL with len > 0 or not 4-byte aligned; out_base NULL
+ * with out_cap > 0; len > 2^40; n > 2^31 - 1; any other format (brotli, deflate and zlib have no concatenation convention);
+ * level or unit_bytes out of range; unknown flag bits; CHIP_W_SEEK_TABLE with another format than zstd, or with
+ * n > 0x8000000 (the format's limit; its other limit, 0x40000000 bytes per frame, is the limit of unit_bytes).
+ * CHIP_E_NOMEM: the scratch could not be allocated.  CHIP_E_LAUNCH: a launch failed, or a unit did not end CHIP_ENC_FINISHED
+ * (which slots of chip_encode_bound bytes rule out).
+ * Scratch per (device, stream), a launch slot kept between calls and released by chip_trim(): the slot area, n * up16(
+ * chip_encode_bound(format, unit_bytes)) bytes -- a little more than the input -- plus 32 bytes per unit of arrays (filled by a
+ * kernel, not uploaded) and 8 bytes per 1024 units, each allocation with a quarter of headroom.  There are no slabs yet: the
+ * whole input is encoded before the first byte is packed.  The calling thread's current device is left as it was.
+ * No reference counterpart.
+ */
+enum { CHIP_W_SEEK_TABLE = 1 };
+enum { CHIP_FILE_OK = 0, CHIP_FILE_NEED_OUTPUT = 1 };
+typedef struct {
+    uint64_t n_units, out_len, table_off;
+    int32_t status;
+    uint32_t pad;
+} chip_file_summary;
+int chip_encode_file(int format, int level, uint32_t unit_bytes, uint32_t flags, const void *in_base, uint64_t len, void *out_base,
+                     uint64_t out_cap, chip_file_summary *summary, void *stream);
+uint64_t chip_encode_file_bound(int format, uint32_t unit_bytes, uint32_t flags, uint64_t len);
 
 /* ---- zstd encoder: encoder::Interface::zstd, src/encoder/zstd.rs ------------------------------------------------------------ */
 

@@ -224,3 +224,49 @@ pub unsafe fn encode_batch_device(opts: &ZlibOptions, n: usize, input: &crate::b
     };
     if rc == sys::CHIP_OK { Ok(()) } else { Err(rc) }
 }
+
+// ---- writing files --------------------------------------------------------------------------------------------
+//
+// No compu counterpart: compu has no container formats.  `encode_batch_device` leaves every unit in its own slot; these two lay the
+// units end to end and write whole files on the device.
+
+///`chip_pack_units`: the ranges `src[src_off[i] .. + src_len[i])` end to end into `dst` (all device buffers; `dst_off`, if given,
+///receives the `n` offsets).  Returns the total; nothing has been written when it exceeds `dst.capacity()`.  Synchronous on `stream`.
+///
+///# Safety
+///
+///The offset / length arrays are read by the GPU: they must describe ranges inside `src`, and `dst` must not overlap `src`.
+pub unsafe fn pack_units_device(n: usize, src: &crate::buffer::DeviceBuffer, src_off: &crate::buffer::DeviceBuffer, src_len: &crate::buffer::DeviceBuffer,
+                                dst: &mut crate::buffer::DeviceBuffer, dst_off: Option<&mut crate::buffer::DeviceBuffer>,
+                                stream: *mut core::ffi::c_void) -> Result<u64, i32> {
+    if src_off.capacity() < 8 * n || src_len.capacity() < 4 * n || dst_off.as_ref().map_or(false, |d| d.capacity() < 8 * n) {
+        return Err(-101);
+    }
+    let mut total = 0u64;
+    let dst_off = dst_off.map_or(ptr::null_mut(), |d| d.as_mut_ptr() as *mut u64);
+    let rc = sys::chip_pack_units(n, src.as_ptr() as *const _, src_off.as_ptr() as *const u64, src_len.as_ptr() as *const u32, dst.as_mut_ptr() as *mut _,
+                                  dst.capacity() as u64, dst_off, &mut total, stream);
+    if rc == sys::CHIP_OK { Ok(total) } else { Err(rc) }
+}
+
+///Size of the output buffer that `encode_file_device` never finds too small (`chip_encode_file_bound`); 0 for arguments it refuses.
+pub fn encode_file_bound(format: core::ffi::c_int, unit_bytes: u32, flags: u32, len: u64) -> u64 {
+    unsafe { sys::chip_encode_file_bound(format, unit_bytes, flags, len) }
+}
+
+///`chip_encode_file`: the first `len` bytes of `input` as a BGZF file (`CHIP_FMT_BGZF`), a file of gzip members (`opts.mode` Gzip) or
+///a file of zstd frames (`CHIP_FMT_ZSTD`, with `CHIP_W_SEEK_TABLE` in `flags` followed by the seekable format's seek table) in `output`.
+///The summary's status is `CHIP_FILE_NEED_OUTPUT`, with the exact size in `out_len` and nothing written, when `output` is too small.
+///Synchronous on `stream`.
+pub fn encode_file_device(format: core::ffi::c_int, level: i32, unit_bytes: u32, flags: u32, input: &crate::buffer::DeviceBuffer, len: usize,
+                          output: &mut crate::buffer::DeviceBuffer, stream: *mut core::ffi::c_void) -> Result<sys::chip_file_summary, i32> {
+    if len > input.capacity() {
+        return Err(-101);
+    }
+    let mut summary = sys::chip_file_summary::default();
+    let rc = unsafe {
+        sys::chip_encode_file(format, level, unit_bytes, flags, input.as_ptr() as *const _, len as u64, output.as_mut_ptr() as *mut _,
+                              output.capacity() as u64, &mut summary, stream)
+    };
+    if rc == sys::CHIP_OK { Ok(summary) } else { Err(rc) }
+}

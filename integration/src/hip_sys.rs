@@ -116,6 +116,24 @@ pub struct chip_zstd_plan_summary {
     pub pad: u32,
 }
 
+///`chip_encode_file` flag: the seek table of zstd's seekable format follows the last frame (`CHIP_FMT_ZSTD` only)
+pub const CHIP_W_SEEK_TABLE: u32 = 1;
+///`chip_file_summary::status`
+pub const CHIP_FILE_OK: i32 = 0;
+pub const CHIP_FILE_NEED_OUTPUT: i32 = 1;
+
+///what `chip_encode_file` wrote: units encoded, the file's length (the exact size needed on `CHIP_FILE_NEED_OUTPUT`), where the seek
+///table starts (`out_len` without one)
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct chip_file_summary {
+    pub n_units: u64,
+    pub out_len: u64,
+    pub table_off: u64,
+    pub status: i32,
+    pub pad: u32,
+}
+
 pub type chip_malloc_fn = unsafe extern "C" fn(opaque: *mut c_void, size: usize) -> *mut c_void;
 pub type chip_free_fn = unsafe extern "C" fn(opaque: *mut c_void, ptr: *mut c_void);
 
@@ -199,4 +217,15 @@ extern "C" {
     pub fn chip_encode_batch_host(format: c_int, level: c_int, n: usize, in_base: *const c_void, in_off: *const u64, in_len: *const u32,
                                   out_base: *mut c_void, out_off: *const u64, out_cap: *const u32, out_len: *mut u32, status: *mut i32, device: c_int,
                                   slice_bytes: usize) -> c_int;
+
+    // ---- writing files: encoded units end to end, and a whole BGZF / gzip / zstd file from a buffer (no reference counterpart)
+    ///device ranges `src_base[src_off[i] .. + src_len[i])` end to end into `dst_base` (device arrays, host `total`); nothing is written
+    ///when `total > dst_cap`; synchronous on `stream`
+    pub fn chip_pack_units(n: usize, src_base: *const c_void, src_off: *const u64, src_len: *const u32, dst_base: *mut c_void, dst_cap: u64,
+                           dst_off: *mut u64, total: *mut u64, stream: *mut c_void) -> c_int;
+    ///cut, encode, pack, trailer: device buffers, host summary; synchronous on `stream`
+    pub fn chip_encode_file(format: c_int, level: c_int, unit_bytes: u32, flags: u32, in_base: *const c_void, len: u64, out_base: *mut c_void,
+                            out_cap: u64, summary: *mut chip_file_summary, stream: *mut c_void) -> c_int;
+    ///the output size that is always enough; 0 for arguments `chip_encode_file` refuses
+    pub fn chip_encode_file_bound(format: c_int, unit_bytes: u32, flags: u32, len: u64) -> u64;
 }
