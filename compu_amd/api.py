@@ -1048,26 +1048,60 @@ def bgzf_eof_block():
     return C.string_at(p, n.value)
 
 
-def bgzf_plan_host(data, max_blocks=None):
-    """chip_bgzf_plan_host over bytes / a uint8 numpy array in host memory: (in_off u64, in_len u32, out_off u64, out_cap u32,
-    summary) of the first min(n_blocks, max_blocks) blocks (None = all of them: one call to count, one to fill)."""
+def _plan_host(fn, raw_cls, wrap, count_field, data, max_units):
+    """A chip_*_plan_host call over bytes / a uint8 numpy array: count (max_units None), then fill."""
     import numpy as np
 
     buf = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8)
-    raw = _BgzfSummary()
+    raw = raw_cls()
     p = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None  # noqa: E731
-    if max_blocks is None:
-        rc = lib().chip_bgzf_plan_host(p(buf), buf.size, 0, None, None, None, None, C.byref(raw))
+    call = getattr(lib(), fn)
+    if max_units is None:
+        rc = call(p(buf), buf.size, 0, None, None, None, None, C.byref(raw))
         if rc != 0:
-            raise RuntimeError(f"chip_bgzf_plan_host failed: {rc}")
-        max_blocks = int(raw.n_blocks)
-    m = int(max_blocks)
+            raise RuntimeError(f"{fn} failed: {rc}")
+        max_units = int(getattr(raw, count_field))
+    m = int(max_units)
     in_off, in_len, out_off, out_cap = np.zeros(m, np.uint64), np.zeros(m, np.uint32), np.zeros(m, np.uint64), np.zeros(m, np.uint32)
-    rc = lib().chip_bgzf_plan_host(p(buf), buf.size, m, p(in_off), p(in_len), p(out_off), p(out_cap), C.byref(raw))
+    rc = call(p(buf), buf.size, m, p(in_off), p(in_len), p(out_off), p(out_cap), C.byref(raw))
     if rc != 0:
-        raise RuntimeError(f"chip_bgzf_plan_host failed: {rc}")
-    k = min(m, int(raw.n_blocks))
-    return in_off[:k], in_len[:k], out_off[:k], out_cap[:k], BgzfSummary(raw)
+        raise RuntimeError(f"{fn} failed: {rc}")
+    k = min(m, int(getattr(raw, count_field)))
+    return in_off[:k], in_len[:k], out_off[:k], out_cap[:k], wrap(raw)
+
+
+def _plan_device(fn, raw_cls, wrap, count_field, in_buf, length, stream, max_units):
+    """A chip_*_plan call over a uint8 device tensor: count (max_units None), then fill."""
+    import torch
+
+    dev = _check_tensors(((in_buf, torch.uint8),))
+    length = int(length)
+    if length < 0 or length > in_buf.numel():
+        raise ValueError(f"length {length} outside the buffer of {in_buf.numel()} bytes")
+    raw = raw_cls()
+    base, sp = (_dp(in_buf) if length else None), _stream_ptr(stream)
+    call = getattr(lib(), fn)
+    with torch.cuda.device(dev):
+        if max_units is None:  # count, then fill
+            rc = call(base, length, 0, None, None, None, None, C.byref(raw), sp)
+            if rc != 0:
+                raise RuntimeError(f"{fn} failed: {rc}")
+            max_units = int(getattr(raw, count_field))
+        m = int(max_units)
+        in_off, out_off = torch.empty(m, dtype=torch.int64, device=dev), torch.empty(m, dtype=torch.int64, device=dev)
+        in_len, out_cap = torch.empty(m, dtype=torch.int32, device=dev), torch.empty(m, dtype=torch.int32, device=dev)
+        q = lambda t: _dp(t) if m else None  # noqa: E731
+        rc = call(base, length, m, q(in_off), q(in_len), q(out_off), q(out_cap), C.byref(raw), sp)
+    if rc != 0:
+        raise RuntimeError(f"{fn} failed: {rc}")
+    k = min(m, int(getattr(raw, count_field)))
+    return in_off[:k], in_len[:k], out_off[:k], out_cap[:k], wrap(raw)
+
+
+def bgzf_plan_host(data, max_blocks=None):
+    """chip_bgzf_plan_host over bytes / a uint8 numpy array in host memory: (in_off u64, in_len u32, out_off u64, out_cap u32,
+    summary) of the first min(n_blocks, max_blocks) blocks (None = all of them: one call to count, one to fill)."""
+    return _plan_host("chip_bgzf_plan_host", _BgzfSummary, BgzfSummary, "n_blocks", data, max_blocks)
 
 
 def bgzf_plan(in_buf, length, stream=None, max_blocks=None):
@@ -1075,29 +1109,7 @@ def bgzf_plan(in_buf, length, stream=None, max_blocks=None):
     returns (in_off int64, in_len int32, out_off int64, out_cap int32, summary) -- device tensors of the first
     min(n_blocks, max_blocks) blocks, ready for decode_batch(ZlibMode.Gzip, ..).  Synchronous on `stream`.  max_blocks None: all
     of them (one call to count, one to fill)."""
-    import torch
-
-    dev = _check_tensors(((in_buf, torch.uint8),))
-    length = int(length)
-    if length < 0 or length > in_buf.numel():
-        raise ValueError(f"length {length} outside the buffer of {in_buf.numel()} bytes")
-    raw = _BgzfSummary()
-    base, sp = (_dp(in_buf) if length else None), _stream_ptr(stream)
-    with torch.cuda.device(dev):
-        if max_blocks is None:  # count, then fill
-            rc = lib().chip_bgzf_plan(base, length, 0, None, None, None, None, C.byref(raw), sp)
-            if rc != 0:
-                raise RuntimeError(f"chip_bgzf_plan failed: {rc}")
-            max_blocks = int(raw.n_blocks)
-        m = int(max_blocks)
-        in_off, out_off = torch.empty(m, dtype=torch.int64, device=dev), torch.empty(m, dtype=torch.int64, device=dev)
-        in_len, out_cap = torch.empty(m, dtype=torch.int32, device=dev), torch.empty(m, dtype=torch.int32, device=dev)
-        q = lambda t: _dp(t) if m else None  # noqa: E731
-        rc = lib().chip_bgzf_plan(base, length, m, q(in_off), q(in_len), q(out_off), q(out_cap), C.byref(raw), sp)
-    if rc != 0:
-        raise RuntimeError(f"chip_bgzf_plan failed: {rc}")
-    k = min(m, int(raw.n_blocks))
-    return in_off[:k], in_len[:k], out_off[:k], out_cap[:k], BgzfSummary(raw)
+    return _plan_device("chip_bgzf_plan", _BgzfSummary, BgzfSummary, "n_blocks", in_buf, length, stream, max_blocks)
 
 
 def bgzf_decode(in_buf, length, stream=None):
@@ -1152,23 +1164,7 @@ class ZstdPlanSummary:
 def zstd_plan_host(data, max_frames=None):
     """chip_zstd_plan_host over bytes / a uint8 numpy array in host memory: (in_off u64, in_len u32, out_off u64, out_cap u32,
     summary) of the first min(n_frames, max_frames) frames (None = all of them: one call to count, one to fill)."""
-    import numpy as np
-
-    buf = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8)
-    raw = _ZstdPlanSummary()
-    p = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None  # noqa: E731
-    if max_frames is None:
-        rc = lib().chip_zstd_plan_host(p(buf), buf.size, 0, None, None, None, None, C.byref(raw))
-        if rc != 0:
-            raise RuntimeError(f"chip_zstd_plan_host failed: {rc}")
-        max_frames = int(raw.n_frames)
-    m = int(max_frames)
-    in_off, in_len, out_off, out_cap = np.zeros(m, np.uint64), np.zeros(m, np.uint32), np.zeros(m, np.uint64), np.zeros(m, np.uint32)
-    rc = lib().chip_zstd_plan_host(p(buf), buf.size, m, p(in_off), p(in_len), p(out_off), p(out_cap), C.byref(raw))
-    if rc != 0:
-        raise RuntimeError(f"chip_zstd_plan_host failed: {rc}")
-    k = min(m, int(raw.n_frames))
-    return in_off[:k], in_len[:k], out_off[:k], out_cap[:k], ZstdPlanSummary(raw)
+    return _plan_host("chip_zstd_plan_host", _ZstdPlanSummary, ZstdPlanSummary, "n_frames", data, max_frames)
 
 
 def zstd_plan(in_buf, length, stream=None, max_frames=None):
@@ -1176,29 +1172,7 @@ def zstd_plan(in_buf, length, stream=None, max_frames=None):
     4): returns (in_off int64, in_len int32, out_off int64, out_cap int32, summary) -- device tensors of the first
     min(n_frames, max_frames) frames; with summary.n_unsized == 0 they are ready for decode_batch(FMT_ZSTD, ..).  Synchronous
     on `stream`.  max_frames None: all of them (one call to count, one to fill)."""
-    import torch
-
-    dev = _check_tensors(((in_buf, torch.uint8),))
-    length = int(length)
-    if length < 0 or length > in_buf.numel():
-        raise ValueError(f"length {length} outside the buffer of {in_buf.numel()} bytes")
-    raw = _ZstdPlanSummary()
-    base, sp = (_dp(in_buf) if length else None), _stream_ptr(stream)
-    with torch.cuda.device(dev):
-        if max_frames is None:  # count, then fill
-            rc = lib().chip_zstd_plan(base, length, 0, None, None, None, None, C.byref(raw), sp)
-            if rc != 0:
-                raise RuntimeError(f"chip_zstd_plan failed: {rc}")
-            max_frames = int(raw.n_frames)
-        m = int(max_frames)
-        in_off, out_off = torch.empty(m, dtype=torch.int64, device=dev), torch.empty(m, dtype=torch.int64, device=dev)
-        in_len, out_cap = torch.empty(m, dtype=torch.int32, device=dev), torch.empty(m, dtype=torch.int32, device=dev)
-        q = lambda t: _dp(t) if m else None  # noqa: E731
-        rc = lib().chip_zstd_plan(base, length, m, q(in_off), q(in_len), q(out_off), q(out_cap), C.byref(raw), sp)
-    if rc != 0:
-        raise RuntimeError(f"chip_zstd_plan failed: {rc}")
-    k = min(m, int(raw.n_frames))
-    return in_off[:k], in_len[:k], out_off[:k], out_cap[:k], ZstdPlanSummary(raw)
+    return _plan_device("chip_zstd_plan", _ZstdPlanSummary, ZstdPlanSummary, "n_frames", in_buf, length, stream, max_frames)
 
 
 def layout_units(out_size, stream=None):

@@ -17,8 +17,6 @@
 // and the tiles end at the total the host compared with the room.
 #include <string.h>
 
-#include <mutex>
-
 #include "chip_internal.h"
 #include "launch_slots.h"
 #include "plan_common.h"
@@ -185,45 +183,23 @@ __global__ __launch_bounds__(256) void file_seek_table_kernel(uint8_t *at, const
     }
 }
 
-// The scratch of one (device, stream): the per-unit arrays with the scan's partials behind them, chip_encode_file's slot area,
-// the summary on the device and its pinned copy.  A launch slot.
-struct FileSlot {
-    uint8_t *arrays = nullptr, *area = nullptr;
-    size_t arrays_cap = 0, area_cap = 0;
-    DevSummary *d_sum = nullptr, *h_sum = nullptr;
-
-    hipError_t summary()
-    {
-        hipError_t e = hipSuccess;
-        if (!d_sum) e = hipMalloc((void **)&d_sum, sizeof(DevSummary));
-        if (e == hipSuccess && !h_sum) e = hipHostMalloc((void **)&h_sum, sizeof(DevSummary), hipHostMallocDefault);
-        return e;
-    }
-    void free()
-    {
-        (void)hipFree(arrays);
-        (void)hipFree(area);
-        (void)hipFree(d_sum);
-        if (h_sum) (void)hipHostFree(h_sum);
-    }
-};
+// The scratch of one (device, stream): buffer 0 the per-unit arrays with the scan's partials behind them, buffer 1
+// chip_encode_file's slot area.  A launch slot.
+using FileSlot = SummarySlot<DevSummary>;
+constexpr uint32_t ARRAYS = 0, AREA = 1;
 SlotCache<FileSlot> g_file_cache;
 
 // lengths -> offsets in `off` (n entries, `part` behind them) and the caller's array; waits for the total
 hipError_t offsets_locked(FileSlot &sl, uint64_t n, const uint32_t *len, const int32_t *status, uint64_t *off, uint64_t *part, uint64_t *user_off,
                           hipStream_t stream)
 {
-    const uint64_t parts = (n + SCAN_THREADS - 1) / SCAN_THREADS;
     const dim3 grid((uint32_t)((n + 255) / 256));
-    hipError_t e = hipMemsetAsync(sl.d_sum, 0, sizeof(DevSummary), stream);
+    const hipError_t e = hipMemsetAsync(sl.d_sum, 0, sizeof(DevSummary), stream);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(pack_widen_kernel, grid, dim3(256), 0, stream, len, status, n, off, sl.d_sum);
-    hipLaunchKernelGGL(plan_scan_local_kernel<uint64_t>, dim3((uint32_t)parts), dim3(SCAN_THREADS), 0, stream, (const uint64_t *)off, off, n, part);
-    hipLaunchKernelGGL(plan_scan_partials_kernel<uint64_t>, dim3(1), dim3(SCAN_THREADS), 0, stream, part, parts, &sl.d_sum->total);
+    enqueue_scan<uint64_t>(off, off, n, part, &sl.d_sum->total, stream);
     hipLaunchKernelGGL(pack_offsets_kernel, grid, dim3(256), 0, stream, off, (const uint64_t *)part, n, user_off);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    if ((e = hipMemcpyAsync(sl.h_sum, sl.d_sum, sizeof(DevSummary), hipMemcpyDeviceToHost, stream)) != hipSuccess) return e;
-    return hipStreamSynchronize(stream);
+    return sl.fetch(stream);
 }
 
 // only enqueues; total > 0 and total <= the room behind dst_base
@@ -240,9 +216,8 @@ hipError_t pack_locked(FileSlot &sl, uint64_t n, const uint8_t *src_base, const 
 {
     hipError_t e = sl.summary();
     if (e != hipSuccess) return e;
-    const uint64_t parts = (n + SCAN_THREADS - 1) / SCAN_THREADS;
-    if ((e = grow_buffer(sl.arrays, sl.arrays_cap, (size_t)(n + parts) * 8)) != hipSuccess) return e;
-    uint64_t *off = (uint64_t *)sl.arrays, *part = off + n;
+    if ((e = sl.grow(ARRAYS, (size_t)(n + scan_parts(n)) * 8)) != hipSuccess) return e;
+    uint64_t *off = (uint64_t *)sl.buf[ARRAYS], *part = off + n;
     if ((e = offsets_locked(sl, n, src_len, nullptr, off, part, dst_off, stream)) != hipSuccess) return e;
     *total = sl.h_sum->total;
     if (*total == 0 || *total > dst_cap) return hipSuccess;
@@ -275,17 +250,18 @@ bool level_ok(int format, int level) { return format == CHIP_FMT_ZSTD ? level >=
 
 // Enqueues everything, waits twice (total, end).  The caller holds the cache's lock.
 hipError_t encode_file_locked(FileSlot &sl, int format, int level, const FileShape &s, uint32_t flags, const uint8_t *in_base, uint64_t len,
-                              uint8_t *out_base, uint64_t out_cap, chip_file_summary *summary, hipStream_t stream, bool &encoder_failed)
+                              uint8_t *out_base, uint64_t out_cap, chip_file_summary *summary, hipStream_t stream)
 {
     hipError_t e = sl.summary();
     if (e != hipSuccess) return e;
     const uint32_t n = (uint32_t)s.n;
-    const size_t slot = up16(chip_encode_bound(format, s.unit)), parts = ((size_t)n + SCAN_THREADS - 1) / SCAN_THREADS;
+    const size_t slot = up16(chip_encode_bound(format, s.unit));
     uint64_t total = 0;
     // in_off (the packed offsets once the encode is done) | out_off | in_len | out_cap | out_len | status | partials
-    if ((e = grow_buffer(sl.arrays, sl.arrays_cap, (size_t)n * 32 + parts * 8)) != hipSuccess) return e;
-    if ((e = grow_buffer(sl.area, sl.area_cap, (size_t)n * slot)) != hipSuccess) return e;
-    uint64_t *in_off = (uint64_t *)sl.arrays, *out_off = in_off + n;
+    if ((e = sl.grow(ARRAYS, (size_t)n * 32 + (size_t)scan_parts(n) * 8)) != hipSuccess) return e;
+    if ((e = sl.grow(AREA, (size_t)n * slot)) != hipSuccess) return e;
+    uint8_t *area = sl.buf[AREA];
+    uint64_t *in_off = (uint64_t *)sl.buf[ARRAYS], *out_off = in_off + n;
     uint32_t *in_len = (uint32_t *)(out_off + n), *cap = in_len + n, *out_len = cap + n;
     int32_t *status = (int32_t *)(out_len + n);
     uint64_t *part = (uint64_t *)(status + n);
@@ -293,15 +269,10 @@ hipError_t encode_file_locked(FileSlot &sl, int format, int level, const FileSha
         hipLaunchKernelGGL(file_units_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, in_off, in_len, out_off, cap, n, s.unit, len, (uint32_t)slot);
         if ((e = hipGetLastError()) != hipSuccess) return e;
         // (an empty input has no buffer: the one unit of length 0 reads nothing, the batch call wants a pointer)
-        if (chip_encode_batch(format, level, n, in_base ? in_base : sl.area, in_off, in_len, sl.area, out_off, cap, out_len, status, stream) != CHIP_OK) {
-            encoder_failed = true;
-            return hipSuccess;
-        }
+        if (chip_encode_batch(format, level, n, in_base ? in_base : area, in_off, in_len, area, out_off, cap, out_len, status, stream) != CHIP_OK)
+            return hipErrorUnknown;  // (the encoder failed: CHIP_E_LAUNCH)
         if ((e = offsets_locked(sl, n, out_len, status, in_off, part, nullptr, stream)) != hipSuccess) return e;
-        if (sl.h_sum->bad) {
-            encoder_failed = true;
-            return hipSuccess;
-        }
+        if (sl.h_sum->bad) return hipErrorUnknown;  // (a unit did not end CHIP_ENC_FINISHED: CHIP_E_LAUNCH)
         total = sl.h_sum->total;
     }
     summary->n_units = n;
@@ -309,7 +280,7 @@ hipError_t encode_file_locked(FileSlot &sl, int format, int level, const FileSha
     summary->out_len = total + s.trailer;
     summary->status = summary->out_len > out_cap ? CHIP_FILE_NEED_OUTPUT : CHIP_FILE_OK;
     if (summary->status != CHIP_FILE_OK) return hipSuccess;
-    if (total) enqueue_copy(n, sl.area, out_off, out_len, out_base, in_off, total, stream);
+    if (total) enqueue_copy(n, area, out_off, out_len, out_base, in_off, total, stream);
     if (format == CHIP_FMT_BGZF) {
         EofWords eof;
         memcpy(eof.w, chip_bgzf_eof_block(nullptr), sizeof(eof.w));
@@ -337,18 +308,12 @@ int chip_pack_units(size_t n, const void *src_base, const uint64_t *src_off, con
     if (!total || (n && (!src_base || !src_off || !src_len)) || (dst_cap && !dst_base) || (uint64_t)n > 0xFFFFFFFFull) return CHIP_E_INVALID;
     *total = 0;
     if (n == 0) return CHIP_OK;
-    int devices = 0;
-    if (hipGetDeviceCount(&devices) != hipSuccess || devices <= 0) return CHIP_E_NO_DEVICE;
-    std::lock_guard<std::mutex> lk(g_file_cache.mu);  // from the slot's lookup to the last launch (and the wait behind it)
-    FileSlot *sl = nullptr;
-    if (g_file_cache.at((hipStream_t)stream, sl) != hipSuccess) return CHIP_E_LAUNCH;
-    const hipError_t e = pack_locked(*sl, n, (const uint8_t *)src_base, src_off, src_len, (uint8_t *)dst_base, dst_cap, dst_off, total, (hipStream_t)stream);
-    if (e != hipSuccess) {
-        (void)hipStreamSynchronize((hipStream_t)stream);  // the slot is handed on only with nothing in flight
-        *total = 0;
-        return e == hipErrorOutOfMemory ? CHIP_E_NOMEM : CHIP_E_LAUNCH;
-    }
-    return CHIP_OK;
+    return with_slot(
+        g_file_cache, stream,
+        [&](FileSlot &sl, hipStream_t s) {
+            return pack_locked(sl, n, (const uint8_t *)src_base, src_off, src_len, (uint8_t *)dst_base, dst_cap, dst_off, total, s);
+        },
+        [&] { *total = 0; });
 }
 
 uint64_t chip_encode_file_bound(int format, uint32_t unit_bytes, uint32_t flags, uint64_t len)
@@ -367,20 +332,12 @@ int chip_encode_file(int format, int level, uint32_t unit_bytes, uint32_t flags,
         !level_ok(format, level))
         return CHIP_E_INVALID;
     *summary = chip_file_summary{0, 0, 0, CHIP_FILE_OK, 0};
-    int devices = 0;
-    if (hipGetDeviceCount(&devices) != hipSuccess || devices <= 0) return CHIP_E_NO_DEVICE;
-    std::lock_guard<std::mutex> lk(g_file_cache.mu);
-    FileSlot *sl = nullptr;
-    if (g_file_cache.at((hipStream_t)stream, sl) != hipSuccess) return CHIP_E_LAUNCH;
-    bool encoder_failed = false;
-    const hipError_t e = encode_file_locked(*sl, format, level, s, flags, (const uint8_t *)in_base, len, (uint8_t *)out_base, out_cap, summary,
-                                            (hipStream_t)stream, encoder_failed);
-    if (e != hipSuccess || encoder_failed) {
-        (void)hipStreamSynchronize((hipStream_t)stream);
-        *summary = chip_file_summary{0, 0, 0, CHIP_FILE_OK, 0};
-        return e == hipErrorOutOfMemory ? CHIP_E_NOMEM : CHIP_E_LAUNCH;
-    }
-    return CHIP_OK;
+    return with_slot(
+        g_file_cache, stream,
+        [&](FileSlot &sl, hipStream_t st) {
+            return encode_file_locked(sl, format, level, s, flags, (const uint8_t *)in_base, len, (uint8_t *)out_base, out_cap, summary, st);
+        },
+        [&] { *summary = chip_file_summary{0, 0, 0, CHIP_FILE_OK, 0}; });
 }
 
 }  // extern "C"

@@ -166,6 +166,47 @@ def large_file():
     return bgzf(pay, level=0), b"".join(pay)
 
 
+def _lead(size, seed):
+    """One block of exactly `size` bytes: the header behind it sits at `size`.  A stored block (31 bytes and up: header 18,
+    stored-block header 5, trailer 8); the two shorter ones, which no stored block reaches, are zlib's fixed-Huffman bodies of 1
+    and 2 payload bytes."""
+    b = block(_text(size - 31, seed), level=0) if size >= 31 else block(b"AC"[:size - 28], level=6)
+    assert len(b) == size
+    return b
+
+
+@functools.lru_cache(maxsize=None)
+def geometry_files():
+    """name -> bytes: headers that straddle the tile (16 KiB) and chunk (16 bytes) boundaries of the candidate search, lengths
+    that are no multiple of 4, and a file of more than 1 024 tiles.  Block 0 places the header of block 1; every file is a whole
+    BGZF file with the EOF block."""
+    out, second = {}, block(_text(300, 21))
+    for k in (1, 2, 3):  # the magic straddles the tile boundary
+        out[f"tile_magic_straddle_{k}"] = _lead(16384 - k, 30 + k) + second + EOF
+    for k in (16, 17):  # BSIZE (header bytes 16, 17) is the first two bytes of the next tile / straddles the boundary
+        out[f"tile_bsize_straddle_{k}"] = _lead(16384 - k, 30 + k) + second + EOF
+    for k in (1, 2, 3):  # the magic straddles a chunk boundary
+        out[f"chunk_magic_straddle_{k}"] = _lead(32 - k, 50 + k) + second + EOF
+    for r in (1, 2, 3):
+        d = _lead(31 + (r - len(second) - 31 - len(EOF)) % 4 + 40, 60 + r) + second + EOF
+        assert len(d) % 4 == r
+        out[f"len_mod_4_is_{r}"] = d
+    # more than 1 024 tiles (16 MiB): headers on both sides of tile 1 024, whose scan partial of the tile counts is not 0
+    rnd = random.Random(1024)
+    big = b"".join(block(rnd.randbytes(65280), level=0) for _ in range(260)) + second + EOF
+    assert len(big) > 1024 * 16384 + 65536 + 28
+    out["past_1024_tiles"] = big
+    for name, d in out.items():
+        rows, summ = walk(d)
+        assert summ[2:] == (len(d), OK, 1) and len(rows) == (262 if name == "past_1024_tiles" else 3), name
+    return out
+
+
+def plan_files():
+    """(name, bytes) of every file the host plan is held against the walk on, and the GPU plan against the host plan"""
+    return fault_files() + sorted(geometry_files().items())
+
+
 def cut(data, size=65280):
     return [data[i:i + size] for i in range(0, len(data), size)]
 

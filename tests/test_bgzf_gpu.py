@@ -52,7 +52,7 @@ def assert_same_plan(torch, lib, data, shift=0, max_blocks=None):
     return got
 
 
-@pytest.mark.parametrize("name,data", B.fault_files(), ids=[n for n, _ in B.fault_files()])
+@pytest.mark.parametrize("name,data", B.plan_files(), ids=[n for n, _ in B.plan_files()])
 def test_plan_equals_host_plan_on_every_cpu_file(gpu, name, data):
     import compu_amd
 

@@ -280,6 +280,9 @@ def geometry_files():
     out["nine_x_300"] = NINE * 300  # more than one 256-thread group of candidates
     out["nine_x_3000"] = NINE * 3000  # two tiles, crosses the 1 024-entry scan partial, 12 doubling levels
     out["nine_x_3000_mixed"] = b"".join((NINE, W.skippable(b"", k % 16), part("unsized_empty"))[k % 3] for k in range(3000))
+    # more than 1 024 tiles (16 MiB): frames start on both sides of tile 1 024, whose scan partial of the tile counts is not 0
+    r = random.Random(1024)
+    out["past_1024_tiles"] = b"".join(raw_frame(r.randbytes(1 << 20)) for _ in range(17)) + NINE
     return out
 
 
