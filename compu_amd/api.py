@@ -55,6 +55,16 @@ class _FileSummary(C.Structure):
     _fields_ = [("n_units", C.c_uint64), ("out_len", C.c_uint64), ("table_off", C.c_uint64), ("status", C.c_int32), ("pad", C.c_uint32)]
 
 
+class _SelectSummary(C.Structure):
+    _fields_ = [("n_sel", C.c_uint64), ("scratch_bytes", C.c_uint64), ("out_len", C.c_uint64), ("n_outside", C.c_uint64),
+                ("bad_index", C.c_uint64), ("status", C.c_int32), ("pad", C.c_uint32)]
+
+
+class _ReadSummary(C.Structure):
+    _fields_ = [("n_units", C.c_uint64), ("out_len", C.c_uint64), ("n_outside", C.c_uint64), ("n_bad", C.c_uint64),
+                ("first_bad", C.c_uint64), ("bad_index", C.c_uint64), ("status", C.c_int32), ("bad_status", C.c_int32)]
+
+
 _lib = None
 
 
@@ -155,6 +165,12 @@ def lib():
     L.chip_encode_file.argtypes = [C.c_int, C.c_int, C.c_uint32, C.c_uint32, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(_FileSummary), vp]
     L.chip_encode_file_bound.restype = C.c_uint64
     L.chip_encode_file_bound.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint64]
+    L.chip_select_units_host.restype = C.c_int
+    L.chip_select_units_host.argtypes = [sz, vp, vp, vp, vp, sz, vp, vp, C.c_uint64] + [vp] * 8 + [C.POINTER(_SelectSummary)]
+    L.chip_select_units.restype = C.c_int
+    L.chip_select_units.argtypes = [sz, vp, vp, vp, vp, sz, vp, vp, C.c_uint64] + [vp] * 8 + [C.POINTER(_SelectSummary), vp]
+    L.chip_read_ranges.restype = C.c_int
+    L.chip_read_ranges.argtypes = [C.c_int, sz, vp, vp, vp, vp, vp, sz, vp, vp, vp, C.c_uint64, vp, vp, C.POINTER(_ReadSummary), vp]
     _lib = L
     return L
 
@@ -1315,3 +1331,215 @@ def encode_file(fmt, level, in_buf, length, unit_bytes=0, flags=0, stream=None, 
 def bgzf_write(in_buf, length, level=6, stream=None):
     """A whole BGZF file of the first `length` bytes of in_buf: encode_file(FMT_BGZF, level, ..) with htslib's block payload."""
     return encode_file(FMT_BGZF, level, in_buf, length, stream=stream)
+
+
+# ---- reading ranges: random access on a plan (include/compu_hip.h, "reading ranges") ------------
+
+
+class ReadStatus(enum.IntEnum):
+    Ok = 0
+    NeedOutput = 1
+    BadLayout = 2
+
+
+class RangeStatus(enum.IntEnum):
+    Ok = 0
+    Outside = 1
+    BadUnit = 2
+
+
+class SelectSummary:
+    """chip_select_summary: n_sel units selected, scratch_bytes their decoded size, out_len the ranges' bytes, n_outside ranges
+    outside the content, status (BadLayout: bad_index is the first unit that does not follow its predecessor)."""
+
+    __slots__ = ("n_sel", "scratch_bytes", "out_len", "n_outside", "bad_index", "status")
+
+    def __init__(self, raw):
+        self.n_sel, self.scratch_bytes, self.out_len = int(raw.n_sel), int(raw.scratch_bytes), int(raw.out_len)
+        self.n_outside, self.bad_index, self.status = int(raw.n_outside), int(raw.bad_index), ReadStatus(raw.status)
+
+    def as_tuple(self):
+        return (self.n_sel, self.scratch_bytes, self.out_len, self.n_outside, self.bad_index, int(self.status))
+
+    def __repr__(self):
+        return (f"SelectSummary(n_sel={self.n_sel}, scratch_bytes={self.scratch_bytes}, out_len={self.out_len}, "
+                f"n_outside={self.n_outside}, bad_index={self.bad_index}, status={self.status.name})")
+
+
+class ReadSummary:
+    """chip_read_summary: n_units decoded, out_len bytes of ranges (the exact size needed on NeedOutput), n_outside, n_bad
+    selected units that did not decode to their size with first_bad the lowest one's index and bad_status its status, status
+    (BadLayout: bad_index says where)."""
+
+    __slots__ = ("n_units", "out_len", "n_outside", "n_bad", "first_bad", "bad_index", "status", "bad_status")
+
+    def __init__(self, raw):
+        self.n_units, self.out_len, self.n_outside = int(raw.n_units), int(raw.out_len), int(raw.n_outside)
+        self.n_bad, self.first_bad, self.bad_index = int(raw.n_bad), int(raw.first_bad), int(raw.bad_index)
+        self.status, self.bad_status = ReadStatus(raw.status), int(raw.bad_status)
+
+    def as_tuple(self):
+        return (self.n_units, self.out_len, self.n_outside, self.n_bad, self.first_bad, self.bad_index, int(self.status), self.bad_status)
+
+    def __repr__(self):
+        return (f"ReadSummary(n_units={self.n_units}, out_len={self.out_len}, n_outside={self.n_outside}, n_bad={self.n_bad}, "
+                f"first_bad={self.first_bad}, bad_index={self.bad_index}, status={self.status.name}, bad_status={self.bad_status})")
+
+
+def select_units_host(in_off, in_len, out_off, out_cap, range_lo, range_len, max_sel=None):
+    """chip_select_units_host over numpy arrays (or sequences) in host memory: the plan's four arrays and the ranges.  Returns
+    (sel_unit u32, sel_in_off u64, sel_in_len u32, sel_out_off u64, sel_out_cap u32, src_off u64, dst_off u64, range_status i32,
+    summary): the sub-batch of the first min(n_sel, max_sel) selected units (None = all of them: one call to count, one to
+    fill) and the three per-range arrays.  On BadLayout every array is empty."""
+    import numpy as np
+
+    arr = lambda a, dt: np.ascontiguousarray(a, dtype=dt)  # noqa: E731
+    in_off, in_len, out_off, out_cap = arr(in_off, np.uint64), arr(in_len, np.uint32), arr(out_off, np.uint64), arr(out_cap, np.uint32)
+    range_lo, range_len = arr(range_lo, np.uint64), arr(range_len, np.uint32)
+    n, m = int(out_cap.size), int(range_len.size)
+    if not (in_off.size == in_len.size == out_off.size == n) or range_lo.size != m:
+        raise ValueError("the plan's arrays, and the ranges' arrays, must have one length each")
+    p = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None  # noqa: E731
+    raw = _SelectSummary()
+    plan = (n, p(in_off), p(in_len), p(out_off), p(out_cap), m, p(range_lo), p(range_len))
+    if max_sel is None:
+        rc = lib().chip_select_units_host(*plan, 0, None, None, None, None, None, None, None, None, C.byref(raw))
+        if rc != 0:
+            raise RuntimeError(f"chip_select_units_host failed: {rc}")
+        max_sel = int(raw.n_sel)
+    k = int(max_sel)
+    sel_unit, sel_in_len, sel_out_cap = np.zeros(k, np.uint32), np.zeros(k, np.uint32), np.zeros(k, np.uint32)
+    sel_in_off, sel_out_off = np.zeros(k, np.uint64), np.zeros(k, np.uint64)
+    src_off, dst_off, status = np.zeros(m, np.uint64), np.zeros(m, np.uint64), np.zeros(m, np.int32)
+    rc = lib().chip_select_units_host(*plan, k, p(sel_unit), p(sel_in_off), p(sel_in_len), p(sel_out_off), p(sel_out_cap), p(src_off), p(dst_off),
+                                      p(status), C.byref(raw))
+    if rc != 0:
+        raise RuntimeError(f"chip_select_units_host failed: {rc}")
+    summ = SelectSummary(raw)
+    k = min(k, summ.n_sel)
+    if summ.status != ReadStatus.Ok:
+        k = m = 0
+    return sel_unit[:k], sel_in_off[:k], sel_in_len[:k], sel_out_off[:k], sel_out_cap[:k], src_off[:m], dst_off[:m], status[:m], summ
+
+
+def _ranges_to_device(ranges, dev):
+    """(range_lo int64, range_len int32) device tensors of a sequence of (lo, len) pairs or a pair of tensors."""
+    import torch
+
+    if isinstance(ranges, tuple) and len(ranges) == 2 and all(isinstance(t, torch.Tensor) for t in ranges):
+        return ranges
+    import numpy as np
+
+    lo = np.array([r[0] for r in ranges], dtype=np.uint64).view(np.int64)
+    ln = np.array([r[1] for r in ranges], dtype=np.uint32).view(np.int32)
+    return torch.from_numpy(lo).to(dev), torch.from_numpy(ln).to(dev)
+
+
+def select_units(in_off, in_len, out_off, out_cap, range_lo, range_len, stream=None, max_sel=None):
+    """chip_select_units on device tensors: the plan (in_off / out_off int64 read as u64, in_len / out_cap int32 read as u32)
+    and the ranges (range_lo int64 read as u64, range_len int32 read as u32).  Returns what select_units_host returns, as device
+    tensors (int64 / int32).  Synchronous on `stream`.  max_sel None: all selected units (one call to count, one to fill)."""
+    import torch
+
+    dev = _check_tensors(((in_off, torch.int64), (in_len, torch.int32), (out_off, torch.int64), (out_cap, torch.int32),
+                          (range_lo, torch.int64), (range_len, torch.int32)))
+    n, m = out_cap.numel(), range_len.numel()
+    if not (in_off.numel() == in_len.numel() == out_off.numel() == n) or range_lo.numel() != m:
+        raise ValueError("the plan's arrays, and the ranges' arrays, must have one length each")
+    q = lambda t: _dp(t) if t.numel() else None  # noqa: E731
+    raw = _SelectSummary()
+    plan = (n, q(in_off), q(in_len), q(out_off), q(out_cap), m, q(range_lo), q(range_len))
+    sp = _stream_ptr(stream)
+    with torch.cuda.device(dev):
+        if max_sel is None:
+            rc = lib().chip_select_units(*plan, 0, None, None, None, None, None, None, None, None, C.byref(raw), sp)
+            if rc != 0:
+                raise RuntimeError(f"chip_select_units failed: {rc}")
+            max_sel = int(raw.n_sel)
+        k = int(max_sel)
+        i64 = lambda c: torch.zeros(c, dtype=torch.int64, device=dev)  # noqa: E731
+        i32 = lambda c: torch.zeros(c, dtype=torch.int32, device=dev)  # noqa: E731
+        sel_unit, sel_in_off, sel_in_len, sel_out_off, sel_out_cap = i32(k), i64(k), i32(k), i64(k), i32(k)
+        src_off, dst_off, status = i64(m), i64(m), i32(m)
+        rc = lib().chip_select_units(*plan, k, q(sel_unit), q(sel_in_off), q(sel_in_len), q(sel_out_off), q(sel_out_cap), q(src_off), q(dst_off),
+                                     q(status), C.byref(raw), sp)
+    if rc != 0:
+        raise RuntimeError(f"chip_select_units failed: {rc}")
+    summ = SelectSummary(raw)
+    k = min(k, summ.n_sel)
+    if summ.status != ReadStatus.Ok:
+        k = m = 0
+    return sel_unit[:k], sel_in_off[:k], sel_in_len[:k], sel_out_off[:k], sel_out_cap[:k], src_off[:m], dst_off[:m], status[:m], summ
+
+
+def read_ranges(fmt, in_buf, in_off, in_len, out_off, out_cap, range_lo, range_len, dst=None, stream=None):
+    """chip_read_ranges on device tensors: the bytes of every range (range_lo int64 read as u64, range_len int32 read as u32, in
+    the coordinates of out_off) of the plan (in_off, in_len, out_off, out_cap) over in_buf, end to end in dst.  Only the units
+    the ranges touch are decoded, each once.  dst None: a tensor of exactly out_len bytes is allocated (a first call with no
+    room sizes it).  With a dst that is too small the summary says NeedOutput with the exact out_len and nothing is written.
+    Returns (dst trimmed to out_len -- None on NeedOutput or BadLayout --, dst_off int64, range_status int32, summary).
+    Synchronous on `stream`."""
+    import torch
+
+    pairs = [(in_buf, torch.uint8), (in_off, torch.int64), (in_len, torch.int32), (out_off, torch.int64), (out_cap, torch.int32),
+             (range_lo, torch.int64), (range_len, torch.int32)] + ([(dst, torch.uint8)] if dst is not None else [])
+    dev = _check_tensors(pairs)
+    n, m = out_cap.numel(), range_len.numel()
+    if not (in_off.numel() == in_len.numel() == out_off.numel() == n) or range_lo.numel() != m:
+        raise ValueError("the plan's arrays, and the ranges' arrays, must have one length each")
+    q = lambda t: _dp(t) if t is not None and t.numel() else None  # noqa: E731
+    dst_off, status = torch.zeros(m, dtype=torch.int64, device=dev), torch.zeros(m, dtype=torch.int32, device=dev)
+    raw = _ReadSummary()
+    sp = _stream_ptr(stream)
+
+    def call(d):
+        rc = lib().chip_read_ranges(int(fmt), n, q(in_buf) if n else None, q(in_off), q(in_len), q(out_off), q(out_cap), m, q(range_lo),
+                                    q(range_len), q(d), d.numel() if d is not None else 0, q(dst_off), q(status), C.byref(raw), sp)
+        if rc != 0:
+            raise RuntimeError(f"chip_read_ranges failed: {rc}")
+
+    with torch.cuda.device(dev):
+        call(dst)
+        if dst is None and raw.status == int(ReadStatus.NeedOutput):
+            dst = torch.empty(int(raw.out_len), dtype=torch.uint8, device=dev)
+            call(dst)
+        elif dst is None:
+            dst = torch.empty(0, dtype=torch.uint8, device=dev)
+    summ = ReadSummary(raw)
+    return (dst[: summ.out_len] if summ.status == ReadStatus.Ok else None), dst_off, status, summ
+
+
+def _read_checked(what, out, status, summ):
+    if summ.status != ReadStatus.Ok:
+        raise ValueError(f"{what}: the plan's layout is broken: {summ!r}")
+    if summ.n_outside:
+        raise ValueError(f"{what}: {summ.n_outside} ranges lie outside the content: {summ!r}")
+    if summ.n_bad:
+        raise RuntimeError(f"{what}: unit {summ.first_bad} did not decode: status {summ.bad_status} ({summ.n_bad} bad units)")
+    return out
+
+
+def bgzf_read(in_buf, length, ranges, stream=None):
+    """Bytes of a BGZF buffer on the device without decoding all of it: plan, then read_ranges(ZlibMode.Gzip).  `ranges` is a
+    sequence of (lo, len) pairs in decoded coordinates, or a pair of device tensors (int64, int32).  Raises ValueError when
+    the file is no whole BGZF file or a range lies outside its content, RuntimeError with the first bad block's index and
+    status when a block a range touches does not decode to its ISIZE.  Returns (the uint8 tensor of the ranges end to end,
+    dst_off int64).  Waits for the result."""
+    in_off, in_len, out_off, out_cap, summ = bgzf_plan(in_buf, length, stream=stream)
+    if summ.status != BgzfStatus.Ok:
+        raise ValueError(f"not a whole BGZF file: {summ!r}")
+    lo, ln = _ranges_to_device(ranges, in_buf.device)
+    out, dst_off, status, rs = read_ranges(ZlibMode.Gzip, in_buf, in_off, in_len, out_off, out_cap, lo, ln, stream=stream)
+    return _read_checked("bgzf_read", out, status, rs), dst_off
+
+
+def zstd_frames_read(in_buf, length, ranges, stream=None):
+    """The same for a buffer of zstd frames (a seekable file): plan, then read_ranges(FMT_ZSTD).  Every frame must state its
+    Frame_Content_Size (a frame without one breaks the layout: ValueError; decode such a file with zstd_frames_decode).
+    Returns (the uint8 tensor of the ranges end to end, dst_off int64).  Waits for the result."""
+    in_off, in_len, out_off, out_cap, summ = zstd_plan(in_buf, length, stream=stream)
+    if summ.status != ZstdPlanStatus.Ok:
+        raise ValueError(f"not a whole series of zstd frames: {summ!r}")
+    lo, ln = _ranges_to_device(ranges, in_buf.device)
+    out, dst_off, status, rs = read_ranges(FMT_ZSTD, in_buf, in_off, in_len, out_off, out_cap, lo, ln, stream=stream)
+    return _read_checked("zstd_frames_read", out, status, rs), dst_off

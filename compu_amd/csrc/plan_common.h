@@ -3,7 +3,7 @@
 // plan pipeline as templates over a format policy (count, emit, describe, successor, doubling, marking, flags, output and the
 // driver that enqueues them: "The container plan" below), the slot with its two growing buffers and its summary, and the scaffold
 // of an entry point (device check, the cache's lock, the slot, the error mapping).  The file writer (file_write.hip, sec. 4.13)
-// takes the scans, the slot and the scaffold.  Everything sits in an anonymous namespace: each translation unit gets kernels of
+// and the range reader (read_ranges.hip, sec. 4.14) take the scans, the slot and the scaffold.  Everything sits in an anonymous namespace: each translation unit gets kernels of
 // its own, and nothing here is seen from outside them.
 #pragma once
 #include <mutex>
@@ -129,7 +129,7 @@ __device__ __forceinline__ uint32_t chunk_word(const uint32_t w[5], uint32_t k)
     return sh ? (lo >> sh) | (hi << (32 - sh)) : lo;
 }
 
-// jump table k + 1 = jump table k applied twice; n_cand is the sink  ([[maybe_unused]]: file_write.hip takes the scans only)
+// jump table k + 1 = jump table k applied twice; n_cand is the sink  ([[maybe_unused]]: file_write.hip and read_ranges.hip take the scans only)
 [[maybe_unused]] __global__ __launch_bounds__(256) void plan_double_kernel(const uint32_t *jump, uint32_t *jump2, uint32_t n_cand)
 {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;

@@ -552,6 +552,30 @@ public:
         if (rc == CHIP_OK && summary.status == CHIP_FILE_OK) cursor_ += summary.out_len;
         return rc;
     }
+    // chip_read_ranges into this buffer's spare capacity: the bytes of n_ranges ranges (DEVICE arrays range_lo / range_len, in the
+    // coordinates of out_off) of the plan over `in`, end to end behind the cursor, which moves by summary.out_len on CHIP_READ_OK.  Only
+    // the units the ranges touch are decoded, each once.  On CHIP_READ_NEED_OUTPUT nothing is written and summary.out_len says how much
+    // room is needed.  dst_off and range_status (DEVICE, may be nullptr) receive one entry per range.  Synchronous on `stream`.
+    int read_ranges(int format, size_t n_units, const DeviceBuffer &in, const uint64_t *in_off, const uint32_t *in_len, const uint64_t *out_off,
+                    const uint32_t *out_cap, size_t n_ranges, const uint64_t *range_lo, const uint32_t *range_len, uint64_t *dst_off,
+                    int32_t *range_status, chip_read_summary &summary, void *stream = nullptr)
+    {
+        const int rc = chip_read_ranges(format, n_units, in.data(), in_off, in_len, out_off, out_cap, n_ranges, range_lo, range_len, buf_ + cursor_,
+                                        cap_ - cursor_, dst_off, range_status, &summary, stream);
+        if (rc == CHIP_OK && summary.status == CHIP_READ_OK) cursor_ += summary.out_len;
+        return rc;
+    }
+    // chip_select_units: the index step of read_ranges alone (DEVICE arrays, HOST summary), for a caller that decodes the sub-batch
+    // sel_in_off / sel_in_len / sel_out_off / sel_out_cap into summary.scratch_bytes of its own.  max_sel 0 with null sel arrays
+    // counts.  Synchronous on `stream`.
+    static int select_units(size_t n_units, const uint64_t *in_off, const uint32_t *in_len, const uint64_t *out_off, const uint32_t *out_cap,
+                            size_t n_ranges, const uint64_t *range_lo, const uint32_t *range_len, uint64_t max_sel, uint32_t *sel_unit,
+                            uint64_t *sel_in_off, uint32_t *sel_in_len, uint64_t *sel_out_off, uint32_t *sel_out_cap, uint64_t *src_off,
+                            uint64_t *dst_off, int32_t *range_status, chip_select_summary &summary, void *stream = nullptr)
+    {
+        return chip_select_units(n_units, in_off, in_len, out_off, out_cap, n_ranges, range_lo, range_len, max_sel, sel_unit, sel_in_off, sel_in_len,
+                                 sel_out_off, sel_out_cap, src_off, dst_off, range_status, &summary, stream);
+    }
     // a whole BGZF file of htslib's block payload
     int bgzf_write(int level, const DeviceBuffer &in, uint64_t len, chip_file_summary &summary, void *stream = nullptr)
     {
@@ -569,6 +593,15 @@ inline int bgzf_plan_host(const uint8_t *in, uint64_t len, uint64_t max_blocks, 
                           uint32_t *out_cap, chip_bgzf_summary &summary)
 {
     return chip_bgzf_plan_host(in, len, max_blocks, in_off, in_len, out_off, out_cap, &summary);
+}
+// chip_select_units_host: the units that byte ranges of a plan's content touch, on host memory (no device needed).
+inline int select_units_host(size_t n_units, const uint64_t *in_off, const uint32_t *in_len, const uint64_t *out_off, const uint32_t *out_cap,
+                             size_t n_ranges, const uint64_t *range_lo, const uint32_t *range_len, uint64_t max_sel, uint32_t *sel_unit,
+                             uint64_t *sel_in_off, uint32_t *sel_in_len, uint64_t *sel_out_off, uint32_t *sel_out_cap, uint64_t *src_off,
+                             uint64_t *dst_off, int32_t *range_status, chip_select_summary &summary)
+{
+    return chip_select_units_host(n_units, in_off, in_len, out_off, out_cap, n_ranges, range_lo, range_len, max_sel, sel_unit, sel_in_off, sel_in_len,
+                                  sel_out_off, sel_out_cap, src_off, dst_off, range_status, &summary);
 }
 // chip_zstd_plan_host: the zstd frame walk over host memory (no device needed); the arrays are what chip_decode_batch_host / _multi take.
 inline int zstd_plan_host(const uint8_t *in, uint64_t len, uint64_t max_frames, uint64_t *in_off, uint32_t *in_len, uint64_t *out_off,

@@ -591,6 +591,101 @@ int chip_encode_file(int format, int level, uint32_t unit_bytes, uint32_t flags,
                      uint64_t out_cap, chip_file_summary *summary, void *stream);
 uint64_t chip_encode_file_bound(int format, uint32_t unit_bytes, uint32_t flags, uint64_t len);
 
+/* ---- reading ranges: random access on a plan (additive API) -------------- */
+
+/*
+ * BGZF blocks and the frames of a seekable zstd file are small so that a reader can fetch a region without decoding the file.
+ * These calls answer "give me bytes [lo, lo + len) of the decoded content" for many ranges at once: the units the ranges touch are
+ * found, each is decoded once, and the ranges land end to end.
+ * The inputs are n_units units with in_off, in_len, out_off, out_cap as chip_bgzf_plan, chip_zstd_plan or chip_layout_units leave
+ * them, and n_ranges ranges (range_lo[r] u64, range_len[r] u32) in content coordinates, the coordinates of out_off.  The answer
+ * is defined by this walk (host and device implement the same one):
+ *   n_ranges == 0 -> an all-zero summary, the layout is not looked at
+ *   layout check.  For every unit i the link to i + 1 FAILS when out_cap[i] == CHIP_ZPLAN_UNSIZED (a frame without a size; the
+ *       last unit too), or out_off[i] + out_cap[i] exceeds 2^64 - 1, or i + 1 < n_units and out_off[i + 1] != out_off[i] +
+ *       out_cap[i].  Any failing link: status = CHIP_READ_BAD_LAYOUT, bad_index = the lowest such i + 1, every other field of the
+ *       summary is 0 and NOTHING else is written.
+ *   begin = out_off[0];  end = out_off[n_units - 1] + out_cap[n_units - 1]     (both 0 for n_units == 0)
+ *   per range r, (lo, len):
+ *     len == 0                          -> CHIP_RANGE_OK, touches no unit, 0 bytes
+ *     lo < begin, or lo + len > end     -> CHIP_RANGE_OUTSIDE, touches no unit, counts 0 bytes (the sum is formed without
+ *                                          wrapping; there is no clipping)
+ *     otherwise                         -> CHIP_RANGE_OK;  first[r] = the last unit u with out_off[u] <= lo: the unit that holds
+ *                                          byte lo (empty units at lo sit in front of it);  last[r] = the same for lo + len - 1
+ *   selection.  Unit u is selected when out_cap[u] > 0 and some range has first <= u <= last: units of no content are never
+ *     decoded.  The selected units ascend by index; k(u) is u's position among them; sel_out_off[k] = the exclusive 64-bit sum of
+ *     the selected units' out_cap, scratch_bytes the total.  The units one range selects are therefore contiguous in that image.
+ *   src_off[r] = sel_out_off[k(first[r])] + (lo - out_off[first[r]])                (0 for a range that touches no unit)
+ *   dst_off[r] = the exclusive 64-bit sum of the lengths that count (len of a range that is OK, 0 for CHIP_RANGE_OUTSIDE)
+ *   out_len    = the sum of those lengths;  n_outside = the number of CHIP_RANGE_OUTSIDE ranges
+ * Ranges may come in any order, overlap, nest and repeat: every one gets its own bytes in the output, a unit is selected once.
+ */
+enum { CHIP_READ_OK = 0, CHIP_READ_NEED_OUTPUT = 1, CHIP_READ_BAD_LAYOUT = 2 };
+enum { CHIP_RANGE_OK = 0, CHIP_RANGE_OUTSIDE = 1, CHIP_RANGE_BAD_UNIT = 2 };
+typedef struct {
+    uint64_t n_sel, scratch_bytes, out_len, n_outside, bad_index;
+    int32_t status; /* CHIP_READ_OK or CHIP_READ_BAD_LAYOUT */
+    uint32_t pad;
+} chip_select_summary;
+
+/* The walk itself on HOST memory: pure host arithmetic, no device needed (as chip_bgzf_plan_host).  sel_unit (the unit's index
+ * in the plan) and the four arrays of the sub-batch, sel_in_off / sel_in_len / sel_out_off / sel_out_cap -- what chip_decode_batch
+ * takes to decode the selection into scratch_bytes bytes -- receive the first min(n_sel, max_sel) selected units and nothing behind
+ * them is written: max_sel = 0 with null arrays counts, a second call fills.  src_off, dst_off and range_status have n_ranges
+ * entries; each may be NULL (not wanted).  CHIP_E_INVALID: summary NULL, a plan array NULL with n_units > 0, range_lo or range_len
+ * NULL with n_ranges > 0, one of the five sel arrays NULL with max_sel > 0, n_units or n_ranges above 2^32 - 1.  CHIP_E_NOMEM:
+ * the 12 bytes per unit and 4 per range of working memory could not be allocated. */
+int chip_select_units_host(size_t n_units, const uint64_t *in_off, const uint32_t *in_len, const uint64_t *out_off, const uint32_t *out_cap,
+                           size_t n_ranges, const uint64_t *range_lo, const uint32_t *range_len, uint64_t max_sel, uint32_t *sel_unit,
+                           uint64_t *sel_in_off, uint32_t *sel_in_len, uint64_t *sel_out_off, uint32_t *sel_out_cap, uint64_t *src_off,
+                           uint64_t *dst_off, int32_t *range_status, chip_select_summary *summary);
+
+/* The same answer for DEVICE arrays (every array pointer; summary is a HOST pointer): the index step alone, for a caller that
+ * decodes into a buffer of its own.  Arguments are checked before the device is looked for.  SYNCHRONOUS on `stream` (n_sel and
+ * scratch_bytes are host arguments of what follows).  Scratch per (device, stream), a launch slot of its own, kept between calls
+ * and released by chip_trim(): 24 bytes per unit, 28 bytes per range, at most 24 bytes per 1024 of either, with a quarter of headroom.
+ * The calling thread's current device is left as it was. */
+int chip_select_units(size_t n_units, const uint64_t *in_off, const uint32_t *in_len, const uint64_t *out_off, const uint32_t *out_cap,
+                      size_t n_ranges, const uint64_t *range_lo, const uint32_t *range_len, uint64_t max_sel, uint32_t *sel_unit,
+                      uint64_t *sel_in_off, uint32_t *sel_in_len, uint64_t *sel_out_off, uint32_t *sel_out_cap, uint64_t *src_off, uint64_t *dst_off,
+                      int32_t *range_status, chip_select_summary *summary, void *stream);
+
+/*
+ * Select, decode and gather, all in DEVICE memory: the bytes of range r land at dst_base[dst_off[r] .. + range_len[r]).  in_base is
+ * the file the plan was made of; `format` goes on to chip_decode_batch(format, n_sel, ..), whose formats, alignment and padding
+ * rules of in_base hold (CHIP_FMT_GZIP for a BGZF plan, CHIP_FMT_ZSTD for a frame plan).  dst_off and range_status are DEVICE
+ * arrays of n_ranges entries, each may be NULL; summary is a HOST pointer.
+ *   status = CHIP_READ_BAD_LAYOUT (bad_index says where): nothing is decoded, nothing at all is written.
+ *   status = CHIP_READ_NEED_OUTPUT when out_len > dst_cap: out_len is the exact size to come back with, dst_off and range_status
+ *            are answered, nothing is decoded (n_units = 0) and no byte of dst_base is written.
+ *   status = CHIP_READ_OK: n_units = n_sel units were decoded, each once, into the slot's scratch area.  A selected unit that did
+ *            not end CHIP_FINISHED with out_len == out_cap is a bad unit: n_bad counts them, first_bad is the lowest one's index
+ *            in the plan and bad_status its decode status (CHIP_FINISHED when only the length was wrong); without one all three
+ *            are 0.  A range whose span first .. last holds a bad unit gets CHIP_RANGE_BAD_UNIT, and the bytes in its own
+ *            [dst_off[r], + len) are unspecified; every other range has its bytes.  Units no range touches are never decoded,
+ *            damaged or not.
+ * Nothing outside dst_base[0 .. out_len) is ever written, at any alignment of dst_base; a destination byte is written once, by
+ * a store that covers only bytes of the output (chip_pack_units' copy).  dst_base must not overlap in_base.
+ * SYNCHRONOUS on `stream`: it waits once for {n_sel, scratch_bytes, out_len} and once at the end.
+ * CHIP_E_INVALID, before the device is looked for: summary NULL; a plan array or in_base NULL with n_units > 0; range_lo or
+ * range_len NULL with n_ranges > 0; dst_base NULL with dst_cap > 0; n_units or n_ranges above 2^32 - 1; a format
+ * chip_decode_batch refuses; in_base not 4-byte aligned.  n_ranges == 0: CHIP_OK, an all-zero summary, the device is not touched.
+ * CHIP_E_NOMEM: the scratch could not be allocated.  CHIP_E_LAUNCH: a launch failed, or more than 2^31 - 1 units were selected.
+ * Scratch per (device, stream), the slot of chip_select_units: 72 bytes per unit (the selection may be every unit: the sub-batch
+ * and the decode's answers are sized for it), 28 bytes per range, and scratch_bytes + 64 for the decoded image, each allocation
+ * with a quarter of headroom.  The calling thread's current device is left as it was.
+ * No reference counterpart: compu has no container formats.  Without it a caller decodes the whole plan and slices, or copies the
+ * plan to the host, searches it there, uploads a sub-batch and issues one copy per range.
+ */
+typedef struct {
+    uint64_t n_units, out_len, n_outside, n_bad, first_bad, bad_index;
+    int32_t status; /* CHIP_READ_* */
+    int32_t bad_status;
+} chip_read_summary;
+int chip_read_ranges(int format, size_t n_units, const void *in_base, const uint64_t *in_off, const uint32_t *in_len, const uint64_t *out_off,
+                     const uint32_t *out_cap, size_t n_ranges, const uint64_t *range_lo, const uint32_t *range_len, void *dst_base,
+                     uint64_t dst_cap, uint64_t *dst_off, int32_t *range_status, chip_read_summary *summary, void *stream);
+
 /* ---- zstd encoder: encoder::Interface::zstd, src/encoder/zstd.rs ------------------------------------------------------------ */
 
 /* ZstdStrategy src/encoder/zstd.rs:33-56 (ZSTD_strategy values; 0 = the level's own).  The GPU encoder has four level groups

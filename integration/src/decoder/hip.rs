@@ -390,3 +390,127 @@ pub unsafe fn layout_units_device(n: usize, out_size: &crate::buffer::DeviceBuff
                                     &mut n_over, stream);
     if rc == sys::CHIP_OK { Ok((total, n_over)) } else { Err(rc) }
 }
+
+///What `select_units_host` answers: the sub-batch of the selected units (`sel_unit` their indices in the plan), `src_off` /
+///`dst_off` / `range_status` per range, and the summary.
+#[derive(Clone, Debug, Default)]
+pub struct Selection {
+    pub sel_unit: alloc::vec::Vec<u32>,
+    pub sel_in_off: alloc::vec::Vec<u64>,
+    pub sel_in_len: alloc::vec::Vec<u32>,
+    pub sel_out_off: alloc::vec::Vec<u64>,
+    pub sel_out_cap: alloc::vec::Vec<u32>,
+    pub src_off: alloc::vec::Vec<u64>,
+    pub dst_off: alloc::vec::Vec<u64>,
+    pub range_status: alloc::vec::Vec<i32>,
+    pub summary: sys::chip_select_summary,
+}
+
+///The units that the byte ranges `(range_lo[r], range_len[r])` of a plan's decoded content touch (`chip_select_units_host`): one
+///call to count, one to fill.  On `CHIP_READ_BAD_LAYOUT` the arrays are empty.  Pure host arithmetic.  No counterpart in this
+///crate.
+pub fn select_units_host(in_off: &[u64], in_len: &[u32], out_off: &[u64], out_cap: &[u32], range_lo: &[u64], range_len: &[u32]) -> Result<Selection, i32> {
+    let (n, m) = (out_cap.len(), range_len.len());
+    if in_off.len() != n || in_len.len() != n || out_off.len() != n || range_lo.len() != m {
+        return Err(-101);
+    }
+    let mut s = Selection::default();
+    let rc = unsafe {
+        sys::chip_select_units_host(n, in_off.as_ptr(), in_len.as_ptr(), out_off.as_ptr(), out_cap.as_ptr(), m, range_lo.as_ptr(), range_len.as_ptr(), 0,
+                                    ptr::null_mut(), ptr::null_mut(), ptr::null_mut(), ptr::null_mut(), ptr::null_mut(), ptr::null_mut(),
+                                    ptr::null_mut(), ptr::null_mut(), &mut s.summary)
+    };
+    if rc != sys::CHIP_OK {
+        return Err(rc);
+    }
+    if s.summary.status != sys::CHIP_READ_OK {
+        return Ok(s);
+    }
+    let k = s.summary.n_sel as usize;
+    s.sel_unit = alloc::vec![0u32; k];
+    s.sel_in_off = alloc::vec![0u64; k];
+    s.sel_in_len = alloc::vec![0u32; k];
+    s.sel_out_off = alloc::vec![0u64; k];
+    s.sel_out_cap = alloc::vec![0u32; k];
+    s.src_off = alloc::vec![0u64; m];
+    s.dst_off = alloc::vec![0u64; m];
+    s.range_status = alloc::vec![0i32; m];
+    let rc = unsafe {
+        sys::chip_select_units_host(n, in_off.as_ptr(), in_len.as_ptr(), out_off.as_ptr(), out_cap.as_ptr(), m, range_lo.as_ptr(), range_len.as_ptr(),
+                                    k as u64, s.sel_unit.as_mut_ptr(), s.sel_in_off.as_mut_ptr(), s.sel_in_len.as_mut_ptr(), s.sel_out_off.as_mut_ptr(),
+                                    s.sel_out_cap.as_mut_ptr(), s.src_off.as_mut_ptr(), s.dst_off.as_mut_ptr(), s.range_status.as_mut_ptr(), &mut s.summary)
+    };
+    if rc == sys::CHIP_OK { Ok(s) } else { Err(rc) }
+}
+
+///The device arrays of a plan: `n` units, `in_off` / `out_off` u64 and `in_len` / `out_cap` u32 entries.
+pub struct PlanArrays<'a> {
+    pub n: usize,
+    pub in_off: &'a crate::buffer::DeviceBuffer,
+    pub in_len: &'a crate::buffer::DeviceBuffer,
+    pub out_off: &'a crate::buffer::DeviceBuffer,
+    pub out_cap: &'a crate::buffer::DeviceBuffer,
+}
+
+impl PlanArrays<'_> {
+    fn fits(&self) -> bool {
+        self.in_off.capacity() >= 8 * self.n && self.out_off.capacity() >= 8 * self.n && self.in_len.capacity() >= 4 * self.n
+            && self.out_cap.capacity() >= 4 * self.n
+    }
+}
+
+///`chip_select_units`: the index step alone, for a caller that decodes into a buffer of its own.  `sel` holds room for `max_sel`
+///rows of the sub-batch (`sel_unit`, then the four arrays of `decode_batch_device`); `src_off`, `dst_off` and `range_status`, if
+///given, get one entry per range.  `max_sel` 0 counts.  Synchronous on `stream`.
+///
+///# Safety
+///
+///As `decode_batch_device`.
+#[allow(clippy::too_many_arguments)]
+pub unsafe fn select_units_device(plan: &PlanArrays, n_ranges: usize, range_lo: &crate::buffer::DeviceBuffer, range_len: &crate::buffer::DeviceBuffer,
+                                  max_sel: usize, sel_unit: &mut crate::buffer::DeviceBuffer, sel: &mut [&mut crate::buffer::DeviceBuffer; 4],
+                                  src_off: Option<&mut crate::buffer::DeviceBuffer>, dst_off: Option<&mut crate::buffer::DeviceBuffer>,
+                                  range_status: Option<&mut crate::buffer::DeviceBuffer>, stream: *mut core::ffi::c_void)
+                                  -> Result<sys::chip_select_summary, i32> {
+    let small = |b: &Option<&mut crate::buffer::DeviceBuffer>, each: usize| b.as_ref().map_or(false, |b| b.capacity() < each * n_ranges);
+    if !plan.fits() || range_lo.capacity() < 8 * n_ranges || range_len.capacity() < 4 * n_ranges || sel_unit.capacity() < 4 * max_sel
+        || sel[0].capacity() < 8 * max_sel || sel[1].capacity() < 4 * max_sel || sel[2].capacity() < 8 * max_sel || sel[3].capacity() < 4 * max_sel
+        || small(&src_off, 8) || small(&dst_off, 8) || small(&range_status, 4)
+    {
+        return Err(-101);
+    }
+    let opt = |b: Option<&mut crate::buffer::DeviceBuffer>| b.map_or(ptr::null_mut(), |b| b.as_mut_ptr());
+    let mut summary = sys::chip_select_summary::default();
+    let rc = sys::chip_select_units(plan.n, plan.in_off.as_ptr() as *const u64, plan.in_len.as_ptr() as *const u32, plan.out_off.as_ptr() as *const u64,
+                                    plan.out_cap.as_ptr() as *const u32, n_ranges, range_lo.as_ptr() as *const u64, range_len.as_ptr() as *const u32,
+                                    max_sel as u64, sel_unit.as_mut_ptr() as *mut u32, sel[0].as_mut_ptr() as *mut u64, sel[1].as_mut_ptr() as *mut u32,
+                                    sel[2].as_mut_ptr() as *mut u64, sel[3].as_mut_ptr() as *mut u32, opt(src_off) as *mut u64, opt(dst_off) as *mut u64,
+                                    opt(range_status) as *mut i32, &mut summary, stream);
+    if rc == sys::CHIP_OK { Ok(summary) } else { Err(rc) }
+}
+
+///`chip_read_ranges`: the bytes of `n_ranges` ranges of the plan's decoded content, end to end in `dst`; only the units the ranges
+///touch are decoded, each once.  `format` is what `decode_batch_device` takes for the plan's units (`BatchFormat::Zlib(ZlibMode::Gzip)` for a
+///BGZF plan).  On `CHIP_READ_NEED_OUTPUT` nothing is written and `summary.out_len` says how much room is needed.  Synchronous on
+///`stream`.
+///
+///# Safety
+///
+///As `decode_batch_device`; `dst` must not overlap `input`.
+#[allow(clippy::too_many_arguments)]
+pub unsafe fn read_ranges_device(format: BatchFormat, input: &crate::buffer::DeviceBuffer, plan: &PlanArrays, n_ranges: usize,
+                                 range_lo: &crate::buffer::DeviceBuffer, range_len: &crate::buffer::DeviceBuffer, dst: &mut crate::buffer::DeviceBuffer,
+                                 dst_off: Option<&mut crate::buffer::DeviceBuffer>, range_status: Option<&mut crate::buffer::DeviceBuffer>,
+                                 stream: *mut core::ffi::c_void) -> Result<sys::chip_read_summary, i32> {
+    let small = |b: &Option<&mut crate::buffer::DeviceBuffer>, each: usize| b.as_ref().map_or(false, |b| b.capacity() < each * n_ranges);
+    if !plan.fits() || range_lo.capacity() < 8 * n_ranges || range_len.capacity() < 4 * n_ranges || small(&dst_off, 8) || small(&range_status, 4) {
+        return Err(-101);
+    }
+    let opt = |b: Option<&mut crate::buffer::DeviceBuffer>| b.map_or(ptr::null_mut(), |b| b.as_mut_ptr());
+    let mut summary = sys::chip_read_summary::default();
+    let rc = sys::chip_read_ranges(format.tag(), plan.n, input.as_ptr() as *const _, plan.in_off.as_ptr() as *const u64, plan.in_len.as_ptr() as *const u32,
+                                   plan.out_off.as_ptr() as *const u64, plan.out_cap.as_ptr() as *const u32, n_ranges, range_lo.as_ptr() as *const u64,
+                                   range_len.as_ptr() as *const u32, dst.as_mut_ptr() as *mut _, dst.capacity() as u64, opt(dst_off) as *mut u64,
+                                   opt(range_status) as *mut i32, &mut summary, stream);
+    if rc == sys::CHIP_OK { Ok(summary) } else { Err(rc) }
+}

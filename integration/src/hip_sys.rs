@@ -134,6 +134,44 @@ pub struct chip_file_summary {
     pub pad: u32,
 }
 
+///`chip_select_summary::status` / `chip_read_summary::status`
+pub const CHIP_READ_OK: i32 = 0;
+pub const CHIP_READ_NEED_OUTPUT: i32 = 1;
+pub const CHIP_READ_BAD_LAYOUT: i32 = 2;
+///`range_status[r]` of `chip_select_units` / `chip_read_ranges`
+pub const CHIP_RANGE_OK: i32 = 0;
+pub const CHIP_RANGE_OUTSIDE: i32 = 1;
+pub const CHIP_RANGE_BAD_UNIT: i32 = 2;
+
+///what the selection found: units selected, their decoded size, the bytes of the ranges, ranges outside the content; on
+///`CHIP_READ_BAD_LAYOUT` only `bad_index` (the lowest unit that does not follow its predecessor) is set
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct chip_select_summary {
+    pub n_sel: u64,
+    pub scratch_bytes: u64,
+    pub out_len: u64,
+    pub n_outside: u64,
+    pub bad_index: u64,
+    pub status: i32,
+    pub pad: u32,
+}
+
+///what `chip_read_ranges` did: units decoded, bytes of ranges (the exact size needed on `CHIP_READ_NEED_OUTPUT`), ranges outside
+///the content, selected units that did not decode to their size, the lowest one's index and decode status
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct chip_read_summary {
+    pub n_units: u64,
+    pub out_len: u64,
+    pub n_outside: u64,
+    pub n_bad: u64,
+    pub first_bad: u64,
+    pub bad_index: u64,
+    pub status: i32,
+    pub bad_status: i32,
+}
+
 pub type chip_malloc_fn = unsafe extern "C" fn(opaque: *mut c_void, size: usize) -> *mut c_void;
 pub type chip_free_fn = unsafe extern "C" fn(opaque: *mut c_void, ptr: *mut c_void);
 
@@ -228,4 +266,22 @@ extern "C" {
                             out_cap: u64, summary: *mut chip_file_summary, stream: *mut c_void) -> c_int;
     ///the output size that is always enough; 0 for arguments `chip_encode_file` refuses
     pub fn chip_encode_file_bound(format: c_int, unit_bytes: u32, flags: u32, len: u64) -> u64;
+
+    // ---- reading ranges: the units that byte ranges of a plan's content touch, decoded once, the ranges end to end (no reference
+    // counterpart)
+    ///the definition on host memory; pure host arithmetic, no device needed.  `max_sel` 0 with null `sel_*` arrays counts
+    pub fn chip_select_units_host(n_units: usize, in_off: *const u64, in_len: *const u32, out_off: *const u64, out_cap: *const u32, n_ranges: usize,
+                                  range_lo: *const u64, range_len: *const u32, max_sel: u64, sel_unit: *mut u32, sel_in_off: *mut u64,
+                                  sel_in_len: *mut u32, sel_out_off: *mut u64, sel_out_cap: *mut u32, src_off: *mut u64, dst_off: *mut u64,
+                                  range_status: *mut i32, summary: *mut chip_select_summary) -> c_int;
+    ///the same answer for device arrays (host summary); synchronous on `stream`
+    pub fn chip_select_units(n_units: usize, in_off: *const u64, in_len: *const u32, out_off: *const u64, out_cap: *const u32, n_ranges: usize,
+                             range_lo: *const u64, range_len: *const u32, max_sel: u64, sel_unit: *mut u32, sel_in_off: *mut u64,
+                             sel_in_len: *mut u32, sel_out_off: *mut u64, sel_out_cap: *mut u32, src_off: *mut u64, dst_off: *mut u64,
+                             range_status: *mut i32, summary: *mut chip_select_summary, stream: *mut c_void) -> c_int;
+    ///select, decode the touched units once, gather: device buffers and arrays, host summary; nothing is written when
+    ///`out_len > dst_cap`; synchronous on `stream`
+    pub fn chip_read_ranges(format: c_int, n_units: usize, in_base: *const c_void, in_off: *const u64, in_len: *const u32, out_off: *const u64,
+                            out_cap: *const u32, n_ranges: usize, range_lo: *const u64, range_len: *const u32, dst_base: *mut c_void, dst_cap: u64,
+                            dst_off: *mut u64, range_status: *mut i32, summary: *mut chip_read_summary, stream: *mut c_void) -> c_int;
 }
