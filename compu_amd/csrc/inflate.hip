@@ -1180,7 +1180,7 @@ __device__ CHIP_PHASE_FN uint32_t walk_round(WaveLds &L, const InWin &w, const u
         const uint32_t bit = 1u << (p & 31u);
         const uint32_t mine = p < own_end_r ? bit : 0u;
         const uint32_t old = atomicOr((uint32_t *)((uint8_t *)L.w.bm + a), mine);
-        jb = old & (bit - mine);  // a boundary of the segment's owner: from here on the two chains are one
+        jb = old & bit & ~mine;  // a boundary of the segment's owner: from here on the two chains are one (one three-input bit operation)
         const uint32_t *wp = (const uint32_t *)((const uint8_t *)L.w.win + a);
         const uint32_t d0 = wp[0], d1 = wp[1], d2 = wp[2];
         const uint32_t lo = __builtin_amdgcn_alignbit(d1, d0, p), hi = __builtin_amdgcn_alignbit(d2, d1, p);
@@ -1190,7 +1190,11 @@ __device__ CHIP_PHASE_FN uint32_t walk_round(WaveLds &L, const InWin &w, const u
         const uint32_t msk = (uint32_t)((int32_t)e >> 31);  // all ones for a length code
         const uint32_t w2 = __builtin_amdgcn_alignbit(hi, lo, n1);
         uint32_t m = L.dist_root[w2 & ((1u << DIST_ROOT) - 1u)] & msk;
-        if (m & D_LONG) m = dist_sub_at(L, m, w2);  // a distance code of more than 8 bits (1 % of the matches): through its sub-table
+        // a distance code of more than 8 bits (1 % of the matches) goes through its sub-table: five steps in six have no such lane
+        if (__any((m & D_LONG) != 0)) {
+            asm volatile("; long distance codes");  // (keeps the skip: the compiler would issue the short region in every step)
+            if (m & D_LONG) m = dist_sub_at(L, m, w2);
+        }
 #ifndef CHIP_EXP_NO_PAIR
         // A literal takes the literal behind it along as one token (a pair) when there is one, it ends inside the chain's limit, and
         // its start is no boundary of the segment's owner: a chain that pairs across the owner's boundary walks one literal out of
@@ -1199,7 +1203,7 @@ __device__ CHIP_PHASE_FN uint32_t walk_round(WaveLds &L, const InWin &w, const u
         const uint32_t r2 = L.lit_root[w2 & ((1u << LIT_ROOT) - 1u)];
         const uint32_t e2 = pool_at(L, r2, w2);
         const uint32_t p2 = p + n1;
-        const uint32_t mk2 = *(const uint32_t *)((const uint8_t *)L.w.bm + ((p2 >> 3) & ~3u));
+        const uint32_t mk2 = __builtin_amdgcn_ubfe(*(const uint32_t *)((const uint8_t *)L.w.bm + ((p2 >> 3) & ~3u)), p2, 1);
 #endif
         const uint32_t cl2 = m & 15u, eb2 = __builtin_amdgcn_ubfe(m, 4, 4);
         // (only a token that is taken uses dm1: its entry has neither D_BAD nor D_LONG, so what lies above bit 8 is the mantissa)
@@ -1208,7 +1212,7 @@ __device__ CHIP_PHASE_FN uint32_t walk_round(WaveLds &L, const InWin &w, const u
         tl = n1 + cl2 + eb2;
 #ifndef CHIP_EXP_NO_PAIR
         const uint32_t n2 = __builtin_amdgcn_ubfe(e2, 10, 5);
-        const bool pair = ((e | e2) & (F_LEN | F_HALT)) == 0 && p2 + n2 <= hard_r && ((mk2 >> (p2 & 31u)) & 1u) == 0;
+        const bool pair = ((e | e2) & (F_LEN | F_HALT)) == 0 && p2 + n2 <= hard_r && mk2 == 0;
         tl += pair ? n2 : 0u;
         const uint32_t pr = pair ? (e2 & 0x00ff0000u) | 0x80000000u : 0u;
 #else
