@@ -51,6 +51,11 @@ class _ZstdPlanSummary(C.Structure):
                 ("in_used", C.c_uint64), ("status", C.c_int32), ("pad", C.c_uint32)]
 
 
+class _GzipPlanSummary(C.Structure):
+    _fields_ = [("n_members", C.c_uint64), ("total_out", C.c_uint64), ("in_used", C.c_uint64), ("status", C.c_int32),
+                ("member_status", C.c_int32)]
+
+
 class _FileSummary(C.Structure):
     _fields_ = [("n_units", C.c_uint64), ("out_len", C.c_uint64), ("table_off", C.c_uint64), ("status", C.c_int32), ("pad", C.c_uint32)]
 
@@ -157,6 +162,8 @@ def lib():
     L.chip_zstd_plan_host.argtypes = [vp, C.c_uint64, C.c_uint64, vp, vp, vp, vp, C.POINTER(_ZstdPlanSummary)]
     L.chip_zstd_plan.restype = C.c_int
     L.chip_zstd_plan.argtypes = [vp, C.c_uint64, C.c_uint64, vp, vp, vp, vp, C.POINTER(_ZstdPlanSummary), vp]
+    L.chip_gzip_plan.restype = C.c_int
+    L.chip_gzip_plan.argtypes = [vp, C.c_uint64, C.c_uint64, vp, vp, vp, vp, C.POINTER(_GzipPlanSummary), vp]
     L.chip_layout_units.restype = C.c_int
     L.chip_layout_units.argtypes = [sz, vp, vp, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), vp]
     L.chip_pack_units.restype = C.c_int
@@ -1236,6 +1243,66 @@ def zstd_frames_decode(in_buf, length, stream=None):
     return out[:total], (in_off, in_len, out_off, out_cap), summ
 
 
+# ---- gzip members: from a file to a batch (include/compu_hip.h, "gzip members") -----------------
+
+GZPLAN_WINDOW = (1 << 29) - 64  # CHIP_GZPLAN_WINDOW: input bytes a member may take
+
+
+class GzipPlanStatus(enum.IntEnum):
+    Ok = 0
+    Truncated = 1
+    BadHeader = 2
+    TooLarge = 3
+    BadMember = 4
+
+
+class GzipPlanSummary:
+    """chip_gzip_plan_summary: n_members and total_out of the whole walk, in_used where it stopped (the start of the member it
+    stopped at), status why, member_status the size pass's status of that member when status is BadMember (else 0)."""
+
+    __slots__ = ("n_members", "total_out", "in_used", "status", "member_status")
+
+    def __init__(self, raw):
+        self.n_members, self.total_out, self.in_used = int(raw.n_members), int(raw.total_out), int(raw.in_used)
+        self.status, self.member_status = GzipPlanStatus(raw.status), int(raw.member_status)
+
+    def as_tuple(self):
+        return (self.n_members, self.total_out, self.in_used, int(self.status), self.member_status)
+
+    def __repr__(self):
+        return (f"GzipPlanSummary(n_members={self.n_members}, total_out={self.total_out}, in_used={self.in_used}, "
+                f"status={self.status.name}, member_status={self.member_status})")
+
+
+def gzip_plan(in_buf, length, stream=None, max_members=None):
+    """chip_gzip_plan over a uint8 device tensor holding `length` bytes of gzip members (4-byte aligned, padded to a multiple of
+    4): returns (in_off int64, in_len int32, out_off int64, out_cap int32, summary) -- device tensors of the first
+    min(n_members, max_members) members, ready for decode_batch(ZlibMode.Gzip, ..) and read_ranges(ZlibMode.Gzip, ..).
+    Synchronous on `stream`.  max_members None: all of them (one call to count, one to fill)."""
+    return _plan_device("chip_gzip_plan", _GzipPlanSummary, GzipPlanSummary, "n_members", in_buf, length, stream, max_members)
+
+
+def gzip_members_decode(in_buf, length, stream=None):
+    """Decode a whole buffer of gzip members on the device, one unit per member: plan, allocate total_out bytes,
+    decode_batch(ZlibMode.Gzip).  Raises ValueError when the buffer is no whole series of members (the summary says where) and
+    RuntimeError with the first bad member's index and status when a member does not decode to its size (a wrong CRC-32: the
+    plan does not see it).  Returns (the uint8 output tensor, (in_off, in_len, out_off, out_cap), summary).  Waits for the
+    decode."""
+    import torch
+
+    in_off, in_len, out_off, out_cap, summ = gzip_plan(in_buf, length, stream=stream)
+    if summ.status != GzipPlanStatus.Ok:
+        raise ValueError(f"not a whole series of gzip members: {summ!r}")
+    out = torch.empty(max(summ.total_out, 4), dtype=torch.uint8, device=in_buf.device)
+    if summ.n_members:
+        out_len, _, status = decode_batch(ZlibMode.Gzip, in_buf, in_off, in_len, out, out_off, out_cap, stream=stream)
+        bad = ((status != int(DecodeStatus.Finished)) | (out_len != out_cap)).nonzero()
+        if bad.numel():
+            i = int(bad[0])
+            raise RuntimeError(f"gzip member {i} did not decode: status {int(status[i])}, {int(out_len[i])} of {int(out_cap[i])} bytes")
+    return out[: summ.total_out], (in_off, in_len, out_off, out_cap), summ
+
+
 # ---- writing files: from a batch to a file (include/compu_hip.h, "writing files") ---------------
 
 W_SEEK_TABLE = 1  # CHIP_W_SEEK_TABLE: the seek table of zstd's seekable format behind the last frame (FMT_ZSTD only)
@@ -1543,3 +1610,14 @@ def zstd_frames_read(in_buf, length, ranges, stream=None):
     lo, ln = _ranges_to_device(ranges, in_buf.device)
     out, dst_off, status, rs = read_ranges(FMT_ZSTD, in_buf, in_off, in_len, out_off, out_cap, lo, ln, stream=stream)
     return _read_checked("zstd_frames_read", out, status, rs), dst_off
+
+
+def gzip_members_read(in_buf, length, ranges, stream=None):
+    """The same for a buffer of gzip members (WARC records, a file encode_file(ZlibMode.Gzip) wrote): gzip_plan, then
+    read_ranges(ZlibMode.Gzip).  Returns (the uint8 tensor of the ranges end to end, dst_off int64).  Waits for the result."""
+    in_off, in_len, out_off, out_cap, summ = gzip_plan(in_buf, length, stream=stream)
+    if summ.status != GzipPlanStatus.Ok:
+        raise ValueError(f"not a whole series of gzip members: {summ!r}")
+    lo, ln = _ranges_to_device(ranges, in_buf.device)
+    out, dst_off, status, rs = read_ranges(ZlibMode.Gzip, in_buf, in_off, in_len, out_off, out_cap, lo, ln, stream=stream)
+    return _read_checked("gzip_members_read", out, status, rs), dst_off

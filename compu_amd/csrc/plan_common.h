@@ -1,4 +1,4 @@
-// What the container plans (bgzf.hip, zstd_plan.hip) have in common, which is everything but the format:
+// What the container plans (bgzf.hip, zstd_plan.hip, gzip_plan.hip) have in common, which is everything but the format:
 // the tile geometry of the candidate search, the chunk loader, the reduce-then-scan kernels and the helper that enqueues them, the
 // plan pipeline as templates over a format policy (count, emit, describe, successor, doubling, marking, flags, output and the
 // driver that enqueues them: "The container plan" below), the slot with its two growing buffers and its summary, and the scaffold
@@ -241,19 +241,23 @@ int with_slot(SlotCache<Slot> &cache, void *stream, Body body, Failed failed)
 //   F::MIN_HEADER                              the shortest header: what the walk needs in front of `len` to look at a position
 //   F::candidates(base, len, n_chunks, g)      the positions of chunk g that may start a unit, as a 16-bit mask
 //   F::describe(base, len, p, gone)            the unit whose header sits at candidate p; gone = p is no candidate (any more)
-// and every kernel below that depends on it is instantiated once per format.  The phases, in stream order:
+// and every kernel below that depends on it is instantiated once per format.  A format whose units do not state their length in a
+// header a single thread can read supplies the describe phase itself (the policy D of plan_locked, KernelDescribe<F> by default:
+// gzip_plan.hip runs the inflate size pass there) and needs no F::describe.  The phases, in stream order:
 //   1. count     plan_count_kernel<F>: one count of candidates per 16 KiB tile
 //   2. scan      exclusive scan of the tile counts (enqueue_scan)
 //      -- the host reads the candidate count and sizes the candidate scratch --
 //   3. emit      plan_emit_kernel<F>: tiles with candidates are read again and the positions written in ascending order;
-//      describe  plan_describe_kernel<F>: each candidate's own thread stores the end position, the cap, the verdict and the kind
+//      describe  D::describe, by default plan_describe_kernel<F>: each candidate's own thread stores the end position, the cap, the
+//                verdict and the kind
 //   4. succ      plan_succ_kernel<F>: successor of a whole candidate = the candidate at its end position (binary search);
 //                everything else leads to the sink (index = number of candidates)
 //   5. double    plan_double_kernel: jump table k+1 = jump table k applied twice, ceil(log2(candidates + 1)) tables
 //   6. mark      plan_mark_kernel: from candidate 0 (if it sits at position 0) top-down through the tables.  What is never marked
 //                is a decoy
 //   7. output    plan_flags_kernel, exclusive 64-bit scan of {frames, skippable, unsized, content bytes}, plan_output_kernel<F>:
-//                scatter of the frames' rows; the one marked candidate without a successor says where and why the walk stopped
+//                scatter of the frames' rows; the one marked candidate without a successor says where and why the walk stopped;
+//                D::finish, by default nothing
 // Order between the phases comes from kernel boundaries on the stream only: no workgroup ever waits for another one.  Every index
 // is checked against the count it belongs to; data that changes under the kernels sets PlanSummary::fault instead of writing out
 // of range.
@@ -262,6 +266,7 @@ int with_slot(SlotCache<Slot> &cache, void *stream, Body body, Failed failed)
 constexpr int32_t PLAN_OK = 0, PLAN_TRUNCATED = 1, PLAN_BAD_HEADER = 2;
 static_assert(CHIP_BGZF_OK == PLAN_OK && CHIP_BGZF_TRUNCATED == PLAN_TRUNCATED && CHIP_BGZF_BAD_HEADER == PLAN_BAD_HEADER, "stop_status");
 static_assert(CHIP_ZPLAN_OK == PLAN_OK && CHIP_ZPLAN_TRUNCATED == PLAN_TRUNCATED && CHIP_ZPLAN_BAD_HEADER == PLAN_BAD_HEADER, "stop_status");
+static_assert(CHIP_GZPLAN_OK == PLAN_OK && CHIP_GZPLAN_TRUNCATED == PLAN_TRUNCATED && CHIP_GZPLAN_BAD_HEADER == PLAN_BAD_HEADER, "stop_status");
 
 constexpr uint32_t KIND_FRAME = 0, KIND_SKIP = 1;  // a unit of the batch / a unit that is stepped over and counted
 
@@ -437,10 +442,30 @@ __global__ __launch_bounds__(256) void plan_output_kernel(const uint64_t *pos, c
     }
 }
 
+// The describe phase plan_locked enqueues when the format brings none of its own: plan_describe_kernel<F>, no scratch, nothing
+// behind the output.  A policy D of a format's own has the same three members --
+//   D::EXTRA                      bytes of scratch per candidate, handed to both calls as `extra` (16-byte aligned, in buffer 1)
+//   D::describe(..)               enqueues on `stream`, between emit and succ, whatever fills end / cap / info of every candidate
+//                                 (info = verdict | kind << 8) from pos; sets ds->fault where the data contradicts the candidates
+//   D::finish(..)                 enqueues behind the output kernel what else the format's summary needs (ds is the slot's summary)
+// and neither waits for the stream.
+template <class F>
+struct KernelDescribe {
+    static constexpr size_t EXTRA = 0;
+    static hipError_t describe(const uint8_t *base, uint64_t len, const uint64_t *pos, uint32_t n_cand, uint64_t *end, uint32_t *cap, uint32_t *info,
+                               uint8_t *, PlanSummary *ds, hipStream_t stream)
+    {
+        hipLaunchKernelGGL(plan_describe_kernel<F>, dim3((n_cand + 255u) / 256u), dim3(256), 0, stream, base, len, pos, n_cand, end, cap, info, ds);
+        return hipSuccess;
+    }
+    static void finish(const uint32_t *, const uint32_t *, uint32_t, const uint8_t *, PlanSummary *, hipStream_t) {}
+};
+
 // The plan of base[0 .. len), len > 0: enqueues everything, waits twice (candidate count, summary) and leaves the summary in
 // `res`; too_many = more candidates than an index holds.  The caller holds the cache's lock.  The slot's buffer 0 holds the tile
-// counts and their scan (16 bytes per 16 KiB of input), buffer 1 the candidate tables (60 + 4 * levels bytes per candidate).
-template <class F, class Sum>
+// counts and their scan (16 bytes per 16 KiB of input), buffer 1 the candidate tables (60 + 4 * levels + D::EXTRA bytes per
+// candidate).
+template <class F, class D = KernelDescribe<F>, class Sum>
 hipError_t plan_locked(SummarySlot<Sum> &sl, const uint8_t *base, uint64_t len, uint64_t max_units, uint64_t *in_off, uint32_t *in_len,
                        uint64_t *out_off, uint32_t *out_cap, hipStream_t stream, PlanSummary &res, bool &too_many)
 {
@@ -470,7 +495,8 @@ hipError_t plan_locked(SummarySlot<Sum> &sl, const uint8_t *base, uint64_t len, 
     const size_t o_acc = 0, o_part = o_acc + (size_t)n_cand * sizeof(PlanAcc), o_pos = o_part + (size_t)scan_parts(n_cand) * sizeof(PlanAcc);
     const size_t o_end = o_pos + (size_t)n_cand * 8, o_cap = o_end + (size_t)n_cand * 8, o_info = up16(o_cap + (size_t)n_cand * 4);
     const size_t o_mark = up16(o_info + (size_t)n_cand * 4), o_jump = up16(o_mark + (size_t)n_cand * 4), jump_stride = up16((size_t)n_cand * 4);
-    if ((e = sl.grow(1, o_jump + jump_stride * levels)) != hipSuccess) return e;
+    const size_t o_extra = o_jump + jump_stride * levels;
+    if ((e = sl.grow(1, o_extra + (size_t)n_cand * D::EXTRA)) != hipSuccess) return e;
     uint8_t *c = sl.buf[1];
     PlanAcc *acc = (PlanAcc *)(c + o_acc), *acc_part = (PlanAcc *)(c + o_part);
     uint64_t *pos = (uint64_t *)(c + o_pos), *end = (uint64_t *)(c + o_end);
@@ -480,7 +506,7 @@ hipError_t plan_locked(SummarySlot<Sum> &sl, const uint8_t *base, uint64_t len, 
 
     hipLaunchKernelGGL(plan_emit_kernel<F>, dim3((uint32_t)n_tiles), dim3(TILE_THREADS), 0, stream, base, len, n_chunks, (const uint64_t *)tile_cnt,
                        (const uint64_t *)tile_excl, (const uint64_t *)tile_part, pos, n_cand, ds);
-    hipLaunchKernelGGL(plan_describe_kernel<F>, cgrid, dim3(256), 0, stream, base, len, (const uint64_t *)pos, n_cand, end, cap, info, ds);
+    if ((e = D::describe(base, len, (const uint64_t *)pos, n_cand, end, cap, info, c + o_extra, ds, stream)) != hipSuccess) return e;
     hipLaunchKernelGGL(plan_succ_kernel<F>, cgrid, dim3(256), 0, stream, (const uint64_t *)pos, (const uint64_t *)end, (const uint32_t *)info, n_cand,
                        len, jump(0), marked, ds);
     for (uint32_t k = 0; k + 1 < levels; k++)
@@ -492,6 +518,7 @@ hipError_t plan_locked(SummarySlot<Sum> &sl, const uint8_t *base, uint64_t len, 
     hipLaunchKernelGGL(plan_output_kernel<F>, cgrid, dim3(256), 0, stream, (const uint64_t *)pos, (const uint64_t *)end, (const uint32_t *)cap,
                        (const uint32_t *)info, (const uint32_t *)marked, (const uint32_t *)jump(0), (const PlanAcc *)acc, (const PlanAcc *)acc_part, n_cand,
                        len, max_units, in_off, in_len, out_off, out_cap, ds);
+    D::finish((const uint32_t *)info, (const uint32_t *)marked, n_cand, (const uint8_t *)(c + o_extra), ds, stream);
     if ((e = sl.fetch(stream)) != hipSuccess) return e;
     if (sl.h_sum->fault) return hipErrorUnknown;  // the input changed between two passes
     res = *sl.h_sum;

@@ -524,6 +524,14 @@ public:
         if (len > in.len()) return CHIP_E_INVALID;
         return chip_zstd_plan(in.data(), len, max_frames, in_off, in_len, out_off, out_cap, &summary, stream);
     }
+    // chip_gzip_plan over the gzip members held in `in` (its first `len` bytes): the four DEVICE arrays of the decode_batch(CHIP_FMT_GZIP, ..)
+    // that follows, for the first min(n_members, max_members) members, and the summary of the whole walk.  Synchronous on `stream`.
+    static int gzip_plan(const DeviceBuffer &in, uint64_t len, uint64_t max_members, uint64_t *in_off, uint32_t *in_len, uint64_t *out_off,
+                         uint32_t *out_cap, chip_gzip_plan_summary &summary, void *stream = nullptr)
+    {
+        if (len > in.len()) return CHIP_E_INVALID;
+        return chip_gzip_plan(in.data(), len, max_members, in_off, in_len, out_off, out_cap, &summary, stream);
+    }
     // chip_layout_units: from the out_size of decode_batch_sizes() to the out_off / out_cap of decode_batch() (DEVICE arrays); `total` is
     // what to allocate, `n_over` counts the units above 4 GiB - 1.  Synchronous on `stream`.
     static int layout_units(size_t n, const uint64_t *out_size, uint64_t *out_off, uint32_t *out_cap, uint64_t &total, uint64_t &n_over,

@@ -333,9 +333,9 @@ int chip_detect_batch(size_t n, const void *in_base, const uint64_t *in_off, con
  * A block at byte p has the 18-byte header htslib writes:  1f 8b 08 04 | MTIME (4) XFL OS, any value | 06 00 (XLEN 6) |
  * 42 43 02 00 ('B' 'C', SLEN 2) | BSIZE (u16 LE).  It is BSIZE + 1 bytes long and ISIZE is the u32 LE in its last 4 bytes.
  * LIMIT: the BC subfield must be the only one.  A block whose extra field holds other subfields as well is valid by the SAM
- * specification and CHIP_BGZF_BAD_HEADER here (no known writer emits one).  Such a file still decodes, without a plan: as ONE
- * CHIP_FMT_GZIP unit with CHIP_F_MEMBERS (chip_decode_batch_ex), one wave walking its members, within the 512 MiB limit of a
- * unit's input.
+ * specification and CHIP_BGZF_BAD_HEADER here (no known writer emits one).  Such a file still decodes: its blocks are gzip
+ * members, which chip_gzip_plan (below) plans by the size pass instead of BSIZE, or as ONE CHIP_FMT_GZIP unit with CHIP_F_MEMBERS
+ * (chip_decode_batch_ex), one wave walking its members, within the 512 MiB limit of a unit's input.
  * The plan of `len` bytes is defined by this walk:
  *   p = 0, n = 0, total = 0
  *   loop: p == len -> OK;  len - p < 18 -> TRUNCATED;  header bytes wrong -> BAD_HEADER;
@@ -459,6 +459,69 @@ int chip_zstd_plan(const void *in_base, uint64_t len, uint64_t max_frames, uint6
 int chip_layout_units(size_t n, const uint64_t *out_size, uint64_t *out_off, uint32_t *out_cap, uint64_t *total, uint64_t *n_over,
                       void *stream);
 
+/* ---- gzip members: from a file to a batch (additive API) ------------------- */
+
+/*
+ * A gzip file may hold many members (RFC 1952 sec. 2.2: WARC / Common Crawl records, `pigz -i` output, `cat a.gz b.gz`, a BGZF file
+ * with foreign subfields, the files chip_encode_file(CHIP_FMT_GZIP) writes).  A member does not state its length: where it ends is
+ * known only once its deflate stream has been walked, which is what the size pass (chip_decode_batch_sizes) answers as in_used.
+ * This call turns such a buffer into the four arrays of chip_decode_batch(CHIP_FMT_GZIP, ..), one unit and so one wave per member,
+ * where the same buffer as ONE unit with CHIP_F_MEMBERS is decoded by a single wave.  The size pass runs over every position that
+ * looks like a member's start, all of them at once, one wave each; the members are the chain of those from position 0.
+ * The plan of `len` bytes is DEFINED by this walk, in which size1(p, room) is what chip_decode_batch_sizes(CHIP_FMT_GZIP, flags 0)
+ * answers for the unit in[p .. p + room): (st, size, iu) = (status, out_size, in_used).
+ *   p = 0; n = 0; total = 0
+ *   loop:
+ *     p == len                 -> OK
+ *     len - p < 4              -> TRUNCATED
+ *     bytes at p are not 1f 8b 08, or (byte[p + 3] & 0xe0) != 0   -> BAD_HEADER
+ *     room = min(len - p, CHIP_GZPLAN_WINDOW)
+ *     (st, size, iu) = size1(p, room)
+ *     st == CHIP_NEED_INPUT    -> room < len - p ? TOO_LARGE : TRUNCATED
+ *     st != CHIP_FINISHED      -> BAD_MEMBER, member_status = st
+ *     size > 0xFFFFFFFE        -> TOO_LARGE        (0xFFFFFFFF stays CHIP_ZPLAN_UNSIZED for chip_read_ranges' layout check)
+ *     member n: in_off = p, in_len = iu, out_off = total, out_cap = size;  n++; total += size; p += iu
+ * summary: n_members = n and total_out = total of the WHOLE walk, status why it stopped, in_used = the p where it stopped: a member
+ * that is cut or refused is not consumed.  member_status is the size pass's status of the member at in_used when status is
+ * CHIP_GZPLAN_BAD_MEMBER (e.g. -3), else 0.
+ * The arrays receive the first min(n_members, max_members) members and nothing behind them is written: max_members = 0 with null
+ * arrays counts, a second call fills.  in_off is relative to the buffer and out_off starts at 0, so the arrays go unchanged to
+ * chip_decode_batch(CHIP_FMT_GZIP, n_members, in_base, in_off, in_len, out, out_off, out_cap, ..) and to
+ * chip_read_ranges(CHIP_FMT_GZIP, ..).
+ * Conventions of chip_zstd_plan: in_base and the four arrays are DEVICE pointers, summary is a HOST pointer; in_base 4-byte
+ * aligned, its allocation padded to a multiple of 4 bytes; len is arbitrary.  SYNCHRONOUS on `stream`: it returns when the arrays
+ * are in device memory and *summary is filled, and waits once in between to size its scratch by the number of candidates.
+ * CHIP_E_INVALID, checked before the device is looked for: summary NULL, a NULL buffer with len > 0, NULL arrays with
+ * max_members > 0, in_base not 4-byte aligned, len > 2^40.  len == 0 is CHIP_OK with an all-zero summary.  More than 2^31 - 1
+ * candidates: CHIP_E_NOMEM.  Input that changes during the call: CHIP_E_LAUNCH, nothing is written out of range.  The calling
+ * thread's current device is left as it was.
+ * Scratch per (device, stream), a launch slot of its own, kept between calls and released by chip_trim(): 16 bytes per 16 KiB of
+ * input and 80 + 4 * ceil(log2(candidates + 1)) bytes per candidate (20 of them the size pass's answers); the size pass itself
+ * runs on the inflate slot of that stream, as chip_decode_batch_sizes does.  A candidate is a position whose four bytes are
+ * 1f 8b 08 and a FLG without reserved bits: random data holds about one per 128 MiB.
+ * What follows from the definition:
+ *   - CRC-32.  The size pass makes every check but the CRC-32 comparison.  A member whose only fault is its CRC is a member of the
+ *     plan and is -3 in the decode that follows (rule 4 of the size pass); its neighbours decode.
+ *   - Trailing bytes.  Bytes behind the last member that are no header (zero padding) stop the plan with BAD_HEADER; the members
+ *     in front stay listed and in_used says where.  As chip_bgzf_plan and chip_zstd_plan, and unlike CHIP_F_MEMBERS, which calls
+ *     them trailing bytes and answers CHIP_FINISHED.
+ *   - 1f 8b 07.  CHIP_F_MEMBERS starts a member at any 1f 8b and answers -3 for 1f 8b 07; the plan answers BAD_HEADER there, and
+ *     for a reserved FLG bit.
+ *   - No host form.  There is no chip_gzip_plan_host: this library has no CPU inflate, and finding a member's end is an inflate.
+ *   - One wave per member.  A file that is ONE huge member still runs on one wave, and a member of more than CHIP_GZPLAN_WINDOW
+ *     input bytes or more than 2^32 - 2 decoded bytes is TOO_LARGE.  This is for files of many members.
+ * No reference counterpart: compu has no container formats.
+ */
+enum { CHIP_GZPLAN_OK = 0, CHIP_GZPLAN_TRUNCATED = 1, CHIP_GZPLAN_BAD_HEADER = 2, CHIP_GZPLAN_TOO_LARGE = 3, CHIP_GZPLAN_BAD_MEMBER = 4 };
+#define CHIP_GZPLAN_WINDOW ((1u << 29) - 64u)  /* input bytes a member may take: the limit of a unit's input */
+typedef struct {
+    uint64_t n_members, total_out, in_used;
+    int32_t status;         /* CHIP_GZPLAN_* */
+    int32_t member_status;  /* CHIP_GZPLAN_BAD_MEMBER: the size pass's status of the member at in_used (e.g. -3); else 0 */
+} chip_gzip_plan_summary;
+int chip_gzip_plan(const void *in_base, uint64_t len, uint64_t max_members, uint64_t *in_off, uint32_t *in_len,
+                   uint64_t *out_off, uint32_t *out_cap, chip_gzip_plan_summary *summary, void *stream);
+
 /* ---- encoder: mirrors encoder::Interface, src/encoder/mod.rs:52-57 ---------------------------- */
 
 typedef struct chip_encoder chip_encoder;
@@ -545,7 +608,7 @@ int chip_pack_units(size_t n, const void *src_base, const uint64_t *src_off, con
                     uint64_t *dst_off, uint64_t *total, void *stream);
 
 /*
- * From a buffer to a file, both in DEVICE memory: the file chip_bgzf_plan, CHIP_F_MEMBERS or chip_zstd_plan reads back.  The
+ * From a buffer to a file, both in DEVICE memory: the file chip_bgzf_plan, chip_gzip_plan (or CHIP_F_MEMBERS) or chip_zstd_plan reads back.  The
  * input is cut into n = ceil(len / unit_bytes) units, unit i = [i * unit_bytes, min(len, (i + 1) * unit_bytes)); every unit is
  * encoded by chip_encode_batch(format, level, ..) -- the same kernels, the same bytes -- into a scratch slot of
  * chip_encode_bound(format, unit_bytes) bytes rounded up to 16; the encoded units are packed end to end into out_base

@@ -373,6 +373,28 @@ pub unsafe fn zstd_plan_device(input: &crate::buffer::DeviceBuffer, len: usize, 
     if rc == sys::CHIP_OK { Ok(summary) } else { Err(rc) }
 }
 
+///`chip_gzip_plan` over the first `len` bytes of a device-resident buffer of gzip members (WARC records, `cat a.gz b.gz`, what
+///`encode_file_device` writes for gzip): fills the four device arrays for the first `max_members` members -- what
+///`decode_batch_device` takes with `BatchFormat::Zlib` in gzip mode -- and returns the summary of the whole walk (`max_members` 0 counts).
+///Synchronous on `stream`.  There is no host form: finding a member's end is an inflate.
+///
+///# Safety
+///
+///As `decode_batch_device`; `input` must be 4-byte aligned and padded to a multiple of 4 bytes.
+pub unsafe fn gzip_plan_device(input: &crate::buffer::DeviceBuffer, len: usize, max_members: usize, in_off: &mut crate::buffer::DeviceBuffer,
+                               in_len: &mut crate::buffer::DeviceBuffer, out_off: &mut crate::buffer::DeviceBuffer, out_cap: &mut crate::buffer::DeviceBuffer,
+                               stream: *mut core::ffi::c_void) -> Result<sys::chip_gzip_plan_summary, i32> {
+    if len > input.capacity() || in_off.capacity() < 8 * max_members || out_off.capacity() < 8 * max_members || in_len.capacity() < 4 * max_members
+        || out_cap.capacity() < 4 * max_members
+    {
+        return Err(-101);
+    }
+    let mut summary = sys::chip_gzip_plan_summary::default();
+    let rc = sys::chip_gzip_plan(input.as_ptr() as *const _, len as u64, max_members as u64, in_off.as_mut_ptr() as *mut u64, in_len.as_mut_ptr() as *mut u32,
+                                 out_off.as_mut_ptr() as *mut u64, out_cap.as_mut_ptr() as *mut u32, &mut summary, stream);
+    if rc == sys::CHIP_OK { Ok(summary) } else { Err(rc) }
+}
+
 ///`chip_layout_units`: from the `out_size` of `decode_batch_sizes_device` to the `out_off` / `out_cap` of `decode_batch_device`
 ///without a host round trip per unit.  Returns `(total, n_over)`: the bytes to allocate and the units above 4 GiB - 1.
 ///Synchronous on `stream`.

@@ -116,6 +116,27 @@ pub struct chip_zstd_plan_summary {
     pub pad: u32,
 }
 
+///`chip_gzip_plan_summary::status`
+pub const CHIP_GZPLAN_OK: i32 = 0;
+pub const CHIP_GZPLAN_TRUNCATED: i32 = 1;
+pub const CHIP_GZPLAN_BAD_HEADER: i32 = 2;
+pub const CHIP_GZPLAN_TOO_LARGE: i32 = 3;
+pub const CHIP_GZPLAN_BAD_MEMBER: i32 = 4;
+///input bytes a gzip member may take: the limit of a unit's input
+pub const CHIP_GZPLAN_WINDOW: u32 = (1 << 29) - 64;
+
+///what the gzip member walk found: members and decoded bytes of the whole walk, the start of the member where it stopped, why, and
+///the size pass's status of that member when `status` is `CHIP_GZPLAN_BAD_MEMBER`
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct chip_gzip_plan_summary {
+    pub n_members: u64,
+    pub total_out: u64,
+    pub in_used: u64,
+    pub status: i32,
+    pub member_status: i32,
+}
+
 ///`chip_encode_file` flag: the seek table of zstd's seekable format follows the last frame (`CHIP_FMT_ZSTD` only)
 pub const CHIP_W_SEEK_TABLE: u32 = 1;
 ///`chip_file_summary::status`
@@ -235,6 +256,9 @@ extern "C" {
     ///the same answer for a buffer in device memory (device arrays, host summary); synchronous on `stream`
     pub fn chip_zstd_plan(in_base: *const c_void, len: u64, max_frames: u64, in_off: *mut u64, in_len: *mut u32, out_off: *mut u64, out_cap: *mut u32,
                           summary: *mut chip_zstd_plan_summary, stream: *mut c_void) -> c_int;
+    ///the member index of a device-resident buffer of gzip members: the size pass over every candidate start, then the chain from 0
+    pub fn chip_gzip_plan(in_base: *const c_void, len: u64, max_members: u64, in_off: *mut u64, in_len: *mut u32, out_off: *mut u64, out_cap: *mut u32,
+                          summary: *mut chip_gzip_plan_summary, stream: *mut c_void) -> c_int;
     ///from a size pass to a decode on the device: offsets (exclusive sum) and clipped capacities of `out_size`; host `total` / `n_over`
     pub fn chip_layout_units(n: usize, out_size: *const u64, out_off: *mut u64, out_cap: *mut u32, total: *mut u64, n_over: *mut u64,
                              stream: *mut c_void) -> c_int;
