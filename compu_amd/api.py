@@ -70,6 +70,11 @@ class _ReadSummary(C.Structure):
                 ("first_bad", C.c_uint64), ("bad_index", C.c_uint64), ("status", C.c_int32), ("bad_status", C.c_int32)]
 
 
+class _InflateIndexSummary(C.Structure):
+    _fields_ = [("n_points", C.c_uint64), ("out_len", C.c_uint64), ("in_used", C.c_uint64), ("end_bit", C.c_uint64), ("status", C.c_int32),
+                ("wrap", C.c_uint32), ("check", C.c_uint32), ("pad", C.c_uint32)]
+
+
 _lib = None
 
 
@@ -178,6 +183,15 @@ def lib():
     L.chip_select_units.argtypes = [sz, vp, vp, vp, vp, sz, vp, vp, C.c_uint64] + [vp] * 8 + [C.POINTER(_SelectSummary), vp]
     L.chip_read_ranges.restype = C.c_int
     L.chip_read_ranges.argtypes = [C.c_int, sz, vp, vp, vp, vp, vp, sz, vp, vp, vp, C.c_uint64, vp, vp, C.POINTER(_ReadSummary), vp]
+    L.chip_inflate_index_build.restype = C.c_int
+    L.chip_inflate_index_build.argtypes = [C.c_int, vp, C.c_uint64, vp, C.c_uint64, C.c_uint32, C.c_uint64, vp, vp, vp, vp,
+                                           C.POINTER(_InflateIndexSummary), vp]
+    L.chip_inflate_index_units_host.restype = C.c_int
+    L.chip_inflate_index_units_host.argtypes = [C.c_int, C.c_uint64, C.c_uint64, vp, vp, vp, C.c_uint64, vp, vp, vp, vp, vp, C.POINTER(i32),
+                                                C.POINTER(C.c_uint64)]
+    L.chip_inflate_index_read.restype = C.c_int
+    L.chip_inflate_index_read.argtypes = [C.c_int, vp, C.c_uint64, C.c_uint64, vp, vp, vp, vp, C.c_uint64, sz, vp, vp, vp, C.c_uint64, vp, vp,
+                                          C.POINTER(_ReadSummary), vp]
     _lib = L
     return L
 
@@ -1621,3 +1635,163 @@ def gzip_members_read(in_buf, length, ranges, stream=None):
     lo, ln = _ranges_to_device(ranges, in_buf.device)
     out, dst_off, status, rs = read_ranges(ZlibMode.Gzip, in_buf, in_off, in_len, out_off, out_cap, lo, ln, stream=stream)
     return _read_checked("gzip_members_read", out, status, rs), dst_off
+
+
+# ---- one large stream: the checkpoint index (include/compu_hip.h, "one large stream") ------------
+
+INDEX_WINDOW = 32768  # bytes of a window slot
+
+
+class InflateIndexSummary:
+    """chip_inflate_index_summary: n_points of the whole walk; out_len, in_used and status as decode_batch answers them for the
+    unit; wrap 0 raw / 1 zlib / 2 gzip; with status Finished, check = the content's CRC-32 / Adler-32 and end_bit = the bit behind
+    the final block."""
+
+    __slots__ = ("n_points", "out_len", "in_used", "end_bit", "status", "wrap", "check")
+
+    def __init__(self, raw):
+        self.n_points, self.out_len, self.in_used, self.end_bit = int(raw.n_points), int(raw.out_len), int(raw.in_used), int(raw.end_bit)
+        self.status, self.wrap, self.check = int(raw.status), int(raw.wrap), int(raw.check)
+
+    def as_tuple(self):
+        return (self.n_points, self.out_len, self.in_used, self.end_bit, self.status, self.wrap, self.check)
+
+    def __repr__(self):
+        return (f"InflateIndexSummary(n_points={self.n_points}, out_len={self.out_len}, in_used={self.in_used}, end_bit={self.end_bit}, "
+                f"status={self.status}, wrap={self.wrap}, check={self.check:#010x})")
+
+
+class InflateIndex:
+    """The checkpoint index of one stream in device memory: pt_bit / pt_out int64 (read as u64), pt_check int32 (read as u32),
+    windows uint8 (32 768 bytes per point), the stream's length `length`, its decoded length `total_out` and its format (the
+    build's wrap: ZlibMode.Deflate, Zlib or Gzip)."""
+
+    __slots__ = ("fmt", "length", "total_out", "pt_bit", "pt_out", "pt_check", "windows")
+
+    def __init__(self, fmt, length, total_out, pt_bit, pt_out, pt_check, windows):
+        self.fmt, self.length, self.total_out = int(fmt), int(length), int(total_out)
+        self.pt_bit, self.pt_out, self.pt_check, self.windows = pt_bit, pt_out, pt_check, windows
+
+    @property
+    def n_points(self):
+        return self.pt_bit.numel()
+
+
+_WRAP_FMT = (-15, 15, 31)  # the format of a wrap: CHIP_FMT_DEFLATE, CHIP_FMT_ZLIB, CHIP_FMT_GZIP
+
+
+def inflate_index_build(fmt, in_buf, length, out_buf, spacing=0, max_points=None, stream=None):
+    """chip_inflate_index_build: decode the ONE unit in_buf[:length] (uint8 device tensor, 4-byte aligned, padded to a multiple of
+    4) into out_buf and record a point every `spacing` decoded bytes (0 = 1 MiB).  Returns (index, summary): an InflateIndex of the
+    first min(n_points, max_points) points -- max_points None: all of them, sized by the worst case of one point per `spacing`
+    bytes of room, or by a counting pass first where that would be more than 1 GiB of windows -- and the InflateIndexSummary.  The decode's answers are decode_batch's for the same unit and room.
+    Synchronous on `stream`."""
+    import torch
+
+    dev = _check_tensors(((in_buf, torch.uint8), (out_buf, torch.uint8)))
+    step = int(spacing) if spacing else 1 << 20
+    q = lambda t: _dp(t) if t.numel() else None  # noqa: E731
+    raw = _InflateIndexSummary()
+
+    def call(k, pt_bit, pt_out, pt_check, windows):
+        with torch.cuda.device(dev):
+            rc = lib().chip_inflate_index_build(int(fmt), _dp(in_buf), int(length), _dp(out_buf), out_buf.numel(), int(spacing), k, pt_bit, pt_out,
+                                                pt_check, windows, C.byref(raw), _stream_ptr(stream))
+        if rc != 0:
+            raise RuntimeError(f"chip_inflate_index_build failed: {rc}")
+
+    if max_points is not None:
+        k = int(max_points)
+    else:
+        k = out_buf.numel() // step + 1  # a point needs `spacing` new bytes: no walk has more
+        if k * INDEX_WINDOW > 1 << 30:   # small spacings: a first pass counts instead of a gigabyte of window slots
+            call(0, None, None, None, None)
+            k = int(raw.n_points)
+    pt_bit, pt_out = torch.zeros(k, dtype=torch.int64, device=dev), torch.zeros(k, dtype=torch.int64, device=dev)
+    pt_check, windows = torch.zeros(k, dtype=torch.int32, device=dev), torch.empty(k * INDEX_WINDOW, dtype=torch.uint8, device=dev)
+    call(k, q(pt_bit), q(pt_out), q(pt_check), q(windows))
+    summ = InflateIndexSummary(raw)
+    n = min(k, summ.n_points)
+    index = InflateIndex(_WRAP_FMT[summ.wrap] if summ.wrap < 3 else int(fmt), length, summ.out_len, pt_bit[:n], pt_out[:n], pt_check[:n],
+                         windows[: n * INDEX_WINDOW])
+    return index, summ
+
+
+def inflate_index_units_host(fmt, length, pt_bit, pt_out, pt_check, total_out):
+    """chip_inflate_index_units_host over numpy arrays (or sequences): the chunks of an index by host arithmetic.  Returns
+    (in_off u64, in_len u32, out_cap u32, win_len u32, resume u32[n, 6], status ReadStatus, bad_index); on BadLayout the arrays
+    are empty."""
+    import numpy as np
+
+    arr = lambda a, dt: np.ascontiguousarray(a, dtype=dt)  # noqa: E731
+    pt_bit, pt_out, pt_check = arr(pt_bit, np.uint64), arr(pt_out, np.uint64), arr(pt_check, np.uint32)
+    n = int(pt_bit.size)
+    if pt_out.size != n or pt_check.size != n:
+        raise ValueError("the index's arrays must have one length")
+    in_off, in_len, out_cap, win_len = np.zeros(n, np.uint64), np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+    resume = np.zeros((n, 6), np.uint32)
+    p = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None  # noqa: E731
+    status, bad = C.c_int32(0), C.c_uint64(0)
+    rc = lib().chip_inflate_index_units_host(int(fmt), int(length), n, p(pt_bit), p(pt_out), p(pt_check), int(total_out), p(in_off), p(in_len),
+                                             p(out_cap), p(win_len), p(resume), C.byref(status), C.byref(bad))
+    if rc != 0:
+        raise RuntimeError(f"chip_inflate_index_units_host failed: {rc}")
+    if status.value != int(ReadStatus.Ok):
+        n = 0
+    return in_off[:n], in_len[:n], out_cap[:n], win_len[:n], resume[:n], ReadStatus(status.value), int(bad.value)
+
+
+def inflate_index_read(index, in_buf, range_lo, range_len, dst=None, stream=None):
+    """chip_inflate_index_read on device tensors: the bytes of every range (range_lo int64 read as u64, range_len int32 read as
+    u32, in content coordinates) of the stream in_buf[:index.length], end to end in dst.  Only the chunks the ranges touch are
+    decoded, each once, and each is verified against the next point's check value.  dst as in read_ranges.  Returns (dst trimmed
+    to out_len -- None on NeedOutput or BadLayout --, dst_off int64, range_status int32, ReadSummary).  Synchronous on `stream`."""
+    import torch
+
+    pairs = [(in_buf, torch.uint8), (index.pt_bit, torch.int64), (index.pt_out, torch.int64), (index.pt_check, torch.int32),
+             (index.windows, torch.uint8), (range_lo, torch.int64), (range_len, torch.int32)] + ([(dst, torch.uint8)] if dst is not None else [])
+    dev = _check_tensors(pairs)
+    n, m = index.pt_bit.numel(), range_len.numel()
+    if index.pt_out.numel() != n or index.pt_check.numel() != n or index.windows.numel() < n * INDEX_WINDOW or range_lo.numel() != m:
+        raise ValueError("the index's arrays, and the ranges' arrays, must have one length each")
+    q = lambda t: _dp(t) if t is not None and t.numel() else None  # noqa: E731
+    dst_off, status = torch.zeros(m, dtype=torch.int64, device=dev), torch.zeros(m, dtype=torch.int32, device=dev)
+    raw = _ReadSummary()
+    sp = _stream_ptr(stream)
+
+    def call(d):
+        rc = lib().chip_inflate_index_read(index.fmt, _dp(in_buf), index.length, n, q(index.pt_bit), q(index.pt_out), q(index.pt_check),
+                                           q(index.windows), index.total_out, m, q(range_lo), q(range_len), q(d),
+                                           d.numel() if d is not None else 0, q(dst_off), q(status), C.byref(raw), sp)
+        if rc != 0:
+            raise RuntimeError(f"chip_inflate_index_read failed: {rc}")
+
+    with torch.cuda.device(dev):
+        call(dst)
+        if dst is None and raw.status == int(ReadStatus.NeedOutput):
+            dst = torch.empty(int(raw.out_len), dtype=torch.uint8, device=dev)
+            call(dst)
+        elif dst is None:
+            dst = torch.empty(0, dtype=torch.uint8, device=dev)
+    summ = ReadSummary(raw)
+    return (dst[: summ.out_len] if summ.status == ReadStatus.Ok else None), dst_off, status, summ
+
+
+def gzip_index_decode(index, in_buf, stream=None):
+    """The whole content of an indexed stream (gzip, zlib or raw deflate), every chunk on a wave of its own: inflate_index_read of
+    [0, total_out) in pieces of at most 2^31 bytes.  With every chunk good the stream's own CRC-32 / Adler-32 is verified.  Raises
+    ValueError on a broken index layout, RuntimeError with the first bad chunk.  Returns the uint8 tensor.  Waits for the result."""
+    piece = 1 << 31
+    ranges = [(lo, min(piece, index.total_out - lo)) for lo in range(0, index.total_out, piece)]
+    lo, ln = _ranges_to_device(ranges, in_buf.device)
+    out, _, status, rs = inflate_index_read(index, in_buf, lo, ln, stream=stream)
+    return _read_checked("gzip_index_decode", out, status, rs)
+
+
+def gzip_index_read(index, in_buf, ranges, stream=None):
+    """Bytes of an indexed stream without decoding all of it.  `ranges` is a sequence of (lo, len) pairs in decoded coordinates,
+    or a pair of device tensors (int64, int32).  Raises as bgzf_read does.  Returns (the uint8 tensor of the ranges end to end,
+    dst_off int64).  Waits for the result."""
+    lo, ln = _ranges_to_device(ranges, in_buf.device)
+    out, dst_off, status, rs = inflate_index_read(index, in_buf, lo, ln, stream=stream)
+    return _read_checked("gzip_index_read", out, status, rs), dst_off

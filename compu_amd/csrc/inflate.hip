@@ -1455,8 +1455,26 @@ __device__ CHIP_PHASE_FN void decode_block(WaveLds &L, InWin &w, uint32_t &pos, 
 #ifndef CHIP_INFLATE_MEMBERS
 #define CHIP_INFLATE_MEMBERS 0
 #endif
+// CHIP_INFLATE_INDEX (inflate_index.hip, chip_inflate_index_build): the unit loop records the block boundaries that are points of
+// the checkpoint index (the walk of include/compu_hip.h) -- lane 0's stores of (bit, out) into the launch's point list, a count, and
+// the bit behind the final block.  Compiled only there, as the member loop is.
+#ifndef CHIP_INFLATE_INDEX
+#define CHIP_INFLATE_INDEX 0
+#endif
+#if CHIP_INFLATE_INDEX
+struct IndexRec {
+    uint64_t *pt_bit, *pt_out;  // the first max_points points (device arrays of the caller, may be null with max_points == 0)
+    uint64_t max_points;
+    uint32_t spacing;           // >= 1
+    uint32_t *walk;             // [0] the points of the whole walk, [1] the bit behind the final block (0: the unit did not finish),
+                                // [2] the wrapper kind the unit turned out to have
+};
+#define INDEX_PARAM , const IndexRec &ix
+#else
+#define INDEX_PARAM
+#endif
 template <bool SIZES>
-__device__ __attribute__((always_inline)) void inflate_unit(const BatchArgs &a, const uint32_t u, WaveLds &L, uint32_t *scratch, uint64_t *out_size)
+__device__ __attribute__((always_inline)) void inflate_unit(const BatchArgs &a, const uint32_t u, WaveLds &L, uint32_t *scratch, uint64_t *out_size INDEX_PARAM)
 {
     const uint32_t lane = lane_id();
 
@@ -1499,6 +1517,9 @@ __device__ __attribute__((always_inline)) void inflate_unit(const BatchArgs &a, 
     uint32_t ck_bit = 0, ck_opos = 0;  // last block boundary reached (streaming decoder: where the next call resumes)
     bool resumed = false;
     uint32_t run_check = 0, run_cov = 0, out_dropped = 0;  // running trailer check: value, stream bytes covered; bytes dropped in front
+#if CHIP_INFLATE_INDEX
+    uint32_t ix_n = 0, ix_out = 0, ix_end = 0;  // points so far, the last point's output count, the bit behind the final block
+#endif
     if (!SIZES && a.resume) {
         const uint32_t *rs = a.resume + RESUME_WORDS * u;
         const uint32_t r0 = rs[0], r1 = rs[1], r2 = rs[2];
@@ -1534,11 +1555,24 @@ next_member:
     __builtin_amdgcn_s_setprio(2);
     while (status == ST_RUNNING) {
         if (last) {
+#if CHIP_INFLATE_INDEX
+            ix_end = pos - start_bit;
+#endif
             status = CHIP_FINISHED;
             break;
         }
         ck_bit = pos - start_bit;
         ck_opos = opos;
+#if CHIP_INFLATE_INDEX
+        if (ix_n == 0 || opos - ix_out >= ix.spacing) {  // (uniform) this boundary is a point
+            if (lane == 0 && ix_n < ix.max_points) {
+                ix.pt_bit[ix_n] = ck_bit;
+                ix.pt_out[ix_n] = opos;
+            }
+            ix_out = opos;
+            ix_n++;
+        }
+#endif
         win_ensure(L, w, pos);
         if (pos + 3 > end_bit) {
             status = CHIP_NEED_INPUT;
@@ -1824,6 +1858,13 @@ next_member:
         if (status == CHIP_NEED_OUTPUT && used == in_len) status = CHIP_NEED_INPUT;
         else if (status == CHIP_NEED_INPUT && in_len == 0) status = CHIP_NEED_OUTPUT;
     }
+#if CHIP_INFLATE_INDEX
+    if (lane == 0) {
+        ix.walk[0] = ix_n;
+        ix.walk[1] = status == CHIP_FINISHED ? ix_end : 0u;
+        ix.walk[2] = wrap;
+    }
+#endif
     if (lane == 0) {
         if constexpr (SIZES) out_size[u] = osize;
         else a.out_len[u] = opos;
@@ -1873,6 +1914,14 @@ hipError_t enqueue_inflate_members(const BatchArgs &a, uint64_t *out_size, uint3
     else hipLaunchKernelGGL(inflate_members_kernel, dim3(blocks), dim3(64), 0, stream, a, scratch, counter);
     return hipGetLastError();
 }
+#elif CHIP_INFLATE_INDEX
+// chip_inflate_index_build (inflate_index.hip includes this file): ONE wave decodes the one unit and records its points.  A
+// translation unit of its own for the reason inflate_sizes.hip has one.
+__global__ __launch_bounds__(64, CHIP_WAVES_PER_SIMD) void inflate_index_kernel(BatchArgs a, IndexRec ix, uint32_t *scratch)
+{
+    __shared__ WaveLds L;
+    inflate_unit<false>(a, 0, L, scratch, nullptr, ix);
+}
 #elif !defined(CHIP_INFLATE_SIZES_TU)
 // Persistent grid: each wave takes the next unit from *next_unit until the batch is exhausted.
 __global__ __launch_bounds__(64, CHIP_WAVES_PER_SIMD) void inflate_kernel(BatchArgs a, uint32_t *scratch, uint32_t *next_unit)
@@ -1917,7 +1966,7 @@ hipError_t enqueue_inflate_sizes(const BatchArgs &a, uint64_t *out_size, uint32_
 }
 #endif  // CHIP_INFLATE_SIZES_TU
 
-#if !defined(CHIP_INFLATE_SIZES_TU) && !CHIP_INFLATE_MEMBERS
+#if !defined(CHIP_INFLATE_SIZES_TU) && !CHIP_INFLATE_MEMBERS && !CHIP_INFLATE_INDEX
 
 namespace {
 // Token scratch and the unit counter of a launch, and the lists of a routed batch: a launch slot ("Launch slots").

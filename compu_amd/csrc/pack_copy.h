@@ -98,8 +98,8 @@ __global__ __launch_bounds__(64 * PACK_WAVES) void pack_copy_kernel(const uint8_
     }
 }
 
-// only enqueues; total > 0 and total <= the room behind dst_base
-void enqueue_copy(uint64_t n, const uint8_t *src_base, const uint64_t *src_off, const uint32_t *src_len, uint8_t *dst_base, const uint64_t *off,
+// only enqueues; total > 0 and total <= the room behind dst_base  ([[maybe_unused]]: inflate_index.hip takes copy_span only)
+[[maybe_unused]] void enqueue_copy(uint64_t n, const uint8_t *src_base, const uint64_t *src_off, const uint32_t *src_len, uint8_t *dst_base, const uint64_t *off,
                   uint64_t total, hipStream_t stream)
 {
     const uint64_t tiles = (total + ((uintptr_t)dst_base & 15u) + PACK_TILE - 1) / PACK_TILE;

@@ -13,6 +13,7 @@
 //   7. verify   one lane per selected unit: a unit that did not end CHIP_FINISHED with out_len == out_cap is counted, the lowest one
 //               kept; a prefix count of those flags tells each range whether its span holds one
 //   8. copy     the destination-driven copy of pack_copy.h: src = the area, src_off, the counted lengths, dst_off
+// chip_inflate_index_read (sec. 4.16, further down) is the same walk over units that are the chunks of a checkpoint index.
 // Order between the phases comes from kernel boundaries on the stream only.  The atomics are integer sums, maxima and counts: the
 // result does not depend on their order.
 #include <new>
@@ -370,6 +371,197 @@ bool decode_format_ok(int format)
            format == CHIP_FMT_BROTLI || format == CHIP_FMT_DETECT;
 }
 
+
+// ---- reading through the checkpoint index of one large stream --------------------------------------------
+// chip_inflate_index_read is the walk above over units that are the chunks of an index.  Its phases, in stream order:
+//   0. units    one lane per chunk: in_off, in_len, out_cap by index_chunk(); a chunk that offends the layout gets the cap
+//               CHIP_ZPLAN_UNSIZED, so that phase 1 fails at exactly that link (an honest chunk's link to its successor holds by
+//               construction) and nothing else is written
+//   1.-5.       select_locked() over (in_off, in_len, pt_out, out_cap)
+//   6a. stage   one lane per selected chunk: its slot [window | chunk] in the area, the resume words, where its content starts
+//   6b. window  four waves per selected chunk: the window slot of the index goes to the front of the chunk's slot
+//   6c. decode  launch_inflate() with BatchArgs::resume: the chunks are resumed units of inflate_kernel
+//   7. verify   one lane per selected chunk: the link to the next point (or the end of the stream) as the header defines "good"
+//   8. copy     twice pack_copy.h's copy: the chunks' content goes end to end into an image behind the slots (the windows between
+//               them are gone), then the ranges are gathered from the image as chip_read_ranges gathers them
+constexpr uint32_t IX_WINDOW = 32768;
+constexpr uint64_t IX_CAP_MAX = 0xFFFFFFF0ull - IX_WINDOW;
+
+struct IxChunk {
+    uint64_t in_off;
+    uint32_t in_len, out_cap, wl, r0;
+    bool bad;
+};
+// chunk k of the index: the arithmetic of include/compu_hip.h (8 * len does not wrap: len <= 2^61)
+__host__ __device__ __forceinline__ IxChunk index_chunk(const uint64_t *pt_bit, const uint64_t *pt_out, uint64_t n, uint64_t len, uint64_t total_out,
+                                                        uint64_t k)
+{
+    const uint64_t bit = pt_bit[k], o = pt_out[k];
+    const bool more = k + 1 < n;
+    const uint64_t next_bit = more ? pt_bit[k + 1] : 0;
+    const uint64_t end_out = more ? pt_out[k + 1] : total_out, end_in = more ? (next_bit >> 3) + ((next_bit & 7u) ? 1u : 0u) : len;
+    IxChunk c{};
+    c.in_off = (bit >> 3) - (((bit & 7u) == 0 && bit != 0) ? 1u : 0u);
+    c.bad = (k == 0 && o != 0) || bit >= 8 * len || (more && next_bit <= bit) || end_out < o || end_out - o > IX_CAP_MAX || end_in < c.in_off ||
+            end_in - c.in_off > CHIP_GZPLAN_WINDOW;
+    if (c.bad) return c;
+    c.in_len = (uint32_t)(end_in - c.in_off);
+    c.out_cap = (uint32_t)(end_out - o);
+    c.wl = o < IX_WINDOW ? (uint32_t)o : IX_WINDOW;
+    c.r0 = (uint32_t)(bit - 8 * c.in_off);
+    return c;
+}
+__host__ __device__ __forceinline__ void index_resume_words(const IxChunk &c, uint32_t wrap, uint32_t check, uint64_t o, uint32_t *rs)
+{
+    rs[0] = c.r0, rs[1] = c.wl, rs[2] = wrap, rs[3] = check, rs[4] = (uint32_t)o, rs[5] = (uint32_t)(o - c.wl);
+}
+
+__global__ __launch_bounds__(256) void ix_units_kernel(const uint64_t *pt_bit, const uint64_t *pt_out, uint64_t n, uint64_t len, uint64_t total_out,
+                                                       uint64_t *in_off, uint32_t *in_len, uint32_t *out_cap)
+{
+    const uint64_t k = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (k >= n) return;
+    const IxChunk c = index_chunk(pt_bit, pt_out, n, len, total_out, k);
+    in_off[k] = c.bad ? 0 : c.in_off;
+    in_len[k] = c.in_len;
+    out_cap[k] = c.bad ? CHIP_ZPLAN_UNSIZED : c.out_cap;
+}
+
+// selected chunk j's slot is area[sel_out_off[j] + 32768 j, + 32768 + cap): the content starts 32 KiB in, the window ends there
+__global__ __launch_bounds__(256) void ix_stage_kernel(const uint64_t *pt_bit, const uint64_t *pt_out, const uint32_t *pt_check, uint64_t n, uint64_t len,
+                                                       uint64_t total_out, uint32_t wrap, const uint32_t *sel_unit, const uint64_t *sel_out_off,
+                                                       uint64_t n_sel, uint64_t *slot_off, uint32_t *slot_cap, uint64_t *content_off, uint32_t *resume)
+{
+    const uint64_t j = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (j >= n_sel) return;
+    const uint64_t k = sel_unit[j];
+    const IxChunk c = index_chunk(pt_bit, pt_out, n, len, total_out, k);
+    const uint64_t at = sel_out_off[j] + (uint64_t)IX_WINDOW * (j + 1);
+    content_off[j] = at;
+    slot_off[j] = at - c.wl;
+    slot_cap[j] = c.wl + c.out_cap;
+    index_resume_words(c, wrap, pt_check[k], pt_out[k], resume + RESUME_WORDS * j);
+}
+
+__global__ __launch_bounds__(256) void ix_window_kernel(const uint8_t *windows, const uint32_t *sel_unit, const uint64_t *slot_off,
+                                                        const uint64_t *content_off, uint8_t *area)
+{
+    const uint32_t lane = lane_id(), wave = rdfirst(threadIdx.x >> 6);
+    const uint64_t at = rdfirst64(slot_off[blockIdx.x]);
+    const uint32_t wl = (uint32_t)(rdfirst64(content_off[blockIdx.x]) - at);
+    const uint8_t *src = windows + (uint64_t)IX_WINDOW * rdfirst(sel_unit[blockIdx.x]);
+    uint8_t *dst = area + at;
+    for (uint32_t p = wave * PACK_TILE; p < wl; p += 4 * PACK_TILE) copy_span(src + p, dst + p, wl - p < PACK_TILE ? wl - p : PACK_TILE, lane);
+}
+
+// behind the decode: the chunks whose link to the next point (or to the end of the stream) does not hold
+__global__ __launch_bounds__(256) void ix_verify_kernel(const uint64_t *pt_bit, const uint32_t *pt_check, uint64_t n, const uint32_t *sel_unit,
+                                                        const uint64_t *sel_in_off, const uint32_t *slot_cap, const uint32_t *resume,
+                                                        const uint32_t *out_len, const int32_t *status, uint64_t n_sel, Cnt32 *flag, DevSummary *ds)
+{
+    const uint64_t j = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (j >= n_sel) return;
+    const uint64_t k = sel_unit[j];
+    const int32_t st = status[j];
+    const uint32_t *rs = resume + RESUME_WORDS * j;
+    bool good = out_len[j] == slot_cap[j];
+    if (k + 1 < n)
+        good = good && (st == CHIP_NEED_INPUT || st == CHIP_NEED_OUTPUT) && rs[0] == (uint32_t)(pt_bit[k + 1] - 8 * sel_in_off[j]) &&
+               rs[1] == slot_cap[j] && rs[3] == pt_check[k + 1];
+    else good = good && st == CHIP_FINISHED;
+    flag[j] = Cnt32{good ? 0u : 1u};
+    if (good) return;
+    atomicAdd((unsigned long long *)&ds->n_bad, 1ull);
+    atomicMax((unsigned long long *)&ds->bad_key, ((unsigned long long)(uint32_t)~sel_unit[j] << 32) | (uint32_t)st);
+}
+
+// what chip_inflate_index_read hands on: the index and the stream
+struct IndexArgs {
+    uint64_t n, len, total_out;
+    const uint64_t *pt_bit, *pt_out;
+    const uint32_t *pt_check;
+    const uint8_t *windows;
+    uint32_t wrap;
+};
+
+SlotCache<ReadSlot> g_index_read_cache;
+
+// Enqueues everything, waits twice (the sizes, the end).  The caller holds the cache's lock.
+hipError_t index_read_locked(ReadSlot &sl, int format, const IndexArgs &x, SelectArgs g, const uint8_t *in_base, uint8_t *dst_base, uint64_t dst_cap,
+                             chip_read_summary *summary, hipStream_t stream)
+{
+    hipError_t e = sl.summary();
+    if (e != hipSuccess) return e;
+    const uint64_t n = x.n, m = g.m;
+    const Arrays a = carve_arrays(n, m, true);
+    // behind chip_read_ranges' arrays: the chunks as units (16 bytes per chunk), the slots (20), the resume words (24)
+    Carve c;
+    c.at = a.bytes;
+    const size_t o_in_off = c.take(n, 8), o_in_len = c.take(n, 4), o_cap = c.take(n, 4), o_slot_off = c.take(n, 8), o_content = c.take(n, 8);
+    const size_t o_slot_cap = c.take(n, 4), o_resume = c.take(n, 4 * RESUME_WORDS);
+    if ((e = sl.grow(ARRAYS, c.at)) != hipSuccess) return e;
+    uint8_t *b = sl.buf[ARRAYS];
+    uint64_t *u_in_off = (uint64_t *)(b + o_in_off), *slot_off = (uint64_t *)(b + o_slot_off), *content_off = (uint64_t *)(b + o_content);
+    uint32_t *u_in_len = (uint32_t *)(b + o_in_len), *u_cap = (uint32_t *)(b + o_cap), *slot_cap = (uint32_t *)(b + o_slot_cap);
+    uint32_t *resume = (uint32_t *)(b + o_resume);
+    if (n) hipLaunchKernelGGL(ix_units_kernel, grid256(n), dim3(256), 0, stream, x.pt_bit, x.pt_out, n, x.len, x.total_out, u_in_off, u_in_len, u_cap);
+    g.in_off = u_in_off, g.in_len = u_in_len, g.out_off = x.pt_out, g.out_cap = u_cap;
+    g.max_sel = n;
+    g.sel_unit = (uint32_t *)(b + a.s_unit), g.sel_in_off = (uint64_t *)(b + a.s_in_off), g.sel_in_len = (uint32_t *)(b + a.s_in_len);
+    g.sel_out_off = (uint64_t *)(b + a.s_out_off), g.sel_out_cap = (uint32_t *)(b + a.s_cap);
+    g.src_off = nullptr;
+    if ((e = select_locked(sl, a, g, stream)) != hipSuccess) return e;
+    const chip_select_summary s = select_summary(*sl.h_sum);
+    // (the failing link i is the lowest offending chunk: select_summary() says i + 1)
+    *summary = chip_read_summary{0, s.out_len, s.n_outside, 0, 0, s.status == CHIP_READ_BAD_LAYOUT ? s.bad_index - 1 : 0, s.status, 0};
+    if (s.status != CHIP_READ_OK) return hipSuccess;
+    if (s.out_len > dst_cap) {
+        summary->status = CHIP_READ_NEED_OUTPUT;
+        return hipSuccess;
+    }
+    if (s.n_sel == 0) return hipSuccess;
+    if (s.n_sel > 0x7fffffffull) return hipErrorUnknown;
+    // the slots [window | chunk] of the selected chunks, then the image of their content end to end (64 bytes of slack behind each)
+    const size_t image_at = up16((size_t)s.scratch_bytes + (size_t)IX_WINDOW * s.n_sel + 64);
+    if ((e = sl.grow(AREA, image_at + (size_t)s.scratch_bytes + 64)) != hipSuccess) return e;
+    uint8_t *area = sl.buf[AREA], *image = area + image_at;
+    uint32_t *d_out_len = (uint32_t *)(b + a.d_out_len), *d_in_used = (uint32_t *)(b + a.d_in_used);
+    int32_t *d_status = (int32_t *)(b + a.d_status);
+    Cnt32 *flag = (Cnt32 *)(b + a.flag), *flag_excl = (Cnt32 *)(b + a.flag_excl), *flag_part = (Cnt32 *)(b + a.flag_part);
+    hipLaunchKernelGGL(ix_stage_kernel, grid256(s.n_sel), dim3(256), 0, stream, x.pt_bit, x.pt_out, x.pt_check, n, x.len, x.total_out, x.wrap,
+                       (const uint32_t *)g.sel_unit, (const uint64_t *)g.sel_out_off, s.n_sel, slot_off, slot_cap, content_off, resume);
+    hipLaunchKernelGGL(ix_window_kernel, dim3((uint32_t)s.n_sel), dim3(256), 0, stream, x.windows, (const uint32_t *)g.sel_unit,
+                       (const uint64_t *)slot_off, (const uint64_t *)content_off, area);
+    BatchArgs ba{};
+    ba.in_base = in_base, ba.in_off = g.sel_in_off, ba.in_len = g.sel_in_len;
+    ba.out_base = area, ba.out_off = slot_off, ba.out_cap = slot_cap;
+    ba.out_len = d_out_len, ba.in_used = d_in_used, ba.status = d_status;
+    ba.n = (uint32_t)s.n_sel, ba.format = format, ba.resume = resume;
+    if ((e = launch_inflate(ba, stream)) != hipSuccess) return e;
+    hipLaunchKernelGGL(ix_verify_kernel, grid256(s.n_sel), dim3(256), 0, stream, x.pt_bit, x.pt_check, n, (const uint32_t *)g.sel_unit,
+                       (const uint64_t *)g.sel_in_off, (const uint32_t *)slot_cap, (const uint32_t *)resume, (const uint32_t *)d_out_len,
+                       (const int32_t *)d_status, s.n_sel, flag, sl.d_sum);
+    if (g.range_status) {
+        enqueue_scan<Cnt32>(flag, flag_excl, s.n_sel, flag_part, &sl.d_sum->flag_total, stream);
+        hipLaunchKernelGGL(rr_bad_ranges_kernel, grid256(m), dim3(256), 0, stream, (const uint32_t *)(b + a.first), (const uint32_t *)(b + a.last),
+                           (const UnitAcc *)(b + a.acc), (const Cnt32 *)flag, (const Cnt32 *)flag_excl, (const Cnt32 *)flag_part, m, g.range_status);
+    }
+    enqueue_copy(s.n_sel, area, (const uint64_t *)content_off, (const uint32_t *)g.sel_out_cap, image, (const uint64_t *)g.sel_out_off, s.scratch_bytes,
+                 stream);
+    enqueue_copy(m, image, (const uint64_t *)(b + a.src), (const uint32_t *)(b + a.counted), dst_base, (const uint64_t *)(b + a.wide), s.out_len, stream);
+    if ((e = sl.fetch(stream)) != hipSuccess) return e;  // the slot is handed on only with nothing in flight
+    const DevSummary &h = *sl.h_sum;
+    summary->n_units = s.n_sel;
+    summary->n_bad = h.n_bad;
+    if (h.n_bad) {
+        summary->first_bad = (uint32_t)~(uint32_t)(h.bad_key >> 32);
+        summary->bad_status = (int32_t)(uint32_t)h.bad_key;
+    }
+    return hipSuccess;
+}
+
+bool index_format_ok(int format) { return format == CHIP_FMT_DEFLATE || format == CHIP_FMT_ZLIB || format == CHIP_FMT_GZIP; }
+uint32_t index_wrap(int format) { return format == CHIP_FMT_DEFLATE ? 0u : format == CHIP_FMT_ZLIB ? 1u : 2u; }
 }  // namespace
 
 }  // namespace chip
@@ -475,6 +667,52 @@ int chip_read_ranges(int format, size_t n_units, const void *in_base, const uint
     return with_slot(
         g_read_cache, stream,
         [&](ReadSlot &sl, hipStream_t s) { return read_ranges_locked(sl, format, g, (const uint8_t *)in_base, (uint8_t *)dst_base, dst_cap, summary, s); },
+        [&] { *summary = chip_read_summary{0, 0, 0, 0, 0, 0, CHIP_READ_OK, 0}; });
+}
+
+int chip_inflate_index_units_host(int format, uint64_t len, uint64_t n_points, const uint64_t *pt_bit, const uint64_t *pt_out,
+                                  const uint32_t *pt_check, uint64_t total_out, uint64_t *in_off, uint32_t *in_len, uint32_t *out_cap,
+                                  uint32_t *win_len, uint32_t *resume, int32_t *status, uint64_t *bad_index)
+{
+    if (!status || !bad_index || !index_format_ok(format) || n_points > 0xFFFFFFFFull || len > (1ull << 61) ||
+        (n_points && (!pt_bit || !pt_out || !pt_check)))
+        return CHIP_E_INVALID;
+    *status = CHIP_READ_OK;
+    *bad_index = 0;
+    for (uint64_t k = 0; k < n_points; k++) {
+        if (!index_chunk(pt_bit, pt_out, n_points, len, total_out, k).bad) continue;
+        *status = CHIP_READ_BAD_LAYOUT;
+        *bad_index = k;
+        return CHIP_OK;
+    }
+    for (uint64_t k = 0; k < n_points; k++) {
+        const IxChunk c = index_chunk(pt_bit, pt_out, n_points, len, total_out, k);
+        if (in_off) in_off[k] = c.in_off;
+        if (in_len) in_len[k] = c.in_len;
+        if (out_cap) out_cap[k] = c.out_cap;
+        if (win_len) win_len[k] = c.wl;
+        if (resume) index_resume_words(c, index_wrap(format), pt_check[k], pt_out[k], resume + RESUME_WORDS * k);
+    }
+    return CHIP_OK;
+}
+
+int chip_inflate_index_read(int format, const void *in_base, uint64_t len, uint64_t n_points, const uint64_t *pt_bit, const uint64_t *pt_out,
+                            const uint32_t *pt_check, const void *windows, uint64_t total_out, size_t n_ranges, const uint64_t *range_lo,
+                            const uint32_t *range_len, void *dst_base, uint64_t dst_cap, uint64_t *dst_off, int32_t *range_status,
+                            chip_read_summary *summary, void *stream)
+{
+    if (!summary || !index_format_ok(format) || !in_base || ((uintptr_t)in_base & 3u) || len > (1ull << 61) || n_points > 0xFFFFFFFFull ||
+        (uint64_t)n_ranges > 0xFFFFFFFFull || (n_points && (!pt_bit || !pt_out || !pt_check || !windows)) || (n_ranges && (!range_lo || !range_len)) ||
+        (dst_cap && !dst_base))
+        return CHIP_E_INVALID;
+    *summary = chip_read_summary{0, 0, 0, 0, 0, 0, CHIP_READ_OK, 0};
+    if (n_ranges == 0) return CHIP_OK;
+    const IndexArgs x{n_points, len, total_out, pt_bit, pt_out, pt_check, (const uint8_t *)windows, index_wrap(format)};
+    const SelectArgs g{n_points, n_ranges, nullptr, nullptr, nullptr, nullptr, range_lo, range_len,    0,
+                       nullptr,  nullptr,  nullptr, nullptr, nullptr, nullptr, dst_off,  range_status};
+    return with_slot(
+        g_index_read_cache, stream,
+        [&](ReadSlot &sl, hipStream_t s) { return index_read_locked(sl, format, x, g, (const uint8_t *)in_base, (uint8_t *)dst_base, dst_cap, summary, s); },
         [&] { *summary = chip_read_summary{0, 0, 0, 0, 0, 0, CHIP_READ_OK, 0}; });
 }
 

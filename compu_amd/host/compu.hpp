@@ -573,6 +573,33 @@ public:
         if (rc == CHIP_OK && summary.status == CHIP_READ_OK) cursor_ += summary.out_len;
         return rc;
     }
+    // chip_inflate_index_build into this buffer's spare capacity: the ONE gzip / zlib / raw deflate stream held in `in` (its first `len`
+    // bytes) is decoded behind the cursor, which moves by summary.out_len, and a point is recorded every `spacing` decoded bytes (0 = 1 MiB)
+    // into the first max_points entries of the DEVICE arrays pt_bit / pt_out / pt_check / windows (32 768 bytes per point).  The decode's
+    // answers are decode_batch()'s for that unit.  Synchronous on `stream`.
+    int inflate_index_build(int format, const DeviceBuffer &in, uint64_t len, uint32_t spacing, uint64_t max_points, uint64_t *pt_bit,
+                            uint64_t *pt_out, uint32_t *pt_check, void *windows, chip_inflate_index_summary &summary, void *stream = nullptr)
+    {
+        if (len > in.len()) return CHIP_E_INVALID;
+        const size_t room = cap_ - cursor_;
+        const int rc = chip_inflate_index_build(format, in.data(), len, buf_ + cursor_, room < 0xFFFFFFF0u ? room : 0xFFFFFFF0u, spacing, max_points,
+                                                pt_bit, pt_out, pt_check, windows, &summary, stream);
+        if (rc == CHIP_OK) cursor_ += summary.out_len;
+        return rc;
+    }
+    // chip_inflate_index_read into this buffer's spare capacity: read_ranges() over the chunks of an index (the DEVICE arrays of
+    // inflate_index_build, n_points of them; total_out = the build's out_len; format = the build's wrap).  Every touched chunk is decoded
+    // once, on a wave of its own, and verified against the next point's check value.  Synchronous on `stream`.
+    int inflate_index_read(int format, const DeviceBuffer &in, uint64_t len, uint64_t n_points, const uint64_t *pt_bit, const uint64_t *pt_out,
+                           const uint32_t *pt_check, const void *windows, uint64_t total_out, size_t n_ranges, const uint64_t *range_lo,
+                           const uint32_t *range_len, uint64_t *dst_off, int32_t *range_status, chip_read_summary &summary, void *stream = nullptr)
+    {
+        if (len > in.len()) return CHIP_E_INVALID;
+        const int rc = chip_inflate_index_read(format, in.data(), len, n_points, pt_bit, pt_out, pt_check, windows, total_out, n_ranges, range_lo,
+                                               range_len, buf_ + cursor_, cap_ - cursor_, dst_off, range_status, &summary, stream);
+        if (rc == CHIP_OK && summary.status == CHIP_READ_OK) cursor_ += summary.out_len;
+        return rc;
+    }
     // chip_select_units: the index step of read_ranges alone (DEVICE arrays, HOST summary), for a caller that decodes the sub-batch
     // sel_in_off / sel_in_len / sel_out_off / sel_out_cap into summary.scratch_bytes of its own.  max_sel 0 with null sel arrays
     // counts.  Synchronous on `stream`.
@@ -610,6 +637,14 @@ inline int select_units_host(size_t n_units, const uint64_t *in_off, const uint3
 {
     return chip_select_units_host(n_units, in_off, in_len, out_off, out_cap, n_ranges, range_lo, range_len, max_sel, sel_unit, sel_in_off, sel_in_len,
                                   sel_out_off, sel_out_cap, src_off, dst_off, range_status, &summary);
+}
+// chip_inflate_index_units_host: the chunks of a checkpoint index by host arithmetic (no device needed); every output array may be nullptr.
+inline int inflate_index_units_host(int format, uint64_t len, uint64_t n_points, const uint64_t *pt_bit, const uint64_t *pt_out,
+                                    const uint32_t *pt_check, uint64_t total_out, uint64_t *in_off, uint32_t *in_len, uint32_t *out_cap,
+                                    uint32_t *win_len, uint32_t *resume, int32_t &status, uint64_t &bad_index)
+{
+    return chip_inflate_index_units_host(format, len, n_points, pt_bit, pt_out, pt_check, total_out, in_off, in_len, out_cap, win_len, resume, &status,
+                                         &bad_index);
 }
 // chip_zstd_plan_host: the zstd frame walk over host memory (no device needed); the arrays are what chip_decode_batch_host / _multi take.
 inline int zstd_plan_host(const uint8_t *in, uint64_t len, uint64_t max_frames, uint64_t *in_off, uint32_t *in_len, uint64_t *out_off,

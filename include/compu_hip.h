@@ -508,8 +508,9 @@ int chip_layout_units(size_t n, const uint64_t *out_size, uint64_t *out_off, uin
  *   - 1f 8b 07.  CHIP_F_MEMBERS starts a member at any 1f 8b and answers -3 for 1f 8b 07; the plan answers BAD_HEADER there, and
  *     for a reserved FLG bit.
  *   - No host form.  There is no chip_gzip_plan_host: this library has no CPU inflate, and finding a member's end is an inflate.
- *   - One wave per member.  A file that is ONE huge member still runs on one wave, and a member of more than CHIP_GZPLAN_WINDOW
- *     input bytes or more than 2^32 - 2 decoded bytes is TOO_LARGE.  This is for files of many members.
+ *   - One wave per member.  A file that is ONE huge member still runs on one wave here, and a member of more than CHIP_GZPLAN_WINDOW
+ *     input bytes or more than 2^32 - 2 decoded bytes is TOO_LARGE.  This is for files of many members; a file of one large member
+ *     is read more than once through its checkpoint index (chip_inflate_index_build, below).
  * No reference counterpart: compu has no container formats.
  */
 enum { CHIP_GZPLAN_OK = 0, CHIP_GZPLAN_TRUNCATED = 1, CHIP_GZPLAN_BAD_HEADER = 2, CHIP_GZPLAN_TOO_LARGE = 3, CHIP_GZPLAN_BAD_MEMBER = 4 };
@@ -748,6 +749,95 @@ typedef struct {
 int chip_read_ranges(int format, size_t n_units, const void *in_base, const uint64_t *in_off, const uint32_t *in_len, const uint64_t *out_off,
                      const uint32_t *out_cap, size_t n_ranges, const uint64_t *range_lo, const uint32_t *range_len, void *dst_base,
                      uint64_t dst_cap, uint64_t *dst_off, int32_t *range_status, chip_read_summary *summary, void *stream);
+
+/* ---- one large stream: the checkpoint index (additive API) ------------------ */
+
+/*
+ * The commonest compressed file is ONE gzip member, or one zlib or raw deflate stream, and a stream is decoded by one wave from its
+ * first bit to its last.  The answer of zran.c, indexed_gzip and `bgzip -r`: decode once and keep a checkpoint every so many bytes
+ * -- the bit position of a block boundary and the 32 KiB of content in front of it.  Every stretch between two checkpoints is then
+ * an independent unit: a second read of the file is a batch, and bytes [lo, lo + n) cost the chunks they touch.
+ *
+ * chip_inflate_index_build IS a decode.  in_base[0 .. len) is one unit (chip_decode_batch's alignment and padding rules), `format`
+ * CHIP_FMT_DEFLATE, CHIP_FMT_ZLIB, CHIP_FMT_GZIP or CHIP_FMT_AUTO, out_base[0 .. out_cap) its room.  The bytes written to
+ * out_base and summary->out_len, in_used and status are exactly what chip_decode_batch(format, 1, ..) answers for the same unit and
+ * room (flags 0): CHIP_NEED_OUTPUT, CHIP_NEED_INPUT, CHIP_NEED_DICT and the negative codes alike.  wrap = 0 raw, 1 zlib, 2 gzip.
+ * With status CHIP_FINISHED, check = the CRC-32 (gzip) / Adler-32 (zlib) of the whole content (0 for raw) and end_bit = the bit
+ * behind the final block's end-of-block code; else both are 0.
+ * The points are DEFINED by this walk.  The decoder reaches the boundaries of blocks b_0, b_1, .. each at the top of its block
+ * loop; s_j = the bit offset of block j's header counted from in_base byte 0, o_j = the decoded bytes in front of block j.
+ *   point 0 = (s_0, 0)
+ *   boundary j >= 1 is a point if and only if o_j - o_(the last point) >= spacing
+ * spacing == 0 means 1 MiB (zran's convention); any spacing >= 1 is allowed, so a boundary with no new output is never a point.
+ * Boundaries reached before the room or the input ran out count.  A unit whose wrapper is refused has n_points = 0.
+ * n_points counts the WHOLE walk; pt_bit, pt_out, pt_check and windows receive the first min(n_points, max_points) points and
+ * nothing behind them is written: max_points = 0 with null arrays is the plain decode with a count.  A truncated index is still a
+ * valid index, its last chunk is just long.  Per point k:
+ *   pt_bit[k]   = s_j           pt_out[k] = o_j
+ *   pt_check[k] = the CRC-32 (gzip) / Adler-32 (zlib) of content[0 .. pt_out[k]), 0 for raw deflate
+ *   windows + 32768 * k: the first wl_k = min(32768, pt_out[k]) bytes are content[pt_out[k] - wl_k .. pt_out[k]); the rest of the
+ *   slot is not written
+ * SYNCHRONOUS on `stream` (it waits for the point count, then for the summary).  summary is a HOST pointer, everything else DEVICE
+ * memory.  CHIP_E_INVALID, before the device is looked for: summary, in_base or out_base NULL; in_base not 4-byte aligned; a format
+ * other than the four; len > CHIP_GZPLAN_WINDOW; out_cap > 2^32 - 16; a NULL array with max_points > 0.  Scratch per (device,
+ * stream), a launch slot of its own, released by chip_trim(): the token rows of one wave (60 KiB).  The calling thread's current
+ * device is left as it was.  The first pass stays one wave: this call costs what chip_decode_batch costs for the unit, plus one
+ * more read of the output for the checks.
+ */
+typedef struct {
+    uint64_t n_points, out_len, in_used, end_bit;
+    int32_t status;
+    uint32_t wrap, check, pad;
+} chip_inflate_index_summary;
+int chip_inflate_index_build(int format, const void *in_base, uint64_t len, void *out_base, uint64_t out_cap, uint32_t spacing,
+                             uint64_t max_points, uint64_t *pt_bit, uint64_t *pt_out, uint32_t *pt_check, void *windows,
+                             chip_inflate_index_summary *summary, void *stream);
+
+/*
+ * The chunks of an index, on HOST arrays: pure arithmetic, no device.  `format` is CHIP_FMT_DEFLATE, CHIP_FMT_ZLIB or
+ * CHIP_FMT_GZIP (the build's wrap 0, 1, 2).  Chunk k runs from point k to point k + 1, the last one to the end of the stream:
+ *   end_out = k + 1 < n_points ? pt_out[k + 1] : total_out          out_cap[k] = end_out - pt_out[k]
+ *   end_in  = k + 1 < n_points ? ceil(pt_bit[k + 1] / 8) : len
+ *   in_off[k] = pt_bit[k] >> 3, one byte less when pt_bit[k] is a multiple of 8 and not 0;   in_len[k] = end_in - in_off[k]
+ *   win_len[k] = wl_k = min(32768, pt_out[k])
+ *   resume[6 k ..] = { pt_bit[k] - 8 * in_off[k], wl_k, wrap, pt_check[k], pt_out[k], pt_out[k] - wl_k }     (low 32 bits)
+ * The inflate kernel reads resume word 0 == 0 as "from the start", hence the byte in front of a byte-aligned point; bit 0, point 0
+ * of a raw stream, IS the start.  The smallest block (a fixed block of only its end-of-block code) is 10 bits and at most 7 bits
+ * trail the next boundary inside a chunk's input: a chunk cannot reach a boundary behind its own end.
+ * Layout check: chunk k OFFENDS when (k == 0 and pt_out[0] != 0), or pt_bit[k] >= 8 * len, or k + 1 < n_points and pt_bit[k + 1] <=
+ * pt_bit[k], or end_out < pt_out[k], or out_cap[k] > 2^32 - 16 - 32768, or in_len[k] > CHIP_GZPLAN_WINDOW.  Any offender:
+ * *status = CHIP_READ_BAD_LAYOUT, *bad_index = the lowest such k, and no array is written.  Else *status = CHIP_READ_OK, *bad_index
+ * = 0.  Each of the five arrays may be NULL (not wanted).  CHIP_E_INVALID: status or bad_index NULL, a point array NULL with
+ * n_points > 0, another format, n_points > 2^32 - 1.
+ */
+int chip_inflate_index_units_host(int format, uint64_t len, uint64_t n_points, const uint64_t *pt_bit, const uint64_t *pt_out,
+                                  const uint32_t *pt_check, uint64_t total_out, uint64_t *in_off, uint32_t *in_len, uint32_t *out_cap,
+                                  uint32_t *win_len, uint32_t *resume, int32_t *status, uint64_t *bad_index);
+
+/*
+ * chip_read_ranges through an index: the units are the chunks above (out_off = pt_out), the arrays of the index and `windows` are
+ * DEVICE memory as the build left them, in_base[0 .. len) is the stream and total_out its decoded length (the build's out_len).
+ * n_ranges == 0: CHIP_OK, an all-zero summary.  Layout check as above: status = CHIP_READ_BAD_LAYOUT, bad_index = the lowest
+ * offending k, nothing is decoded or written.  Selection, dst_off, CHIP_RANGE_OUTSIDE, CHIP_READ_NEED_OUTPUT and the write rules
+ * of dst_base are exactly chip_read_ranges' walk over those units.
+ * Every selected chunk is decoded once, as a RESUMED unit of the batch decoder, into a scratch slot [window | chunk].  A chunk that
+ * is not the last is GOOD if and only if its run ended CHIP_NEED_INPUT or CHIP_NEED_OUTPUT at the boundary pt_bit[k + 1] with
+ * exactly the chunk's output and a running check equal to pt_check[k + 1]; the last chunk if and only if it ended CHIP_FINISHED
+ * with exactly its output (the kernel has then compared the trailer's check, and gzip's ISIZE, itself).  By induction over these
+ * links a read of [0, total_out) with n_bad == 0 has verified the stream's own CRC-32 / Adler-32, whether or not the index is
+ * trusted.  Bad chunks are reported as chip_read_ranges reports bad units: n_bad, first_bad (the chunk's k), bad_status (its decode
+ * status) and CHIP_RANGE_BAD_UNIT for the ranges whose span holds one; every other range has its bytes.
+ * SYNCHRONOUS on `stream`.  CHIP_E_INVALID, before the device is looked for: summary NULL; in_base NULL or not 4-byte aligned; a
+ * format other than the three (CHIP_FMT_AUTO too: the build's wrap says which); len > 2^61; a point array or windows NULL with
+ * n_points > 0; range_lo or range_len NULL with n_ranges > 0; dst_base NULL with dst_cap > 0; n_points or n_ranges above 2^32 - 1.
+ * Scratch per (device, stream), a launch slot of its own: 132 bytes per chunk, 28 per range, and for the selection twice its
+ * content plus 32 KiB per chunk (the slots, and the image the ranges are gathered from).  The calling thread's current device is
+ * left as it was.  No wave waits for another: the chunks are independent units.
+ */
+int chip_inflate_index_read(int format, const void *in_base, uint64_t len, uint64_t n_points, const uint64_t *pt_bit,
+                            const uint64_t *pt_out, const uint32_t *pt_check, const void *windows, uint64_t total_out, size_t n_ranges,
+                            const uint64_t *range_lo, const uint32_t *range_len, void *dst_base, uint64_t dst_cap, uint64_t *dst_off,
+                            int32_t *range_status, chip_read_summary *summary, void *stream);
 
 /* ---- zstd encoder: encoder::Interface::zstd, src/encoder/zstd.rs ------------------------------------------------------------ */
 

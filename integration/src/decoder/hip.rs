@@ -536,3 +536,75 @@ pub unsafe fn read_ranges_device(format: BatchFormat, input: &crate::buffer::Dev
                                    opt(range_status) as *mut i32, &mut summary, stream);
     if rc == sys::CHIP_OK { Ok(summary) } else { Err(rc) }
 }
+
+///The device arrays of a checkpoint index: `n` points, `pt_bit` / `pt_out` u64 and `pt_check` u32 entries, `windows` 32 768 bytes
+///per point.
+pub struct IndexArrays<'a> {
+    pub n: usize,
+    pub pt_bit: &'a crate::buffer::DeviceBuffer,
+    pub pt_out: &'a crate::buffer::DeviceBuffer,
+    pub pt_check: &'a crate::buffer::DeviceBuffer,
+    pub windows: &'a crate::buffer::DeviceBuffer,
+}
+
+impl IndexArrays<'_> {
+    fn fits(&self) -> bool {
+        self.pt_bit.capacity() >= 8 * self.n && self.pt_out.capacity() >= 8 * self.n && self.pt_check.capacity() >= 4 * self.n
+            && self.windows.capacity() >= sys::CHIP_INDEX_WINDOW * self.n
+    }
+}
+
+///`chip_inflate_index_build`: decodes the ONE gzip / zlib / raw deflate stream in the first `len` bytes of `input` into `output` --
+///the answers are `decode_batch_device`'s for that unit -- and records a point every `spacing` decoded bytes (0 = 1 MiB) into the
+///first `max_points` entries of the four arrays (`max_points` 0 counts).  Synchronous on `stream`.  No counterpart in this crate.
+///
+///# Safety
+///
+///As `decode_batch_device`; `input` must be 4-byte aligned and padded to a multiple of 4 bytes.
+#[allow(clippy::too_many_arguments)]
+pub unsafe fn inflate_index_build_device(mode: ZlibMode, input: &crate::buffer::DeviceBuffer, len: usize,
+                                         output: &mut crate::buffer::DeviceBuffer, spacing: u32, max_points: usize,
+                                         pt_bit: &mut crate::buffer::DeviceBuffer, pt_out: &mut crate::buffer::DeviceBuffer,
+                                         pt_check: &mut crate::buffer::DeviceBuffer, windows: &mut crate::buffer::DeviceBuffer,
+                                         stream: *mut core::ffi::c_void) -> Result<sys::chip_inflate_index_summary, i32> {
+    if len > input.capacity() || pt_bit.capacity() < 8 * max_points || pt_out.capacity() < 8 * max_points || pt_check.capacity() < 4 * max_points
+        || windows.capacity() < sys::CHIP_INDEX_WINDOW * max_points
+    {
+        return Err(-101);
+    }
+    let mut summary = sys::chip_inflate_index_summary::default();
+    let rc = sys::chip_inflate_index_build(BatchFormat::Zlib(mode).tag(), input.as_ptr() as *const _, len as u64, output.as_mut_ptr() as *mut _,
+                                           output.capacity() as u64, spacing, max_points as u64, pt_bit.as_mut_ptr() as *mut u64,
+                                           pt_out.as_mut_ptr() as *mut u64, pt_check.as_mut_ptr() as *mut u32, windows.as_mut_ptr() as *mut _,
+                                           &mut summary, stream);
+    if rc == sys::CHIP_OK { Ok(summary) } else { Err(rc) }
+}
+
+///`chip_inflate_index_read`: the bytes of `n_ranges` ranges of an indexed stream's content, end to end in `dst`; only the chunks
+///the ranges touch are decoded, each once and on a wave of its own, and each is verified against the next point's check value.
+///`mode` is the build's `wrap` (Deflate, Zlib or Gzip; not Auto), `total_out` its `out_len`.  Synchronous on `stream`.
+///
+///# Safety
+///
+///As `read_ranges_device`.
+#[allow(clippy::too_many_arguments)]
+pub unsafe fn inflate_index_read_device(mode: ZlibMode, input: &crate::buffer::DeviceBuffer, len: usize, index: &IndexArrays,
+                                        total_out: u64, n_ranges: usize, range_lo: &crate::buffer::DeviceBuffer,
+                                        range_len: &crate::buffer::DeviceBuffer, dst: &mut crate::buffer::DeviceBuffer,
+                                        dst_off: Option<&mut crate::buffer::DeviceBuffer>, range_status: Option<&mut crate::buffer::DeviceBuffer>,
+                                        stream: *mut core::ffi::c_void) -> Result<sys::chip_read_summary, i32> {
+    let small = |b: &Option<&mut crate::buffer::DeviceBuffer>, each: usize| b.as_ref().map_or(false, |b| b.capacity() < each * n_ranges);
+    if len > input.capacity() || !index.fits() || range_lo.capacity() < 8 * n_ranges || range_len.capacity() < 4 * n_ranges || small(&dst_off, 8)
+        || small(&range_status, 4)
+    {
+        return Err(-101);
+    }
+    let opt = |b: Option<&mut crate::buffer::DeviceBuffer>| b.map_or(ptr::null_mut(), |b| b.as_mut_ptr());
+    let mut summary = sys::chip_read_summary::default();
+    let rc = sys::chip_inflate_index_read(BatchFormat::Zlib(mode).tag(), input.as_ptr() as *const _, len as u64, index.n as u64,
+                                          index.pt_bit.as_ptr() as *const u64, index.pt_out.as_ptr() as *const u64, index.pt_check.as_ptr() as *const u32,
+                                          index.windows.as_ptr() as *const _, total_out, n_ranges, range_lo.as_ptr() as *const u64,
+                                          range_len.as_ptr() as *const u32, dst.as_mut_ptr() as *mut _, dst.capacity() as u64, opt(dst_off) as *mut u64,
+                                          opt(range_status) as *mut i32, &mut summary, stream);
+    if rc == sys::CHIP_OK { Ok(summary) } else { Err(rc) }
+}

@@ -193,6 +193,24 @@ pub struct chip_read_summary {
     pub bad_status: i32,
 }
 
+///what `chip_inflate_index_build` found: points of the whole walk; `out_len`, `in_used`, `status` as `chip_decode_batch` answers
+///them for the unit; `wrap` 0 raw / 1 zlib / 2 gzip; with `CHIP_FINISHED`, `check` the content's CRC-32 / Adler-32 and `end_bit`
+///the bit behind the final block
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct chip_inflate_index_summary {
+    pub n_points: u64,
+    pub out_len: u64,
+    pub in_used: u64,
+    pub end_bit: u64,
+    pub status: i32,
+    pub wrap: u32,
+    pub check: u32,
+    pub pad: u32,
+}
+///bytes of a window slot of the checkpoint index
+pub const CHIP_INDEX_WINDOW: usize = 32768;
+
 pub type chip_malloc_fn = unsafe extern "C" fn(opaque: *mut c_void, size: usize) -> *mut c_void;
 pub type chip_free_fn = unsafe extern "C" fn(opaque: *mut c_void, ptr: *mut c_void);
 
@@ -308,4 +326,21 @@ extern "C" {
     pub fn chip_read_ranges(format: c_int, n_units: usize, in_base: *const c_void, in_off: *const u64, in_len: *const u32, out_off: *const u64,
                             out_cap: *const u32, n_ranges: usize, range_lo: *const u64, range_len: *const u32, dst_base: *mut c_void, dst_cap: u64,
                             dst_off: *mut u64, range_status: *mut i32, summary: *mut chip_read_summary, stream: *mut c_void) -> c_int;
+
+    // ---- one large stream: the checkpoint index of a gzip / zlib / raw deflate stream (no reference counterpart)
+    ///decode the one unit and record a point every `spacing` decoded bytes (0 = 1 MiB): device buffers and arrays, host summary;
+    ///`max_points` 0 with null arrays is the plain decode with a count; synchronous on `stream`
+    pub fn chip_inflate_index_build(format: c_int, in_base: *const c_void, len: u64, out_base: *mut c_void, out_cap: u64, spacing: u32, max_points: u64,
+                                    pt_bit: *mut u64, pt_out: *mut u64, pt_check: *mut u32, windows: *mut c_void,
+                                    summary: *mut chip_inflate_index_summary, stream: *mut c_void) -> c_int;
+    ///the chunks of an index on host memory: pure host arithmetic, no device needed; every output array may be null
+    pub fn chip_inflate_index_units_host(format: c_int, len: u64, n_points: u64, pt_bit: *const u64, pt_out: *const u64, pt_check: *const u32,
+                                         total_out: u64, in_off: *mut u64, in_len: *mut u32, out_cap: *mut u32, win_len: *mut u32, resume: *mut u32,
+                                         status: *mut i32, bad_index: *mut u64) -> c_int;
+    ///`chip_read_ranges` over the chunks of an index: each touched chunk is decoded once as a resumed unit and verified against
+    ///the next point's check value; synchronous on `stream`
+    pub fn chip_inflate_index_read(format: c_int, in_base: *const c_void, len: u64, n_points: u64, pt_bit: *const u64, pt_out: *const u64,
+                                   pt_check: *const u32, windows: *const c_void, total_out: u64, n_ranges: usize, range_lo: *const u64,
+                                   range_len: *const u32, dst_base: *mut c_void, dst_cap: u64, dst_off: *mut u64, range_status: *mut i32,
+                                   summary: *mut chip_read_summary, stream: *mut c_void) -> c_int;
 }
