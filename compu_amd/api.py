@@ -1135,6 +1135,37 @@ def _plan_device(fn, raw_cls, wrap, count_field, in_buf, length, stream, max_uni
     return in_off[:k], in_len[:k], out_off[:k], out_cap[:k], wrap(raw)
 
 
+def _whole_plan(plan, ok, refusal, in_buf, length, stream):
+    """plan(in_buf, length) of a whole file: its five results, or ValueError(`refusal` and the summary) when the status is not `ok`."""
+    planned = plan(in_buf, length, stream=stream)
+    if planned[4].status != ok:
+        raise ValueError(f"{refusal}: {planned[4]!r}")
+    return planned
+
+
+def _decode_planned(fmt, noun, in_buf, in_off, in_len, out_off, out_cap, total, stream):
+    """decode_batch of a planned batch into a new tensor of max(total, 4) bytes, trimmed to `total`.  RuntimeError names the first
+    `noun` (a unit of the plan) that did not end Finished with out_len == out_cap."""
+    import torch
+
+    out = torch.empty(max(total, 4), dtype=torch.uint8, device=in_buf.device)
+    if in_off.numel():
+        out_len, _, status = decode_batch(fmt, in_buf, in_off, in_len, out, out_off, out_cap, stream=stream)
+        bad = ((status != int(DecodeStatus.Finished)) | (out_len != out_cap)).nonzero()
+        if bad.numel():
+            i = int(bad[0])
+            raise RuntimeError(f"{noun} {i} did not decode: status {int(status[i])}, {int(out_len[i])} of {int(out_cap[i])} bytes")
+    return out[:total]
+
+
+def _plan_read(what, plan, ok, refusal, fmt, in_buf, length, ranges, stream):
+    """What bgzf_read, zstd_frames_read and gzip_members_read do: the whole file's plan, read_ranges over it, _read_checked."""
+    in_off, in_len, out_off, out_cap, _ = _whole_plan(plan, ok, refusal, in_buf, length, stream)
+    lo, ln = _ranges_to_device(ranges, in_buf.device)
+    out, dst_off, status, rs = read_ranges(fmt, in_buf, in_off, in_len, out_off, out_cap, lo, ln, stream=stream)
+    return _read_checked(what, out, status, rs), dst_off
+
+
 def bgzf_plan_host(data, max_blocks=None):
     """chip_bgzf_plan_host over bytes / a uint8 numpy array in host memory: (in_off u64, in_len u32, out_off u64, out_cap u32,
     summary) of the first min(n_blocks, max_blocks) blocks (None = all of them: one call to count, one to fill)."""
@@ -1153,19 +1184,8 @@ def bgzf_decode(in_buf, length, stream=None):
     """Decode a whole BGZF buffer on the device: plan, allocate total_out bytes, decode_batch(ZlibMode.Gzip).  Raises ValueError
     when the file is no whole BGZF file (the summary says where) and RuntimeError with the first bad block's index and status
     when a block does not decode to its ISIZE.  Returns the uint8 output tensor.  Waits for the decode."""
-    import torch
-
-    in_off, in_len, out_off, out_cap, summ = bgzf_plan(in_buf, length, stream=stream)
-    if summ.status != BgzfStatus.Ok:
-        raise ValueError(f"not a whole BGZF file: {summ!r}")
-    out = torch.empty(max(summ.total_out, 4), dtype=torch.uint8, device=in_buf.device)
-    if summ.n_blocks:
-        out_len, _, status = decode_batch(ZlibMode.Gzip, in_buf, in_off, in_len, out, out_off, out_cap, stream=stream)
-        bad = ((status != int(DecodeStatus.Finished)) | (out_len != out_cap)).nonzero()
-        if bad.numel():
-            i = int(bad[0])
-            raise RuntimeError(f"BGZF block {i} did not decode: status {int(status[i])}, {int(out_len[i])} of {int(out_cap[i])} bytes")
-    return out[: summ.total_out]
+    in_off, in_len, out_off, out_cap, summ = _whole_plan(bgzf_plan, BgzfStatus.Ok, "not a whole BGZF file", in_buf, length, stream)
+    return _decode_planned(ZlibMode.Gzip, "BGZF block", in_buf, in_off, in_len, out_off, out_cap, summ.total_out, stream)
 
 
 # ---- zstd frames: from a file to a batch (include/compu_hip.h, "zstd frames") -------------------
@@ -1236,25 +1256,15 @@ def zstd_frames_decode(in_buf, length, stream=None):
     no whole series of frames (the summary says where) or a frame decodes to more than a unit can hold, and RuntimeError with
     the first bad frame's index and status when a frame does not decode to its size.  Returns (the uint8 output tensor,
     (in_off, in_len, out_off, out_cap) as used for the decode, summary).  Waits for the decode."""
-    import torch
-
-    in_off, in_len, out_off, out_cap, summ = zstd_plan(in_buf, length, stream=stream)
-    if summ.status != ZstdPlanStatus.Ok:
-        raise ValueError(f"not a whole series of zstd frames: {summ!r}")
+    in_off, in_len, out_off, out_cap, summ = _whole_plan(zstd_plan, ZstdPlanStatus.Ok, "not a whole series of zstd frames", in_buf, length, stream)
     total = summ.total_out
     if summ.n_unsized:
         out_size, _, _ = decode_batch_sizes(FMT_ZSTD, in_buf, in_off, in_len, stream=stream)
         out_off, out_cap, total, n_over = layout_units(out_size, stream=stream)
         if n_over:
             raise ValueError(f"{n_over} frames decode to more than 4 GiB - 1: {summ!r}")
-    out = torch.empty(max(total, 4), dtype=torch.uint8, device=in_buf.device)
-    if summ.n_frames:
-        out_len, _, status = decode_batch(FMT_ZSTD, in_buf, in_off, in_len, out, out_off, out_cap, stream=stream)
-        bad = ((status != int(DecodeStatus.Finished)) | (out_len != out_cap)).nonzero()
-        if bad.numel():
-            i = int(bad[0])
-            raise RuntimeError(f"zstd frame {i} did not decode: status {int(status[i])}, {int(out_len[i])} of {int(out_cap[i])} bytes")
-    return out[:total], (in_off, in_len, out_off, out_cap), summ
+    out = _decode_planned(FMT_ZSTD, "zstd frame", in_buf, in_off, in_len, out_off, out_cap, total, stream)
+    return out, (in_off, in_len, out_off, out_cap), summ
 
 
 # ---- gzip members: from a file to a batch (include/compu_hip.h, "gzip members") -----------------
@@ -1302,19 +1312,9 @@ def gzip_members_decode(in_buf, length, stream=None):
     RuntimeError with the first bad member's index and status when a member does not decode to its size (a wrong CRC-32: the
     plan does not see it).  Returns (the uint8 output tensor, (in_off, in_len, out_off, out_cap), summary).  Waits for the
     decode."""
-    import torch
-
-    in_off, in_len, out_off, out_cap, summ = gzip_plan(in_buf, length, stream=stream)
-    if summ.status != GzipPlanStatus.Ok:
-        raise ValueError(f"not a whole series of gzip members: {summ!r}")
-    out = torch.empty(max(summ.total_out, 4), dtype=torch.uint8, device=in_buf.device)
-    if summ.n_members:
-        out_len, _, status = decode_batch(ZlibMode.Gzip, in_buf, in_off, in_len, out, out_off, out_cap, stream=stream)
-        bad = ((status != int(DecodeStatus.Finished)) | (out_len != out_cap)).nonzero()
-        if bad.numel():
-            i = int(bad[0])
-            raise RuntimeError(f"gzip member {i} did not decode: status {int(status[i])}, {int(out_len[i])} of {int(out_cap[i])} bytes")
-    return out[: summ.total_out], (in_off, in_len, out_off, out_cap), summ
+    in_off, in_len, out_off, out_cap, summ = _whole_plan(gzip_plan, GzipPlanStatus.Ok, "not a whole series of gzip members", in_buf, length, stream)
+    out = _decode_planned(ZlibMode.Gzip, "gzip member", in_buf, in_off, in_len, out_off, out_cap, summ.total_out, stream)
+    return out, (in_off, in_len, out_off, out_cap), summ
 
 
 # ---- writing files: from a batch to a file (include/compu_hip.h, "writing files") ---------------
@@ -1553,6 +1553,41 @@ def select_units(in_off, in_len, out_off, out_cap, range_lo, range_len, stream=N
     return sel_unit[:k], sel_in_off[:k], sel_in_len[:k], sel_out_off[:k], sel_out_cap[:k], src_off[:m], dst_off[:m], status[:m], summ
 
 
+def _dp_or_none(t):
+    return _dp(t) if t is not None and t.numel() else None
+
+
+def _read_call(name, pairs, mismatch, m, dst, stream, call):
+    """What read_ranges and inflate_index_read share.  `pairs` (and dst) go through _check_tensors, `mismatch` (the message, when the
+    caller's arrays do not fit each other) raises ValueError; dst_off and the status of the m ranges are allocated; `call` makes
+    the C call, given its last six arguments (dst, its size, dst_off, range_status, summary, stream), once, or with dst None twice:
+    a first call with no room sizes dst.  Returns what the two return."""
+    import torch
+
+    dev = _check_tensors(pairs + ([(dst, torch.uint8)] if dst is not None else []))
+    if mismatch:
+        raise ValueError(mismatch)
+    q = _dp_or_none
+    dst_off, status = torch.zeros(m, dtype=torch.int64, device=dev), torch.zeros(m, dtype=torch.int32, device=dev)
+    raw = _ReadSummary()
+    sp = _stream_ptr(stream)
+
+    def run(d):
+        rc = call(q(d), d.numel() if d is not None else 0, q(dst_off), q(status), C.byref(raw), sp)
+        if rc != 0:
+            raise RuntimeError(f"{name} failed: {rc}")
+
+    with torch.cuda.device(dev):
+        run(dst)
+        if dst is None and raw.status == int(ReadStatus.NeedOutput):
+            dst = torch.empty(int(raw.out_len), dtype=torch.uint8, device=dev)
+            run(dst)
+        elif dst is None:
+            dst = torch.empty(0, dtype=torch.uint8, device=dev)
+    summ = ReadSummary(raw)
+    return (dst[: summ.out_len] if summ.status == ReadStatus.Ok else None), dst_off, status, summ
+
+
 def read_ranges(fmt, in_buf, in_off, in_len, out_off, out_cap, range_lo, range_len, dst=None, stream=None):
     """chip_read_ranges on device tensors: the bytes of every range (range_lo int64 read as u64, range_len int32 read as u32, in
     the coordinates of out_off) of the plan (in_off, in_len, out_off, out_cap) over in_buf, end to end in dst.  Only the units
@@ -1563,31 +1598,13 @@ def read_ranges(fmt, in_buf, in_off, in_len, out_off, out_cap, range_lo, range_l
     import torch
 
     pairs = [(in_buf, torch.uint8), (in_off, torch.int64), (in_len, torch.int32), (out_off, torch.int64), (out_cap, torch.int32),
-             (range_lo, torch.int64), (range_len, torch.int32)] + ([(dst, torch.uint8)] if dst is not None else [])
-    dev = _check_tensors(pairs)
+             (range_lo, torch.int64), (range_len, torch.int32)]
     n, m = out_cap.numel(), range_len.numel()
-    if not (in_off.numel() == in_len.numel() == out_off.numel() == n) or range_lo.numel() != m:
-        raise ValueError("the plan's arrays, and the ranges' arrays, must have one length each")
-    q = lambda t: _dp(t) if t is not None and t.numel() else None  # noqa: E731
-    dst_off, status = torch.zeros(m, dtype=torch.int64, device=dev), torch.zeros(m, dtype=torch.int32, device=dev)
-    raw = _ReadSummary()
-    sp = _stream_ptr(stream)
-
-    def call(d):
-        rc = lib().chip_read_ranges(int(fmt), n, q(in_buf) if n else None, q(in_off), q(in_len), q(out_off), q(out_cap), m, q(range_lo),
-                                    q(range_len), q(d), d.numel() if d is not None else 0, q(dst_off), q(status), C.byref(raw), sp)
-        if rc != 0:
-            raise RuntimeError(f"chip_read_ranges failed: {rc}")
-
-    with torch.cuda.device(dev):
-        call(dst)
-        if dst is None and raw.status == int(ReadStatus.NeedOutput):
-            dst = torch.empty(int(raw.out_len), dtype=torch.uint8, device=dev)
-            call(dst)
-        elif dst is None:
-            dst = torch.empty(0, dtype=torch.uint8, device=dev)
-    summ = ReadSummary(raw)
-    return (dst[: summ.out_len] if summ.status == ReadStatus.Ok else None), dst_off, status, summ
+    mismatch = not (in_off.numel() == in_len.numel() == out_off.numel() == n) or range_lo.numel() != m
+    q = _dp_or_none
+    return _read_call("chip_read_ranges", pairs, mismatch and "the plan's arrays, and the ranges' arrays, must have one length each", m, dst, stream,
+                      lambda *out: lib().chip_read_ranges(int(fmt), n, q(in_buf) if n else None, q(in_off), q(in_len), q(out_off), q(out_cap), m,
+                                                          q(range_lo), q(range_len), *out))
 
 
 def _read_checked(what, out, status, summ):
@@ -1606,35 +1623,21 @@ def bgzf_read(in_buf, length, ranges, stream=None):
     the file is no whole BGZF file or a range lies outside its content, RuntimeError with the first bad block's index and
     status when a block a range touches does not decode to its ISIZE.  Returns (the uint8 tensor of the ranges end to end,
     dst_off int64).  Waits for the result."""
-    in_off, in_len, out_off, out_cap, summ = bgzf_plan(in_buf, length, stream=stream)
-    if summ.status != BgzfStatus.Ok:
-        raise ValueError(f"not a whole BGZF file: {summ!r}")
-    lo, ln = _ranges_to_device(ranges, in_buf.device)
-    out, dst_off, status, rs = read_ranges(ZlibMode.Gzip, in_buf, in_off, in_len, out_off, out_cap, lo, ln, stream=stream)
-    return _read_checked("bgzf_read", out, status, rs), dst_off
+    return _plan_read("bgzf_read", bgzf_plan, BgzfStatus.Ok, "not a whole BGZF file", ZlibMode.Gzip, in_buf, length, ranges, stream)
 
 
 def zstd_frames_read(in_buf, length, ranges, stream=None):
     """The same for a buffer of zstd frames (a seekable file): plan, then read_ranges(FMT_ZSTD).  Every frame must state its
     Frame_Content_Size (a frame without one breaks the layout: ValueError; decode such a file with zstd_frames_decode).
     Returns (the uint8 tensor of the ranges end to end, dst_off int64).  Waits for the result."""
-    in_off, in_len, out_off, out_cap, summ = zstd_plan(in_buf, length, stream=stream)
-    if summ.status != ZstdPlanStatus.Ok:
-        raise ValueError(f"not a whole series of zstd frames: {summ!r}")
-    lo, ln = _ranges_to_device(ranges, in_buf.device)
-    out, dst_off, status, rs = read_ranges(FMT_ZSTD, in_buf, in_off, in_len, out_off, out_cap, lo, ln, stream=stream)
-    return _read_checked("zstd_frames_read", out, status, rs), dst_off
+    return _plan_read("zstd_frames_read", zstd_plan, ZstdPlanStatus.Ok, "not a whole series of zstd frames", FMT_ZSTD, in_buf, length, ranges, stream)
 
 
 def gzip_members_read(in_buf, length, ranges, stream=None):
     """The same for a buffer of gzip members (WARC records, a file encode_file(ZlibMode.Gzip) wrote): gzip_plan, then
     read_ranges(ZlibMode.Gzip).  Returns (the uint8 tensor of the ranges end to end, dst_off int64).  Waits for the result."""
-    in_off, in_len, out_off, out_cap, summ = gzip_plan(in_buf, length, stream=stream)
-    if summ.status != GzipPlanStatus.Ok:
-        raise ValueError(f"not a whole series of gzip members: {summ!r}")
-    lo, ln = _ranges_to_device(ranges, in_buf.device)
-    out, dst_off, status, rs = read_ranges(ZlibMode.Gzip, in_buf, in_off, in_len, out_off, out_cap, lo, ln, stream=stream)
-    return _read_checked("gzip_members_read", out, status, rs), dst_off
+    return _plan_read("gzip_members_read", gzip_plan, GzipPlanStatus.Ok, "not a whole series of gzip members", ZlibMode.Gzip, in_buf, length, ranges,
+                      stream)
 
 
 # ---- one large stream: the checkpoint index (include/compu_hip.h, "one large stream") ------------
@@ -1749,32 +1752,14 @@ def inflate_index_read(index, in_buf, range_lo, range_len, dst=None, stream=None
     import torch
 
     pairs = [(in_buf, torch.uint8), (index.pt_bit, torch.int64), (index.pt_out, torch.int64), (index.pt_check, torch.int32),
-             (index.windows, torch.uint8), (range_lo, torch.int64), (range_len, torch.int32)] + ([(dst, torch.uint8)] if dst is not None else [])
-    dev = _check_tensors(pairs)
+             (index.windows, torch.uint8), (range_lo, torch.int64), (range_len, torch.int32)]
     n, m = index.pt_bit.numel(), range_len.numel()
-    if index.pt_out.numel() != n or index.pt_check.numel() != n or index.windows.numel() < n * INDEX_WINDOW or range_lo.numel() != m:
-        raise ValueError("the index's arrays, and the ranges' arrays, must have one length each")
-    q = lambda t: _dp(t) if t is not None and t.numel() else None  # noqa: E731
-    dst_off, status = torch.zeros(m, dtype=torch.int64, device=dev), torch.zeros(m, dtype=torch.int32, device=dev)
-    raw = _ReadSummary()
-    sp = _stream_ptr(stream)
-
-    def call(d):
-        rc = lib().chip_inflate_index_read(index.fmt, _dp(in_buf), index.length, n, q(index.pt_bit), q(index.pt_out), q(index.pt_check),
-                                           q(index.windows), index.total_out, m, q(range_lo), q(range_len), q(d),
-                                           d.numel() if d is not None else 0, q(dst_off), q(status), C.byref(raw), sp)
-        if rc != 0:
-            raise RuntimeError(f"chip_inflate_index_read failed: {rc}")
-
-    with torch.cuda.device(dev):
-        call(dst)
-        if dst is None and raw.status == int(ReadStatus.NeedOutput):
-            dst = torch.empty(int(raw.out_len), dtype=torch.uint8, device=dev)
-            call(dst)
-        elif dst is None:
-            dst = torch.empty(0, dtype=torch.uint8, device=dev)
-    summ = ReadSummary(raw)
-    return (dst[: summ.out_len] if summ.status == ReadStatus.Ok else None), dst_off, status, summ
+    mismatch = index.pt_out.numel() != n or index.pt_check.numel() != n or index.windows.numel() < n * INDEX_WINDOW or range_lo.numel() != m
+    q = _dp_or_none
+    return _read_call("chip_inflate_index_read", pairs, mismatch and "the index's arrays, and the ranges' arrays, must have one length each", m, dst,
+                      stream, lambda *out: lib().chip_inflate_index_read(index.fmt, _dp(in_buf), index.length, n, q(index.pt_bit), q(index.pt_out),
+                                                                         q(index.pt_check), q(index.windows), index.total_out, m, q(range_lo),
+                                                                         q(range_len), *out))
 
 
 def gzip_index_decode(index, in_buf, stream=None):

@@ -1,7 +1,11 @@
 // Reading ranges: random access on a plan.  Given the four arrays of a plan and many byte ranges of the
 // decoded content, chip_select_units[_host] names the units the ranges touch and where each range lies in their decoded image;
-// chip_read_ranges decodes exactly those units once and lands the ranges end to end.  The definition is in include/compu_hip.h;
-// the host walk and the kernels below implement it.  The phases on the device, in stream order:
+// a read decodes exactly those units once and lands the ranges end to end.  The definition is in include/compu_hip.h; the host
+// walk and the kernels below implement it.  One driver, read_locked<Source>(), serves two sources of units: the caller's plan
+// (chip_read_ranges, PlanSource) and the chunks of a checkpoint index (chip_inflate_index_read, sec. 4.16, IndexSource).  The
+// phases on the device, in stream order:
+//   0. units    Source::carve and units: an index fills the four arrays of its units, arrays of its own in buffer ARRAYS; a plan
+//               brings them
 //   1. link     one lane per unit: out_off[i] + out_cap[i] == out_off[i + 1], no unsized cap, no wrap; the lowest failing link wins
 //               (every later kernel returns at once when there is one: a broken layout writes nothing)
 //   2. span     one lane per range: verdict, two binary searches, +1 at first and -1 behind last in a zeroed difference array
@@ -9,11 +13,13 @@
 //   4. select   exclusive {count, bytes} scan over the selected units, scatter of the sub-batch rows
 //   5. ranges   exclusive scan of the lengths that count (dst_off), then per range src_off and the status
 //      -- the host reads {n_sel, scratch_bytes, out_len} and compares with the room --
-//   6. decode   (chip_read_ranges) chip_decode_batch over the sub-batch into the slot's area
-//   7. verify   one lane per selected unit: a unit that did not end CHIP_FINISHED with out_len == out_cap is counted, the lowest one
-//               kept; a prefix count of those flags tells each range whether its span holds one
-//   8. copy     the destination-driven copy of pack_copy.h: src = the area, src_off, the counted lengths, dst_off
-// chip_inflate_index_read (sec. 4.16, further down) is the same walk over units that are the chunks of a checkpoint index.
+//   6. decode   Source::decode: the sub-batch (a BatchArgs) into the slot's area, buffer AREA of Source::area bytes:
+//               chip_decode_batch for a plan, resumed units for an index
+//   7. verify   (Source::decode still) one lane per selected unit: a unit that is not "good" as its source defines it gets
+//               flag[k] = 1, is counted in ds->n_bad, the lowest one kept in ds->bad_key; a prefix count of the flags tells each
+//               range whether its span holds one
+//   8. copy     the destination-driven copy of pack_copy.h: src = Source::image, the selected units' content end to end (a source
+//               that has to lay it there enqueues that first), src_off, the counted lengths, dst_off
 // Order between the phases comes from kernel boundaries on the stream only.  The atomics are integer sums, maxima and counts: the
 // result does not depend on their order.
 #include <new>
@@ -298,63 +304,16 @@ hipError_t select_units_locked(ReadSlot &sl, const SelectArgs &g, chip_select_su
     return hipSuccess;
 }
 
-// Enqueues everything, waits twice (the sizes, the end).  The caller holds the cache's lock.
-hipError_t read_ranges_locked(ReadSlot &sl, int format, SelectArgs g, const uint8_t *in_base, uint8_t *dst_base, uint64_t dst_cap,
-                              chip_read_summary *summary, hipStream_t stream)
+bool range_args_ok(size_t n_ranges, const uint64_t *range_lo, const uint32_t *range_len)
 {
-    hipError_t e = sl.summary();
-    if (e != hipSuccess) return e;
-    const uint64_t n = g.n, m = g.m;
-    const Arrays a = carve_arrays(n, m, true);
-    if ((e = sl.grow(ARRAYS, a.bytes)) != hipSuccess) return e;
-    uint8_t *b = sl.buf[ARRAYS];
-    g.max_sel = n;
-    g.sel_unit = (uint32_t *)(b + a.s_unit), g.sel_in_off = (uint64_t *)(b + a.s_in_off), g.sel_in_len = (uint32_t *)(b + a.s_in_len);
-    g.sel_out_off = (uint64_t *)(b + a.s_out_off), g.sel_out_cap = (uint32_t *)(b + a.s_cap);
-    g.src_off = nullptr;
-    if ((e = select_locked(sl, a, g, stream)) != hipSuccess) return e;
-    const chip_select_summary s = select_summary(*sl.h_sum);
-    *summary = chip_read_summary{0, s.out_len, s.n_outside, 0, 0, s.bad_index, s.status, 0};
-    if (s.status != CHIP_READ_OK) return hipSuccess;
-    if (s.out_len > dst_cap) {
-        summary->status = CHIP_READ_NEED_OUTPUT;
-        return hipSuccess;
-    }
-    if (s.n_sel == 0) return hipSuccess;  // (then out_len is 0 as well: every range that counts touches a unit)
-    // the decoded image of the selected units, end to end (64 bytes of slack behind it)
-    if ((e = sl.grow(AREA, (size_t)s.scratch_bytes + 64)) != hipSuccess) return e;
-    uint8_t *area = sl.buf[AREA];
-    uint32_t *d_out_len = (uint32_t *)(b + a.d_out_len), *d_in_used = (uint32_t *)(b + a.d_in_used);
-    int32_t *d_status = (int32_t *)(b + a.d_status);
-    Cnt32 *flag = (Cnt32 *)(b + a.flag), *flag_excl = (Cnt32 *)(b + a.flag_excl), *flag_part = (Cnt32 *)(b + a.flag_part);
-    const int rc = chip_decode_batch(format, (size_t)s.n_sel, in_base, g.sel_in_off, g.sel_in_len, area, g.sel_out_off, g.sel_out_cap, d_out_len,
-                                     d_in_used, d_status, stream);
-    if (rc != CHIP_OK) return rc == CHIP_E_NOMEM ? hipErrorOutOfMemory : hipErrorUnknown;  // (CHIP_E_LAUNCH; more than 2^31 - 1 units too)
-    hipLaunchKernelGGL(rr_verify_kernel, grid256(s.n_sel), dim3(256), 0, stream, (const uint32_t *)g.sel_unit, (const uint32_t *)g.sel_out_cap,
-                       (const uint32_t *)d_out_len, (const int32_t *)d_status, s.n_sel, flag, sl.d_sum);
-    if (g.range_status) {
-        enqueue_scan<Cnt32>(flag, flag_excl, s.n_sel, flag_part, &sl.d_sum->flag_total, stream);
-        hipLaunchKernelGGL(rr_bad_ranges_kernel, grid256(m), dim3(256), 0, stream, (const uint32_t *)(b + a.first), (const uint32_t *)(b + a.last),
-                           (const UnitAcc *)(b + a.acc), (const Cnt32 *)flag, (const Cnt32 *)flag_excl, (const Cnt32 *)flag_part, m, g.range_status);
-    }
-    enqueue_copy(m, area, (const uint64_t *)(b + a.src), (const uint32_t *)(b + a.counted), dst_base, (const uint64_t *)(b + a.wide), s.out_len, stream);
-    if ((e = sl.fetch(stream)) != hipSuccess) return e;  // the slot is handed on only with nothing in flight
-    const DevSummary &h = *sl.h_sum;
-    summary->n_units = s.n_sel;
-    summary->n_bad = h.n_bad;
-    if (h.n_bad) {
-        summary->first_bad = (uint32_t)~(uint32_t)(h.bad_key >> 32);
-        summary->bad_status = (int32_t)(uint32_t)h.bad_key;
-    }
-    return hipSuccess;
+    return (uint64_t)n_ranges <= 0xFFFFFFFFull && !(n_ranges && (!range_lo || !range_len));
 }
 
 bool plan_args_ok(size_t n_units, const uint64_t *in_off, const uint32_t *in_len, const uint64_t *out_off, const uint32_t *out_cap, size_t n_ranges,
                   const uint64_t *range_lo, const uint32_t *range_len)
 {
-    if ((uint64_t)n_units > 0xFFFFFFFFull || (uint64_t)n_ranges > 0xFFFFFFFFull) return false;
-    if (n_units && (!in_off || !in_len || !out_off || !out_cap)) return false;
-    return !(n_ranges && (!range_lo || !range_len));
+    if ((uint64_t)n_units > 0xFFFFFFFFull || (n_units && (!in_off || !in_len || !out_off || !out_cap))) return false;
+    return range_args_ok(n_ranges, range_lo, range_len);
 }
 
 bool select_args_ok(size_t n_units, const uint64_t *in_off, const uint32_t *in_len, const uint64_t *out_off, const uint32_t *out_cap, size_t n_ranges,
@@ -371,19 +330,17 @@ bool decode_format_ok(int format)
            format == CHIP_FMT_BROTLI || format == CHIP_FMT_DETECT;
 }
 
-
 // ---- reading through the checkpoint index of one large stream --------------------------------------------
-// chip_inflate_index_read is the walk above over units that are the chunks of an index.  Its phases, in stream order:
-//   0. units    one lane per chunk: in_off, in_len, out_cap by index_chunk(); a chunk that offends the layout gets the cap
-//               CHIP_ZPLAN_UNSIZED, so that phase 1 fails at exactly that link (an honest chunk's link to its successor holds by
-//               construction) and nothing else is written
-//   1.-5.       select_locked() over (in_off, in_len, pt_out, out_cap)
+// The units are the chunks of an index.  What IndexSource (further down) puts into the source's phases of the walk above:
+//   0. units    one lane per chunk: in_off, in_len, out_cap by index_chunk(), out_off = pt_out; a chunk that offends the layout gets
+//               the cap CHIP_ZPLAN_UNSIZED, so that phase 1 fails at exactly that link (an honest chunk's link to its successor
+//               holds by construction) and nothing else is written
 //   6a. stage   one lane per selected chunk: its slot [window | chunk] in the area, the resume words, where its content starts
 //   6b. window  four waves per selected chunk: the window slot of the index goes to the front of the chunk's slot
 //   6c. decode  launch_inflate() with BatchArgs::resume: the chunks are resumed units of inflate_kernel
 //   7. verify   one lane per selected chunk: the link to the next point (or the end of the stream) as the header defines "good"
-//   8. copy     twice pack_copy.h's copy: the chunks' content goes end to end into an image behind the slots (the windows between
-//               them are gone), then the ranges are gathered from the image as chip_read_ranges gathers them
+//   8. copy     once more pack_copy.h's copy, in front of the driver's: the chunks' content goes end to end into an image behind
+//               the slots (the windows between them are gone); the ranges are gathered from that image
 constexpr uint32_t IX_WINDOW = 32768;
 constexpr uint64_t IX_CAP_MAX = 0xFFFFFFF0ull - IX_WINDOW;
 
@@ -475,84 +432,127 @@ __global__ __launch_bounds__(256) void ix_verify_kernel(const uint64_t *pt_bit, 
     atomicMax((unsigned long long *)&ds->bad_key, ((unsigned long long)(uint32_t)~sel_unit[j] << 32) | (uint32_t)st);
 }
 
-// what chip_inflate_index_read hands on: the index and the stream
-struct IndexArgs {
-    uint64_t n, len, total_out;
+bool index_format_ok(int format) { return format == CHIP_FMT_DEFLATE || format == CHIP_FMT_ZLIB || format == CHIP_FMT_GZIP; }
+uint32_t index_wrap(int format) { return format == CHIP_FMT_DEFLATE ? 0u : format == CHIP_FMT_ZLIB ? 1u : 2u; }
+
+// ---- the read driver and its two sources ---------------------------------------------------------------------------------------
+// A source is the template parameter of read_locked(), as D is plan_locked()'s: the hooks the phase list at the top names, none of
+// which waits for the stream, and LINK_BACK, how far the failing link that select_summary() names is ahead of the bad_index that
+// the source's header promises.
+struct PlanSource {
+    void carve(Carve &) {}
+    void units(uint8_t *, SelectArgs &, hipStream_t) {}
+    static constexpr uint64_t LINK_BACK = 0;
+    static size_t area(const chip_select_summary &s) { return (size_t)s.scratch_bytes + 64; }  // the units end to end, 64 bytes of slack
+    static hipError_t decode(const BatchArgs &ba, const uint32_t *unit, Cnt32 *flag, DevSummary *ds, hipStream_t stream)
+    {
+        const int rc = chip_decode_batch(ba.format, ba.n, ba.in_base, ba.in_off, ba.in_len, ba.out_base, ba.out_off, ba.out_cap, ba.out_len, ba.in_used,
+                                         ba.status, stream);
+        if (rc != CHIP_OK) return rc == CHIP_E_NOMEM ? hipErrorOutOfMemory : hipErrorUnknown;  // (CHIP_E_LAUNCH)
+        hipLaunchKernelGGL(rr_verify_kernel, grid256(ba.n), dim3(256), 0, stream, unit, ba.out_cap, (const uint32_t *)ba.out_len,
+                           (const int32_t *)ba.status, (uint64_t)ba.n, flag, ds);
+        return hipSuccess;
+    }
+    static const uint8_t *image(const BatchArgs &ba, uint64_t, hipStream_t) { return ba.out_base; }
+};
+
+struct IndexSource {
+    uint64_t len, n, total_out;
     const uint64_t *pt_bit, *pt_out;
     const uint32_t *pt_check;
     const uint8_t *windows;
-    uint32_t wrap;
+    // in buffer ARRAYS: the chunks as units (16 bytes per chunk), the slots (20), the resume words (24)
+    size_t o_in_off = 0, o_in_len = 0, o_cap = 0, o_slot_off = 0, o_content = 0, o_slot_cap = 0, o_resume = 0;
+    uint64_t *slot_off = nullptr, *content_off = nullptr;
+    uint32_t *slot_cap = nullptr, *resume = nullptr;
+
+    void carve(Carve &c)
+    {
+        o_in_off = c.take(n, 8), o_in_len = c.take(n, 4), o_cap = c.take(n, 4), o_slot_off = c.take(n, 8), o_content = c.take(n, 8);
+        o_slot_cap = c.take(n, 4), o_resume = c.take(n, 4 * RESUME_WORDS);
+    }
+    void units(uint8_t *b, SelectArgs &g, hipStream_t stream)
+    {
+        uint64_t *u_in_off = (uint64_t *)(b + o_in_off);
+        uint32_t *u_in_len = (uint32_t *)(b + o_in_len), *u_cap = (uint32_t *)(b + o_cap);
+        slot_off = (uint64_t *)(b + o_slot_off), content_off = (uint64_t *)(b + o_content);
+        slot_cap = (uint32_t *)(b + o_slot_cap), resume = (uint32_t *)(b + o_resume);
+        if (n) hipLaunchKernelGGL(ix_units_kernel, grid256(n), dim3(256), 0, stream, pt_bit, pt_out, n, len, total_out, u_in_off, u_in_len, u_cap);
+        g.in_off = u_in_off, g.in_len = u_in_len, g.out_off = pt_out, g.out_cap = u_cap;
+    }
+    static constexpr uint64_t LINK_BACK = 1;  // (the failing link i is the lowest offending chunk: select_summary() says i + 1)
+    // the slots [window | chunk] of the selected chunks, then the image of their content end to end (64 bytes of slack behind each)
+    static size_t image_at(uint64_t n_sel, uint64_t scratch_bytes) { return up16((size_t)scratch_bytes + (size_t)IX_WINDOW * n_sel + 64); }
+    static size_t area(const chip_select_summary &s) { return image_at(s.n_sel, s.scratch_bytes) + (size_t)s.scratch_bytes + 64; }
+    hipError_t decode(const BatchArgs &ba, const uint32_t *unit, Cnt32 *flag, DevSummary *ds, hipStream_t stream) const
+    {
+        const uint64_t n_sel = ba.n;
+        hipLaunchKernelGGL(ix_stage_kernel, grid256(n_sel), dim3(256), 0, stream, pt_bit, pt_out, pt_check, n, len, total_out, index_wrap(ba.format), unit,
+                           ba.out_off, n_sel, slot_off, slot_cap, content_off, resume);
+        hipLaunchKernelGGL(ix_window_kernel, dim3(ba.n), dim3(256), 0, stream, windows, unit, (const uint64_t *)slot_off,
+                           (const uint64_t *)content_off, ba.out_base);
+        BatchArgs r = ba;  // the chunks as resumed units, each into its slot
+        r.out_off = slot_off, r.out_cap = slot_cap, r.resume = resume;
+        const hipError_t e = launch_inflate(r, stream);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(ix_verify_kernel, grid256(n_sel), dim3(256), 0, stream, pt_bit, pt_check, n, unit, ba.in_off, (const uint32_t *)slot_cap,
+                           (const uint32_t *)resume, (const uint32_t *)ba.out_len, (const int32_t *)ba.status, n_sel, flag, ds);
+        return hipSuccess;
+    }
+    const uint8_t *image(const BatchArgs &ba, uint64_t scratch_bytes, hipStream_t stream) const
+    {
+        uint8_t *image = ba.out_base + image_at(ba.n, scratch_bytes);
+        enqueue_copy(ba.n, ba.out_base, (const uint64_t *)content_off, ba.out_cap, image, ba.out_off, scratch_bytes, stream);
+        return image;
+    }
 };
 
 SlotCache<ReadSlot> g_index_read_cache;
 
-// Enqueues everything, waits twice (the sizes, the end).  The caller holds the cache's lock.
-hipError_t index_read_locked(ReadSlot &sl, int format, const IndexArgs &x, SelectArgs g, const uint8_t *in_base, uint8_t *dst_base, uint64_t dst_cap,
-                             chip_read_summary *summary, hipStream_t stream)
+constexpr chip_select_summary SELECT_NOTHING{0, 0, 0, 0, 0, CHIP_READ_OK, 0};
+constexpr chip_read_summary READ_NOTHING{0, 0, 0, 0, 0, 0, CHIP_READ_OK, 0};
+
+// One read: enqueues everything, waits twice (the sizes, the end).  g brings the ranges and the caller's outputs, with a plan its
+// four arrays.  The caller holds the cache's lock.
+template <class Source>
+hipError_t read_locked(ReadSlot &sl, Source src, int format, const uint8_t *in_base, SelectArgs g, uint8_t *dst_base, uint64_t dst_cap,
+                       chip_read_summary *summary, hipStream_t stream)
 {
     hipError_t e = sl.summary();
     if (e != hipSuccess) return e;
-    const uint64_t n = x.n, m = g.m;
+    const uint64_t n = g.n, m = g.m;
     const Arrays a = carve_arrays(n, m, true);
-    // behind chip_read_ranges' arrays: the chunks as units (16 bytes per chunk), the slots (20), the resume words (24)
-    Carve c;
-    c.at = a.bytes;
-    const size_t o_in_off = c.take(n, 8), o_in_len = c.take(n, 4), o_cap = c.take(n, 4), o_slot_off = c.take(n, 8), o_content = c.take(n, 8);
-    const size_t o_slot_cap = c.take(n, 4), o_resume = c.take(n, 4 * RESUME_WORDS);
+    Carve c{a.bytes};
+    src.carve(c);
     if ((e = sl.grow(ARRAYS, c.at)) != hipSuccess) return e;
     uint8_t *b = sl.buf[ARRAYS];
-    uint64_t *u_in_off = (uint64_t *)(b + o_in_off), *slot_off = (uint64_t *)(b + o_slot_off), *content_off = (uint64_t *)(b + o_content);
-    uint32_t *u_in_len = (uint32_t *)(b + o_in_len), *u_cap = (uint32_t *)(b + o_cap), *slot_cap = (uint32_t *)(b + o_slot_cap);
-    uint32_t *resume = (uint32_t *)(b + o_resume);
-    if (n) hipLaunchKernelGGL(ix_units_kernel, grid256(n), dim3(256), 0, stream, x.pt_bit, x.pt_out, n, x.len, x.total_out, u_in_off, u_in_len, u_cap);
-    g.in_off = u_in_off, g.in_len = u_in_len, g.out_off = x.pt_out, g.out_cap = u_cap;
     g.max_sel = n;
     g.sel_unit = (uint32_t *)(b + a.s_unit), g.sel_in_off = (uint64_t *)(b + a.s_in_off), g.sel_in_len = (uint32_t *)(b + a.s_in_len);
     g.sel_out_off = (uint64_t *)(b + a.s_out_off), g.sel_out_cap = (uint32_t *)(b + a.s_cap);
-    g.src_off = nullptr;
+    src.units(b, g, stream);
     if ((e = select_locked(sl, a, g, stream)) != hipSuccess) return e;
     const chip_select_summary s = select_summary(*sl.h_sum);
-    // (the failing link i is the lowest offending chunk: select_summary() says i + 1)
-    *summary = chip_read_summary{0, s.out_len, s.n_outside, 0, 0, s.status == CHIP_READ_BAD_LAYOUT ? s.bad_index - 1 : 0, s.status, 0};
-    if (s.status != CHIP_READ_OK) return hipSuccess;
-    if (s.out_len > dst_cap) {
-        summary->status = CHIP_READ_NEED_OUTPUT;
-        return hipSuccess;
-    }
-    if (s.n_sel == 0) return hipSuccess;
-    if (s.n_sel > 0x7fffffffull) return hipErrorUnknown;
-    // the slots [window | chunk] of the selected chunks, then the image of their content end to end (64 bytes of slack behind each)
-    const size_t image_at = up16((size_t)s.scratch_bytes + (size_t)IX_WINDOW * s.n_sel + 64);
-    if ((e = sl.grow(AREA, image_at + (size_t)s.scratch_bytes + 64)) != hipSuccess) return e;
-    uint8_t *area = sl.buf[AREA], *image = area + image_at;
-    uint32_t *d_out_len = (uint32_t *)(b + a.d_out_len), *d_in_used = (uint32_t *)(b + a.d_in_used);
-    int32_t *d_status = (int32_t *)(b + a.d_status);
+    *summary = chip_read_summary{0, s.out_len, s.n_outside, 0, 0, s.status == CHIP_READ_OK ? 0 : s.bad_index - Source::LINK_BACK, s.status, 0};
+    if (s.status == CHIP_READ_OK && s.out_len > dst_cap) summary->status = CHIP_READ_NEED_OUTPUT;
+    if (summary->status != CHIP_READ_OK || s.n_sel == 0) return hipSuccess;  // (no unit: no byte either, a range that counts touches one)
+    if (s.n_sel > 0x7fffffffull) return hipErrorUnknown;  // (more units than a batch counts)
+    if ((e = sl.grow(AREA, Source::area(s))) != hipSuccess) return e;
+    BatchArgs ba{};  // the sub-batch: the selected units decode into the area
+    ba.format = format, ba.in_base = in_base, ba.n = (uint32_t)s.n_sel;
+    ba.in_off = g.sel_in_off, ba.in_len = g.sel_in_len, ba.out_base = sl.buf[AREA], ba.out_off = g.sel_out_off, ba.out_cap = g.sel_out_cap;
+    ba.out_len = (uint32_t *)(b + a.d_out_len), ba.in_used = (uint32_t *)(b + a.d_in_used), ba.status = (int32_t *)(b + a.d_status);
     Cnt32 *flag = (Cnt32 *)(b + a.flag), *flag_excl = (Cnt32 *)(b + a.flag_excl), *flag_part = (Cnt32 *)(b + a.flag_part);
-    hipLaunchKernelGGL(ix_stage_kernel, grid256(s.n_sel), dim3(256), 0, stream, x.pt_bit, x.pt_out, x.pt_check, n, x.len, x.total_out, x.wrap,
-                       (const uint32_t *)g.sel_unit, (const uint64_t *)g.sel_out_off, s.n_sel, slot_off, slot_cap, content_off, resume);
-    hipLaunchKernelGGL(ix_window_kernel, dim3((uint32_t)s.n_sel), dim3(256), 0, stream, x.windows, (const uint32_t *)g.sel_unit,
-                       (const uint64_t *)slot_off, (const uint64_t *)content_off, area);
-    BatchArgs ba{};
-    ba.in_base = in_base, ba.in_off = g.sel_in_off, ba.in_len = g.sel_in_len;
-    ba.out_base = area, ba.out_off = slot_off, ba.out_cap = slot_cap;
-    ba.out_len = d_out_len, ba.in_used = d_in_used, ba.status = d_status;
-    ba.n = (uint32_t)s.n_sel, ba.format = format, ba.resume = resume;
-    if ((e = launch_inflate(ba, stream)) != hipSuccess) return e;
-    hipLaunchKernelGGL(ix_verify_kernel, grid256(s.n_sel), dim3(256), 0, stream, x.pt_bit, x.pt_check, n, (const uint32_t *)g.sel_unit,
-                       (const uint64_t *)g.sel_in_off, (const uint32_t *)slot_cap, (const uint32_t *)resume, (const uint32_t *)d_out_len,
-                       (const int32_t *)d_status, s.n_sel, flag, sl.d_sum);
+    if ((e = src.decode(ba, (const uint32_t *)g.sel_unit, flag, sl.d_sum, stream)) != hipSuccess) return e;
     if (g.range_status) {
         enqueue_scan<Cnt32>(flag, flag_excl, s.n_sel, flag_part, &sl.d_sum->flag_total, stream);
         hipLaunchKernelGGL(rr_bad_ranges_kernel, grid256(m), dim3(256), 0, stream, (const uint32_t *)(b + a.first), (const uint32_t *)(b + a.last),
                            (const UnitAcc *)(b + a.acc), (const Cnt32 *)flag, (const Cnt32 *)flag_excl, (const Cnt32 *)flag_part, m, g.range_status);
     }
-    enqueue_copy(s.n_sel, area, (const uint64_t *)content_off, (const uint32_t *)g.sel_out_cap, image, (const uint64_t *)g.sel_out_off, s.scratch_bytes,
-                 stream);
-    enqueue_copy(m, image, (const uint64_t *)(b + a.src), (const uint32_t *)(b + a.counted), dst_base, (const uint64_t *)(b + a.wide), s.out_len, stream);
+    enqueue_copy(m, src.image(ba, s.scratch_bytes, stream), (const uint64_t *)(b + a.src), (const uint32_t *)(b + a.counted), dst_base,
+                 (const uint64_t *)(b + a.wide), s.out_len, stream);
     if ((e = sl.fetch(stream)) != hipSuccess) return e;  // the slot is handed on only with nothing in flight
     const DevSummary &h = *sl.h_sum;
-    summary->n_units = s.n_sel;
-    summary->n_bad = h.n_bad;
+    summary->n_units = s.n_sel, summary->n_bad = h.n_bad;
     if (h.n_bad) {
         summary->first_bad = (uint32_t)~(uint32_t)(h.bad_key >> 32);
         summary->bad_status = (int32_t)(uint32_t)h.bad_key;
@@ -560,8 +560,18 @@ hipError_t index_read_locked(ReadSlot &sl, int format, const IndexArgs &x, Selec
     return hipSuccess;
 }
 
-bool index_format_ok(int format) { return format == CHIP_FMT_DEFLATE || format == CHIP_FMT_ZLIB || format == CHIP_FMT_GZIP; }
-uint32_t index_wrap(int format) { return format == CHIP_FMT_DEFLATE ? 0u : format == CHIP_FMT_ZLIB ? 1u : 2u; }
+// What both read entry points do once their arguments are in order.
+template <class Source>
+int read_with_slot(SlotCache<ReadSlot> &cache, const Source &src, int format, const void *in_base, const SelectArgs &g, void *dst_base, uint64_t dst_cap,
+                   chip_read_summary *summary, void *stream)
+{
+    *summary = READ_NOTHING;
+    if (g.m == 0) return CHIP_OK;
+    return with_slot(
+        cache, stream,
+        [&](ReadSlot &sl, hipStream_t s) { return read_locked(sl, src, format, (const uint8_t *)in_base, g, (uint8_t *)dst_base, dst_cap, summary, s); },
+        [&] { *summary = READ_NOTHING; });
+}
 }  // namespace
 
 }  // namespace chip
@@ -578,7 +588,7 @@ int chip_select_units_host(size_t n_units, const uint64_t *in_off, const uint32_
     if (!select_args_ok(n_units, in_off, in_len, out_off, out_cap, n_ranges, range_lo, range_len, max_sel, sel_unit, sel_in_off, sel_in_len,
                         sel_out_off, sel_out_cap, summary))
         return CHIP_E_INVALID;
-    *summary = chip_select_summary{0, 0, 0, 0, 0, CHIP_READ_OK, 0};
+    *summary = SELECT_NOTHING;
     if (n_ranges == 0) return CHIP_OK;
     const uint64_t n = n_units, m = n_ranges;
     for (uint64_t i = 0; i < n; i++) {
@@ -644,13 +654,13 @@ int chip_select_units(size_t n_units, const uint64_t *in_off, const uint32_t *in
     if (!select_args_ok(n_units, in_off, in_len, out_off, out_cap, n_ranges, range_lo, range_len, max_sel, sel_unit, sel_in_off, sel_in_len,
                         sel_out_off, sel_out_cap, summary))
         return CHIP_E_INVALID;
-    *summary = chip_select_summary{0, 0, 0, 0, 0, CHIP_READ_OK, 0};
+    *summary = SELECT_NOTHING;
     if (n_ranges == 0) return CHIP_OK;
     const SelectArgs g{n_units, n_ranges, in_off, in_len, out_off, out_cap, range_lo, range_len, max_sel, sel_unit, sel_in_off, sel_in_len,
                        sel_out_off, sel_out_cap, src_off, dst_off, range_status};
     return with_slot(
         g_read_cache, stream, [&](ReadSlot &sl, hipStream_t s) { return select_units_locked(sl, g, summary, s); },
-        [&] { *summary = chip_select_summary{0, 0, 0, 0, 0, CHIP_READ_OK, 0}; });
+        [&] { *summary = SELECT_NOTHING; });
 }
 
 int chip_read_ranges(int format, size_t n_units, const void *in_base, const uint64_t *in_off, const uint32_t *in_len, const uint64_t *out_off,
@@ -660,14 +670,9 @@ int chip_read_ranges(int format, size_t n_units, const void *in_base, const uint
     if (!summary || !plan_args_ok(n_units, in_off, in_len, out_off, out_cap, n_ranges, range_lo, range_len) || (n_units && !in_base) ||
         ((uintptr_t)in_base & 3u) || (dst_cap && !dst_base) || !decode_format_ok(format))
         return CHIP_E_INVALID;
-    *summary = chip_read_summary{0, 0, 0, 0, 0, 0, CHIP_READ_OK, 0};
-    if (n_ranges == 0) return CHIP_OK;
     const SelectArgs g{n_units, n_ranges, in_off,  in_len,  out_off, out_cap, range_lo, range_len,   0,
                        nullptr, nullptr,  nullptr, nullptr, nullptr, nullptr, dst_off,  range_status};
-    return with_slot(
-        g_read_cache, stream,
-        [&](ReadSlot &sl, hipStream_t s) { return read_ranges_locked(sl, format, g, (const uint8_t *)in_base, (uint8_t *)dst_base, dst_cap, summary, s); },
-        [&] { *summary = chip_read_summary{0, 0, 0, 0, 0, 0, CHIP_READ_OK, 0}; });
+    return read_with_slot(g_read_cache, PlanSource{}, format, in_base, g, dst_base, dst_cap, summary, stream);
 }
 
 int chip_inflate_index_units_host(int format, uint64_t len, uint64_t n_points, const uint64_t *pt_bit, const uint64_t *pt_out,
@@ -702,18 +707,12 @@ int chip_inflate_index_read(int format, const void *in_base, uint64_t len, uint6
                             chip_read_summary *summary, void *stream)
 {
     if (!summary || !index_format_ok(format) || !in_base || ((uintptr_t)in_base & 3u) || len > (1ull << 61) || n_points > 0xFFFFFFFFull ||
-        (uint64_t)n_ranges > 0xFFFFFFFFull || (n_points && (!pt_bit || !pt_out || !pt_check || !windows)) || (n_ranges && (!range_lo || !range_len)) ||
-        (dst_cap && !dst_base))
+        (n_points && (!pt_bit || !pt_out || !pt_check || !windows)) || !range_args_ok(n_ranges, range_lo, range_len) || (dst_cap && !dst_base))
         return CHIP_E_INVALID;
-    *summary = chip_read_summary{0, 0, 0, 0, 0, 0, CHIP_READ_OK, 0};
-    if (n_ranges == 0) return CHIP_OK;
-    const IndexArgs x{n_points, len, total_out, pt_bit, pt_out, pt_check, (const uint8_t *)windows, index_wrap(format)};
+    const IndexSource x{len, n_points, total_out, pt_bit, pt_out, pt_check, (const uint8_t *)windows};
     const SelectArgs g{n_points, n_ranges, nullptr, nullptr, nullptr, nullptr, range_lo, range_len,    0,
                        nullptr,  nullptr,  nullptr, nullptr, nullptr, nullptr, dst_off,  range_status};
-    return with_slot(
-        g_index_read_cache, stream,
-        [&](ReadSlot &sl, hipStream_t s) { return index_read_locked(sl, format, x, g, (const uint8_t *)in_base, (uint8_t *)dst_base, dst_cap, summary, s); },
-        [&] { *summary = chip_read_summary{0, 0, 0, 0, 0, 0, CHIP_READ_OK, 0}; });
+    return read_with_slot(g_index_read_cache, x, format, in_base, g, dst_base, dst_cap, summary, stream);
 }
 
 }  // extern "C"

@@ -3,8 +3,11 @@ derived from the writer's block records and the system zlib, at spacing 1 and at
 build's decode answers equal chip_decode_batch's for the same unit and room, errors included.  chip_inflate_index_read: the window
 edges of a chunk; whole files (alice29, 2.5 MiB of bench data; zlib levels 1, 6, 9; raw, zlib, gzip) through the index equal
 zlib.decompress; ranges of every kind; damage behind the build names the chunk and spares the others; a truncated index reads
-the whole content.  Truth is zlib and tests/deflate_writer.py.  Without the feature every test fails at the missing symbols."""
+the whole content; too little room, a broken index layout and nothing to read write nothing; null dst_off / range_status change
+no byte; a plan read over the same chunks as gzip members answers the same.  Truth is zlib and tests/deflate_writer.py.  Without the
+feature every test fails at the missing symbols."""
 import ctypes as C
+import zlib
 
 import numpy as np
 import pytest
@@ -18,7 +21,7 @@ POISON, GUARD, WINDOW = 0xEE, 64, 32768
 POISON64 = int.from_bytes(bytes([POISON]) * 8, "little")
 FINISHED, NEED_INPUT, NEED_OUTPUT = 2, 0, 1
 RANGE_OK, RANGE_OUTSIDE, RANGE_BAD_UNIT = 0, 1, 2
-READ_OK, READ_NEED_OUTPUT = 0, 1
+READ_OK, READ_NEED_OUTPUT, READ_BAD_LAYOUT = 0, 1, 2
 
 
 def upload(torch, data):
@@ -349,3 +352,186 @@ def test_a_truncated_index_reads_the_whole_content(gpu, max_points):
     assert compu_amd.gzip_index_decode(index, d_in).cpu().numpy().tobytes() == content
     out, dst_off = compu_amd.gzip_index_read(index, d_in, [(100000, 50), (5, 7)])
     assert out.cpu().numpy().tobytes() == content[100000:100050] + content[5:12] and u64(dst_off) == [0, 50]
+
+
+# ---- what the index read shares with the plan read: the room, the layout, nothing to read, null outputs -------------------------
+# One small stream (IC.edges: eight blocks, 57 KiB) at spacing 1, so that every block with content is a chunk.
+
+
+def edges_index(gpu, fmt):
+    """-> (content by the system zlib, the stream, its index at spacing 1, the stream on the device)"""
+    s = IC.edges(fmt)
+    content = zlib.decompress(s.data, R.FMT[fmt])
+    index, d_in, _ = index_of(gpu, fmt, s.data, len(content), 1)
+    assert index.n_points >= 3
+    return content, s, index, d_in
+
+
+def host_selection(index, ranges):
+    """what the read has to answer, by host arithmetic alone: chip_inflate_index_units_host for the chunks, chip_select_units_host
+    over them -> (dst_off, range status, SelectSummary)"""
+    import compu_amd
+
+    pt_bit, pt_out, pt_check = u64(index.pt_bit), u64(index.pt_out), u32(index.pt_check)
+    in_off, in_len, out_cap, _, _, status, _ = compu_amd.inflate_index_units_host(index.fmt, index.length, pt_bit, pt_out, pt_check, index.total_out)
+    assert status == READ_OK
+    lo, ln = np.array([r[0] for r in ranges], np.uint64), np.array([r[1] for r in ranges], np.uint32)
+    *_, dst_off, range_status, summ = compu_amd.select_units_host(in_off, in_len, pt_out, out_cap, lo, ln)
+    return dst_off.tolist(), range_status.tolist(), summ
+
+
+def raw_read(gpu, index, d_in, ranges, room, outputs=True):
+    """chip_inflate_index_read through compu_amd.lib() into a poisoned dst with guards and poisoned dst_off / range_status, both null
+    when `outputs` is false -> (all bytes of dst and its guards, dst_off, range_status, the summary as a tuple)"""
+    import compu_amd
+    from compu_amd.api import _ranges_to_device, _ReadSummary
+
+    m = len(ranges)
+    lo, ln = _ranges_to_device(ranges, gpu.device("cuda")) if m else (None, None)
+    box = gpu.full((GUARD + room + GUARD,), POISON, dtype=gpu.uint8, device="cuda")
+    dst_off = gpu.full((m * 8 + 8,), POISON, dtype=gpu.uint8, device="cuda").view(gpu.int64)
+    status = gpu.full((m * 4 + 4,), POISON, dtype=gpu.uint8, device="cuda").view(gpu.int32)
+    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+    raw = _ReadSummary(7, 7, 7, 7, 7, 7, 1, 7)  # whatever the caller left there
+    gpu.cuda.synchronize()
+    rc = compu_amd.lib().chip_inflate_index_read(index.fmt, p(d_in), index.length, index.n_points, p(index.pt_bit), p(index.pt_out),
+                                                 p(index.pt_check), p(index.windows), index.total_out, m, p(lo), p(ln),
+                                                 C.c_void_p(box.data_ptr() + GUARD), room, p(dst_off) if outputs else None,
+                                                 p(status) if outputs else None, C.byref(raw), None)
+    assert rc == 0
+    gpu.cuda.synchronize()
+    return box.cpu().numpy().tobytes(), u64(dst_off), u32(status), compu_amd.ReadSummary(raw).as_tuple()
+
+
+def edge_ranges(outs, total):
+    """ranges across chunk edges, inside one chunk, of length 0, outside the content, out of order"""
+    return [(outs[1] - 7, 20), (outs[2] - 1, outs[4] - outs[2] + 2), (outs[3] + 5, 100), (outs[2], 0), (total, 0), (total - 1, 2), (total + 9, 1),
+            (total - 1, 1), (3, 40)]
+
+
+@pytest.mark.parametrize("fmt", IC.WRAPPERS)
+def test_need_output_writes_nothing_and_sizes_the_second_call(gpu, fmt):
+    content, _, index, d_in = edges_index(gpu, fmt)
+    ranges = edge_ranges(u64(index.pt_out), len(content))
+    want_off, want_status, want = host_selection(index, ranges)
+    assert want.n_outside == 2 and want.n_sel >= 4 and want.out_len == sum(ln for (_, ln), st in zip(ranges, want_status) if st == RANGE_OK)
+    got, guards, dst_off, status, summ = read(gpu, index, d_in, ranges, room=want.out_len - 1)
+    assert summ.as_tuple() == (0, want.out_len, want.n_outside, 0, 0, 0, READ_NEED_OUTPUT, 0)
+    assert got == bytes([POISON]) * (want.out_len - 1) and guards, "no byte of dst, and none of the 64 behind it"
+    assert (dst_off, status) == (want_off, want_status)
+    got, guards, dst_off, status, summ = read(gpu, index, d_in, ranges, room=summ.out_len)
+    assert summ.as_tuple() == (want.n_sel, want.out_len, want.n_outside, 0, 0, 0, READ_OK, 0) and guards
+    assert got == b"".join(content[lo:lo + ln] for (lo, ln), st in zip(ranges, want_status) if st == RANGE_OK)
+    assert (dst_off, status) == (want_off, want_status)
+
+
+@pytest.mark.parametrize("fmt", IC.WRAPPERS)
+def test_a_broken_index_layout_names_the_chunk_and_writes_nothing(gpu, fmt):
+    import compu_amd
+
+    content, _, index, d_in = edges_index(gpu, fmt)
+    ranges = edge_ranges(u64(index.pt_out), len(content))
+    room = len(content)
+    untouched = bytes([POISON]) * (GUARD + room + GUARD)
+    # pt_out[k] above pt_out[k + 1] for an inner k; a point that does not move on in the stream; content in front of the first point
+    for name, k, value, chunk in (("pt_out", 2, u64(index.pt_out)[3] + 1, 2), ("pt_bit", 2, u64(index.pt_bit)[1], 1), ("pt_out", 0, 1, 0)):
+        arrays = dict(pt_bit=index.pt_bit.clone(), pt_out=index.pt_out.clone())
+        arrays[name][k] = value
+        broken = compu_amd.InflateIndex(index.fmt, index.length, index.total_out, arrays["pt_bit"], arrays["pt_out"], index.pt_check, index.windows)
+        pt_bit, pt_out = u64(broken.pt_bit), u64(broken.pt_out)
+        *rows, status, bad = compu_amd.inflate_index_units_host(index.fmt, index.length, pt_bit, pt_out, u32(index.pt_check), index.total_out)
+        assert (int(status), bad) == (READ_BAD_LAYOUT, chunk)
+        assert R.units(R.WRAP[fmt], index.length, pt_bit, pt_out, u32(index.pt_check), index.total_out)[:2] == (READ_BAD_LAYOUT, chunk)
+        box, dst_off, range_status, summ = raw_read(gpu, broken, d_in, ranges, room)
+        assert summ == (0, 0, 0, 0, 0, bad, READ_BAD_LAYOUT, 0), "the lowest offending chunk, not the link behind it"
+        assert box == untouched and set(dst_off) == {POISON64} and set(range_status) == {POISON64 & 0xFFFFFFFF}
+
+
+@pytest.mark.parametrize("fmt", IC.WRAPPERS)
+def test_nothing_to_read(gpu, fmt):
+    import compu_amd
+    from compu_amd.api import _ranges_to_device
+
+    content, _, index, d_in = edges_index(gpu, fmt)
+    outs, total = u64(index.pt_out), len(content)
+    untouched = bytes([POISON]) * (GUARD + 32 + GUARD)
+    # no ranges: CHIP_OK and the zero summary, whatever the caller left there
+    box, dst_off, status, summ = raw_read(gpu, index, d_in, [], 32)
+    assert summ == (0, 0, 0, 0, 0, 0, READ_OK, 0) and box == untouched and dst_off == [POISON64] and status == [POISON64 & 0xFFFFFFFF]
+    lo, ln = _ranges_to_device([(0, 1)], gpu.device("cuda"))
+    out, _, _, rs = compu_amd.inflate_index_read(index, d_in, lo[:0], ln[:0])
+    assert rs.as_tuple() == (0, 0, 0, 0, 0, 0, READ_OK, 0) and out.numel() == 0
+    # ranges of length 0, inside, on a chunk's edge, at the end and far outside: nothing is decoded
+    ranges = [(0, 0), (outs[1], 0), (outs[2] + 3, 0), (total, 0), ((1 << 64) - 1, 0)]
+    want_off, want_status, want = host_selection(index, ranges)
+    assert (want.n_sel, want.out_len, want.n_outside) == (0, 0, 0) and want_status == [RANGE_OK] * len(ranges)
+    box, dst_off, status, summ = raw_read(gpu, index, d_in, ranges, 32)
+    assert summ == (0, 0, 0, 0, 0, 0, READ_OK, 0) and box == untouched
+    assert (dst_off[:-1], status[:-1]) == (want_off, want_status) == ([0] * len(ranges), [RANGE_OK] * len(ranges))
+
+
+@pytest.mark.parametrize("damaged", [False, True])
+@pytest.mark.parametrize("fmt", IC.WRAPPERS)
+def test_null_dst_off_and_range_status_change_no_byte(gpu, fmt, damaged):
+    """without range_status the scan of the bad flags is skipped: dst and the summary are those of the call that has both"""
+    content, s, index, d_in = edges_index(gpu, fmt)
+    outs, total = u64(index.pt_out), len(content)
+    ranges = edge_ranges(outs, total) + [(0, total)]
+    want_off, want_status, want = host_selection(index, ranges)
+    n_bad, bad_chunk = 0, 0
+    if damaged:  # one byte of the 20 000 stored ones flipped behind the build: raw deflate has no check value to miss
+        data, at = IC.flipped_stored_byte(s, 5)
+        d_in = upload(gpu, data)
+        bad_chunk = max(k for k, o in enumerate(outs) if o <= at)
+        n_bad = 0 if fmt == "raw" else 1
+    with_both = raw_read(gpu, index, d_in, ranges, want.out_len)
+    with_none = raw_read(gpu, index, d_in, ranges, want.out_len, outputs=False)
+    assert with_none[0] == with_both[0] and with_none[3] == with_both[3]
+    assert set(with_none[1]) == {POISON64} and set(with_none[2]) == {POISON64 & 0xFFFFFFFF}
+    box, dst_off, status, summ = with_both
+    assert summ[:5] == (want.n_sel, want.out_len, want.n_outside, n_bad, bad_chunk if n_bad else 0) and summ[6] == READ_OK
+    assert box[:GUARD] == box[GUARD + want.out_len:] == bytes([POISON]) * GUARD and dst_off[:-1] == want_off
+    if n_bad:
+        touched = [st == RANGE_OK and ln > 0 and lo < outs[bad_chunk + 1] and lo + ln > outs[bad_chunk] for (lo, ln), st in zip(ranges, want_status)]
+        assert status[:-1] == [RANGE_BAD_UNIT if t else st for t, st in zip(touched, want_status)] and any(touched) and not all(touched)
+    else:
+        assert status[:-1] == want_status
+        truth = content if not damaged else content[:at] + bytes([content[at] ^ 0x55]) + content[at + 1:]
+        assert box[GUARD:GUARD + want.out_len] == b"".join(truth[lo:lo + ln] for (lo, ln), st in zip(ranges, want_status) if st == RANGE_OK)
+
+
+@pytest.mark.parametrize("fmt", IC.WRAPPERS)
+def test_the_plan_read_and_the_index_read_agree(gpu, fmt):
+    """The same content as five gzip members (a plan whose units are whole members) and as one stream whose five blocks are the
+    members' content (an index at spacing 1 whose chunks are those blocks): the two reads answer the same."""
+    import compu_amd
+    import deflate_writer as W
+    import gzip_plan_cases as GP
+    from compu_amd.api import _ranges_to_device
+
+    pieces = [GP.text(3000, 1), GP.noise(1, 2), GP.text(4096, 3), GP.noise(2500, 4), GP.text(777, 5)]
+    content = b"".join(pieces)
+    cum = [sum(len(p) for p in pieces[:k]) for k in range(len(pieces) + 1)]
+    members = b"".join(GP.member(p) for p in pieces)
+    assert b"".join(zlib.decompress(GP.member(p), 31) for p in pieces) == content
+    d = W.Deflate()
+    d.dynamic(list(pieces[0])).stored(pieces[1]).fixed(list(pieces[2])).stored(pieces[3]).dynamic(list(pieces[4]), final=True)
+    one = W.wrap(d, fmt)
+    assert zlib.decompress(one.data, R.FMT[fmt]) == content
+    buf = upload(gpu, members)
+    *rows, ps = compu_amd.gzip_plan(buf, len(members))
+    index, d_in, _ = index_of(gpu, fmt, one.data, len(content), 1)
+    assert (ps.n_members, int(ps.status)) == (5, 0) and u64(rows[2]) == u64(index.pt_out) == cum[:-1] and u32(rows[3]) == [len(p) for p in pieces]
+    total = len(content)
+    ranges = [(cum[1] - 5, 10), (cum[3] - 1, 2), (cum[2], 0), (total, 0), (0, total), (total - 1, 2), (total + 5, 1), (cum[4], 1), (10, 20),
+              (cum[2] + 1, cum[3] - cum[2] - 2)]
+    want_off, want_status, want = host_selection(index, ranges)
+    assert want.n_outside == 2 and want.n_sel == 5
+    lo, ln = _ranges_to_device(ranges, gpu.device("cuda"))
+    by_plan = compu_amd.read_ranges(31, buf, *rows, lo, ln)
+    by_index = compu_amd.inflate_index_read(index, d_in, lo, ln)
+    for out, dst_off, status, summ in (by_plan, by_index):
+        assert summ.as_tuple() == (want.n_sel, want.out_len, want.n_outside, 0, 0, 0, READ_OK, 0)
+        assert (u64(dst_off), status.cpu().tolist()) == (want_off, want_status)
+        assert out.cpu().numpy().tobytes() == b"".join(content[lo:lo + ln] for (lo, ln), st in zip(ranges, want_status) if st == RANGE_OK)
+    assert gpu.equal(by_plan[0], by_index[0]) and gpu.equal(by_plan[1], by_index[1]) and gpu.equal(by_plan[2], by_index[2])
