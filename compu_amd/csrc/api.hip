@@ -180,13 +180,13 @@ int chip_decode_batch_ex(int format, uint32_t flags, size_t n, const void *in_ba
     case CHIP_FMT_DEFLATE:
     case CHIP_FMT_ZLIB:
     case CHIP_FMT_GZIP:
-    case CHIP_FMT_AUTO: e = launch_inflate(a, (hipStream_t)stream); break;
+    case CHIP_FMT_AUTO: e = launch_inflate(a, nullptr, (hipStream_t)stream); break;
     case CHIP_FMT_ZSTD: e = launch_zstd_decode(a, 0, (hipStream_t)stream); break;
     case CHIP_FMT_BROTLI: e = launch_brotli_decode(a, (hipStream_t)stream); break;  // CHIP_F_COMPU_STATUS changes nothing
     case CHIP_FMT_DETECT:
         // Detection::detect routes every unit: one pass buckets the batch by format, then each decoder runs over its own
         // (homogeneous) list of units -- all of it one critical section of the (device, stream) slot (inflate.hip)
-        e = launch_routed(a, (hipStream_t)stream);
+        e = launch_routed(a, nullptr, (hipStream_t)stream);
         break;
     default: return CHIP_E_INVALID;
     }
@@ -216,8 +216,8 @@ int chip_decode_batch_sizes(int format, uint32_t flags, size_t n, const void *in
     a.flags = flags;
     hipError_t e;
     if (format == CHIP_FMT_ZSTD) e = launch_zstd_sizes(a, out_size, 0, (hipStream_t)stream);
-    else if (format == CHIP_FMT_DETECT) e = launch_routed_sizes(a, out_size, (hipStream_t)stream);  // routed as launch_routed routes a decode batch
-    else e = launch_inflate_sizes(a, out_size, (hipStream_t)stream);
+    else if (format == CHIP_FMT_DETECT) e = launch_routed(a, out_size, (hipStream_t)stream);  // routed as a decode batch is
+    else e = launch_inflate(a, out_size, (hipStream_t)stream);
     return e == hipSuccess ? CHIP_OK : CHIP_E_LAUNCH;
 }
 
@@ -868,7 +868,7 @@ bool dec_run(chip_decoder *d)
         Meta *dm = d->d_meta;
         BatchArgs a = batch_args(d->format, 1, d->d_in, &dm->in_off, &dm->in_len, d->d_out, &dm->out_off, &dm->out_cap, &dm->out_len, &dm->in_used, &dm->status);
         a.resume = inflate ? dm->resume : d->d_zres;
-        hipError_t e = inflate  ? launch_inflate(a, d->stream)
+        hipError_t e = inflate  ? launch_inflate(a, nullptr, d->stream)
                        : brotli ? launch_brotli_decode(a, d->stream)
                                 : launch_zstd_decode(a, d->window_log_max, d->stream);
         if (e != hipSuccess) return false;

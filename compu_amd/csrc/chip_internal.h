@@ -67,19 +67,15 @@ constexpr uint32_t F_COMPU_STATUS = 1u;  // = CHIP_F_COMPU_STATUS
 constexpr uint32_t F_MEMBERS = 2u;       // = CHIP_F_MEMBERS
 
 // launchers (each only enqueues on `stream`)
-hipError_t launch_inflate(const BatchArgs &a, hipStream_t stream);
-// the size pass (chip_decode_batch_sizes): a.out_base / out_off / out_cap / out_len are not read; the decoded length of unit i goes to
-// out_size[i].  Shares the (device, stream) slot of launch_inflate.
-hipError_t launch_inflate_sizes(const BatchArgs &a, uint64_t *out_size, hipStream_t stream);
-// zstd_sizes.hip: the zstd size pass; the routed size pass (CHIP_FMT_DETECT): router + both size kernels under one lock of the slot,
-// as launch_routed
-hipError_t launch_zstd_sizes(const BatchArgs &a, uint64_t *out_size, int window_log_max, hipStream_t stream);
-hipError_t launch_route_sizes(const BatchArgs &a, uint64_t *out_size, uint32_t *sel_inflate, uint32_t *sel_zstd, uint32_t *counts, hipStream_t stream);
-hipError_t launch_routed_sizes(const BatchArgs &a, uint64_t *out_size, hipStream_t stream);
-// (inflate_sizes.hip: the launch itself, for launch_inflate_sizes, which holds the slot)
+// inflate.hip: out_size == nullptr decodes the batch.  Else the size pass (chip_decode_batch_sizes): a.out_base / out_off / out_cap /
+// out_len are not read; the decoded length of unit i goes to out_size[i].  Both share one (device, stream) slot.
+hipError_t launch_inflate(const BatchArgs &a, uint64_t *out_size, hipStream_t stream);
+// (inflate_sizes.hip: the size pass's launch itself, for launch_inflate, which holds the slot)
 hipError_t enqueue_inflate_sizes(const BatchArgs &a, uint64_t *out_size, uint32_t *scratch, uint32_t *counter, uint32_t blocks, hipStream_t stream);
 // (inflate_members.hip: the same for a CHIP_F_MEMBERS batch; out_size != nullptr launches the size pass, else the decoder)
 hipError_t enqueue_inflate_members(const BatchArgs &a, uint64_t *out_size, uint32_t *scratch, uint32_t *counter, uint32_t blocks, hipStream_t stream);
+// zstd_sizes.hip: the zstd size pass
+hipError_t launch_zstd_sizes(const BatchArgs &a, uint64_t *out_size, int window_log_max, hipStream_t stream);
 // (zstd_members.hip, zstd_members_sizes.hip: the CHIP_F_MEMBERS kernels behind launch_zstd_decode / launch_zstd_sizes)
 hipError_t launch_zstd_members(const BatchArgs &a, int window_log_max, hipStream_t stream);
 hipError_t launch_zstd_members_sizes(const BatchArgs &a, uint64_t *out_size, int window_log_max, hipStream_t stream);
@@ -88,12 +84,12 @@ hipError_t release_scratch();                 // every slot of the current devic
 void release_scratch_of(hipStream_t stream);  // the slots of one (drained) stream of the current device
 hipError_t launch_zstd_decode(const BatchArgs &a, int window_log_max, hipStream_t stream);
 // Detection-driven router of a mixed batch: appends the index of every gzip / zlib unit to sel_inflate and of every zstd
-// frame to sel_zstd (counts[0], counts[1], zeroed by the call) and answers units that are neither at once.
-hipError_t launch_route(const BatchArgs &a, uint32_t *sel_inflate, uint32_t *sel_zstd, uint32_t *counts, hipStream_t stream);
-// device scratch of a routed batch on `stream`, cached with the inflate slot: two index lists of n entries + 2 counters
-hipError_t route_scratch(hipStream_t stream, size_t n, uint32_t **sel_inflate, uint32_t **sel_zstd, uint32_t **counts);
-// a whole CHIP_FMT_DETECT batch (router + both decoders over their lists) under one lock of the (device, stream) slot
-hipError_t launch_routed(const BatchArgs &a, hipStream_t stream);
+// frame to sel_zstd (counts[0], counts[1], zeroed by the call) and answers units that are neither at once (their length to
+// out_size, the size pass's array, when that is given).
+hipError_t launch_route(const BatchArgs &a, uint64_t *out_size, uint32_t *sel_inflate, uint32_t *sel_zstd, uint32_t *counts, hipStream_t stream);
+// a whole CHIP_FMT_DETECT batch (router + both decoders over their lists, or with out_size both size kernels) under one lock of the
+// (device, stream) slot, with which the router's scratch is cached
+hipError_t launch_routed(const BatchArgs &a, uint64_t *out_size, hipStream_t stream);
 hipError_t launch_detect(size_t n, const uint8_t *in_base, const uint64_t *in_off, const uint32_t *in_len, int32_t *kind,
                          hipStream_t stream);
 hipError_t launch_deflate_l1(const BatchArgs &a, int level, uint32_t flags, uint32_t check_seed, uint64_t total_before,

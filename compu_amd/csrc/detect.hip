@@ -39,23 +39,14 @@ __global__ void route_sizes_kernel(BatchArgs a, uint64_t *out_size, uint32_t *se
     route_unit(a, out_size, sel_inflate, sel_zstd, counts);
 }
 
-hipError_t launch_route(const BatchArgs &a, uint32_t *sel_inflate, uint32_t *sel_zstd, uint32_t *counts, hipStream_t stream)
+hipError_t launch_route(const BatchArgs &a, uint64_t *out_size, uint32_t *sel_inflate, uint32_t *sel_zstd, uint32_t *counts, hipStream_t stream)
 {
     if (a.n == 0) return hipSuccess;
     hipError_t e = hipMemsetAsync(counts, 0, 8, stream);
     if (e != hipSuccess) return e;
     uint32_t blocks = (a.n + 255u) / 256u;
-    hipLaunchKernelGGL(route_kernel, dim3(blocks), dim3(256), 0, stream, a, sel_inflate, sel_zstd, counts);
-    return hipGetLastError();
-}
-
-hipError_t launch_route_sizes(const BatchArgs &a, uint64_t *out_size, uint32_t *sel_inflate, uint32_t *sel_zstd, uint32_t *counts, hipStream_t stream)
-{
-    if (a.n == 0) return hipSuccess;
-    hipError_t e = hipMemsetAsync(counts, 0, 8, stream);
-    if (e != hipSuccess) return e;
-    uint32_t blocks = (a.n + 255u) / 256u;
-    hipLaunchKernelGGL(route_sizes_kernel, dim3(blocks), dim3(256), 0, stream, a, out_size, sel_inflate, sel_zstd, counts);
+    if (out_size) hipLaunchKernelGGL(route_sizes_kernel, dim3(blocks), dim3(256), 0, stream, a, out_size, sel_inflate, sel_zstd, counts);
+    else hipLaunchKernelGGL(route_kernel, dim3(blocks), dim3(256), 0, stream, a, sel_inflate, sel_zstd, counts);
     return hipGetLastError();
 }
 

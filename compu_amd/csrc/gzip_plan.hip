@@ -7,11 +7,11 @@
 // ("The container plan") with the format below and a describe phase of its own.
 //   candidates  every byte position is tested in 16-byte loads for `1f 8b 08` and a FLG byte without reserved bits
 //   describe    gzip_room_kernel: in_len of candidate i = what lies behind it, at most CHIP_GZPLAN_WINDOW;
-//               launch_inflate_sizes(): one wave per candidate, all members (and all decoys) in parallel, pos[] is the batch's in_off;
+//               launch_inflate() with out_size: one wave per candidate, all members (and all decoys) in parallel, pos[] is the batch's in_off;
 //               gzip_convert_kernel: (status, out_size, in_used) becomes end / cap / verdict by the rules of the walk
 // What the marking never reaches is a decoy: header bytes inside a stored block, a whole member inside an FEXTRA field, an MTIME
 // that spells the magic.  A decoy's size pass ends with an error or at the end of the buffer like any damaged unit's.
-// Locks: the plan's cache first, then the inflate slot's (launch_inflate_sizes takes it itself), the order read_ranges.hip has;
+// Locks: the plan's cache first, then the inflate slot's (launch_inflate takes it itself), the order read_ranges.hip has;
 // nothing in inflate.hip takes a plan's lock.
 #include "chip_internal.h"
 #include "launch_slots.h"
@@ -139,7 +139,7 @@ struct SizePassDescribe {
         a.status = s.status;
         a.n = n_cand;
         a.format = CHIP_FMT_GZIP;
-        const hipError_t e = launch_inflate_sizes(a, s.out_size, stream);
+        const hipError_t e = launch_inflate(a, s.out_size, stream);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(gzip_convert_kernel, cgrid, dim3(256), 0, stream, base, len, pos, n_cand, (const uint32_t *)s.in_len,
                            (const int32_t *)s.status, (const uint64_t *)s.out_size, (const uint32_t *)s.in_used, end, cap, info, ds);

@@ -1,9 +1,8 @@
 // The checkpoint index of ONE large deflate stream, its build: chip_inflate_index_build.
 //
-// The build is a decode that takes notes.  inflate_index_kernel is inflate.hip's unit loop compiled with the recording
+// The build is a decode that takes notes.  inflate_index_kernel is inflate_unit.h's unit loop compiled with the recording
 // (CHIP_INFLATE_INDEX, see inflate_unit there): one wave decodes the unit as inflate_kernel would and stores the (bit, out) of every
-// block boundary that is a point.  It has a translation unit of its own for the reason inflate_sizes.hip and inflate_members.hip
-// have one: inflate_kernel and the three kernels next to it must come out of the build as they were.  Behind it, in stream order:
+// block boundary that is a point.  This translation unit keeps the recording out of the batch kernels.  Behind it, in stream order:
 //   windows   index_windows_kernel: per stored point the up to 32 KiB of content in front of it, out of the decoded output
 //   checks    index_checks_kernel: one wave runs the stream's check (CRC-32 / Adler-32) from point to point over the decoded output,
 //             every step wave-parallel (wave_crc32 / wave_adler32 with the previous point's value as seed), and to the end of a
@@ -11,12 +10,19 @@
 //             it); a pass of its own reads the output once more at a few percent of what the one-wave decode costs.
 // The read side (chip_inflate_index_read, chip_inflate_index_units_host) is in read_ranges.hip.
 #define CHIP_INFLATE_INDEX 1
-#include "inflate.hip"
+#include "inflate_unit.h"
 
 #include "pack_copy.h"
 #include "plan_common.h"
 
 namespace chip {
+
+// ONE wave decodes the one unit and records its points
+__global__ __launch_bounds__(64, CHIP_WAVES_PER_SIMD) void inflate_index_kernel(BatchArgs a, IndexRec ix, uint32_t *scratch)
+{
+    __shared__ WaveLds L;
+    inflate_unit<false>(a, 0, L, scratch, nullptr, ix);
+}
 
 namespace {
 

@@ -493,7 +493,7 @@ struct IndexSource {
                            (const uint64_t *)content_off, ba.out_base);
         BatchArgs r = ba;  // the chunks as resumed units, each into its slot
         r.out_off = slot_off, r.out_cap = slot_cap, r.resume = resume;
-        const hipError_t e = launch_inflate(r, stream);
+        const hipError_t e = launch_inflate(r, nullptr, stream);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(ix_verify_kernel, grid256(n_sel), dim3(256), 0, stream, pt_bit, pt_check, n, unit, ba.in_off, (const uint32_t *)slot_cap,
                            (const uint32_t *)resume, (const uint32_t *)ba.out_len, (const int32_t *)ba.status, n_sel, flag, ds);

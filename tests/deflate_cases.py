@@ -10,7 +10,7 @@ from collections import namedtuple
 
 import deflate_writer as W
 
-# compu_amd/csrc/inflate.hip
+# compu_amd/csrc/inflate_unit.h
 S_BITS = 320            # a lane's walk segment
 XT_BITS = 1536          # how far a lane walks past its segment (dynamic blocks)
 XT_BITS_FIXED = 3072    # (fixed blocks)

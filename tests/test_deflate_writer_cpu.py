@@ -131,7 +131,7 @@ def _src(path):
 
 def test_geometry_constants_are_the_kernels():
     """the edges the cases are placed around move with the kernel's geometry: a change there must fail here, not quietly"""
-    inf, api = _src("compu_amd/csrc/inflate.hip"), _src("compu_amd/csrc/api.hip")
+    inf, api = _src("compu_amd/csrc/inflate_unit.h"), _src("compu_amd/csrc/api.hip")
 
     def define(name):
         return int(re.search(rf"#define {name} (\d+)", inf).group(1))

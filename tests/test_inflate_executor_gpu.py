@@ -1,4 +1,4 @@
-"""The LZ77 executor of the inflate kernel (flush_tokens / round_issue / round_finish / lds_put in compu_amd/csrc/inflate.hip)
+"""The LZ77 executor of the inflate kernel (flush_tokens / round_issue / round_finish / lds_put in compu_amd/csrc/inflate_unit.h)
 against the oracle, on streams built here from zlib and from hand-made bit streams (tests/deflate_writer.py), as raw deflate and
 as gzip, at all four byte misalignments of the output:
 

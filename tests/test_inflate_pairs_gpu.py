@@ -1,4 +1,4 @@
-"""Literal pairs in the inflate kernel (compu_amd/csrc/inflate.hip: the walk's `token` step, flush_tokens, count_tokens,
+"""Literal pairs in the inflate kernel (compu_amd/csrc/inflate_unit.h: the walk's `token` step, flush_tokens, count_tokens,
 overflow_bit): a literal token may carry the literal behind it, and nothing a caller sees may change for it.  Streams are built
 with tests/deflate_writer.py and run as raw deflate and as gzip at output misalignments 0-3:
 

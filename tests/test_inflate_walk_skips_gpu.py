@@ -1,4 +1,4 @@
-"""Wave-uniform skips in the inflate walk's step (compu_amd/csrc/inflate.hip, walk_round's `token`).  The sub-table read of a
+"""Wave-uniform skips in the inflate walk's step (compu_amd/csrc/inflate_unit.h, walk_round's `token`).  The sub-table read of a
 distance code of more than 8 bits runs only in a step in which some lane has one; the pair's mark bit, which is always 0 for a
 second code that starts inside the lane's own segment, is still read in every step (a skip of that read was built and measured
 slower, profiles/walk_skips_ab.md), and the cases that would break such a skip stay here for whoever tries it again.  No skip

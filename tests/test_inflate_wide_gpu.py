@@ -1,4 +1,4 @@
-"""The 16-byte accesses of the inflate kernel and its walk step's table layout (compu_amd/csrc/inflate.hip: the chunk store at the
+"""The 16-byte accesses of the inflate kernel and its walk step's table layout (compu_amd/csrc/inflate_unit.h: the chunk store at the
 end of flush_tokens, the window staging at the top of walk_round, the `token` step and the tables it reads).
 
   * chunk store: decoded lengths around 16, 1 024 (one wide trip) and 2 560 (CHUNK_BYTES), every unit at every output offset
