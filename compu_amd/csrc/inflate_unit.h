@@ -1167,6 +1167,14 @@ __device__ CHIP_PHASE_FN uint32_t walk_round(WaveLds &L, const InWin &w, const u
     uint32_t q = s0 - wbase, tl = 0, nst = 0;
     uint32_t jb = 0, z = 0;  // of the lane's last token: join bit, halt flags
     bool run = s0 < end_bit;
+    // nx = the stream's bits from q on, of which a step uses the low 15: the 9 of the root index and the at most 6 of a sub-table's.
+    // Every step leaves them for the next one out of the 64 bits it holds anyway, so that the next step's two table reads start
+    // from a register and not from its window read, which lands while they are in flight.
+    uint32_t nx;
+    {
+        const uint32_t *wp = (const uint32_t *)((const uint8_t *)L.w.win + ((q >> 3) & ~3u));
+        nx = __builtin_amdgcn_alignbit(wp[1], wp[0], q);
+    }
     // A token's work is straight-line code; a lane whose token cannot be taken (it joined another chain, met an end-of-block or
     // invalid code, or the token ends behind `hard`) drops out with jb / z / pn as that step left them: the reason is read off them
     // after the loop.
@@ -1180,26 +1188,31 @@ __device__ CHIP_PHASE_FN uint32_t walk_round(WaveLds &L, const InWin &w, const u
         const uint32_t *wp = (const uint32_t *)((const uint8_t *)L.w.win + a);
         const uint32_t d0 = wp[0], d1 = wp[1], d2 = wp[2];
         const uint32_t lo = __builtin_amdgcn_alignbit(d1, d0, p), hi = __builtin_amdgcn_alignbit(d2, d1, p);
-        const uint32_t r = L.lit_root[lo & ((1u << LIT_ROOT) - 1u)];
-        const uint32_t e = pool_at(L, r, lo);
+        const uint32_t r = L.lit_root[nx & ((1u << LIT_ROOT) - 1u)];  // (nx and lo agree in their low 16 bits)
+        const uint32_t e = pool_at(L, r, nx);
         const uint32_t n1 = __builtin_amdgcn_ubfe(e, 10, 5);
         const uint32_t msk = (uint32_t)((int32_t)e >> 31);  // all ones for a length code
         const uint32_t w2 = __builtin_amdgcn_alignbit(hi, lo, n1);
         uint32_t m = L.dist_root[w2 & ((1u << DIST_ROOT) - 1u)] & msk;
+#ifndef CHIP_EXP_NO_PAIR
+        // A literal takes the literal behind it along as one token (a pair) when there is one, it ends inside the chain's limit, and
+        // its start is no boundary of the segment's owner: a chain that pairs across the owner's boundary walks one literal out of
+        // phase with the owner and cannot join before the run of literals ends.  (Inside its own segment a lane sees no mark in
+        // front of it.)  Whatever else the second code is, the literal goes alone, and that code is met as a token's first.
+        // The second code's root entry and its mark word have their addresses as soon as n1 is known: both reads go out beside the
+        // distance root's, in front of the branch below, and share its wait (one LDS round trip, not two).
+        const uint32_t p2 = p + n1;
+        const uint32_t r2 = L.lit_root[w2 & ((1u << LIT_ROOT) - 1u)];
+        const uint32_t mw2 = *(const uint32_t *)((const uint8_t *)L.w.bm + ((p2 >> 3) & ~3u));
+#endif
         // a distance code of more than 8 bits (1 % of the matches) goes through its sub-table: five steps in six have no such lane
         if (__any((m & D_LONG) != 0)) {
             asm volatile("; long distance codes");  // (keeps the skip: the compiler would issue the short region in every step)
             if (m & D_LONG) m = dist_sub_at(L, m, w2);
         }
 #ifndef CHIP_EXP_NO_PAIR
-        // A literal takes the literal behind it along as one token (a pair) when there is one, it ends inside the chain's limit, and
-        // its start is no boundary of the segment's owner: a chain that pairs across the owner's boundary walks one literal out of
-        // phase with the owner and cannot join before the run of literals ends.  (Inside its own segment a lane sees no mark in
-        // front of it.)  Whatever else the second code is, the literal goes alone, and that code is met as a token's first.
-        const uint32_t r2 = L.lit_root[w2 & ((1u << LIT_ROOT) - 1u)];
         const uint32_t e2 = pool_at(L, r2, w2);
-        const uint32_t p2 = p + n1;
-        const uint32_t mk2 = __builtin_amdgcn_ubfe(*(const uint32_t *)((const uint8_t *)L.w.bm + ((p2 >> 3) & ~3u)), p2, 1);
+        const uint32_t mk2 = __builtin_amdgcn_ubfe(mw2, p2, 1);
 #endif
         const uint32_t cl2 = m & 15u, eb2 = __builtin_amdgcn_ubfe(m, 4, 4);
         // (only a token that is taken uses dm1: its entry has neither D_BAD nor D_LONG, so what lies above bit 8 is the mantissa)
@@ -1214,6 +1227,10 @@ __device__ CHIP_PHASE_FN uint32_t walk_round(WaveLds &L, const InWin &w, const u
 #else
         const uint32_t pr = 0;
 #endif
+        // hi:lo is 64 bits from p on.  A token has at most 48: a match's length code of 15 bits and 5 extra ones (n1 <= 20), then a
+        // distance code of 15 bits and 13 extra ones; a pair has 15 + 15.  That leaves at least 16 bits of the next position.
+        static_assert((15 + 5) + (15 + 13) == 48 && 64 - 48 >= LIT_ROOT + (15 - LIT_ROOT), "the next step's index bits are in hi:lo");
+        nx = (uint32_t)((((uint64_t)hi << 32) | lo) >> (tl & 63u));
         q = p + tl;
         if ((jb | z) != 0 || q > hard_r) return false;
         const uint32_t v = __builtin_amdgcn_ubfe(lo, e, e >> 5) + __builtin_amdgcn_ubfe(e, 16, 10);  // (a length's entry brings the match bit)
