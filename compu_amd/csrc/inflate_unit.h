@@ -58,10 +58,11 @@ __device__ __forceinline__ GAS T *rdfirst_gptr(T *p)
 #define STAT_ARG
 #endif
 // stat slots (cycles): 0 other header work, 1 walk set-up (first window chunks), 2 walk, 3 path resolve, 4 code lengths (+ block
-// header), 5 table build, 6 checksum/trailer, 7 flush preparation (piece entry ranks), 16 token groups (fetch, placement,
+// header), 5 table build, 6 checksum/trailer, 16 token groups (fetch, placement,
 // literals, match queue), 17 match rounds, 18 chunk store, 20 rest of the flush; (counts): 8 walk rounds (macro-rounds), 9 pieces
 // on the path, 10 tokens, 11 walk trips (8 tokens each), 12 parallel copy passes, 13 chunks, 14 match rounds, 15 matches
-// copied by the whole wave, 19 pieces claimed, 21 lane-tokens decoded by the walk
+// copied by the whole wave, 21 lane-tokens decoded by the walk; block headers: 7 rounds of the code-length loop, 19 passes of the
+// counting sort, 22 / 23 trips of the literal/length / distance sub-table fill
 
 // ---- code-length alphabet: table entry format of round 1 (one level, 7-bit root) --------------------
 // [3:0] code length, [31:16] symbol
@@ -274,7 +275,7 @@ __device__ __forceinline__ uint32_t canon_index_in(const HuffMeta &H, const Cano
 // Code lengths -> canonical description H and the symbols in canonical order (RFC 1951 sec. 3.2.2), with zlib's acceptance
 // rules.  Wave-cooperative; lens[], count[] live in LDS.  Returns 0, -1 (invalid set) or 1 (empty set); uniform.
 template <typename SortedT, typename MakeT>
-__device__ __forceinline__ int canon_prep(uint32_t *count, const uint8_t *lens, int n_, bool code_lengths, SortedT *sorted, HuffMeta &H, MakeT make)
+__device__ __forceinline__ int canon_prep(uint32_t *count, const uint8_t *lens, int n_, bool code_lengths, SortedT *sorted, HuffMeta &H, MakeT make STAT_PARAM)
 {
     const uint32_t lane = lane_id();
     const int n = (int)rdfirst((uint32_t)n_);
@@ -297,45 +298,56 @@ __device__ __forceinline__ int canon_prep(uint32_t *count, const uint8_t *lens, 
     const uint32_t maxlen = present ? 31u - (uint32_t)__clz((int)present) : 0u;
     const bool over = __any(lane <= 15 && lim > 32768u);
     const int left = rdlane(lim, 15) < 32768u ? 1 : 0;
-    uint32_t mynext = off;
     if (lane <= 15) {
         H.limit15[lane] = lim;
         H.offs[lane] = off;
+        count[lane] = off;  // from here on: the place in sorted[] of the next symbol of length `lane`
     }
     if (lane == 0) H.maxlen = maxlen;
     WSYNC();
     if (maxlen == 0) return 1;
     if (over) return -1;
     if (left > 0 && (code_lengths || maxlen != 1)) return -1;
-    // stable counting sort by (length, symbol)
+    // stable counting sort by (length, symbol), 64 symbols per pass.  `same` = the lanes whose length equals this lane's: four
+    // ballots, one per bit of the length, each taken as it stands or complemented.  The lane's rank among them is its place
+    // behind count[l]; the last lane of each length moves count[l] on for the next pass.
     for (int base = 0; base < n; base += 64) {
-        int s = base + (int)lane;
-        uint32_t l = s < n ? lens[s] : 0;
-        for (uint32_t pm = present & 0xfffeu; pm; pm &= pm - 1u) {  // the lengths that occur
-            const uint32_t ll = (uint32_t)__builtin_ctz(pm);
-            uint64_t m = __ballot(l == ll);
-            uint32_t bp = rdlane(mynext, ll);
-            if (l == ll) sorted[bp + __popcll(m & lanemask_lt())] = make((uint32_t)s, l);
-            if (lane == ll) mynext += __popcll(m);
+        STAT_ADD(19, 1);
+        const int s = base + (int)lane;
+        const uint32_t l = s < n ? lens[s] : 0;
+        uint64_t same = ~0ull;
+#pragma unroll
+        for (uint32_t b = 0; b < 4; b++) {
+            const bool bit = (l >> b) & 1u;
+            const uint64_t m = __ballot(bit);
+            same &= bit ? m : ~m;
         }
+        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(same >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)same, 0u));
+        const uint32_t cnt = (uint32_t)__popcll(same);
+        const uint32_t at = count[l];
+        if (l) sorted[at + rank] = make((uint32_t)s, l);
+        if (l && rank + 1u == cnt) count[l] = at + cnt;
+        LSYNC();
     }
     WSYNC();
     return 0;
 }
 
 // The code-length alphabet's one-level table (zlib: a set made only of zeros reads as symbol 0 of length 1).
-__device__ CHIP_PHASE_FN int build_cl_table(WaveLds &L)
+__device__ CHIP_PHASE_FN int build_cl_table(WaveLds &L STAT_PARAM)
 {
     const uint32_t lane = lane_id();
     HuffMeta &H = L.hdr.cl_h;
-    const int r = canon_prep(L.hdr.count, L.hdr.lens, 19, true, L.hdr.cl_sorted, H, [](uint32_t s, uint32_t l) { return mk_entry(l, 0, K_LIT, s); });
+    const int r = canon_prep(L.hdr.count, L.hdr.lens, 19, true, L.hdr.cl_sorted, H, [](uint32_t s, uint32_t l) { return mk_entry(l, 0, K_LIT, s); } STAT_ARG);
     if (r < 0) return -1;
+    const CanonLim CL = canon_limits(H);
     for (uint32_t idx = lane; idx < (1u << CL_ROOT); idx += 64) {
         uint32_t e = mk_entry(1, 0, K_LIT, 0);
         if (r == 0) {
             uint32_t l;
-            const uint32_t ci = canon_index(H, __brev(idx) >> 17, l);  // codes are at most 7 bits: the root covers them all
-            e = ci == 0xffffffffu ? mk_entry(H.maxlen, 0, K_BAD, 0) : L.hdr.cl_sorted[ci];
+            const uint32_t x15 = __brev(idx) >> 17;  // codes are at most 7 bits: the root covers them all
+            const uint32_t ci = canon_index_in<1, CL_ROOT>(H, CL, x15 < CL.lim[15] ? x15 : 0u, l);
+            e = x15 < CL.lim[15] ? L.hdr.cl_sorted[ci] : mk_entry(rdfirst(H.maxlen), 0, K_BAD, 0);
         }
         L.hdr.cl_lut[idx] = e;
     }
@@ -343,19 +355,42 @@ __device__ CHIP_PHASE_FN int build_cl_table(WaveLds &L)
     return 0;
 }
 
+// Sub-table fill: one entry per lane and trip over the concatenation of a batch's sub-tables (`total` entries, flat index f).  A
+// lane that holds a root prefix (have) owns the 2^sb entries from flat index `start` on.  Per trip of 64 flat indices every
+// prefix that begins in the trip, or runs into it from the trip before, drops a head word (lane + 1, start, sb) at its first
+// index of the trip in heads[] (64 words of LDS); a running maximum hands every index the head in front of it, its owner's.
+// put(f, p, t, sb): flat index f is entry t of lane p's sub-table of 2^sb entries.
+static_assert(POOL_U16 <= 0x2000u, "a head word holds a flat index in 13 bits");
+template <typename PutT>
+__device__ __forceinline__ void fill_flat(uint32_t *heads, bool have, uint32_t sb, uint32_t start, uint32_t total, PutT put)
+{
+    const uint32_t lane = lane_id();
+    const uint32_t end = have ? start + (1u << sb) : 0u;
+    const uint32_t head = ((lane + 1u) << 16) | (start << 3) | sb;  // start < 2^13 (POOL_U16), sb < 8
+    for (uint32_t f0 = 0; f0 < total; f0 += 64) {
+        heads[lane] = 0;
+        if (end > f0 && start < f0 + 64u) heads[start > f0 ? start - f0 : 0u] = head;
+        LSYNC();
+        const uint32_t h = wave_incl_max_scan(heads[lane]);
+        LSYNC();  // (the next trip's stores stay behind this read)
+        const uint32_t f = f0 + lane;
+        if (f < total) put(f, (h >> 16) - 1u, f - ((h >> 3) & 0x1fffu), h & 7u);
+    }
+}
+
 // Literal/length tables of a block from lens[0..n).  Returns 0, -1 (invalid set), or 1 (the codes' entries do not fit pool[]: cannot
 // happen, see POOL_WORDS).  `used` = words of pool[] taken.
-__device__ CHIP_PHASE_FN int build_litlen(WaveLds &L, const uint8_t *lens, int n, uint32_t &used)
+__device__ CHIP_PHASE_FN int build_litlen(WaveLds &L, const uint8_t *lens, int n, uint32_t &used STAT_PARAM)
 {
     const uint32_t lane = lane_id();
     HuffMeta &H = L.hdr.lit_h;
     uint16_t *const sorted = L.hdr.lit_sorted;
-    const int r = canon_prep(L.hdr.count, lens, n, false, sorted, H, [](uint32_t s, uint32_t) { return (uint16_t)s; });
+    const int r = canon_prep(L.hdr.count, lens, n, false, sorted, H, [](uint32_t s, uint32_t) { return (uint16_t)s; } STAT_ARG);
     if (r != 0) return -1;  // no literal/length code at all cannot be: the end-of-block code exists
     const CanonLim CL = canon_limits(H);
     const uint32_t lim_r = CL.lim[LIT_ROOT], top = CL.lim[15];
     const uint32_t nshort = rdfirst(H.offs[LIT_ROOT + 1 <= 15 ? LIT_ROOT + 1 : 15]);  // symbols with codes of up to nine bits come first
-    const uint32_t nsym = rdfirst(H.offs[15]) + rdfirst(L.hdr.count[15]);
+    const uint32_t nsym = rdfirst(L.hdr.count[15]);  // where the sort's place for 15-bit codes ended: behind the last symbol
     const uint32_t nfirst = rdfirst(H.maxlen) <= (uint32_t)LIT_ROOT ? nsym : nshort;
     if (nfirst + 1 > POOL_WORDS) return 1;
     for (uint32_t i = lane; i < nfirst; i += 64) {
@@ -393,18 +428,17 @@ __device__ CHIP_PHASE_FN int build_litlen(WaveLds &L, const uint8_t *lens, int n
             const uint32_t off = used + incl - size;
             const uint32_t total = rdlane(incl, 63);
             if (used + total > POOL_WORDS) return 1;
-            if (have) {
-                for (uint32_t t = 0; t < size; t++) {
-                    const uint32_t x15 = sb ? xj + ((__brev(t) >> (32 - sb)) << (15 - LIT_ROOT - sb)) : xj;
-                    uint32_t l, e = bad_e;
-                    if (x15 < top) {
-                        const uint32_t s = sorted[canon_index_in<LIT_ROOT + 1, 15>(H, CL, x15, l)];
-                        e = make_final(s, l);
-                    }
-                    L.pool[off + t] = e;
+            STAT_ADD(22, (total + 63u) / 64u);
+            if (have) L.lit_root[__brev(xj >> (15 - LIT_ROOT)) >> (32 - LIT_ROOT)] = (uint16_t)((off << 5) | sb);
+            fill_flat(L.hdr.cl_lut, have, sb, incl - size, total, [&](uint32_t f, uint32_t p, uint32_t t, uint32_t b) {
+                const uint32_t x15 = lim_r + (j0 + p) * P + ((__brev(t) >> (32 - b)) << (15 - LIT_ROOT - b));
+                uint32_t l, e = bad_e;
+                if (x15 < top) {
+                    const uint32_t s = sorted[canon_index_in<LIT_ROOT + 1, 15>(H, CL, x15, l)];
+                    e = make_final(s, l);
                 }
-                L.lit_root[__brev(xj >> (15 - LIT_ROOT)) >> (32 - LIT_ROOT)] = (uint16_t)((off << 5) | sb);
-            }
+                L.pool[used + f] = e;
+            });
             used += total;
         }
     }
@@ -413,12 +447,12 @@ __device__ CHIP_PHASE_FN int build_litlen(WaveLds &L, const uint8_t *lens, int n
 }
 
 // Distance tables from lens[0..n); `used` = pool words the literal/length tables took.  Returns 0, -1 or 1 as build_litlen.
-__device__ CHIP_PHASE_FN int build_dist(WaveLds &L, const uint8_t *lens, int n, uint32_t used)
+__device__ CHIP_PHASE_FN int build_dist(WaveLds &L, const uint8_t *lens, int n, uint32_t used STAT_PARAM)
 {
     const uint32_t lane = lane_id();
     HuffMeta &H = L.hdr.dist_h;
     uint16_t *const sorted = L.hdr.dist_sorted;
-    const int r = canon_prep(L.hdr.count, lens, n, false, sorted, H, [](uint32_t s, uint32_t) { return (uint16_t)s; });
+    const int r = canon_prep(L.hdr.count, lens, n, false, sorted, H, [](uint32_t s, uint32_t) { return (uint16_t)s; } STAT_ARG);
     if (r < 0) return -1;
     if (r == 1) {  // no distance code: zlib accepts the block, every match is invalid
         for (uint32_t idx = lane; idx < (1u << DIST_ROOT); idx += 64) L.dist_root[idx] = (uint16_t)(1u | D_BAD);
@@ -455,19 +489,18 @@ __device__ CHIP_PHASE_FN int build_dist(WaveLds &L, const uint8_t *lens, int n, 
             const uint32_t incl = wave_incl_scan(size);
             const uint32_t total = rdlane(incl, 63);
             if (2 * used + used16 + total > POOL_U16) return 1;
+            STAT_ADD(23, (total + 63u) / 64u);
             const uint32_t base16 = POOL_U16 - used16 - incl;  // sub-tables grow downwards from the top
-            if (have) {
-                for (uint32_t t = 0; t < size; t++) {
-                    const uint32_t x15 = sb ? xj + ((__brev(t) >> (32 - sb)) << (15 - DIST_ROOT - sb)) : xj;
-                    uint32_t l, e = maxlen | D_BAD;
-                    if (x15 < top) {
-                        const uint32_t s = sorted[canon_index_in<DIST_ROOT + 1, 15>(H, CL, x15, l)];
-                        e = make_dist16(s, l);
-                    }
-                    pool16[base16 + t] = (uint16_t)e;
+            if (have) L.dist_root[__brev(xj >> (15 - DIST_ROOT)) >> (32 - DIST_ROOT)] = (uint16_t)(D_LONG | sb | ((2u * base16 - DIST_SUB_BYTES) << 3));
+            fill_flat(L.hdr.cl_lut, have, sb, incl - size, total, [&](uint32_t f, uint32_t p, uint32_t t, uint32_t b) {
+                const uint32_t x15 = lim_r + (j0 + p) * P + ((__brev(t) >> (32 - b)) << (15 - DIST_ROOT - b));
+                uint32_t l, e = maxlen | D_BAD;
+                if (x15 < top) {
+                    const uint32_t s = sorted[canon_index_in<DIST_ROOT + 1, 15>(H, CL, x15, l)];
+                    e = make_dist16(s, l);
                 }
-                L.dist_root[__brev(xj >> (15 - DIST_ROOT)) >> (32 - DIST_ROOT)] = (uint16_t)(D_LONG | sb | ((2u * base16 - DIST_SUB_BYTES) << 3));
-            }
+                pool16[POOL_U16 - used16 - (f - t) - (1u << b) + t] = (uint16_t)e;  // the owner's base16, entry t
+            });
             used16 += total;
         }
     }
@@ -1673,20 +1706,22 @@ next_member:
             }
             WSYNC();
             pos += 3 * ncode;
-            if (build_cl_table(L)) {
+            if (build_cl_table(L STAT_ARG)) {
                 status = Z_DATA_ERROR;
                 break;
             }
             // Code lengths of the two alphabets, 64 bit positions per round: lane i decodes the code-length symbol
             // that would start at bit pos + i; the symbols really present are the chain 0 -> 0 + bits(0) -> ...,
-            // followed with scalar readlanes; a prefix sum of the run lengths along the chain gives every symbol
+            // found by pointer doubling; a prefix sum of the run lengths along the chain gives every symbol
             // its place in lens[], and a running maximum hands each "repeat previous" symbol the last explicit
             // length in front of it.  (zlib reads these one by one; errors keep its order: the first bad symbol.)
             uint32_t have = 0, total = nlen + ndist, prevlen = 0;
             win_ensure(L, w, pos, 316 * 14 + 160);
-            for (uint32_t k = lane; k < 320; k += 64) L.hdr.lens[k] = 0;  // zero runs (17/18) then need no stores
+            static_assert(offsetof(WaveLds, hdr.lens) % 4 == 0 && sizeof(L.hdr.lens) == 320, "lens[] is zeroed a dword at a time");
+            for (uint32_t k = lane; k < 320 / 4; k += 64) ((uint32_t *)L.hdr.lens)[k] = 0;  // zero runs (17/18) then need no stores
             WSYNC();
             while (have < total) {
+                STAT_ADD(7, 1);
                 const uint32_t bp = pos + lane;
                 uint32_t lo, hi;
                 win_bits(L, w, bp, lo, hi);
@@ -1697,7 +1732,9 @@ next_member:
                 const uint32_t run = sym < 16 ? 1u : (sym == 18 ? 11u : 3u) + bfe(lo, cl, eb);
                 const uint32_t nx = lane + tl;
                 // The symbols really present start at 0, nx(0), nx(nx(0)), ...: lane n finds the n-th of these positions (powers of nx
-                // by doubling, composed along the bits of n; 64 = the chain has left the 64 positions) and flags it.
+                // by doubling, composed along the bits of n; 64 = the chain has left the 64 positions) and flags it.  (Measured and
+                // not kept, profiles/block_headers_ab.md: fewer doubling steps by the shortest code, the chain followed with scalar
+                // lane reads, flags pushed through LDS with one gather per step.)
                 uint32_t nth = 0;
                 {
                     uint32_t pw = nx < 64u ? nx : 64u;
@@ -1752,8 +1789,8 @@ next_member:
         if (build) {
             eob_len = rdfirst(L.hdr.lens[256]);
             uint32_t used = 0;
-            const int r1 = build_litlen(L, L.hdr.lens, (int)nlen, used);
-            const int r2 = r1 ? r1 : build_dist(L, L.hdr.lens + nlen, (int)ndist, used);
+            const int r1 = build_litlen(L, L.hdr.lens, (int)nlen, used STAT_ARG);
+            const int r2 = r1 ? r1 : build_dist(L, L.hdr.lens + nlen, (int)ndist, used STAT_ARG);
             if (r1 || r2) {  // an invalid set of code lengths (the pool cannot overflow: see POOL_WORDS)
                 status = Z_DATA_ERROR;
                 break;

@@ -33,13 +33,14 @@ b.record()
 torch.cuda.synchronize()
 assert (st == 2).all() and torch.equal(d_out, torch.from_numpy(pay).to(dev))
 s = stats.cpu().numpy().reshape(n, 24).astype(np.float64)
-names = ["hdr other", "window load", "walk", "resolve", "hdr:codelens", "hdr:build", "trailer", "-", "super-rounds", "path pieces", "tokens", "walk trips", "copy passes",
-         "chunks", "match rounds", "wave copies", "fl:token groups", "fl:match rounds", "fl:chunk store", "-", "fl:tail", "lanes walking", "-", "-"]
-tot = s[:, :8].sum(axis=1).mean() + s[:, 16:21].sum(axis=1).mean()
+names = ["hdr other", "window load", "walk", "resolve", "hdr:codelens", "hdr:build", "trailer", "cl rounds", "super-rounds", "path pieces", "tokens", "walk trips", "copy passes",
+         "chunks", "match rounds", "wave copies", "fl:token groups", "fl:match rounds", "fl:chunk store", "sort passes", "fl:tail", "lanes walking", "lit fill trips", "dist fill trips"]
+CYCLES = [0, 1, 2, 3, 4, 5, 6, 16, 17, 18, 20]  # the slots that hold cycles; the others are counts
+tot = s[:, CYCLES].sum(axis=1).mean()
 print(f"kind={kind} units={n} kernel={a.elapsed_time(b):.3f} ms; mean cycles/unit {tot:.0f}")
 for i, nm in enumerate(names):
     if nm == "-":
         continue
     m = s[:, i].mean()
-    print(f"  {nm:14s} {m:12.1f}" + (f"  ({100 * m / tot:5.1f}%)" if (i < 8 or i >= 16) else ""))
+    print(f"  {nm:15s} {m:12.2f}" + (f"  ({100 * m / tot:5.1f}%)" if i in CYCLES else ""))
 print(f"  super-rounds/unit {s[:, 8].mean():.2f}; walk trips/unit {s[:, 11].mean():.0f} (x4 tokens); lanes on the path per super-round {s[:, 9].sum() / s[:, 8].sum():.1f}; tokens/unit {s[:, 10].mean():.0f}; passes per match round {s[:, 12].sum() / max(1, s[:, 14].sum()):.2f}")
