@@ -492,7 +492,7 @@ ZE_FN bool huf_write_tree(Work &w, Out &o, uint32_t nw, uint32_t maxl, uint32_t 
     uint32_t nsym = 13;
     while (!wc[nsym - 1]) nsym--;
     const uint32_t tl = 6;
-    int16_t norm[13];
+    int16_t norm[13] = {0};
     fse_normalize(wc, nsym, nw, tl, norm);
     fse_build_ct(w, w.wct, norm, nsym, tl);
     const uint32_t hdr = o.pos;
