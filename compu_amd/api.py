@@ -78,6 +78,12 @@ class _InflateIndexSummary(C.Structure):
 _lib = None
 
 
+class _InflateParallelSummary(C.Structure):
+    _fields_ = [("n_points", C.c_uint64), ("out_len", C.c_uint64), ("in_used", C.c_uint64), ("end_bit", C.c_uint64), ("total_out", C.c_uint64),
+                ("n_starts", C.c_uint64), ("n_false", C.c_uint64), ("status", C.c_int32), ("wrap", C.c_uint32), ("check", C.c_uint32),
+                ("path", C.c_uint32)]
+
+
 def lib():
     """Load libcompu_hip.so.  Raises if it has not been built: there is no fallback codec."""
     global _lib
@@ -192,6 +198,13 @@ def lib():
     L.chip_inflate_index_read.restype = C.c_int
     L.chip_inflate_index_read.argtypes = [C.c_int, vp, C.c_uint64, C.c_uint64, vp, vp, vp, vp, C.c_uint64, sz, vp, vp, vp, C.c_uint64, vp, vp,
                                           C.POINTER(_ReadSummary), vp]
+    L.chip_inflate_find_starts_host.restype = C.c_int
+    L.chip_inflate_find_starts_host.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint64, vp, C.POINTER(C.c_uint64)]
+    L.chip_inflate_find_starts.restype = C.c_int
+    L.chip_inflate_find_starts.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint64, vp, C.POINTER(C.c_uint64), vp]
+    L.chip_inflate_parallel.restype = C.c_int
+    L.chip_inflate_parallel.argtypes = [C.c_int, vp, C.c_uint64, vp, C.c_uint64, C.c_uint32, C.c_uint64, vp, vp, vp, vp,
+                                        C.POINTER(_InflateParallelSummary), vp]
     _lib = L
     return L
 
@@ -1780,3 +1793,111 @@ def gzip_index_read(index, in_buf, ranges, stream=None):
     lo, ln = _ranges_to_device(ranges, in_buf.device)
     out, dst_off, status, rs = inflate_index_read(index, in_buf, lo, ln, stream=stream)
     return _read_checked("gzip_index_read", out, status, rs), dst_off
+
+
+# ---- one large stream: block starts (include/compu_hip.h, "block starts") -------------------------
+
+
+def inflate_find_starts_host(data, first_bit, chunk_bytes, max_starts=None):
+    """chip_inflate_find_starts_host over bytes / a uint8 numpy array in host memory: per chunk of `chunk_bytes` behind the first,
+    the least bit position behind `first_bit` (the bit of the stream's first block header) at which a dynamic block header the
+    decoder accepts begins.  Returns (starts u64, ascending: the first min(n, max_starts) of them, None = all: one call to count,
+    one to fill; n).  A start is a candidate, not a confirmed boundary."""
+    import numpy as np
+
+    buf = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8)
+    p = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None  # noqa: E731
+    n = C.c_uint64(0)
+    if max_starts is None:
+        rc = lib().chip_inflate_find_starts_host(p(buf), buf.size, int(first_bit), int(chunk_bytes), 0, None, C.byref(n))
+        if rc != 0:
+            raise RuntimeError(f"chip_inflate_find_starts_host failed: {rc}")
+        max_starts = n.value
+    m = int(max_starts)
+    starts = np.zeros(m, np.uint64)
+    rc = lib().chip_inflate_find_starts_host(p(buf), buf.size, int(first_bit), int(chunk_bytes), m, p(starts), C.byref(n))
+    if rc != 0:
+        raise RuntimeError(f"chip_inflate_find_starts_host failed: {rc}")
+    return starts[: min(m, n.value)], int(n.value)
+
+
+def inflate_find_starts(in_buf, length, first_bit, chunk_bytes, stream=None, max_starts=None):
+    """chip_inflate_find_starts over a uint8 device tensor holding `length` bytes of one deflate stream: the same answer as
+    inflate_find_starts_host, one wave per chunk.  Returns (starts int64 device tensor read as u64, n).  Synchronous on `stream`."""
+    import torch
+
+    dev = _check_tensors(((in_buf, torch.uint8),))
+    length = int(length)
+    if length < 0 or length > in_buf.numel():
+        raise ValueError(f"length {length} outside the buffer of {in_buf.numel()} bytes")
+    base, sp, n = (_dp(in_buf) if length else None), _stream_ptr(stream), C.c_uint64(0)
+    with torch.cuda.device(dev):
+        if max_starts is None:
+            rc = lib().chip_inflate_find_starts(base, length, int(first_bit), int(chunk_bytes), 0, None, C.byref(n), sp)
+            if rc != 0:
+                raise RuntimeError(f"chip_inflate_find_starts failed: {rc}")
+            max_starts = n.value
+        m = int(max_starts)
+        starts = torch.empty(m, dtype=torch.int64, device=dev)
+        rc = lib().chip_inflate_find_starts(base, length, int(first_bit), int(chunk_bytes), m, _dp(starts) if m else None, C.byref(n), sp)
+    if rc != 0:
+        raise RuntimeError(f"chip_inflate_find_starts failed: {rc}")
+    return starts[: min(m, n.value)], int(n.value)
+
+
+PAR_SERIAL, PAR_PARALLEL = 0, 1  # chip_inflate_parallel_summary::path
+PAR_DEFAULT_CHUNK = 128 << 10
+
+
+class InflateParallelSummary:
+    """chip_inflate_parallel_summary: the index build's fields; total_out (with status NeedOutput and out_len 0: the size to come
+    back with); n_starts the finder's count, n_false those that were no boundaries; path PAR_SERIAL or PAR_PARALLEL."""
+
+    __slots__ = ("n_points", "out_len", "in_used", "end_bit", "total_out", "n_starts", "n_false", "status", "wrap", "check", "path")
+
+    def __init__(self, raw):
+        for name in self.__slots__:
+            setattr(self, name, int(getattr(raw, name)))
+
+    def as_tuple(self):
+        return tuple(getattr(self, name) for name in self.__slots__)
+
+    def __repr__(self):
+        return "InflateParallelSummary(" + ", ".join(f"{name}={getattr(self, name)}" for name in self.__slots__) + ")"
+
+
+def inflate_parallel(fmt, in_buf, length, out_buf=None, chunk_bytes=0, index=False, stream=None):
+    """chip_inflate_parallel: decode the ONE stream in_buf[:length] (uint8 device tensor, 4-byte aligned, padded to a multiple of 4)
+    with a wave per chunk of `chunk_bytes` (0 = 128 KiB) that holds a block start.  out_buf None: a first call asks for the size, a
+    tensor of that size is allocated and the second call decodes.  Returns (out trimmed to out_len, summary), or with index=True
+    (out, InflateIndex of the chain's chunks -- what gzip_index_read takes --, summary).  Synchronous on `stream`."""
+    import torch
+
+    pairs = [(in_buf, torch.uint8)] + ([(out_buf, torch.uint8)] if out_buf is not None else [])
+    dev = _check_tensors(pairs)
+    length = int(length)
+    raw = _InflateParallelSummary()
+
+    def call(out, k, pt_bit, pt_out, pt_check, windows):
+        with torch.cuda.device(dev):
+            rc = lib().chip_inflate_parallel(int(fmt), _dp(in_buf), length, _dp(out) if out is not None and out.numel() else None,
+                                             out.numel() if out is not None else 0, int(chunk_bytes), k, pt_bit, pt_out, pt_check, windows,
+                                             C.byref(raw), _stream_ptr(stream))
+        if rc != 0:
+            raise RuntimeError(f"chip_inflate_parallel failed: {rc}")
+
+    if out_buf is None:
+        call(None, 0, None, None, None, None)
+        out_buf = torch.empty(int(raw.total_out) if raw.status == int(DecodeStatus.NeedOutput) else 0, dtype=torch.uint8, device=dev)
+    k = -(-max(length, 1) // (int(chunk_bytes) or PAR_DEFAULT_CHUNK)) if index else 0  # a chunk has at most one point
+    pt_bit, pt_out = torch.zeros(k, dtype=torch.int64, device=dev), torch.zeros(k, dtype=torch.int64, device=dev)
+    pt_check, windows = torch.zeros(k, dtype=torch.int32, device=dev), torch.empty(k * INDEX_WINDOW, dtype=torch.uint8, device=dev)
+    q = lambda t: _dp(t) if t.numel() else None  # noqa: E731
+    call(out_buf, k, q(pt_bit), q(pt_out), q(pt_check), q(windows))
+    summ = InflateParallelSummary(raw)
+    if not index:
+        return out_buf[: summ.out_len], summ
+    n = min(k, summ.n_points) if summ.status != int(DecodeStatus.NeedOutput) else 0
+    idx = InflateIndex(_WRAP_FMT[summ.wrap] if summ.wrap < 3 else int(fmt), length, summ.out_len, pt_bit[:n], pt_out[:n], pt_check[:n],
+                       windows[: n * INDEX_WINDOW])
+    return out_buf[: summ.out_len], idx, summ

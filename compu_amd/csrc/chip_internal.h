@@ -74,6 +74,10 @@ hipError_t launch_inflate(const BatchArgs &a, uint64_t *out_size, hipStream_t st
 hipError_t enqueue_inflate_sizes(const BatchArgs &a, uint64_t *out_size, uint32_t *scratch, uint32_t *counter, uint32_t blocks, hipStream_t stream);
 // (inflate_members.hip: the same for a CHIP_F_MEMBERS batch; out_size != nullptr launches the size pass, else the decoder)
 hipError_t enqueue_inflate_members(const BatchArgs &a, uint64_t *out_size, uint32_t *scratch, uint32_t *counter, uint32_t blocks, hipStream_t stream);
+// (inflate_parallel_markers.hip: the marker decode of chip_inflate_parallel, for inflate_parallel.hip, which holds the slot: a.n units
+// that begin at bit bit0[u] of their first input byte and write 16-bit elements; a.out_off counts bytes, a.out_cap and a.out_len
+// elements; `blocks` waves with SCRATCH_WORDS of token rows each)
+hipError_t enqueue_inflate_markers(const BatchArgs &a, const uint32_t *bit0, uint32_t *scratch, uint32_t *counter, uint32_t blocks, hipStream_t stream);
 // zstd_sizes.hip: the zstd size pass
 hipError_t launch_zstd_sizes(const BatchArgs &a, uint64_t *out_size, int window_log_max, hipStream_t stream);
 // (zstd_members.hip, zstd_members_sizes.hip: the CHIP_F_MEMBERS kernels behind launch_zstd_decode / launch_zstd_sizes)

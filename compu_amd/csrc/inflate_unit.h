@@ -41,6 +41,27 @@ __device__ __forceinline__ GAS T *rdfirst_gptr(T *p)
 #define CHIP_PHASE_FN __attribute__((always_inline))
 #endif
 
+// The two variants of the parallel decode of one stream (inflate_parallel.hip, inflate_parallel_markers.hip),
+// compiled only there, as the member loop and the index recording are: without the macros this file's tokens are what they were.
+// CHIP_INFLATE_SPEC: the speculative size pass.  Unit u >= 1 begins at a block start the finder named, without a wrapper; a match
+// may reach in front of the unit's first byte (how far is recorded, not refused); at every block boundary the unit looks for the
+// boundary in the sorted list of starts behind its own and ends there, LINKED to that start.
+// CHIP_INFLATE_MARKERS: the marker decode.  The unit begins at a bit offset like a resumed one and its output is 16-bit elements:
+// literals 0 .. 255, and 0x8000 | j for the byte j of the 32 768 in front of the unit's first, which nobody knows yet.
+#ifndef CHIP_INFLATE_SPEC
+#define CHIP_INFLATE_SPEC 0
+#endif
+#ifndef CHIP_INFLATE_MARKERS
+#define CHIP_INFLATE_MARKERS 0
+#endif
+#if CHIP_INFLATE_SPEC
+#define SPEC_PARAM , uint32_t &sp_reach
+#define SPEC_ARG , sp_reach
+#else
+#define SPEC_PARAM
+#define SPEC_ARG
+#endif
+
 // Diagnostic build (-DCHIP_STATS): per-unit cycle and event counters; compiled out of the product.
 #ifdef CHIP_STATS
 #define STAT_DECL unsigned long long st_[24] = {0}; unsigned long long st_t0_ = 0
@@ -1381,7 +1402,7 @@ __device__ CHIP_PHASE_FN uint32_t walk_round(WaveLds &L, const InWin &w, const u
 // the first byte (a distance is at most 32 768): until then a second sweep over the same tokens, now with a running position,
 // makes the decoder's "invalid distance too far back" check; the first offending token in stream order decides, and the length
 // counted in front of it is what the decoder would have written.  `osize` is wave-uniform.  Returns false on that error.
-__device__ CHIP_PHASE_FN bool count_tokens(WaveLds &L, const uint32_t *grow_, uint32_t ntok_, uint32_t npieces_, uint64_t &osize, int32_t &status)
+__device__ CHIP_PHASE_FN bool count_tokens(WaveLds &L, const uint32_t *grow_, uint32_t ntok_, uint32_t npieces_, uint64_t &osize, int32_t &status SPEC_PARAM)
 {
     const uint32_t lane = lane_id();
     GAS const uint32_t *const grow = rdfirst_gptr(grow_);
@@ -1406,6 +1427,27 @@ __device__ CHIP_PHASE_FN bool count_tokens(WaveLds &L, const uint32_t *grow_, ui
     }
     const uint32_t incl = wave_incl_scan(sum);  // (a round's tokens give less than 64 * 256 * 258 bytes)
     const uint32_t olo = rdfirst((uint32_t)osize), ohi = rdfirst((uint32_t)(osize >> 32));
+#if CHIP_INFLATE_SPEC
+    if (ohi == 0 && olo < 32768u) {  // a distance may reach in front of the unit's first byte: the farthest reach is kept, nothing is refused
+        uint32_t at = olo + incl - sum, reach = 0;
+        for (uint32_t kq = k0 & ~3u; __any(kq < kend); kq += 4u) {
+            if (kq < kend) {
+                const u32x4 t = *(GAS const u32x4 *)(row + 8u * kq);
+                const uint32_t t4[4] = {t.x, t.y, t.z, t.w};
+#pragma unroll
+                for (uint32_t j = 0; j < 4; j++)
+                    if (kq + j >= k0 && kq + j < kend) {
+                        const uint32_t dist = __builtin_amdgcn_ubfe(t4[j], 10, 16) + 1u;
+                        if ((t4[j] & 512u) != 0 && dist > at && dist - at > reach) reach = dist - at;
+                        at += tok_olen(t4[j]);
+                    }
+            }
+        }
+        const uint32_t far = rdlane(wave_incl_max_scan(reach), 63u);
+        if (far > sp_reach) sp_reach = far;
+    }
+    (void)status;
+#else
     if (ohi == 0 && olo < 32768u) {
         uint32_t at = olo + incl - sum, badat = 0xffffffffu;
         for (uint32_t kq = k0 & ~3u; __any(kq < kend); kq += 4u) {
@@ -1428,9 +1470,119 @@ __device__ CHIP_PHASE_FN bool count_tokens(WaveLds &L, const uint32_t *grow_, ui
             return false;
         }
     }
+#endif
     osize = (((uint64_t)ohi << 32) | olo) + rdlane(incl, 63u);
     return true;
 }
+
+#if CHIP_INFLATE_MARKERS
+// ---- the marker decode's executor: 16-bit elements, a plain one ------------------------------------------------------------------
+// Element x of the unit's output lives at gout[x]; the element at x - d of a match that reaches in front of x = 0 is the marker
+// 0x8000 | (32768 + x - d): nothing stands there in memory, the unit in front owns those elements.  64 tokens per trip (lane =
+// token, found in the rows as overflow_bit() finds them): a prefix sum places them, the literals are stored at once, then the
+// matches are copied in passes: the short ones whose source is final each by their own lane, the others one by one by the whole
+// wave.  Between a pass's stores and the loads of the next one stands a fence of the workgroup's scope (one wave: a wait for the
+// stores; the L1 is this CU's alone).
+#define MSYNC() __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup")
+constexpr uint32_t MARK = 0x8000u, MARK_WINDOW = 32768u;
+constexpr uint32_t LANE_COPY16 = 32;  // elements a lane copies for its own match; longer matches are the whole wave's
+
+__device__ __forceinline__ void copy_match16(GAS uint16_t *gout, uint32_t x, uint32_t len, uint32_t dist)
+{
+    const uint32_t lane = lane_id();
+    const int32_t sx = (int32_t)x - (int32_t)dist;
+    for (uint32_t i = lane; i < len; i += 64) {
+        // a self-overlapping match repeats its first `dist` elements; all of them lie below x and are complete
+        const int32_t s = sx + (int32_t)(dist >= len ? i : small_mod(i, dist));
+        const uint16_t v = s < 0 ? (uint16_t)(MARK | (uint32_t)(s + (int32_t)MARK_WINDOW)) : gout[s];
+        gout[x + i] = v;
+    }
+    MSYNC();
+}
+
+// As flush_tokens(): executes the batch's tokens into gout (elements) at opos.  A token that does not fit `cap` elements whole stops
+// the unit with CHIP_NEED_OUTPUT (a chunk of the chain ends on a token's end); a distance beyond the marker window is an error.
+__device__ CHIP_PHASE_FN bool flush_tokens16(WaveLds &L, const uint32_t *grow_, uint32_t ntok_, uint32_t npieces_, uint16_t *gout_, uint32_t &opos_,
+                                             uint32_t cap_, int32_t &status)
+{
+    const uint32_t lane = lane_id();
+    GAS const uint32_t *const grow = rdfirst_gptr(grow_);
+    GAS uint16_t *const gout = rdfirst_gptr(gout_);
+    const uint32_t ntok = rdfirst(ntok_), npieces = rdfirst(npieces_), cap = rdfirst(cap_);
+    uint32_t opos = rdfirst(opos_);
+    if (ntok == 0) return true;
+    const uint32_t pfirst = lane < npieces ? L.fl.pk[2u * lane] : 0xffffffffu;
+    const uint32_t pdelta = lane < npieces ? L.fl.pk[2u * lane + 1u] : 0u;
+    for (uint32_t g = 0; g < ntok; g += 64u) {
+        const uint32_t nvalid = ntok - g < 64u ? ntok - g : 64u;
+        const uint32_t t = g + lane < ntok ? g + lane : ntok - 1u;
+        uint32_t k = 0;  // pieces that start at or before token t
+        for (uint32_t q = 0; q < npieces; q++) k += rdlane(pfirst, q) <= t ? 1u : 0u;
+        const uint32_t d = lane_gather(pdelta, k - 1u);
+        const uint32_t tok = grow[(d >> 16) + row_word((t + d) & 0xffffu)];
+        const bool ismatch = (tok & 512u) != 0, pair = (int32_t)tok < 0;
+        const uint32_t len = tok & 0x1ffu, dist = __builtin_amdgcn_ubfe(tok, 10, 16) + 1u;
+        const uint32_t olen = lane < nvalid ? tok_olen(tok) : 0u;
+        const uint32_t incl = wave_incl_scan(olen);
+        const uint32_t start = opos + incl - olen;
+        const uint64_t validm = nvalid == 64u ? ~0ull : (1ull << nvalid) - 1ull;
+        const uint64_t nofit = __ballot(olen > cap - start || start > cap) & validm;
+        const uint64_t badm = __ballot(ismatch && dist > start + MARK_WINDOW) & validm;
+        const uint64_t stopm = nofit | badm;
+        const uint32_t nacc = stopm ? (uint32_t)__ffsll((long long)stopm) - 1u : nvalid;
+        if (lane < nacc && !ismatch) gout[start] = (uint16_t)(tok & 0xffu);
+        if (lane < nacc && !ismatch && pair) gout[start + 1u] = (uint16_t)((tok >> 16) & 0xffu);
+        MSYNC();
+        // The matches, as round_finish() takes them: every element below the first pending match is final, so every pending match
+        // whose source ends there (and is short) is copied by its own lane, all of them at once; when the first pending one is not
+        // among them (long, self-overlapping, or fed by a match of this pass) the whole wave copies it.
+        uint64_t pend = __ballot(lane < nacc && ismatch);
+        const int32_t sx = (int32_t)start - (int32_t)dist;
+        while (pend) {
+            const uint32_t f = (uint32_t)__ffsll((long long)pend) - 1u;
+            const uint32_t wp = rdlane(start, f);
+            const bool ready = ((pend >> lane) & 1ull) && len <= LANE_COPY16 && sx + (int32_t)len <= (int32_t)wp;
+            const uint64_t rm = __ballot(ready);
+            if (!((rm >> f) & 1ull)) {
+                copy_match16(gout, wp, rdlane(len, f), rdlane(dist, f));
+                pend &= pend - 1ull;
+                continue;
+            }
+            const uint32_t n = ready ? len : 0u;
+            for (uint32_t i0 = 0; __any(i0 < n); i0 += 8u) {
+                uint16_t v[8];
+#pragma unroll
+                for (uint32_t j = 0; j < 8; j++) {
+                    const int32_t s = sx + (int32_t)(i0 + j);
+                    v[j] = 0;
+                    if (i0 + j < n) v[j] = s < 0 ? (uint16_t)(MARK | (uint32_t)(s + (int32_t)MARK_WINDOW)) : gout[s];
+                }
+#pragma unroll
+                for (uint32_t j = 0; j < 8; j++)
+                    if (i0 + j < n) gout[start + i0 + j] = v[j];
+            }
+            MSYNC();
+            pend &= ~rm;
+        }
+        opos = nacc == 64u ? opos + rdlane(incl, 63u) : rdlane(start, nacc);
+        if (stopm) {
+            opos_ = opos;
+            status = ((badm & ~nofit) >> nacc) & 1ull ? Z_DATA_ERROR : (int32_t)CHIP_NEED_OUTPUT;
+            return false;
+        }
+    }
+    opos_ = opos;
+    return true;
+}
+
+// a stored block's payload, widened: n bytes from byte offset `so` of the unit's input to n elements at gdst
+__device__ __forceinline__ void wave_copy_stored16(uint16_t *gdst, const uint32_t *g32, uint32_t so, uint32_t n)
+{
+    const uint8_t *gsrc = (const uint8_t *)g32 + so;
+    for (uint32_t i = lane_id(); i < n; i += 64u) gdst[i] = gsrc[i];
+    MSYNC();
+}
+#endif
 
 // ---- a block's tokens: super-rounds of walk, path resolve, execution ------------------------------------
 // Decode the tokens of one deflate block from bit `pos` on (tables are in LDS), executing them into gout.  On return `pos` is
@@ -1439,7 +1591,7 @@ __device__ CHIP_PHASE_FN bool count_tokens(WaveLds &L, const uint32_t *grow_, ui
 template <bool SIZES>
 __device__ CHIP_PHASE_FN void decode_block(WaveLds &L, InWin &w, uint32_t &pos, const uint32_t end_bit, uint8_t *gout, uint32_t &opos,
                                            const uint32_t cap, int32_t &status, uint32_t *rows, const uint32_t xt_bits, const uint32_t eob_len,
-                                           const uint32_t flags, uint64_t &osize STAT_PARAM)
+                                           const uint32_t flags, uint64_t &osize STAT_PARAM SPEC_PARAM)
 {
     pos = rdfirst(pos);
     opos = rdfirst(opos);
@@ -1458,9 +1610,13 @@ __device__ CHIP_PHASE_FN void decode_block(WaveLds &L, InWin &w, uint32_t &pos, 
         asm volatile("" ::"s"(npk), "s"(ntok));
 #else
         if constexpr (SIZES) {
-            if (npk) flushed = count_tokens(L, rows, ntok, npk, osize, st2);
+            if (npk) flushed = count_tokens(L, rows, ntok, npk, osize, st2 SPEC_ARG);
         } else {
+#if CHIP_INFLATE_MARKERS
+            if (npk) flushed = flush_tokens16(L, rows, ntok, npk, (uint16_t *)gout, opos, cap, st2);
+#else
             if (npk) flushed = flush_tokens(L, rows, ntok, npk, gout, opos, cap, st2, ovf STAT_ARG);
+#endif
         }
 #endif
         w.win0 = 0xffffffffu;  // the phases used the header window's place
@@ -1519,8 +1675,34 @@ struct IndexRec {
 #else
 #define INDEX_PARAM
 #endif
+#if CHIP_INFLATE_SPEC
+// how a unit of the speculative size pass ended, and what it found
+enum : uint32_t { SPEC_RAN = 0, SPEC_LINKED = 1, SPEC_GAVE_UP = 2 };  // RAN: to the status it answers (finished, error, end of input)
+constexpr uint32_t SPEC_PASS_MAX = 8;  // starts a unit walks over without linking before it gives up
+struct SpecOut {
+    uint64_t size;     // decoded length
+    uint64_t end_bit;  // of the stream: the boundary it linked at; the bit behind the final block; else the last boundary reached
+    uint32_t kind, link;  // SPEC_*; LINKED: the unit it linked to (1 + the start's index)
+    int32_t status;
+    uint32_t reach;    // the farthest a match reached in front of the unit's first byte
+    uint32_t wrap, first_bit;  // unit 0: the wrapper kind, the bit of the first block header
+};
+struct SpecRec {
+    const uint64_t *starts;  // the finder's answer, ascending; unit u >= 1 begins at starts[u - 1], unit 0 at the stream's beginning
+    uint32_t n_starts;
+    SpecOut *out;            // one per unit
+};
+#define SPEC_REC_PARAM , const SpecRec &sp
+#else
+#define SPEC_REC_PARAM
+#endif
+#if CHIP_INFLATE_MARKERS
+#define MARK_PARAM , const uint32_t *mk_bit0  // per unit: the bit of its first block header in its first input byte
+#else
+#define MARK_PARAM
+#endif
 template <bool SIZES>
-__device__ __attribute__((always_inline)) void inflate_unit(const BatchArgs &a, const uint32_t u, WaveLds &L, uint32_t *scratch, uint64_t *out_size INDEX_PARAM)
+__device__ __attribute__((always_inline)) void inflate_unit(const BatchArgs &a, const uint32_t u, WaveLds &L, uint32_t *scratch, uint64_t *out_size INDEX_PARAM SPEC_REC_PARAM MARK_PARAM)
 {
     const uint32_t lane = lane_id();
 
@@ -1581,6 +1763,19 @@ __device__ __attribute__((always_inline)) void inflate_unit(const BatchArgs &a, 
             out_dropped = rs[5];
         }
     }
+#if CHIP_INFLATE_SPEC
+    uint32_t sp_next = u;  // the first start behind the unit's own
+    uint32_t sp_passed = 0, sp_kind = SPEC_RAN, sp_link = 0, sp_reach = 0, sp_first = 0, sp_end = 0;
+    const uint64_t sp_bit0 = 8ull * a.in_off[u];  // the unit's first byte in bits of the stream
+    if (u) {
+        resumed = true;  // no wrapper: a block header, at the bit the start names
+        pos = start_bit + (uint32_t)(sp.starts[u - 1u] & 7u);
+    }
+#endif
+#if CHIP_INFLATE_MARKERS
+    resumed = true;
+    pos = start_bit + mk_bit0[u];
+#endif
 #if CHIP_INFLATE_MEMBERS
 next_member:
 #endif
@@ -1597,12 +1792,18 @@ next_member:
         pos += rdfirst(hdr) * 8u;
     }
     if (status == ST_RUNNING) win_load(L, w, pos >> 5);
+#if CHIP_INFLATE_SPEC
+    sp_first = pos - start_bit;
+#endif
 
     __builtin_amdgcn_s_setprio(2);
     while (status == ST_RUNNING) {
         if (last) {
 #if CHIP_INFLATE_INDEX
             ix_end = pos - start_bit;
+#endif
+#if CHIP_INFLATE_SPEC
+            sp_end = pos - start_bit;
 #endif
             status = CHIP_FINISHED;
             break;
@@ -1617,6 +1818,21 @@ next_member:
             }
             ix_out = opos;
             ix_n++;
+        }
+#endif
+#if CHIP_INFLATE_SPEC
+        {  // (uniform) is this boundary a start behind the unit's own?
+            const uint64_t b = sp_bit0 + ck_bit;
+            while (sp_next < sp.n_starts && sp.starts[sp_next] < b) sp_next++, sp_passed++;
+            if (sp_next < sp.n_starts && sp.starts[sp_next] == b) {
+                sp_kind = SPEC_LINKED;
+                sp_link = sp_next + 1u;
+                break;
+            }
+            if (sp_passed > SPEC_PASS_MAX) {
+                sp_kind = SPEC_GAVE_UP;
+                break;
+            }
         }
 #endif
         win_ensure(L, w, pos);
@@ -1651,7 +1867,11 @@ next_member:
             } else {
                 uint32_t room = cap - opos;
                 if (ncopy > room) ncopy = room;
+#if CHIP_INFLATE_MARKERS
+                wave_copy_stored16((uint16_t *)gout + opos, w.g32, pos >> 3, ncopy);
+#else
                 wave_copy_stored(gout + opos, w.g32, w.total_dw, pos >> 3, ncopy);
+#endif
                 opos += ncopy;
             }
             pos += ncopy * 8u;
@@ -1799,7 +2019,7 @@ next_member:
         }
         STAT_ACC(0);
         __builtin_amdgcn_s_setprio(0);
-        decode_block<SIZES>(L, w, pos, end_bit, gout, opos, cap, status, scratch, tables == 1 ? XT_BITS_FIXED : XT_BITS, eob_len, a.flags, osize STAT_ARG);
+        decode_block<SIZES>(L, w, pos, end_bit, gout, opos, cap, status, scratch, tables == 1 ? XT_BITS_FIXED : XT_BITS, eob_len, a.flags, osize STAT_ARG SPEC_ARG);
         __builtin_amdgcn_s_setprio(2);  // block headers and table builds are short dependent chains: ahead of the other waves' bulk work
         STAT_T0();
     }
@@ -1914,6 +2134,10 @@ next_member:
         ix.walk[1] = status == CHIP_FINISHED ? ix_end : 0u;
         ix.walk[2] = wrap;
     }
+#endif
+#if CHIP_INFLATE_SPEC
+    if (lane == 0)
+        sp.out[u] = SpecOut{osize, sp_bit0 + (status == CHIP_FINISHED ? sp_end : ck_bit), sp_kind, sp_link, status, sp_reach, wrap, sp_first};
 #endif
     if (lane == 0) {
         if constexpr (SIZES) out_size[u] = osize;

@@ -839,6 +839,90 @@ int chip_inflate_index_read(int format, const void *in_base, uint64_t len, uint6
                             const uint64_t *range_lo, const uint32_t *range_len, void *dst_base, uint64_t dst_cap, uint64_t *dst_off,
                             int32_t *range_status, chip_read_summary *summary, void *stream);
 
+/* ---- one large stream: block starts (additive API) ------------------------- */
+
+/*
+ * The first pass of a parallel decode of ONE stream: where, behind its beginning, may a wave start?  A deflate block can be decoded
+ * from its first bit on by whoever knows that bit, and a dynamic block's header can be recognised without decoding what is in front
+ * of it (pugz, rapidgzip).  These two calls look for such headers; they decode nothing, build no table and use no window.
+ * A bit position p of in[0 .. len) (bit p = bit p % 8 of byte p / 8, as the index's pt_bit counts) is a CANDIDATE if and only if
+ *   - the three bits at p are BFINAL = 0, BTYPE = 2;
+ *   - the dynamic header that starts there is one the decoder's header path accepts: HLIT <= 29 and HDIST <= 29; a complete
+ *     code-length code; the code-length sequence decodes within HLIT + HDIST + 258 entries by zlib's rules (no repeat of a previous
+ *     length at entry 0, no run past the last entry); the end-of-block code has a length; the literal/length and the distance set
+ *     are ones zlib's inflate_table accepts (not over-subscribed; incomplete only as a single code of length 1; a distance set
+ *     without any code is accepted);
+ *   - the header, to the last bit of its last code-length symbol, lies inside the buffer.
+ * Stored blocks, fixed blocks and final blocks are never candidates.  With B = chunk_bytes, the START of chunk k, k = 1 ..
+ * ceil(len / B) - 1, is the least candidate p with 8 k B <= p < 8 (k + 1) B and p > first_bit, or none.  first_bit is the bit of the
+ * stream's first block header (the caller's to know: 0 for raw deflate, behind the wrapper else); chunk 0 has no start.
+ * A candidate is not a promise.  Bits inside a block's data, and a stored block's payload, can spell a header; a decode that begins at a start has to be confirmed by the decode that arrives there from the front.
+ * Every real boundary of a non-final dynamic block, on the other hand, IS a candidate, so a chunk that holds one has a start at or
+ * in front of it.
+ * starts receives, ascending, the starts of the chunks that have one: the first min(*n, max) of them, and nothing behind them is
+ * written; *n counts them all.  max = 0 with a null array counts, a second call fills.
+ * chip_inflate_find_starts_host: `in`, starts and n are HOST memory; pure host arithmetic, no device.
+ * chip_inflate_find_starts: the same answer for a buffer in DEVICE memory; starts is a DEVICE array, n a HOST pointer.  SYNCHRONOUS
+ * on `stream`.  A wave per 2 KiB piece of a chunk tests 64 consecutive positions at a time with the 13-bit pre-filter (the first
+ * three conditions: 11 % of random positions pass), the survivors check their whole header, and a chunk's pieces stop at its first
+ * hit.  Scratch per (device,
+ * stream), a launch slot of its own, released by chip_trim(): 8 bytes per chunk.  The calling thread's current device is left as it
+ * was.
+ * CHIP_E_INVALID, for both before a device is looked for: n NULL; a NULL buffer with len > 0; a NULL array with max > 0; chunk_bytes
+ * outside 256 .. CHIP_GZPLAN_WINDOW; len > CHIP_GZPLAN_WINDOW (a unit's limit); first_bit > 8 len.  No alignment is asked of the
+ * buffer.  No reference counterpart: compu decodes a stream on one thread.
+ */
+int chip_inflate_find_starts_host(const uint8_t *in, uint64_t len, uint64_t first_bit, uint32_t chunk_bytes, uint64_t max,
+                                  uint64_t *starts, uint64_t *n);
+int chip_inflate_find_starts(const void *in_base, uint64_t len, uint64_t first_bit, uint32_t chunk_bytes, uint64_t max,
+                             uint64_t *starts, uint64_t *n, void *stream);
+
+/*
+ * chip_inflate_parallel: ONE raw deflate / zlib / gzip stream decoded by the whole GPU, with the checkpoint index of the section above
+ * as a by-product.  Arguments, formats, limits, alignment, the host `summary` and the counted-then-filled point arrays are
+ * chip_inflate_index_build's; chunk_bytes is 0 (128 KiB) or 256 .. CHIP_GZPLAN_WINDOW; out_base may be NULL when out_cap is 0.
+ * How: every chunk of chunk_bytes with a start (above) gets a wave that decodes from its start on without output (the size pass
+ * with two licences: no wrapper, and matches may reach up to 32 768 bytes in front of the wave's first byte -- how far is recorded),
+ * and ends where it arrives at a later start: it is LINKED to it.  A wave that walks over CHIP_PAR_PASS_MAX (8) starts without
+ * arriving at one gives up.  The CHAIN follows the links from the stream's beginning; its members are real boundaries by induction and
+ * every start that is not on it was false (n_false) and cost its wave.  The stream is CLEAN when the chain ends in a finished final
+ * block, no chunk's reach exceeds the content in front of it and the trailer is whole.  Then every chain chunk is decoded once more,
+ * into 16-bit elements (a literal, or a marker for "byte j of the 32 768 in front of this chunk"), one workgroup turns each chunk's
+ * last 32 KiB into the next chunk's window along the chain, a parallel pass resolves the markers into out_base, and the per-chunk
+ * CRC-32 / Adler-32 are combined along the chain into pt_check and the stream's check, which is compared with the trailer.
+ * The contract:
+ *   - A clean stream of at least two chain chunks, total_out <= out_cap: path = CHIP_PAR_PARALLEL.  The bytes, out_len, in_used and
+ *     status (CHIP_FINISHED) are chip_decode_batch(format, 1, ..)'s for the unit; wrap, check and end_bit as in the index build;
+ *     total_out = out_len.  The POINTS are the stream's first block and every start on the chain: a property of the stream and
+ *     chunk_bytes, not of scheduling.  pt_bit, pt_out, pt_check and windows hold the first min(n_points, max_points) of them in
+ *     the index's layout and go to chip_inflate_index_read unchanged.
+ *   - The same with total_out > out_cap: status = CHIP_NEED_OUTPUT, out_len = 0, total_out = the exact size to come back with
+ *     (chip_pack_units' convention, and the one deliberate difference from chip_decode_batch).  No byte at or behind out_base +
+ *     out_cap is written, the bytes in front of it are unspecified, the point arrays are not written.
+ *   - Anything else -- an error, a truncation, CHIP_NEED_DICT, a wrong check value or ISIZE, a wave that gave up, a stream of one
+ *     block, no start on the chain: path = CHIP_PAR_SERIAL and the answer is the serial decode's, chip_inflate_index_build with a
+ *     spacing no stream reaches: chip_decode_batch's out_len, in_used, status and bytes, n_points = 1 (the first block) or 0 (the
+ *     wrapper was refused).  If that decode ends CHIP_NEED_OUTPUT and the one-unit size pass finishes, the answer is the room-short
+ *     one above with the size pass's total_out.  A multi-member gzip buffer: the first member only.
+ * n_starts = the finder's count (0 when the call never got there), n_false as above (0 on the serial path).
+ * SYNCHRONOUS on `stream`; it waits for the wrapper, the starts, the links, the trailer's bytes and the result; the chain, the sums
+ * and the combination of the checks are host work between those waits.  CHIP_E_INVALID as the index build, and:
+ * a chunk_bytes outside the range; out_base NULL with out_cap > 0.
+ * Scratch per (device, stream), a launch slot of its own, released by chip_trim(): 2 * total_out bytes for the elements; 64 KiB of
+ * token rows per unit of the size pass, at most 128 MiB; 32 KiB per chain chunk when max_points is below the chain's length (the
+ * windows nobody asked for); about 100 bytes per chunk of the input.  CHIP_E_NOMEM if it cannot be had.
+ */
+enum { CHIP_PAR_SERIAL = 0, CHIP_PAR_PARALLEL = 1 };
+#define CHIP_PAR_PASS_MAX 8
+typedef struct {
+    uint64_t n_points, out_len, in_used, end_bit, total_out, n_starts, n_false;
+    int32_t status;
+    uint32_t wrap, check, path; /* path: CHIP_PAR_SERIAL, CHIP_PAR_PARALLEL */
+} chip_inflate_parallel_summary;
+int chip_inflate_parallel(int format, const void *in_base, uint64_t len, void *out_base, uint64_t out_cap, uint32_t chunk_bytes,
+                          uint64_t max_points, uint64_t *pt_bit, uint64_t *pt_out, uint32_t *pt_check, void *windows,
+                          chip_inflate_parallel_summary *summary, void *stream);
+
 /* ---- zstd encoder: encoder::Interface::zstd, src/encoder/zstd.rs ------------------------------------------------------------ */
 
 /* ZstdStrategy src/encoder/zstd.rs:33-56 (ZSTD_strategy values; 0 = the level's own).  The GPU encoder has four level groups

@@ -608,3 +608,63 @@ pub unsafe fn inflate_index_read_device(mode: ZlibMode, input: &crate::buffer::D
                                           opt(range_status) as *mut i32, &mut summary, stream);
     if rc == sys::CHIP_OK { Ok(summary) } else { Err(rc) }
 }
+
+///`chip_inflate_find_starts_host`: the block starts of the deflate stream in `input` (host memory), whose first block header is at
+///bit `first_bit`: per chunk of `chunk_bytes` behind the first, the least bit position at which a dynamic block header the decoder
+///accepts begins.  Pure host arithmetic; a start is a candidate, not a confirmed boundary.  No counterpart in this crate.
+pub fn inflate_find_starts_host(input: &[u8], first_bit: u64, chunk_bytes: u32) -> Result<Vec<u64>, i32> {
+    let mut n = 0u64;
+    let rc = unsafe { sys::chip_inflate_find_starts_host(input.as_ptr(), input.len() as u64, first_bit, chunk_bytes, 0, ptr::null_mut(), &mut n) };
+    if rc != sys::CHIP_OK {
+        return Err(rc);
+    }
+    let mut starts = vec![0u64; n as usize];
+    let rc = unsafe { sys::chip_inflate_find_starts_host(input.as_ptr(), input.len() as u64, first_bit, chunk_bytes, n, starts.as_mut_ptr(), &mut n) };
+    if rc == sys::CHIP_OK { Ok(starts) } else { Err(rc) }
+}
+
+///`chip_inflate_find_starts`: the same answer for the first `len` bytes of a device-resident buffer, one wave per chunk.  The first
+///`max` starts go to `starts` (u64 entries, ascending; `max` 0 counts); returns the number of starts of the whole buffer.
+///Synchronous on `stream`.
+///
+///# Safety
+///
+///As `decode_batch_device`.
+pub unsafe fn inflate_find_starts_device(input: &crate::buffer::DeviceBuffer, len: usize, first_bit: u64, chunk_bytes: u32, max: usize,
+                                         starts: &mut crate::buffer::DeviceBuffer, stream: *mut core::ffi::c_void) -> Result<u64, i32> {
+    if len > input.capacity() || starts.capacity() < 8 * max {
+        return Err(-101);
+    }
+    let mut n = 0u64;
+    let rc = sys::chip_inflate_find_starts(input.as_ptr() as *const _, len as u64, first_bit, chunk_bytes, max as u64, starts.as_mut_ptr() as *mut u64,
+                                           &mut n, stream);
+    if rc == sys::CHIP_OK { Ok(n) } else { Err(rc) }
+}
+
+///`chip_inflate_parallel`: decodes the ONE gzip / zlib / raw deflate stream in the first `len` bytes of `input` into `output` with a
+///wave per chunk of `chunk_bytes` (0 = the default) in which a block start is found, and leaves the checkpoint index of the chain's
+///chunks in the first `max_points` entries of the four arrays (`max_points` 0 counts).  A clean stream's answers are
+///`decode_batch_device`'s for the unit; with too little room the summary says `CHIP_NEED_OUTPUT`, `out_len` 0 and the `total_out`
+///to come back with; whatever is not clean is decoded serially (`path` 0).  Synchronous on `stream`.  No counterpart in this crate.
+///
+///# Safety
+///
+///As `inflate_index_build_device`.
+#[allow(clippy::too_many_arguments)]
+pub unsafe fn inflate_parallel_device(mode: ZlibMode, input: &crate::buffer::DeviceBuffer, len: usize, output: &mut crate::buffer::DeviceBuffer,
+                                      chunk_bytes: u32, max_points: usize, pt_bit: &mut crate::buffer::DeviceBuffer,
+                                      pt_out: &mut crate::buffer::DeviceBuffer, pt_check: &mut crate::buffer::DeviceBuffer,
+                                      windows: &mut crate::buffer::DeviceBuffer, stream: *mut core::ffi::c_void)
+                                      -> Result<sys::chip_inflate_parallel_summary, i32> {
+    if len > input.capacity() || pt_bit.capacity() < 8 * max_points || pt_out.capacity() < 8 * max_points || pt_check.capacity() < 4 * max_points
+        || windows.capacity() < sys::CHIP_INDEX_WINDOW * max_points
+    {
+        return Err(-101);
+    }
+    let mut summary = sys::chip_inflate_parallel_summary::default();
+    let rc = sys::chip_inflate_parallel(BatchFormat::Zlib(mode).tag(), input.as_ptr() as *const _, len as u64, output.as_mut_ptr() as *mut _,
+                                        output.capacity() as u64, chunk_bytes, max_points as u64, pt_bit.as_mut_ptr() as *mut u64,
+                                        pt_out.as_mut_ptr() as *mut u64, pt_check.as_mut_ptr() as *mut u32, windows.as_mut_ptr() as *mut _,
+                                        &mut summary, stream);
+    if rc == sys::CHIP_OK { Ok(summary) } else { Err(rc) }
+}

@@ -211,6 +211,27 @@ pub struct chip_inflate_index_summary {
 ///bytes of a window slot of the checkpoint index
 pub const CHIP_INDEX_WINDOW: usize = 32768;
 
+///`chip_inflate_parallel_summary::path`
+pub const CHIP_PAR_SERIAL: u32 = 0;
+pub const CHIP_PAR_PARALLEL: u32 = 1;
+///what `chip_inflate_parallel` answers: the index build's fields, `total_out` (with `CHIP_NEED_OUTPUT` and `out_len` 0: the size to
+///come back with), the finder's `n_starts`, the `n_false` of them that were no boundaries, and which `path` decoded
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct chip_inflate_parallel_summary {
+    pub n_points: u64,
+    pub out_len: u64,
+    pub in_used: u64,
+    pub end_bit: u64,
+    pub total_out: u64,
+    pub n_starts: u64,
+    pub n_false: u64,
+    pub status: i32,
+    pub wrap: u32,
+    pub check: u32,
+    pub path: u32,
+}
+
 pub type chip_malloc_fn = unsafe extern "C" fn(opaque: *mut c_void, size: usize) -> *mut c_void;
 pub type chip_free_fn = unsafe extern "C" fn(opaque: *mut c_void, ptr: *mut c_void);
 
@@ -343,4 +364,16 @@ extern "C" {
                                    pt_check: *const u32, windows: *const c_void, total_out: u64, n_ranges: usize, range_lo: *const u64,
                                    range_len: *const u32, dst_base: *mut c_void, dst_cap: u64, dst_off: *mut u64, range_status: *mut i32,
                                    summary: *mut chip_read_summary, stream: *mut c_void) -> c_int;
+    ///the block starts of one deflate stream in host memory: per chunk behind the first, the least bit position where a dynamic
+    ///block header the decoder accepts begins; pure host arithmetic; `max` 0 with a null array counts
+    pub fn chip_inflate_find_starts_host(input: *const u8, len: u64, first_bit: u64, chunk_bytes: u32, max: u64, starts: *mut u64,
+                                         n: *mut u64) -> c_int;
+    ///the same for a buffer in device memory (`starts` a device array, `n` a host pointer); synchronous on `stream`
+    pub fn chip_inflate_find_starts(in_base: *const c_void, len: u64, first_bit: u64, chunk_bytes: u32, max: u64, starts: *mut u64, n: *mut u64,
+                                    stream: *mut c_void) -> c_int;
+    ///ONE stream decoded by the whole GPU, a wave per chunk with a block start, with the checkpoint index as a by-product; arguments as
+    ///`chip_inflate_index_build`, `chunk_bytes` 0 = the default; synchronous on `stream`
+    pub fn chip_inflate_parallel(format: c_int, in_base: *const c_void, len: u64, out_base: *mut c_void, out_cap: u64, chunk_bytes: u32, max_points: u64,
+                                 pt_bit: *mut u64, pt_out: *mut u64, pt_check: *mut u32, windows: *mut c_void,
+                                 summary: *mut chip_inflate_parallel_summary, stream: *mut c_void) -> c_int;
 }
