@@ -84,6 +84,16 @@ class _InflateParallelSummary(C.Structure):
                 ("path", C.c_uint32)]
 
 
+class _InflateCursor(C.Structure):
+    _fields_ = [("in_total", C.c_uint64), ("out_total", C.c_uint64), ("bit", C.c_uint32), ("phase", C.c_uint32), ("wrap", C.c_uint32),
+                ("check", C.c_uint32), ("hist", C.c_uint32), ("error", C.c_int32)]
+
+
+class _InflateNextSummary(C.Structure):
+    _fields_ = [("in_used", C.c_uint64), ("out_len", C.c_uint64), ("need_out", C.c_uint64), ("n_chunks", C.c_uint64), ("n_starts", C.c_uint64),
+                ("n_false", C.c_uint64), ("status", C.c_int32), ("path", C.c_uint32)]
+
+
 def lib():
     """Load libcompu_hip.so.  Raises if it has not been built: there is no fallback codec."""
     global _lib
@@ -205,6 +215,9 @@ def lib():
     L.chip_inflate_parallel.restype = C.c_int
     L.chip_inflate_parallel.argtypes = [C.c_int, vp, C.c_uint64, vp, C.c_uint64, C.c_uint32, C.c_uint64, vp, vp, vp, vp,
                                         C.POINTER(_InflateParallelSummary), vp]
+    L.chip_inflate_parallel_next.restype = C.c_int
+    L.chip_inflate_parallel_next.argtypes = [C.c_int, C.POINTER(_InflateCursor), vp, vp, C.c_uint64, vp, C.c_uint64, C.c_uint32,
+                                             C.POINTER(_InflateNextSummary), vp]
     _lib = L
     return L
 
@@ -1901,3 +1914,148 @@ def inflate_parallel(fmt, in_buf, length, out_buf=None, chunk_bytes=0, index=Fal
     idx = InflateIndex(_WRAP_FMT[summ.wrap] if summ.wrap < 3 else int(fmt), length, summ.out_len, pt_bit[:n], pt_out[:n], pt_check[:n],
                        windows[: n * INDEX_WINDOW])
     return out_buf[: summ.out_len], idx, summ
+
+
+CUR_HEADER, CUR_BLOCKS, CUR_TRAILER, CUR_DONE, CUR_ERROR = range(5)  # chip_inflate_cursor::phase
+FMT_AUTO = 47  # CHIP_FMT_AUTO: zlib or gzip
+
+
+class InflateCursor:
+    """chip_inflate_cursor and its 32 KiB device window: where a slabbed decode of ONE stream stands.  A fresh one is the beginning of
+    a stream of format `fmt` (-15 raw, 15 zlib, 31 gzip, 47 either wrapper).  The fields (in_total, out_total, bit, phase, wrap,
+    check, hist, error) read and write the C struct `raw`; copy() is an independent cursor at the same place."""
+
+    FIELDS = tuple(name for name, _ in _InflateCursor._fields_)
+
+    def __init__(self, fmt=FMT_AUTO, device=None):
+        import torch
+
+        self.fmt = int(fmt)
+        self.raw = _InflateCursor()
+        self.window = torch.zeros(INDEX_WINDOW, dtype=torch.uint8, device=device if device is not None else "cuda")
+
+    def __getattr__(self, name):
+        if name in InflateCursor.FIELDS:
+            return int(getattr(self.raw, name))
+        raise AttributeError(name)
+
+    def __setattr__(self, name, value):
+        if name in InflateCursor.FIELDS:
+            setattr(self.raw, name, int(value))
+        else:
+            object.__setattr__(self, name, value)
+
+    def copy(self):
+        other = InflateCursor(self.fmt, self.window.device)
+        C.memmove(C.byref(other.raw), C.byref(self.raw), C.sizeof(_InflateCursor))
+        other.window.copy_(self.window)
+        return other
+
+    def __repr__(self):
+        return "InflateCursor(" + ", ".join(f"{name}={getattr(self, name)}" for name in self.FIELDS) + ")"
+
+
+class InflateNextSummary:
+    """chip_inflate_next_summary: in_used bytes of the slab lie in front of the new cursor byte, out_len bytes were delivered, need_out
+    is the size of the piece that did not fit (0: not known), n_chunks / n_starts / n_false describe the slab, status says why the
+    call stopped (a DecodeStatus value, 3 = needs a dictionary, or a negative error) and path which path decoded."""
+
+    FIELDS = tuple(name for name, _ in _InflateNextSummary._fields_)
+
+    def __init__(self, raw):
+        for name in self.FIELDS:
+            setattr(self, name, int(getattr(raw, name)))
+
+    def __repr__(self):
+        return "InflateNextSummary(" + ", ".join(f"{name}={getattr(self, name)}" for name in self.FIELDS) + ")"
+
+
+def inflate_parallel_next(cursor, in_buf, out_buf, chunk_bytes=0, stream=None):
+    """chip_inflate_parallel_next: decode the next part of the stream `cursor` stands in.  in_buf (uint8 device tensor, any alignment;
+    the bytes up to the next multiple of 4 behind it must belong to an allocation) holds the stream from byte cursor.in_total on,
+    out_buf the room.  The cursor moves; the bytes are out_buf[:summary.out_len] and the next slab begins summary.in_used bytes
+    further.  Synchronous on `stream`."""
+    import torch
+
+    dev = _check_tensors([(in_buf, torch.uint8), (out_buf, torch.uint8), (cursor.window, torch.uint8)])
+    raw = _InflateNextSummary()
+    with torch.cuda.device(dev):
+        rc = lib().chip_inflate_parallel_next(cursor.fmt, C.byref(cursor.raw), _dp(cursor.window), _dp(in_buf) if in_buf.numel() else None, in_buf.numel(),
+                                              _dp(out_buf) if out_buf.numel() else None, out_buf.numel(), int(chunk_bytes), C.byref(raw),
+                                              _stream_ptr(stream))
+    if rc != 0:
+        raise RuntimeError(f"chip_inflate_parallel_next failed: {rc}")
+    return InflateNextSummary(raw)
+
+
+def inflate_parallel_stream(source, sink=None, slab_bytes=64 << 20, out_bytes=256 << 20, chunk_bytes=0, members=False, fmt=FMT_AUTO, device=None):
+    """One gzip / zlib / raw deflate stream of ANY length through inflate_parallel_next: `source` (bytes-like, or a binary file object)
+    is uploaded slab after slab, every call's bytes are downloaded and written to `sink` (a binary file object; None: they are
+    returned as bytes).  The slab doubles when a call finds no whole step in it, the room doubles (or goes to need_out) when the
+    next piece does not fit.  members=True: behind a finished gzip member a new one is begun while 1f 8b follows, as gzip -d does.
+    Raises DecodeError(code) on an error in the stream and EOFError when the source ends inside the stream.  Returns the bytes, or
+    with a sink the number of bytes written."""
+    import numpy as np
+    import torch
+
+    dev = torch.device(device if device is not None else "cuda")
+    read = source.read if hasattr(source, "read") else None
+    view, taken = (None, 0) if read else (memoryview(source).cast("B"), 0)
+    pending, eof = bytearray(), False
+    slab, room = max(int(slab_bytes), 1), max(int(out_bytes), 1)
+    parts, written = [], 0
+    cur = InflateCursor(fmt, dev)
+    d_in, d_out = None, None
+    while True:
+        slab, room = min(slab, GZPLAN_WINDOW), min(room, 0xFFFFFFF0)
+        while not eof and len(pending) < slab:
+            want = slab - len(pending)
+            if read:
+                piece = read(want)
+            else:
+                piece = view[taken : taken + want]
+                taken += len(piece)
+            if not len(piece):
+                eof = True
+            pending += piece
+        n = min(len(pending), slab)
+        if d_in is None or d_in.numel() < n + 4:
+            d_in = torch.zeros(max(slab, n) + 4, dtype=torch.uint8, device=dev)
+        if d_out is None or d_out.numel() < room:
+            d_out = torch.empty(room, dtype=torch.uint8, device=dev)
+        if n:
+            d_in[:n].copy_(torch.from_numpy(np.frombuffer(bytes(pending[:n]), dtype=np.uint8).copy()))
+        s = inflate_parallel_next(cur, d_in[:n], d_out[:room], chunk_bytes)
+        if s.out_len:
+            got = d_out[: s.out_len].cpu().numpy().tobytes()
+            written += len(got)
+            if sink is None:
+                parts.append(got)
+            else:
+                sink.write(got)
+        del pending[: s.in_used]
+        if s.status == int(DecodeStatus.Finished):
+            if members and cur.wrap == 2:
+                while not eof and len(pending) < 2:  # (two bytes decide; a short read is not the end)
+                    piece = read(2 - len(pending)) if read else view[taken : taken + 2 - len(pending)]
+                    taken += 0 if read else len(piece)
+                    eof = not len(piece)
+                    pending += piece
+                if bytes(pending[:2]) == b"\x1f\x8b":
+                    cur = InflateCursor(31, dev)
+                    continue
+            break
+        if s.status not in (int(DecodeStatus.NeedInput), int(DecodeStatus.NeedOutput)):
+            raise DecodeError(s.status)
+        if s.in_used == 0 and s.out_len == 0:
+            if s.status == int(DecodeStatus.NeedOutput):
+                if room >= 0xFFFFFFF0:
+                    raise DecodeError(-5)  # a piece beyond a call's room
+                room = max(2 * room, s.need_out)
+            elif n < len(pending) or not eof:
+                if slab >= GZPLAN_WINDOW:
+                    raise DecodeError(-5)  # a block beyond a call's slab
+                slab *= 2
+            else:
+                raise EOFError("the source ends inside the stream")
+    return b"".join(parts) if sink is None else written

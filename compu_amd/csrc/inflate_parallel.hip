@@ -17,6 +17,8 @@
 // No wave waits for another outside the one workgroup of the windows.  Whatever is not a clean stream of at least two chain chunks
 // -- an error, a truncation, a wrong check value, a wave that gave up, no start at all -- is answered by the serial decode of the
 // unit (chip_inflate_index_build), so that the answer is chip_decode_batch's.
+// chip_inflate_parallel_next (sec. 4.18, below) runs the same passes over a SLAB of a stream of any length, from a cursor the caller
+// carries: unit 0 begins at the cursor, the windows start from the carried one, and what did not end at a start is the next call's.
 #define CHIP_INFLATE_SPEC 1
 #include "inflate_unit.h"
 
@@ -26,6 +28,7 @@
 #include <utility>
 #include <vector>
 
+#include "check_combine.h"
 #include "launch_slots.h"
 #include "plan_common.h"
 
@@ -79,11 +82,13 @@ __global__ __launch_bounds__(64) void par_wrapper_kernel(const uint8_t *in, uint
 }
 
 // unit u of the size pass: from the byte that holds its start to the end of the stream
-__global__ __launch_bounds__(256) void par_spec_units_kernel(const uint64_t *starts, uint32_t n_units, uint32_t len, uint64_t *in_off, uint32_t *in_len)
+// (unit 0 from byte0: 0, or the byte a carried cursor stands in)
+__global__ __launch_bounds__(256) void par_spec_units_kernel(const uint64_t *starts, uint32_t n_units, uint32_t len, uint32_t byte0, uint64_t *in_off,
+                                                             uint32_t *in_len)
 {
     const uint32_t u = blockIdx.x * 256u + threadIdx.x;
     if (u >= n_units) return;
-    const uint64_t byte = u ? starts[u - 1u] >> 3 : 0;
+    const uint64_t byte = u ? starts[u - 1u] >> 3 : byte0;
     in_off[u] = byte < len ? byte : len;
     in_len[u] = byte < len ? len - (uint32_t)byte : 0u;
 }
@@ -107,26 +112,38 @@ __device__ __forceinline__ uint8_t resolved(uint32_t e, const uint8_t *w, uint32
 // W_(k+1)[i] = content[pt_out[k + 1] - wl + i]: an element of chunk k resolved through W_k, or, in front of a chunk shorter than 32 KiB,
 // a byte of W_k itself.  One workgroup, chunk after chunk; the window it reads and the one it writes stay in LDS (the slots in
 // memory are for the resolve pass and the caller), so that a step is one round of element loads, LDS look-ups and a barrier.
-__global__ __launch_bounds__(1024) void par_windows_kernel(const uint16_t *__restrict__ img, const uint64_t *__restrict__ pt_out, uint32_t n, Windows W)
+// hist > 0 (chip_inflate_parallel_next): the content goes on from an earlier call, whose last hist bytes are carry[0 .. hist).  They
+// are W_0, and every pt_out counts from the first of them on (element q of the call stands at img[q - hist]).
+__global__ __launch_bounds__(1024) void par_windows_kernel(const uint16_t *__restrict__ img, const uint64_t *__restrict__ pt_out, uint32_t n, Windows W,
+                                                           const uint8_t *__restrict__ carry, uint32_t hist)
 {
     __shared__ uint8_t win[2][WINDOW];
     constexpr uint32_t PER = WINDOW / 1024u, COPY = 0x10000u;  // COPY | j: byte j of W_k as it stands
     // the elements of step k (they do not depend on any window: step k + 1's are loaded while step k works)
     auto load = [&](uint32_t k, uint32_t(&e)[PER]) {
-        const uint64_t o0 = pt_out[k], o1 = pt_out[k + 1u];
+        const uint64_t o0 = pt_out[k] + hist, o1 = pt_out[k + 1u] + hist;
         const uint32_t wl0 = o0 < WINDOW ? (uint32_t)o0 : WINDOW, wl1 = o1 < WINDOW ? (uint32_t)o1 : WINDOW;
 #pragma unroll
         for (uint32_t j = 0; j < PER; j++) {  // every load of the step goes out before the first one is waited for
             const uint32_t i = threadIdx.x + 1024u * j;
             const uint64_t q = o1 - wl1 + i;
             e[j] = 0;
-            if (i < wl1) e[j] = q >= o0 ? (uint32_t)img[q] : COPY | (uint32_t)(q - (o0 - wl0));
+            if (i < wl1) e[j] = q >= o0 ? (uint32_t)img[q - hist] : COPY | (uint32_t)(q - (o0 - wl0));
         }
     };
     uint32_t e[PER] = {}, en[PER] = {};
     if (n >= 2) load(0, e);
+    if (hist) {  // (uniform) W_0, in LDS and in its slot
+        uint8_t *g0 = W.slot(0);
+        for (uint32_t i = threadIdx.x; i < hist; i += 1024u) {
+            const uint8_t v = carry[i];
+            win[0][i] = v;
+            g0[i] = v;
+        }
+        __syncthreads();
+    }
     for (uint32_t k = 0; k + 1u < n; k++) {
-        const uint64_t o0 = pt_out[k], o1 = pt_out[k + 1u];
+        const uint64_t o0 = pt_out[k] + hist, o1 = pt_out[k + 1u] + hist;
         const uint32_t wl0 = o0 < WINDOW ? (uint32_t)o0 : WINDOW, wl1 = o1 < WINDOW ? (uint32_t)o1 : WINDOW;
         const uint8_t *w0 = win[k & 1u];
         uint8_t *w1 = win[(k + 1u) & 1u], *g1 = W.slot(k + 1u);
@@ -148,14 +165,45 @@ __global__ __launch_bounds__(1024) void par_windows_kernel(const uint16_t *__res
     }
 }
 
-// blockIdx.x = chunk, blockIdx.y = its share of the chunk's elements
-__global__ __launch_bounds__(256) void par_resolve_kernel(const uint16_t *img, const uint64_t *pt_out, uint32_t n, uint64_t total, Windows W, uint8_t *out)
+// blockIdx.x = chunk, blockIdx.y = its share of the chunk's elements.  hist: content in front of out[0] that W_0 holds (above).
+// first_bad (or nullptr): the least q whose element is a marker for a byte in front of the content -- a distance too far back that
+// no size pass has vouched against (the one-wave path of chip_inflate_parallel_next); the caller sets it to ~0 before.
+__global__ __launch_bounds__(256) void par_resolve_kernel(const uint16_t *img, const uint64_t *pt_out, uint32_t n, uint64_t total, Windows W, uint8_t *out,
+                                                          uint32_t hist, unsigned long long *first_bad)
 {
     const uint32_t k = blockIdx.x;
     const uint64_t o0 = pt_out[k], o1 = k + 1u < n ? pt_out[k + 1u] : total;
-    const uint32_t wl0 = o0 < WINDOW ? (uint32_t)o0 : WINDOW;
+    const uint32_t wl0 = o0 + hist < WINDOW ? (uint32_t)o0 + hist : WINDOW;
     const uint8_t *w0 = W.slot(k);
-    for (uint64_t q = o0 + blockIdx.y * 256u + threadIdx.x; q < o1; q += 256u * gridDim.y) out[q] = resolved(img[q], w0, wl0);
+    for (uint64_t q = o0 + blockIdx.y * 256u + threadIdx.x; q < o1; q += 256u * gridDim.y) {
+        const uint32_t e = img[q];
+        out[q] = resolved(e, w0, wl0);
+        if (first_bad && e >= 256u && (e & 0x7fffu) < WINDOW - wl0) atomicMin(first_bad, (unsigned long long)q);
+    }
+}
+
+// The window a later call starts from: the last min(hist + n, 32 768) bytes of (the hist bytes of `window`, then out[0 .. n)), written
+// over `window`.  One workgroup: every thread holds its bytes before the first one is stored.
+__global__ __launch_bounds__(1024) void par_carry_kernel(uint8_t *window, uint32_t hist, const uint8_t *out, uint64_t n)
+{
+    constexpr uint32_t PER = WINDOW / 1024u;
+    const uint64_t all = hist + n;
+    const uint32_t keep = all < WINDOW ? (uint32_t)all : WINDOW;
+    const uint64_t first = all - keep;  // of the joined bytes
+    uint8_t v[PER];
+#pragma unroll
+    for (uint32_t j = 0; j < PER; j++) {
+        const uint32_t i = threadIdx.x + 1024u * j;
+        const uint64_t q = first + i;
+        v[j] = 0;
+        if (i < keep) v[j] = q < hist ? window[q] : out[q - hist];
+    }
+    __syncthreads();
+#pragma unroll
+    for (uint32_t j = 0; j < PER; j++) {
+        const uint32_t i = threadIdx.x + 1024u * j;
+        if (i < keep) window[i] = v[j];
+    }
 }
 
 // chk[k] = the check of chunk k's bytes alone
@@ -169,57 +217,11 @@ __global__ __launch_bounds__(64) void par_checks_kernel(const uint8_t *out, cons
     if (lane_id() == 0) chk[k] = rdfirst(v);
 }
 
-// ---- combining check values (host): zlib's crc32_combine and adler32_combine ---------------------------------------------------
-constexpr uint32_t CRC_POLY = 0xedb88320u;
-uint32_t multmodp(uint32_t a, uint32_t b)  // a(x) * b(x) mod P, reflected
-{
-    uint32_t m = 1u << 31, p = 0;
-    for (;;) {
-        if (a & m) {
-            p ^= b;
-            if ((a & (m - 1)) == 0) break;
-        }
-        m >>= 1;
-        b = b & 1 ? (b >> 1) ^ CRC_POLY : b >> 1;
-    }
-    return p;
-}
-uint32_t x8nmodp(uint64_t n)  // x^(8 n) mod P
-{
-    struct Squares {
-        uint32_t sq[32];  // x^(2^k)
-        Squares()
-        {
-            sq[0] = 1u << 30;
-            for (int k = 1; k < 32; k++) sq[k] = multmodp(sq[k - 1], sq[k - 1]);
-        }
-    };
-    static const Squares t;
-    const uint32_t *sq = t.sq;
-    uint32_t p = 1u << 31;
-    for (unsigned k = 3; n; n >>= 1, k++)
-        if (n & 1) p = multmodp(sq[k & 31], p);
-    return p;
-}
-uint32_t crc32_append(uint32_t crc1, uint32_t crc2, uint64_t len2) { return multmodp(x8nmodp(len2), crc1) ^ crc2; }
-uint32_t adler32_append(uint32_t a1, uint32_t a2, uint64_t len2)
-{
-    constexpr uint32_t BASE = 65521;
-    const uint32_t rem = (uint32_t)(len2 % BASE);
-    uint32_t s1 = a1 & 0xffffu, s2 = (uint32_t)(((uint64_t)rem * s1) % BASE);
-    s1 += (a2 & 0xffffu) + BASE - 1;
-    s2 += (a1 >> 16) + (a2 >> 16) + BASE - rem;
-    if (s1 >= BASE) s1 -= BASE;
-    if (s1 >= BASE) s1 -= BASE;
-    if (s2 >= (BASE << 1)) s2 -= BASE << 1;
-    if (s2 >= BASE) s2 -= BASE;
-    return s1 | (s2 << 16);
-}
-
 // CHIP_PAR_TIMING in the environment: the device time between the phases of every call, on stderr (events on the call's stream;
 // a phase's figure holds the host's wait or work that stands between its two events)
 struct PhaseClock {
     hipStream_t stream;
+    const char *what = "inflate_parallel";
     bool on = getenv("CHIP_PAR_TIMING") != nullptr;
     std::vector<std::pair<const char *, hipEvent_t>> ev;
     void mark(const char *name)
@@ -233,7 +235,7 @@ struct PhaseClock {
     {
         for (size_t i = 1; i < ev.size(); i++) {
             float ms = 0;
-            if (hipEventElapsedTime(&ms, ev[i - 1].second, ev[i].second) == hipSuccess) fprintf(stderr, "[chip] inflate_parallel %-8s %9.3f ms\n", ev[i].first, ms);
+            if (hipEventElapsedTime(&ms, ev[i - 1].second, ev[i].second) == hipSuccess) fprintf(stderr, "[chip] %s %-8s %9.3f ms\n", what, ev[i].first, ms);
         }
         for (auto &e : ev) (void)hipEventDestroy(e.second);
     }
@@ -340,7 +342,7 @@ hipError_t parallel_locked(ParSlot &sl, const ParCall &c, hipStream_t stream, bo
     const uint32_t U = (uint32_t)n_starts + 1u;
     const size_t rows_bytes = (size_t)(U < MAX_WAVES ? U : MAX_WAVES) * SCRATCH_WORDS * 4;
     if ((e = sl.grow(1, rows_bytes)) != hipSuccess) return e;
-    hipLaunchKernelGGL(par_spec_units_kernel, dim3((U + 255u) / 256u), dim3(256), 0, stream, (const uint64_t *)starts, U, c.len, in_off, in_len);
+    hipLaunchKernelGGL(par_spec_units_kernel, dim3((U + 255u) / 256u), dim3(256), 0, stream, (const uint64_t *)starts, U, c.len, 0u, in_off, in_len);
     if ((e = hipMemsetAsync(counter, 0, 4, stream)) != hipSuccess) return e;
     {
         BatchArgs a{};
@@ -435,9 +437,10 @@ hipError_t parallel_locked(ParSlot &sl, const ParCall &c, hipStream_t stream, bo
         if ((e = enqueue_inflate_markers(a, bit0, (uint32_t *)sl.buf[1], counter, C < MAX_WAVES ? C : MAX_WAVES, stream)) != hipSuccess) return e;
     }
     clock.mark("markers");
-    hipLaunchKernelGGL(par_windows_kernel, dim3(1), dim3(1024), 0, stream, (const uint16_t *)img, (const uint64_t *)d_pt_out, C, W);
+    hipLaunchKernelGGL(par_windows_kernel, dim3(1), dim3(1024), 0, stream, (const uint16_t *)img, (const uint64_t *)d_pt_out, C, W, (const uint8_t *)nullptr, 0u);
     clock.mark("windows");
-    hipLaunchKernelGGL(par_resolve_kernel, dim3(C, 8), dim3(256), 0, stream, (const uint16_t *)img, (const uint64_t *)d_pt_out, C, total, W, c.out);
+    hipLaunchKernelGGL(par_resolve_kernel, dim3(C, 8), dim3(256), 0, stream, (const uint16_t *)img, (const uint64_t *)d_pt_out, C, total, W, c.out, 0u,
+                       (unsigned long long *)nullptr);
     clock.mark("resolve");
     if (wrap)
         hipLaunchKernelGGL(par_checks_kernel, dim3(C), dim3(64), 0, stream, (const uint8_t *)c.out, (const uint64_t *)d_pt_out, C, total, wrap, chk);
@@ -471,6 +474,352 @@ hipError_t parallel_locked(ParSlot &sl, const ParCall &c, hipStream_t stream, bo
     s = chip_inflate_parallel_summary{C, total, (uint64_t)tk + need, end_bit, total, n_starts, n_false, CHIP_FINISHED, wrap, run, CHIP_PAR_PARALLEL};
     serial = false;
     return hipSuccess;
+}
+
+
+// ---- chip_inflate_parallel_next: the same passes over a SLAB of a stream, from a carried cursor ---------------
+
+// One step through the blocks of the slab, from the block boundary at bit `fb` of it.
+struct BlocksOut {
+    uint64_t end_bit = 0;  // the boundary reached (behind the final block when finished)
+    uint64_t out_len = 0, need_out = 0, n_chunks = 0, n_starts = 0, n_false = 0;
+    bool finished = false;  // the final block was delivered
+    int32_t status = CHIP_NEED_INPUT;  // NEED_INPUT / NEED_OUTPUT: why the blocks stopped; an error: sticky
+    uint32_t path = CHIP_PAR_SERIAL;
+};
+
+struct NextCall {
+    const uint8_t *in;
+    uint32_t len;
+    uint8_t *out;
+    uint64_t out_cap;
+    uint32_t chunk_bytes;
+    uint8_t *window;
+    chip_inflate_cursor *cur;
+};
+
+hipError_t blocks_locked(ParSlot &sl, const NextCall &c, uint64_t fb, hipStream_t stream, PhaseClock &clock, BlocksOut &r)
+{
+    chip_inflate_cursor &cur = *c.cur;
+    const uint32_t hist = cur.hist;
+    hipError_t e = hipSuccess;
+    if (fb + 3 > 8ull * c.len) return hipSuccess;  // not even a block's first three bits
+    const uint32_t B = c.chunk_bytes ? c.chunk_bytes : DEFAULT_CHUNK;
+    const uint32_t n_chunks = (uint32_t)(((uint64_t)c.len + B - 1) / B);
+    r.n_chunks = n_chunks;
+
+    const size_t N = n_chunks;
+    size_t at = 0;
+    auto take = [&](size_t bytes) { const size_t o = at; at += up16(bytes); return o; };
+    const size_t o_counter = take(16), o_bad = take(16), o_starts = take(N * 8), o_in_off = take(N * 8), o_in_len = take(N * 4), o_in_used = take(N * 4),
+                 o_status = take(N * 4), o_size = take(N * 8), o_spec = take(N * sizeof(SpecOut)), o_bit0 = take(N * 4), o_out_off = take(N * 8),
+                 o_out_cap = take(N * 4), o_out_len = take(N * 4), o_pt_out = take((N + 1) * 8), o_chk = take(N * 4), o_resume = take(RESUME_WORDS * 4);
+    if ((e = sl.grow(0, at)) != hipSuccess) return e;
+    uint8_t *w = sl.buf[0];
+    uint32_t *counter = (uint32_t *)(w + o_counter);
+    unsigned long long *first_bad = (unsigned long long *)(w + o_bad);
+    uint64_t *starts = (uint64_t *)(w + o_starts), *in_off = (uint64_t *)(w + o_in_off), *out_size = (uint64_t *)(w + o_size);
+    uint32_t *in_len = (uint32_t *)(w + o_in_len), *in_used = (uint32_t *)(w + o_in_used);
+    int32_t *status = (int32_t *)(w + o_status);
+    SpecOut *spec = (SpecOut *)(w + o_spec);
+    uint32_t *bit0 = (uint32_t *)(w + o_bit0), *out_cap = (uint32_t *)(w + o_out_cap), *out_len = (uint32_t *)(w + o_out_len), *chk = (uint32_t *)(w + o_chk);
+    uint64_t *out_off = (uint64_t *)(w + o_out_off), *d_pt_out = (uint64_t *)(w + o_pt_out);
+    uint32_t *resume = (uint32_t *)(w + o_resume);
+    auto up = [&](void *dst, const void *src, size_t bytes) { return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream) : hipSuccess; };
+
+    uint64_t n_starts = 0;
+    if (n_chunks >= 2) {
+        const int rc = chip_inflate_find_starts(c.in, c.len, fb, B, n_chunks - 1, starts, &n_starts, stream);
+        if (rc != CHIP_OK) return rc == CHIP_E_NOMEM ? hipErrorOutOfMemory : hipErrorUnknown;
+        if (n_starts > n_chunks - 1) return hipErrorUnknown;
+    }
+    r.n_starts = n_starts;
+    clock.mark("find");
+
+    // ---- the speculative size pass; unit 0 begins at the cursor
+    const uint32_t U = (uint32_t)n_starts + 1u;
+    const size_t rows_bytes = (size_t)(U < MAX_WAVES ? U : MAX_WAVES) * SCRATCH_WORDS * 4;
+    if ((e = sl.grow(1, rows_bytes)) != hipSuccess) return e;
+    hipLaunchKernelGGL(par_spec_units_kernel, dim3((U + 255u) / 256u), dim3(256), 0, stream, (const uint64_t *)starts, U, c.len, (uint32_t)(fb >> 3), in_off,
+                       in_len);
+    if ((e = hipMemsetAsync(counter, 0, 4, stream)) != hipSuccess) return e;
+    {
+        BatchArgs a{};
+        a.in_base = c.in, a.in_off = in_off, a.in_len = in_len, a.in_used = in_used, a.status = status;
+        a.n = U, a.format = CHIP_FMT_DEFLATE;
+        const SpecRec sp{starts, (uint32_t)n_starts, spec, (uint32_t)(fb & 7u)};
+        hipLaunchKernelGGL(inflate_spec_kernel, dim3(U < MAX_WAVES ? U : MAX_WAVES), dim3(64), 0, stream, a, sp, out_size, (uint32_t *)sl.buf[1], counter);
+    }
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    std::vector<SpecOut> so(U);
+    if ((e = hipMemcpyAsync(so.data(), spec, (size_t)U * sizeof(SpecOut), hipMemcpyDeviceToHost, stream)) != hipSuccess) return e;
+    if ((e = hipStreamSynchronize(stream)) != hipSuccess) return e;
+    clock.mark("sizes");
+
+    // ---- the chain: its members that ended LINKED, or in the final block, and are clean; what follows is the next call's
+    std::vector<uint64_t> pt_bit, pt_out, size;  // per kept member; pt_bit has the end of the last one behind them
+    bool finished = false;
+    uint64_t total = 0, links = 0;  // links: the starts the chain arrived at (the dropped member's too)
+    pt_bit.push_back(fb);
+    for (uint32_t u = 0;;) {
+        const SpecOut &o = so[u];
+        const bool fin = o.kind == SPEC_RAN && o.status == CHIP_FINISHED;
+        if (o.kind != SPEC_LINKED && !fin) break;
+        if (o.reach > total + hist || o.size > CHUNK_OUT_MAX) break;  // a match in front of stream byte 0: the one-wave path names it
+        if (o.end_bit <= pt_bit.back() && !fin) return hipErrorUnknown;
+        if (o.end_bit > 8ull * c.len || o.end_bit < pt_bit.back()) return hipErrorUnknown;
+        pt_out.push_back(total);
+        size.push_back(o.size);
+        pt_bit.push_back(o.end_bit);
+        total += o.size;
+        if (fin) {
+            finished = true;
+            break;
+        }
+        if (o.link <= u || o.link >= U) return hipErrorUnknown;  // (the input changed under the kernels)
+        u = o.link;
+        links++;
+    }
+    const uint32_t K = (uint32_t)size.size();
+
+    if (K >= 1 && so[0].kind == SPEC_LINKED) {
+        // ---- the parallel path: the members that fit the room
+        uint32_t D = 0;
+        uint64_t give = 0;
+        while (D < K && give + size[D] <= c.out_cap) give += size[D++];
+        r.path = CHIP_PAR_PARALLEL;
+        r.n_false = n_starts - links;
+        if (D < K) r.status = CHIP_NEED_OUTPUT, r.need_out = size[D];
+        if (D == 0) {
+            r.end_bit = fb;
+            return hipSuccess;
+        }
+        const size_t img_off = up16(rows_bytes), win_off = img_off + up16(2 * (size_t)give + 64);
+        if ((e = sl.grow(1, win_off + (size_t)WINDOW * D + 16)) != hipSuccess) return e;
+        uint16_t *img = (uint16_t *)(sl.buf[1] + img_off);
+        const Windows W{nullptr, sl.buf[1] + win_off, 0};
+        std::vector<uint64_t> m_in_off(D), m_out_off(D);
+        std::vector<uint32_t> m_in_len(D), m_bit0(D), m_out_cap(D);
+        for (uint32_t k = 0; k < D; k++) {
+            m_in_off[k] = pt_bit[k] >> 3;
+            const uint64_t end = k + 1u == K && finished ? (uint64_t)c.len : (pt_bit[k + 1u] + 7) >> 3;
+            m_in_len[k] = (uint32_t)(end - m_in_off[k]);
+            m_bit0[k] = (uint32_t)(pt_bit[k] & 7u);
+            m_out_off[k] = 2 * pt_out[k];
+            m_out_cap[k] = (uint32_t)size[k];
+        }
+        if ((e = up(in_off, m_in_off.data(), (size_t)D * 8)) != hipSuccess || (e = up(in_len, m_in_len.data(), (size_t)D * 4)) != hipSuccess ||
+            (e = up(bit0, m_bit0.data(), (size_t)D * 4)) != hipSuccess || (e = up(out_off, m_out_off.data(), (size_t)D * 8)) != hipSuccess ||
+            (e = up(out_cap, m_out_cap.data(), (size_t)D * 4)) != hipSuccess || (e = up(d_pt_out, pt_out.data(), (size_t)D * 8)) != hipSuccess)
+            return e;
+        if ((e = hipMemsetAsync(counter, 0, 4, stream)) != hipSuccess) return e;
+        clock.mark("chain");
+        {
+            BatchArgs a{};
+            a.in_base = c.in, a.in_off = in_off, a.in_len = in_len;
+            a.out_base = (uint8_t *)img, a.out_off = out_off, a.out_cap = out_cap;
+            a.out_len = out_len, a.in_used = in_used, a.status = status;
+            a.n = D, a.format = CHIP_FMT_DEFLATE;
+            if ((e = enqueue_inflate_markers(a, bit0, (uint32_t *)sl.buf[1], counter, D < MAX_WAVES ? D : MAX_WAVES, stream)) != hipSuccess) return e;
+        }
+        clock.mark("markers");
+        hipLaunchKernelGGL(par_windows_kernel, dim3(1), dim3(1024), 0, stream, (const uint16_t *)img, (const uint64_t *)d_pt_out, D, W, (const uint8_t *)c.window,
+                           hist);
+        clock.mark("windows");
+        hipLaunchKernelGGL(par_resolve_kernel, dim3(D, 8), dim3(256), 0, stream, (const uint16_t *)img, (const uint64_t *)d_pt_out, D, give, W, c.out, hist,
+                           (unsigned long long *)nullptr);
+        clock.mark("resolve");
+        if (cur.wrap)
+            hipLaunchKernelGGL(par_checks_kernel, dim3(D), dim3(64), 0, stream, (const uint8_t *)c.out, (const uint64_t *)d_pt_out, D, give, cur.wrap, chk);
+        clock.mark("checks");
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        std::vector<uint32_t> h_len(D), h_chk(D, 0);
+        std::vector<int32_t> h_status(D);
+        if ((e = hipMemcpyAsync(h_len.data(), out_len, (size_t)D * 4, hipMemcpyDeviceToHost, stream)) != hipSuccess) return e;
+        if ((e = hipMemcpyAsync(h_status.data(), status, (size_t)D * 4, hipMemcpyDeviceToHost, stream)) != hipSuccess) return e;
+        if (cur.wrap && (e = hipMemcpyAsync(h_chk.data(), chk, (size_t)D * 4, hipMemcpyDeviceToHost, stream)) != hipSuccess) return e;
+        if ((e = hipStreamSynchronize(stream)) != hipSuccess) return e;
+        bool confirmed = true;
+        for (uint32_t k = 0; k < D; k++) {
+            const bool ended = k + 1u == K && finished ? h_status[k] == CHIP_FINISHED : (h_status[k] == CHIP_NEED_INPUT || h_status[k] == CHIP_NEED_OUTPUT);
+            if (!ended || h_len[k] != m_out_cap[k]) confirmed = false;
+        }
+        if (confirmed) {
+            hipLaunchKernelGGL(par_carry_kernel, dim3(1), dim3(1024), 0, stream, c.window, hist, (const uint8_t *)c.out, give);
+            if ((e = hipGetLastError()) != hipSuccess) return e;
+            append_checks(cur, h_chk.data(), size.data(), D);
+            clock.mark("combine");
+            r.out_len = give;
+            r.end_bit = pt_bit[D];
+            r.finished = finished && D == K;
+            return hipSuccess;
+        }
+        // (the marker decode did not confirm the size pass: the one-wave path decides, and the bytes written so far are rewritten)
+        r = BlocksOut{};
+        r.n_chunks = n_chunks, r.n_starts = n_starts;
+    }
+
+    // ---- the one-wave path: unit 0 again, as a marker decode that ends at a boundary -- where it linked, else the last one it
+    // reaches in slab and room (the resume record names it)
+    const SpecOut &o0 = so[0];
+    // an error: what stands in front of the block it is in is true content and is delivered first (the input ends with that
+    // boundary's byte); with the cursor at that block the error is the answer
+    const bool bad = o0.kind == SPEC_RAN && o0.status < 0;
+    if (bad && o0.end_bit <= fb) {
+        r.end_bit = fb;
+        r.status = o0.status;
+        return hipSuccess;
+    }
+    const uint64_t room = o0.size < c.out_cap ? o0.size : c.out_cap;
+    const uint64_t in_end = o0.kind == SPEC_LINKED || bad ? (o0.end_bit + 7) >> 3 : (uint64_t)c.len;
+    const size_t img_off = up16(SCRATCH_WORDS * 4);
+    if ((e = sl.grow(1, img_off + up16(2 * (size_t)room + 64))) != hipSuccess) return e;
+    uint16_t *img = (uint16_t *)(sl.buf[1] + img_off);
+    {
+        const uint64_t h_in_off = fb >> 3, h_out_off = 0, h_pt_out = 0;
+        const uint32_t h_in_len = (uint32_t)(in_end - h_in_off), h_bit0 = (uint32_t)(fb & 7u), h_cap = (uint32_t)room;
+        if ((e = up(in_off, &h_in_off, 8)) != hipSuccess || (e = up(in_len, &h_in_len, 4)) != hipSuccess || (e = up(bit0, &h_bit0, 4)) != hipSuccess ||
+            (e = up(out_off, &h_out_off, 8)) != hipSuccess || (e = up(out_cap, &h_cap, 4)) != hipSuccess || (e = up(d_pt_out, &h_pt_out, 8)) != hipSuccess)
+            return e;
+        if ((e = hipMemsetAsync(counter, 0, 4, stream)) != hipSuccess) return e;
+        if ((e = hipMemsetAsync(resume, 0, RESUME_WORDS * 4, stream)) != hipSuccess) return e;
+        if ((e = hipMemsetAsync(first_bad, 0xFF, 8, stream)) != hipSuccess) return e;
+        BatchArgs a{};
+        a.in_base = c.in, a.in_off = in_off, a.in_len = in_len;
+        a.out_base = (uint8_t *)img, a.out_off = out_off, a.out_cap = out_cap;
+        a.out_len = out_len, a.in_used = in_used, a.status = status;
+        a.n = 1, a.format = CHIP_FMT_DEFLATE, a.resume = resume;
+        if ((e = enqueue_inflate_markers(a, bit0, (uint32_t *)sl.buf[1], counter, 1, stream)) != hipSuccess) return e;
+    }
+    uint32_t h_res[RESUME_WORDS], h_len = 0, h_used = 0;
+    int32_t h_status = 0;
+    if ((e = hipMemcpyAsync(h_res, resume, sizeof h_res, hipMemcpyDeviceToHost, stream)) != hipSuccess) return e;
+    if ((e = hipMemcpyAsync(&h_len, out_len, 4, hipMemcpyDeviceToHost, stream)) != hipSuccess) return e;
+    if ((e = hipMemcpyAsync(&h_used, in_used, 4, hipMemcpyDeviceToHost, stream)) != hipSuccess) return e;
+    if ((e = hipMemcpyAsync(&h_status, status, 4, hipMemcpyDeviceToHost, stream)) != hipSuccess) return e;
+    if ((e = hipStreamSynchronize(stream)) != hipSuccess) return e;
+    clock.mark("wave");
+    const uint64_t bit_base = 8ull * (fb >> 3);
+    uint64_t give = 0;
+    if (h_status == CHIP_FINISHED) {
+        give = h_len;
+        r.finished = true;
+        r.end_bit = bit_base + 8ull * h_used;  // (the bits behind the final block up to the byte's end belong to it)
+    } else if (h_status == CHIP_NEED_INPUT || h_status == CHIP_NEED_OUTPUT) {
+        give = h_res[1];
+        r.end_bit = h_res[0] ? bit_base + h_res[0] : fb;
+        if (r.end_bit < fb || r.end_bit > 8ull * c.len || give > h_len) return hipErrorUnknown;
+        // the room was cut to what the size pass counted: only a caller's room below that is a reason to ask for more
+        r.status = c.out_cap < o0.size ? CHIP_NEED_OUTPUT : CHIP_NEED_INPUT;
+    } else {
+        give = h_len;  // what decoded in front of the error
+        r.end_bit = fb;
+        r.status = h_status;
+    }
+    if (give > room) return hipErrorUnknown;
+    if (give) {
+        const Windows W{c.window, nullptr, 1};  // W_0 is the carried window as it stands
+        hipLaunchKernelGGL(par_resolve_kernel, dim3(1, 64), dim3(256), 0, stream, (const uint16_t *)img, (const uint64_t *)d_pt_out, 1u, give, W, c.out, hist,
+                           first_bad);
+        unsigned long long bad = 0;
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        if ((e = hipMemcpyAsync(&bad, first_bad, 8, hipMemcpyDeviceToHost, stream)) != hipSuccess) return e;
+        if ((e = hipStreamSynchronize(stream)) != hipSuccess) return e;
+        if (bad < give) {  // invalid distance too far back, at content byte `bad` of the call
+            give = bad;
+            r.finished = false;
+            r.end_bit = fb;
+            r.status = Z_DATA_ERROR;
+        }
+    }
+    if (give) {
+        uint32_t h_chk = 0;
+        if (cur.wrap) {
+            hipLaunchKernelGGL(par_checks_kernel, dim3(1), dim3(64), 0, stream, (const uint8_t *)c.out, (const uint64_t *)d_pt_out, 1u, give, cur.wrap, chk);
+            if ((e = hipMemcpyAsync(&h_chk, chk, 4, hipMemcpyDeviceToHost, stream)) != hipSuccess) return e;
+        }
+        hipLaunchKernelGGL(par_carry_kernel, dim3(1), dim3(1024), 0, stream, c.window, hist, (const uint8_t *)c.out, give);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        if ((e = hipStreamSynchronize(stream)) != hipSuccess) return e;
+        append_checks(cur, &h_chk, &give, 1);
+    }
+    r.out_len = give;
+    return hipSuccess;
+}
+
+hipError_t next_locked(ParSlot &sl, int format, const NextCall &c, chip_inflate_next_summary &s, hipStream_t stream)
+{
+    chip_inflate_cursor &cur = *c.cur;
+    if (cur.phase == CHIP_CUR_DONE) {
+        s.status = CHIP_FINISHED;
+        return hipSuccess;
+    }
+    if (cur.phase >= CHIP_CUR_ERROR) {
+        s.status = cur.phase == CHIP_CUR_ERROR && cur.error != CHIP_OK ? cur.error : (int32_t)CHIP_E_INVALID;
+        return hipSuccess;
+    }
+    hipError_t e = sl.summary();
+    if (e != hipSuccess) return e;
+    PhaseClock clock{stream, "inflate_next"};
+    clock.mark("start");
+    auto fail = [&](int32_t st) {  // sticky
+        cur.phase = CHIP_CUR_ERROR;
+        cur.error = st;
+        s.status = st;
+    };
+    uint64_t at_bit = cur.bit;  // of the slab: where the cursor stands
+    if (cur.phase == CHIP_CUR_HEADER) {
+        uint32_t wrap = 0, hdr = 0;
+        if (format != CHIP_FMT_DEFLATE) {
+            hipLaunchKernelGGL(par_wrapper_kernel, dim3(1), dim3(64), 0, stream, c.in, c.len, (int32_t)format, sl.d_sum);
+            if ((e = sl.fetch(stream)) != hipSuccess) return e;
+            const int32_t st = sl.h_sum->w_status;
+            if (st == CHIP_NEED_INPUT) return hipSuccess;
+            if (st != ST_RUNNING) {
+                fail(st);
+                return hipSuccess;
+            }
+            wrap = sl.h_sum->w_wrap, hdr = sl.h_sum->w_hdr;
+        }
+        clock.mark("wrapper");
+        cur.wrap = wrap;
+        cur.check = wrap == 1 ? 1u : 0u;
+        cur.phase = CHIP_CUR_BLOCKS;
+        at_bit = 8ull * hdr;
+    }
+    if (cur.phase == CHIP_CUR_BLOCKS) {
+        BlocksOut r;
+        r.end_bit = at_bit;
+        if ((e = blocks_locked(sl, c, at_bit, stream, clock, r)) != hipSuccess) return e;
+        s.out_len = r.out_len, s.need_out = r.need_out, s.n_chunks = r.n_chunks, s.n_starts = r.n_starts, s.n_false = r.n_false, s.path = r.path;
+        cursor_delivered(cur, r.out_len);
+        at_bit = r.end_bit;
+        if (r.status != CHIP_NEED_INPUT && r.status != CHIP_NEED_OUTPUT) fail(r.status);
+        else if (r.finished) {
+            cur.phase = CHIP_CUR_TRAILER;
+            at_bit = (r.end_bit + 7) & ~7ull;
+        } else s.status = r.status;
+    }
+    if (cur.phase == CHIP_CUR_TRAILER) {
+        const uint64_t tk = at_bit >> 3;
+        const uint32_t need = cur.wrap == 2 ? 8u : cur.wrap == 1 ? 4u : 0u;
+        uint8_t t[8] = {0};
+        if (c.len - tk < need) {
+            s.status = CHIP_NEED_INPUT;
+        } else {
+            if (need && (e = hipMemcpyAsync(t, c.in + tk, need, hipMemcpyDeviceToHost, stream)) != hipSuccess) return e;
+            if (need && (e = hipStreamSynchronize(stream)) != hipSuccess) return e;
+            at_bit += 8ull * need;
+            if (!trailer_matches(cur, t)) {
+                fail(Z_DATA_ERROR);  // incorrect data check / incorrect length check
+            } else {
+                cur.phase = CHIP_CUR_DONE;
+                s.status = CHIP_FINISHED;
+            }
+        }
+    }
+    s.in_used = cursor_advance(cur, at_bit);
+    return hipStreamSynchronize(stream);
 }
 
 }  // namespace
@@ -509,6 +858,28 @@ int chip_inflate_parallel(int format, const void *in_base, uint64_t len, void *o
             return e;
         },
         [&] { *summary = none; });
+}
+
+int chip_inflate_parallel_next(int format, chip_inflate_cursor *cur, void *window, const void *in_base, uint64_t len, void *out_base, uint64_t out_cap,
+                               uint32_t chunk_bytes, chip_inflate_next_summary *summary, void *stream)
+{
+    // arguments first, the device second: a refusal needs no GPU
+    if (format != CHIP_FMT_DEFLATE && format != CHIP_FMT_ZLIB && format != CHIP_FMT_GZIP && format != CHIP_FMT_AUTO) return CHIP_E_INVALID;
+    if (!summary || !cur || !window || (!in_base && len) || (!out_base && out_cap) || len > CHIP_GZPLAN_WINDOW || out_cap > 0xFFFFFFF0ull)
+        return CHIP_E_INVALID;
+    if (chunk_bytes && (chunk_bytes < 256 || chunk_bytes > CHIP_GZPLAN_WINDOW)) return CHIP_E_INVALID;
+    if (cur->bit > 7 || cur->phase > CHIP_CUR_ERROR || cur->wrap > 2 || cur->hist != (cur->out_total < WINDOW ? cur->out_total : WINDOW))
+        return CHIP_E_INVALID;
+    const chip_inflate_next_summary none{0, 0, 0, 0, 0, 0, CHIP_NEED_INPUT, CHIP_PAR_SERIAL};
+    *summary = none;
+    const chip_inflate_cursor before = *cur;
+    const NextCall c{(const uint8_t *)in_base, (uint32_t)len, (uint8_t *)out_base, out_cap, chunk_bytes, (uint8_t *)window, cur};
+    return with_slot(
+        g_par_cache, stream, [&](ParSlot &sl, hipStream_t s) { return next_locked(sl, format, c, *summary, s); },
+        [&] {
+            *summary = none;
+            *cur = before;  // (the window may hold a later state: a failed call ends the decode)
+        });
 }
 
 }  // extern "C"

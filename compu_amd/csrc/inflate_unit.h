@@ -1691,6 +1691,7 @@ struct SpecRec {
     const uint64_t *starts;  // the finder's answer, ascending; unit u >= 1 begins at starts[u - 1], unit 0 at the stream's beginning
     uint32_t n_starts;
     SpecOut *out;            // one per unit
+    uint32_t bit0 = 0;       // unit 0: the bit of its first byte it begins at (a stream taken up at a block boundary: no wrapper, raw format)
 };
 #define SPEC_REC_PARAM , const SpecRec &sp
 #else
@@ -1770,6 +1771,8 @@ __device__ __attribute__((always_inline)) void inflate_unit(const BatchArgs &a, 
     if (u) {
         resumed = true;  // no wrapper: a block header, at the bit the start names
         pos = start_bit + (uint32_t)(sp.starts[u - 1u] & 7u);
+    } else {
+        pos += sp.bit0;
     }
 #endif
 #if CHIP_INFLATE_MARKERS

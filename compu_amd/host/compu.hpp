@@ -600,6 +600,33 @@ public:
         if (rc == CHIP_OK && summary.status == CHIP_READ_OK) cursor_ += summary.out_len;
         return rc;
     }
+    // chip_inflate_parallel into this buffer's spare capacity: inflate_index_build()'s stream decoded with a wave per chunk of chunk_bytes
+    // (0 = 128 KiB) that holds a block start; the point arrays receive the chain's chunks.  With too little room summary.status is
+    // CHIP_NEED_OUTPUT and summary.total_out the size to come back with.  Synchronous on `stream`.
+    int inflate_parallel(int format, const DeviceBuffer &in, uint64_t len, uint32_t chunk_bytes, uint64_t max_points, uint64_t *pt_bit, uint64_t *pt_out,
+                         uint32_t *pt_check, void *windows, chip_inflate_parallel_summary &summary, void *stream = nullptr)
+    {
+        if (len > in.len()) return CHIP_E_INVALID;
+        const size_t room = cap_ - cursor_;
+        const int rc = chip_inflate_parallel(format, in.data(), len, buf_ + cursor_, room < 0xFFFFFFF0u ? room : 0xFFFFFFF0u, chunk_bytes, max_points,
+                                             pt_bit, pt_out, pt_check, windows, &summary, stream);
+        if (rc == CHIP_OK) cursor_ += summary.out_len;
+        return rc;
+    }
+    // chip_inflate_parallel_next into this buffer's spare capacity: the next part of ONE stream of any length.  `slab` holds `len` bytes of
+    // the stream from byte cur.in_total on (from offset `from` of the buffer: the caller keeps what a call did not consume and moves on by
+    // summary.in_used), `window` is the cursor's 32 768 bytes of DEVICE memory.  The cursor of this buffer moves by summary.out_len;
+    // summary.status says why the call stopped.  Synchronous on `stream`.
+    int inflate_parallel_next(int format, chip_inflate_cursor &cur, void *window, const DeviceBuffer &slab, uint64_t from, uint64_t len,
+                              uint32_t chunk_bytes, chip_inflate_next_summary &summary, void *stream = nullptr)
+    {
+        if (from > slab.len() || len > slab.len() - from) return CHIP_E_INVALID;
+        const size_t room = cap_ - cursor_;
+        const int rc = chip_inflate_parallel_next(format, &cur, window, slab.data() + from, len, buf_ + cursor_, room < 0xFFFFFFF0u ? room : 0xFFFFFFF0u,
+                                                  chunk_bytes, &summary, stream);
+        if (rc == CHIP_OK) cursor_ += summary.out_len;
+        return rc;
+    }
     // chip_select_units: the index step of read_ranges alone (DEVICE arrays, HOST summary), for a caller that decodes the sub-batch
     // sel_in_off / sel_in_len / sel_out_off / sel_out_cap into summary.scratch_bytes of its own.  max_sel 0 with null sel arrays
     // counts.  Synchronous on `stream`.

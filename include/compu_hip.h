@@ -923,6 +923,65 @@ int chip_inflate_parallel(int format, const void *in_base, uint64_t len, void *o
                           uint64_t max_points, uint64_t *pt_bit, uint64_t *pt_out, uint32_t *pt_check, void *windows,
                           chip_inflate_parallel_summary *summary, void *stream);
 
+/*
+ * chip_inflate_parallel_next: the NEXT PART of one raw deflate / zlib / gzip stream of any length, by the passes of
+ * chip_inflate_parallel over a SLAB of it.  The caller owns a CURSOR, plain host data that may be copied and
+ * saved (all zero = the beginning of a stream), and beside it 32 768 bytes of DEVICE memory, `window`, which a copy of the cursor
+ * needs a copy of.  in_base is a device pointer to stream byte cur->in_total and len the bytes of the stream that stand there, at
+ * most CHIP_GZPLAN_WINDOW per call.  in_base needs no alignment; the bytes up to the next multiple of 4 behind the slab must be
+ * readable.  out_cap is at most 2^32 - 16.  format as chip_inflate_parallel (it is read while phase = HEADER only);
+ * chunk_bytes is 0 (128 KiB) or 256 .. CHIP_GZPLAN_WINDOW.  SYNCHRONOUS on `stream`.
+ * Where a call ends: it moves the cursor from a block boundary to a later TRUE block boundary of the stream, or through the
+ * trailer.  It delivers exactly the content between the two at out_base[0 .. out_len), leaves in `window` the last cur->hist bytes
+ * of the content delivered so far (bytes of the old window are kept when fewer than 32 768 were delivered), brings cur->check up
+ * to cur->out_total, and answers in_used, the whole bytes in front of the new cursor byte: the next slab begins at in_base +
+ * in_used.  Chunks are slab-relative (chunk k is slab bytes [k B, (k + 1) B)), so where calls end depends on slab and room; the bytes
+ * never do.  status says why the call stopped:
+ *   - CHIP_FINISHED: the final block and the whole trailer were in the slab; the Adler-32 was compared, or the CRC-32 and ISIZE
+ *     (with out_total mod 2^32).  phase = CHIP_CUR_DONE; in_used counts through the trailer and nothing behind it.
+ *   - CHIP_NEED_INPUT: everything deliverable was delivered.  in_used == 0 && out_len == 0: the slab holds no whole step -- an
+ *     incomplete header, a block longer than the slab, a cut trailer; come back with a longer slab.
+ *   - CHIP_NEED_OUTPUT: the next piece was whole in the slab and did not fit the room left.  need_out is its decoded size where the
+ *     call knows it: always on the parallel path, else 0.
+ *   - CHIP_NEED_DICT or a negative code: sticky; phase = CHIP_CUR_ERROR, cur->error keeps it and every later call answers it.
+ *     out_len counts the bytes of true content delivered in front of the error.
+ * Progress: a call whose slab holds at least one whole block behind the cursor, with room for its bytes, advances the cursor.
+ * The parallel path (path = CHIP_PAR_PARALLEL) is chip_inflate_parallel's on the slab: unit 0 of the size pass begins at the cursor
+ * instead of a wrapper; a match of the first chain chunk may reach cur->hist bytes back; the window walk starts from the carried
+ * window.  A chain member that ended neither LINKED nor in the final block -- normally the last one, which ran out of slab -- is
+ * dropped and decoded again by the next call; chain chunks are delivered while they fit out_cap; their checks are appended to
+ * cur->check.  The one-wave path (CHIP_PAR_SERIAL) advances a slab on which the chain reaches no start (no start at all, a wave
+ * that gave up, a chunk the size pass does not vouch for): one wave decodes from the cursor to the last block boundary it reaches
+ * inside slab and room.  An error is found and reported there.
+ * A stream that fits one slab with ample room answers with the bytes, the total and the check of chip_inflate_parallel on it.
+ * n_chunks = ceil(len / B); n_starts and n_false as chip_inflate_parallel's, for this slab.
+ * CHIP_E_INVALID, before a device is looked for: a format other than the four; cur, window or summary NULL; in_base NULL with
+ * len > 0; out_base NULL with out_cap > 0; len > CHIP_GZPLAN_WINDOW; out_cap > 2^32 - 16; a chunk_bytes outside the range; a cursor
+ * no call has left (bit > 7, an unknown phase or wrap, hist != min(out_total, 32 768)).  CHIP_E_NOMEM / CHIP_E_LAUNCH: the cursor
+ * is as it was, the window may not be: the decode cannot go on.
+ * Scratch per (device, stream), in chip_inflate_parallel's launch slot, released by chip_trim(): twice the bytes delivered in the
+ * call for the elements (one-wave path: twice the room it could use); 64 KiB of token rows per unit of the size pass, at most
+ * 128 MiB; 32 KiB per delivered chain chunk; about 100 bytes per chunk of the slab.  It does not depend on the stream's length.
+ */
+enum { CHIP_CUR_HEADER = 0, CHIP_CUR_BLOCKS = 1, CHIP_CUR_TRAILER = 2, CHIP_CUR_DONE = 3, CHIP_CUR_ERROR = 4 };
+typedef struct {
+    uint64_t in_total;  /* whole bytes of the stream in front of the byte the next call starts in */
+    uint64_t out_total; /* bytes delivered so far */
+    uint32_t bit;       /* 0..7: where in that byte the next block header begins */
+    uint32_t phase;     /* CHIP_CUR_* */
+    uint32_t wrap;      /* 0 raw, 1 zlib, 2 gzip (known once phase > HEADER) */
+    uint32_t check;     /* running Adler-32 / CRC-32 over out_total bytes */
+    uint32_t hist;      /* valid bytes of `window`: min(out_total, 32768) */
+    int32_t error;      /* the sticky status once phase == ERROR */
+} chip_inflate_cursor;  /* all zero = the beginning of a stream */
+typedef struct {
+    uint64_t in_used, out_len, need_out, n_chunks, n_starts, n_false;
+    int32_t status; /* why the call stopped */
+    uint32_t path;  /* CHIP_PAR_SERIAL, CHIP_PAR_PARALLEL */
+} chip_inflate_next_summary;
+int chip_inflate_parallel_next(int format, chip_inflate_cursor *cur, void *window, const void *in_base, uint64_t len, void *out_base,
+                               uint64_t out_cap, uint32_t chunk_bytes, chip_inflate_next_summary *summary, void *stream);
+
 /* ---- zstd encoder: encoder::Interface::zstd, src/encoder/zstd.rs ------------------------------------------------------------ */
 
 /* ZstdStrategy src/encoder/zstd.rs:33-56 (ZSTD_strategy values; 0 = the level's own).  The GPU encoder has four level groups

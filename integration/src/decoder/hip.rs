@@ -668,3 +668,25 @@ pub unsafe fn inflate_parallel_device(mode: ZlibMode, input: &crate::buffer::Dev
                                         &mut summary, stream);
     if rc == sys::CHIP_OK { Ok(summary) } else { Err(rc) }
 }
+
+///`chip_inflate_parallel_next`: decodes the next part of one gzip / zlib / raw deflate stream of any length.  `slab` holds `len`
+///bytes of the stream from byte `cursor.in_total` on, `window` (at least 32 768 bytes) the last `cursor.hist` bytes of the content
+///delivered so far; the call delivers whole chain chunks or blocks into `output` while they fit, moves the cursor to a later block
+///boundary (or through the trailer) and says in the summary how many bytes of the slab lie in front of the new cursor, how many
+///bytes it delivered and why it stopped.  Synchronous on `stream`.  No counterpart in this crate.
+///
+///# Safety
+///
+///As `inflate_parallel_device`; `window` must be the one the cursor was left with.
+pub unsafe fn inflate_parallel_next_device(mode: ZlibMode, cursor: &mut sys::chip_inflate_cursor, window: &mut crate::buffer::DeviceBuffer,
+                                           slab: &crate::buffer::DeviceBuffer, len: usize, output: &mut crate::buffer::DeviceBuffer,
+                                           chunk_bytes: u32, stream: *mut core::ffi::c_void)
+                                           -> Result<sys::chip_inflate_next_summary, i32> {
+    if len > slab.capacity() || window.capacity() < sys::CHIP_INDEX_WINDOW {
+        return Err(-101);
+    }
+    let mut summary = sys::chip_inflate_next_summary::default();
+    let rc = sys::chip_inflate_parallel_next(BatchFormat::Zlib(mode).tag(), cursor, window.as_mut_ptr() as *mut _, slab.as_ptr() as *const _,
+                                             len as u64, output.as_mut_ptr() as *mut _, output.capacity() as u64, chunk_bytes, &mut summary, stream);
+    if rc == sys::CHIP_OK { Ok(summary) } else { Err(rc) }
+}

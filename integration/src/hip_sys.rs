@@ -232,6 +232,41 @@ pub struct chip_inflate_parallel_summary {
     pub path: u32,
 }
 
+///`chip_inflate_cursor::phase`
+pub const CHIP_CUR_HEADER: u32 = 0;
+pub const CHIP_CUR_BLOCKS: u32 = 1;
+pub const CHIP_CUR_TRAILER: u32 = 2;
+pub const CHIP_CUR_DONE: u32 = 3;
+pub const CHIP_CUR_ERROR: u32 = 4;
+///where a slabbed decode of one stream stands (`chip_inflate_parallel_next`): plain host data, all zero = the beginning of a stream;
+///the last `hist` bytes of the content live in 32 768 bytes of device memory beside it
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct chip_inflate_cursor {
+    pub in_total: u64,
+    pub out_total: u64,
+    pub bit: u32,
+    pub phase: u32,
+    pub wrap: u32,
+    pub check: u32,
+    pub hist: u32,
+    pub error: i32,
+}
+///what one `chip_inflate_parallel_next` call answers: the bytes it consumed and delivered, the size of the piece that did not fit
+///(`need_out`), the slab's chunks, starts and false starts, why it stopped and which `path` decoded
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct chip_inflate_next_summary {
+    pub in_used: u64,
+    pub out_len: u64,
+    pub need_out: u64,
+    pub n_chunks: u64,
+    pub n_starts: u64,
+    pub n_false: u64,
+    pub status: i32,
+    pub path: u32,
+}
+
 pub type chip_malloc_fn = unsafe extern "C" fn(opaque: *mut c_void, size: usize) -> *mut c_void;
 pub type chip_free_fn = unsafe extern "C" fn(opaque: *mut c_void, ptr: *mut c_void);
 
@@ -376,4 +411,7 @@ extern "C" {
     pub fn chip_inflate_parallel(format: c_int, in_base: *const c_void, len: u64, out_base: *mut c_void, out_cap: u64, chunk_bytes: u32, max_points: u64,
                                  pt_bit: *mut u64, pt_out: *mut u64, pt_check: *mut u32, windows: *mut c_void,
                                  summary: *mut chip_inflate_parallel_summary, stream: *mut c_void) -> c_int;
+    pub fn chip_inflate_parallel_next(format: c_int, cur: *mut chip_inflate_cursor, window: *mut c_void, in_base: *const c_void, len: u64,
+                                      out_base: *mut c_void, out_cap: u64, chunk_bytes: u32, summary: *mut chip_inflate_next_summary,
+                                      stream: *mut c_void) -> c_int;
 }
