@@ -51,6 +51,22 @@ class _ZstdPlanSummary(C.Structure):
                 ("in_used", C.c_uint64), ("status", C.c_int32), ("pad", C.c_uint32)]
 
 
+class _ZstdBlock(C.Structure):
+    _fields_ = [("offset", C.c_uint64), ("size", C.c_uint32), ("lit_regen", C.c_uint32), ("lit_comp", C.c_uint32), ("n_seq", C.c_uint32),
+                ("type", C.c_uint8), ("flags", C.c_uint8), ("lit_type", C.c_uint8), ("mode", C.c_uint8 * 3), ("pad", C.c_uint8 * 2),
+                ("src", C.c_int32 * 4)]
+
+
+class _ZstdBlocksSummary(C.Structure):
+    _fields_ = [("n_blocks", C.c_uint64), ("in_used", C.c_uint64), ("content_size", C.c_uint64), ("window_size", C.c_uint64),
+                ("status", C.c_int32), ("descriptor", C.c_uint32), ("header_bytes", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class _ZstdParallelSummary(C.Structure):
+    _fields_ = [("n_blocks", C.c_uint64), ("n_sequences", C.c_uint64), ("out_len", C.c_uint64), ("in_used", C.c_uint64), ("total_out", C.c_uint64),
+                ("status", C.c_int32), ("path", C.c_uint32), ("rounds", C.c_uint32), ("check", C.c_uint32)]
+
+
 class _GzipPlanSummary(C.Structure):
     _fields_ = [("n_members", C.c_uint64), ("total_out", C.c_uint64), ("in_used", C.c_uint64), ("status", C.c_int32),
                 ("member_status", C.c_int32)]
@@ -183,6 +199,12 @@ def lib():
     L.chip_zstd_plan_host.argtypes = [vp, C.c_uint64, C.c_uint64, vp, vp, vp, vp, C.POINTER(_ZstdPlanSummary)]
     L.chip_zstd_plan.restype = C.c_int
     L.chip_zstd_plan.argtypes = [vp, C.c_uint64, C.c_uint64, vp, vp, vp, vp, C.POINTER(_ZstdPlanSummary), vp]
+    L.chip_zstd_blocks_host.restype = C.c_int
+    L.chip_zstd_blocks_host.argtypes = [vp, C.c_uint64, C.c_uint64, vp, C.POINTER(_ZstdBlocksSummary)]
+    L.chip_zstd_parallel.restype = C.c_int
+    L.chip_zstd_parallel.argtypes = [vp, C.c_uint64, vp, C.c_uint64, C.c_int, C.c_uint32, C.POINTER(_ZstdParallelSummary), vp]
+    L.chip_zstd_blocks.restype = C.c_int
+    L.chip_zstd_blocks.argtypes = [vp, C.c_uint64, C.c_uint64, vp, C.POINTER(_ZstdBlocksSummary), vp]
     L.chip_gzip_plan.restype = C.c_int
     L.chip_gzip_plan.argtypes = [vp, C.c_uint64, C.c_uint64, vp, vp, vp, vp, C.POINTER(_GzipPlanSummary), vp]
     L.chip_layout_units.restype = C.c_int
@@ -1256,6 +1278,156 @@ def zstd_plan(in_buf, length, stream=None, max_frames=None):
     min(n_frames, max_frames) frames; with summary.n_unsized == 0 they are ready for decode_batch(FMT_ZSTD, ..).  Synchronous
     on `stream`.  max_frames None: all of them (one call to count, one to fill)."""
     return _plan_device("chip_zstd_plan", _ZstdPlanSummary, ZstdPlanSummary, "n_frames", in_buf, length, stream, max_frames)
+
+
+ZBLOCKS_UNSIZED = 0xFFFFFFFFFFFFFFFF  # CHIP_ZBLOCKS_UNSIZED: content_size of a frame without Frame_Content_Size
+ZBLOCK_LAST, ZBLOCK_MALFORMED = 1, 2  # chip_zstd_block.flags
+ZSRC_HUF, ZSRC_LL, ZSRC_OF, ZSRC_ML = 0, 1, 2, 3  # the columns of chip_zstd_block.src
+
+
+def zstd_block_dtype():
+    """chip_zstd_block as a numpy record: offset, size, lit_regen, lit_comp, n_seq, type, flags, lit_type, mode[3], src[4]."""
+    import numpy as np
+
+    dt = np.dtype([("offset", "<u8"), ("size", "<u4"), ("lit_regen", "<u4"), ("lit_comp", "<u4"), ("n_seq", "<u4"), ("type", "u1"),
+                   ("flags", "u1"), ("lit_type", "u1"), ("mode", "u1", (3,)), ("pad", "u1", (2,)), ("src", "<i4", (4,))])
+    assert dt.itemsize == C.sizeof(_ZstdBlock)
+    return dt
+
+
+class ZstdBlocksSummary:
+    """chip_zstd_blocks_summary: n_blocks the walk counted, in_used (the frame's end, 0 when the walk stopped early), content_size
+    (ZBLOCKS_UNSIZED without Frame_Content_Size), window_size, status why the walk stopped, the frame header descriptor and the
+    frame header's length."""
+
+    __slots__ = ("n_blocks", "in_used", "content_size", "window_size", "status", "descriptor", "header_bytes")
+
+    def __init__(self, raw):
+        self.n_blocks, self.in_used, self.content_size = int(raw.n_blocks), int(raw.in_used), int(raw.content_size)
+        self.window_size, self.status = int(raw.window_size), ZstdPlanStatus(raw.status)
+        self.descriptor, self.header_bytes = int(raw.descriptor), int(raw.header_bytes)
+
+    def as_tuple(self):
+        return (self.n_blocks, self.in_used, self.content_size, self.window_size, int(self.status), self.descriptor, self.header_bytes)
+
+    def __repr__(self):
+        return (f"ZstdBlocksSummary(n_blocks={self.n_blocks}, in_used={self.in_used}, content_size={self.content_size}, "
+                f"window_size={self.window_size}, status={self.status.name}, descriptor={self.descriptor:#x}, header_bytes={self.header_bytes})")
+
+
+def zstd_blocks_host(data, max_blocks=None):
+    """chip_zstd_blocks_host over bytes / a uint8 numpy array in host memory: (blocks, summary) of the FIRST frame -- blocks a
+    numpy record array (zstd_block_dtype) of the first min(n_blocks, max_blocks) blocks (None = all of them: one call to count,
+    one to fill).  Read from headers alone; nothing is decoded."""
+    import numpy as np
+
+    buf = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8)
+    raw = _ZstdBlocksSummary()
+    p = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None  # noqa: E731
+    call = lib().chip_zstd_blocks_host
+    if max_blocks is None:
+        rc = call(p(buf), buf.size, 0, None, C.byref(raw))
+        if rc != 0:
+            raise RuntimeError(f"chip_zstd_blocks_host failed: {rc}")
+        max_blocks = int(raw.n_blocks)
+    m = int(max_blocks)
+    blocks = np.zeros(m, zstd_block_dtype())
+    rc = call(p(buf), buf.size, m, p(blocks), C.byref(raw))
+    if rc != 0:
+        raise RuntimeError(f"chip_zstd_blocks_host failed: {rc}")
+    return blocks[:min(m, int(raw.n_blocks))], ZstdBlocksSummary(raw)
+
+
+def zstd_blocks(in_buf, length, stream=None, max_blocks=None):
+    """chip_zstd_blocks over a uint8 device tensor holding `length` bytes that begin with a zstd frame (4-byte aligned, padded to
+    a multiple of 4): (blocks, summary), blocks a uint8 device tensor of shape (k, 48) holding the chip_zstd_block records of the
+    first k = min(n_blocks, max_blocks) blocks (`.cpu().numpy().view(zstd_block_dtype())` reads them).  Synchronous on `stream`.
+    max_blocks None: all of them (one call to count, one to fill)."""
+    import torch
+
+    dev = _check_tensors(((in_buf, torch.uint8),))
+    length = int(length)
+    if length < 0 or length > in_buf.numel():
+        raise ValueError(f"length {length} outside the buffer of {in_buf.numel()} bytes")
+    raw = _ZstdBlocksSummary()
+    base, sp = (_dp(in_buf) if length else None), _stream_ptr(stream)
+    call = lib().chip_zstd_blocks
+    with torch.cuda.device(dev):
+        if max_blocks is None:  # count, then fill
+            rc = call(base, length, 0, None, C.byref(raw), sp)
+            if rc != 0:
+                raise RuntimeError(f"chip_zstd_blocks failed: {rc}")
+            max_blocks = int(raw.n_blocks)
+        m = int(max_blocks)
+        blocks = torch.empty((m, C.sizeof(_ZstdBlock)), dtype=torch.uint8, device=dev)
+        rc = call(base, length, m, _dp(blocks) if m else None, C.byref(raw), sp)
+    if rc != 0:
+        raise RuntimeError(f"chip_zstd_blocks failed: {rc}")
+    return blocks[:min(m, int(raw.n_blocks))], ZstdBlocksSummary(raw)
+
+
+ZPAR_SERIAL, ZPAR_PARALLEL, ZPAR_REFUSED = 0, 1, 2  # chip_zstd_parallel_summary.path
+ZPAR_NO_CHECKSUM = 1  # CHIP_ZPAR_NO_CHECKSUM
+ZPAR_ROUNDS_MAX = 40
+
+
+class ZstdParallelSummary:
+    """chip_zstd_parallel_summary: n_blocks and n_sequences of the frame (parallel path), out_len, in_used, total_out (the size to
+    come back with on NeedOutput), status, path (ZPAR_*), rounds of the jump pass, check."""
+
+    __slots__ = ("n_blocks", "n_sequences", "out_len", "in_used", "total_out", "status", "path", "rounds", "check")
+
+    def __init__(self, raw):
+        self.n_blocks, self.n_sequences, self.out_len = int(raw.n_blocks), int(raw.n_sequences), int(raw.out_len)
+        self.in_used, self.total_out, self.status = int(raw.in_used), int(raw.total_out), int(raw.status)
+        self.path, self.rounds, self.check = int(raw.path), int(raw.rounds), int(raw.check)
+
+    def as_tuple(self):
+        """everything but `rounds`, which may differ from call to call"""
+        return (self.n_blocks, self.n_sequences, self.out_len, self.in_used, self.total_out, self.status, self.path, self.check)
+
+    def __repr__(self):
+        return (f"ZstdParallelSummary(n_blocks={self.n_blocks}, n_sequences={self.n_sequences}, out_len={self.out_len}, in_used={self.in_used}, "
+                f"total_out={self.total_out}, status={self.status}, path={self.path}, rounds={self.rounds}, check={self.check})")
+
+
+def zstd_parallel(in_buf, length, out_buf=None, window_log_max=0, checksum=True, stream=None):
+    """chip_zstd_parallel over a uint8 device tensor holding `length` bytes that begin with ONE zstd frame (4-byte aligned, padded
+    to a multiple of 4): (out, summary).  With `out_buf` (a uint8 device tensor) the content goes there and `out` is its first
+    out_len bytes.  Without, the call is made with no room first, then with a new tensor of total_out bytes; a frame that takes the
+    serial path states no size that way (the batch decode's NeedOutput carries none), so it is sized by decode_batch_sizes as one
+    unit and decoded with that room -- a frame that is refused, or in error, comes back as the empty tensor and its summary.
+    checksum=False waives the comparison of Content_Checksum on the parallel path.  Synchronous on `stream`."""
+    import torch
+
+    dev = _check_tensors(((in_buf, torch.uint8),) + (((out_buf, torch.uint8),) if out_buf is not None else ()))
+    length = int(length)
+    if length < 0 or length > in_buf.numel():
+        raise ValueError(f"length {length} outside the buffer of {in_buf.numel()} bytes")
+    raw = _ZstdParallelSummary()
+    flags = 0 if checksum else ZPAR_NO_CHECKSUM
+    base, sp = (_dp(in_buf) if length else None), _stream_ptr(stream)
+
+    def call(out):
+        cap = out.numel() if out is not None else 0
+        rc = lib().chip_zstd_parallel(base, length, _dp(out) if cap else None, cap, int(window_log_max), flags, C.byref(raw), sp)
+        if rc != 0:
+            raise RuntimeError(f"chip_zstd_parallel failed: {rc}")
+
+    with torch.cuda.device(dev):
+        if out_buf is None:
+            call(None)
+            need = int(raw.total_out) if raw.status == int(DecodeStatus.NeedOutput) else 0
+            if raw.status == int(DecodeStatus.NeedOutput) and raw.path == ZPAR_SERIAL and length <= 1 << 28:
+                one = lambda v, dt: torch.tensor([v], dtype=torch.int64, device=dev).to(dt)  # noqa: E731
+                size, _, st = decode_batch_sizes(FMT_ZSTD, in_buf, one(0, torch.int64), one(length, torch.int32), stream=stream)
+                need = int(size[0]) if int(st[0]) == int(DecodeStatus.Finished) and int(size[0]) <= 0xFFFFFFFF else 0
+            out_buf = torch.empty(need, dtype=torch.uint8, device=dev)
+            if need:
+                call(out_buf)
+        else:
+            call(out_buf)
+    return out_buf[:int(raw.out_len)], ZstdParallelSummary(raw)
 
 
 def layout_units(out_size, stream=None):

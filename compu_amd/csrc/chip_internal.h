@@ -63,6 +63,19 @@ struct BatchArgs {
     const uint32_t *sel_n = nullptr;
     uint32_t flags = 0;  // CHIP_F_* of chip_decode_batch_ex (include/compu_hip.h)
 };
+// What zstd_tokens_kernel (zstd.hip compiled with CHIP_ZSTD_TOKENS; zstd_tokens.hip) takes beside a BatchArgs whose units are the blocks
+// of ONE frame: in_off 0 and in_len the frame's for every unit, out_off / out_cap the block's literal slot in scratch.
+struct ZTokArgs {
+    const chip_zstd_block *blocks;  // chip_zstd_blocks' records
+    const uint32_t *seq_base;       // sequences in front of each block
+    uint32_t *tok;                  // 3 words per sequence: literal length, match length, offset (bit 31: symbolic)
+    uint32_t *res;                  // 8 words per block: rep0..2 handed on, literal mode (0 input, 1 RLE, 2 slot), its place / byte, Regenerated_Size
+    uint64_t window;
+};
+constexpr uint32_t ZTOK_SLOT_SLACK = 8736;  // a literal slot is Regenerated_Size + this: the Huffman walk's scratch rows (zstd.hip asserts it)
+hipError_t launch_zstd_tokens(const BatchArgs &a, const ZTokArgs &tk, hipStream_t stream);
+// (zstd_tokens.hip) XXH64 of n bytes on one wave, its low 32 bits to *got
+hipError_t launch_zstd_xxh(const uint8_t *p, uint32_t n, uint32_t *got, hipStream_t stream);
 constexpr uint32_t F_COMPU_STATUS = 1u;  // = CHIP_F_COMPU_STATUS
 constexpr uint32_t F_MEMBERS = 2u;       // = CHIP_F_MEMBERS
 

@@ -987,7 +987,20 @@ __device__ void wave_match_copy(uint8_t *dst, uint32_t offset, uint32_t n)
 #ifndef CHIP_ZSTD_MEMBERS
 #define CHIP_ZSTD_MEMBERS 0
 #endif
-#ifndef CHIP_ZSTD_SIZES_TU
+#ifndef CHIP_ZSTD_TOKENS
+#define CHIP_ZSTD_TOKENS 0
+#endif
+// CHIP_ZSTD_TOKENS (zstd_tokens.hip; chip_zstd_parallel): one wave takes ONE compressed block of a frame whose
+// blocks chip_zstd_blocks has described.  It first replays the table descriptions of the blocks its block reuses a table of (tk_replay:
+// headers and table builds only), then decodes the block's literals into its scratch slot (the unit's output range) and stores the
+// sequences as (literal length, match length, offset) instead of executing them.  The repeat offsets start SYMBOLIC: bit 31 set,
+// [30:29] = k, [28:0] = n stands for max(rep_in[k] - n, 1).  Checks that need the absolute position stay out.  Without the macro this
+// file's tokens are what they were.
+#if CHIP_ZSTD_TOKENS
+#define CHIP_ZSTD_SIZES 0
+static_assert(HSCR_BYTES + 16 <= ZTOK_SLOT_SLACK, "the literal slot holds the scratch rows in front of the literals");
+__global__ __launch_bounds__(64, CHIP_ZSTD_WAVES) void zstd_tokens_kernel(BatchArgs a, int wlog_max, ZTokArgs tk)
+#elif !defined(CHIP_ZSTD_SIZES_TU)
 #define CHIP_ZSTD_SIZES 0
 #if CHIP_ZSTD_MEMBERS
 __global__ __launch_bounds__(64, CHIP_ZSTD_WAVES) void zstd_members_kernel(BatchArgs a, int wlog_max)
@@ -1004,6 +1017,10 @@ __global__ __launch_bounds__(64, CHIP_ZSTD_WAVES) void zstd_sizes_kernel(BatchAr
 #endif
 {
     constexpr bool SIZES = CHIP_ZSTD_SIZES != 0;
+    constexpr bool TOKENS = CHIP_ZSTD_TOKENS != 0;
+#if !CHIP_ZSTD_TOKENS
+    constexpr bool tk_replay = false;
+#endif
     __shared__ ZLds L;
     if (blockIdx.x >= (a.sel_n ? *a.sel_n : a.n)) return;
     const uint32_t u = a.sel ? a.sel[blockIdx.x] : blockIdx.x;
@@ -1121,10 +1138,34 @@ __global__ __launch_bounds__(64, CHIP_ZSTD_WAVES) void zstd_sizes_kernel(BatchAr
     };
 
     // ---- frame header (sec. 3.1.1.1) ------------------------------------------------------------
+#if CHIP_ZSTD_TOKENS
+    // the passes of this wave: the blocks whose tables its block reuses, in ascending order, then the block itself
+    const chip_zstd_block tk_me = tk.blocks[u];
+    uint32_t tk_src[4], tk_n = 0, tk_pass = 0;
+    bool tk_replay = false;
+    if (tk_me.type != 2) {  // raw and RLE blocks are placed from their description
+        status = CHIP_FINISHED;
+        opos = tk_me.size;
+        goto done;
+    }
+    for (uint32_t k = 0; k < 4; k++) {
+        const bool need = k == 0 ? tk_me.lit_type == 3 : (tk_me.n_seq != 0 && tk_me.mode[k - 1] == 3);
+        if (!need) continue;
+        const int32_t sj = tk_me.src[k];
+        if (sj < 0 || (uint32_t)sj >= u) ZFAIL(ZSTD_E_CORRUPTION);  // a reuse without a source: not clean
+        uint32_t at = 0;
+        while (at < tk_n && tk_src[at] < (uint32_t)sj) at++;
+        if (at < tk_n && tk_src[at] == (uint32_t)sj) continue;
+        for (uint32_t m = tk_n; m > at; m--) tk_src[m] = tk_src[m - 1];
+        tk_src[at] = (uint32_t)sj;
+        tk_n++;
+    }
+    window = tk.window;
+#endif
 #if CHIP_ZSTD_MEMBERS
 next_frame:
 #endif
-    if (!resumed) {
+    if (!resumed && !TOKENS) {
         if (END - ip < 4) ZNEED_INPUT();
         uint32_t magic = rd32_at(b, ip * 8u);
         if ((magic & 0xFFFFFFF0u) == 0x184D2A50u) {  // skippable frame (sec. 3.1.2): a frame without content
@@ -1168,6 +1209,16 @@ next_frame:
 
     // ---- blocks (sec. 3.1.1.2) --------------------------------------------------------------------
     while (!blocks_done) {
+#if CHIP_ZSTD_TOKENS
+        tk_replay = tk_pass < tk_n;
+        // (the unit's input begins at the earliest block this wave reads, not at the frame's: the cursors here are 32-bit bit positions)
+        ip = B0 + (uint32_t)((tk_replay ? tk.blocks[tk_src[tk_pass]].offset : tk_me.offset) - a.in_off[u]);
+        if (!tk_replay) {
+            rep0 = 0x80000000u;
+            rep1 = 0xA0000000u;
+            rep2 = 0xC0000000u;
+        }
+#endif
         if (END - ip < 3) ZNEED_INPUT();
         const uint32_t bh = rd32_at(b, ip * 8u) & 0xffffffu;
         const uint32_t last = bh & 1u, type = (bh >> 1) & 3u, bsz = bh >> 3;
@@ -1265,8 +1316,8 @@ next_frame:
                     if (c < 0) ZFAIL(ZSTD_E_CORRUPTION);
                     lp += (uint32_t)c;
                     lleft -= (uint32_t)c;
-                } else if (!L.huf_valid) ZFAIL(30);  // treeless without a previous table: dictionary_corrupted
-                if (regen > cap - opos) {
+                } else if (!tk_replay && !L.huf_valid) ZFAIL(30);  // treeless without a previous table: dictionary_corrupted
+                if (!tk_replay && regen > cap - opos) {
                     status = CHIP_NEED_OUTPUT;
                     goto done;
                 }
@@ -1289,7 +1340,7 @@ next_frame:
                     st0 = lp + 6;
                 }
                 bool sbad = false;
-                if (SIZES) {
+                if (SIZES || tk_replay) {
                     // the streams' contents are not looked at: they are skipped by their stated size
                 } else if (streams == 4) {
                     // 16 lanes per stream (see huf_decode4)
@@ -1397,6 +1448,9 @@ next_frame:
                 p += 3;
                 left -= 3;
             }
+#if CHIP_ZSTD_TOKENS
+            if (!tk_replay && nseq != tk_me.n_seq) ZFAIL(ZSTD_E_CORRUPTION);  // (the token room was laid out from the description)
+#endif
             const uint32_t block_out0 = opos;
             uint32_t lpos = 0;
             auto copy_literals = [&](uint32_t n) {
@@ -1406,6 +1460,13 @@ next_frame:
                 else wave_copy_bytes(gout + opos, gout + lit_out + lpos, n);
             };
             if (nseq == 0) {
+#if CHIP_ZSTD_TOKENS
+                if (tk_replay) {
+                    tk_pass++;
+                    rewind_to = ~0u;
+                    continue;
+                }
+#endif
                 if (left != 0) ZFAIL(ZSTD_E_CORRUPTION);
             } else {
                 if (left < 1) ZFAIL(ZSTD_E_CORRUPTION);
@@ -1437,7 +1498,7 @@ next_frame:
                         if (fse_build(L, t, nsym, al)) ZFAIL(ZSTD_E_CORRUPTION);
                         p += (uint32_t)c;
                         left -= (uint32_t)c;
-                    } else if (!*t.valid) ZFAIL(ZSTD_E_CORRUPTION);
+                    } else if (!tk_replay && !*t.valid) ZFAIL(ZSTD_E_CORRUPTION);
                     if (mode != 3) {
                         // A freshly built table is re-coded for the serial state chain below: [4:0] state bits (used as
                         // they are as v_bfe widths and offsets), [11:5] MINUS (state bits + extra bits of the code) modulo 128
@@ -1457,6 +1518,13 @@ next_frame:
                 }
                 WSYNC();
                 ZT_END(14, zt14);
+#if CHIP_ZSTD_TOKENS
+                if (tk_replay) {  // the tables are what this pass was for
+                    tk_pass++;
+                    rewind_to = ~0u;
+                    continue;
+                }
+#endif
                 BackBits s0;
                 if (!bb_init(b, s0, p, left)) ZFAIL(ZSTD_E_CORRUPTION);
                 SeqBits s;
@@ -1726,8 +1794,8 @@ next_frame:
                             const uint32_t idx = rdlane(ov, j) - (rdlane(ll, j) != 0 ? 1u : 0u);  // 3 means rep0 - 1
                             uint32_t offset = rep0;
                             if (idx != 0) {
-                                uint32_t t = idx == 3 ? rep0 - 1 : (idx == 1 ? rep1 : rep2);
-                                t += !t;
+                                uint32_t t = idx == 3 ? (TOKENS ? ((rep0 & 0x80000000u) ? rep0 + 1 : (rep0 > 1 ? rep0 - 1 : 1u)) : rep0 - 1) : (idx == 1 ? rep1 : rep2);
+                                if (!TOKENS) t += !t;
                                 if (idx != 1) rep2 = rep1;
                                 rep1 = rep0;
                                 rep0 = t;
@@ -1748,8 +1816,8 @@ next_frame:
                     else if (lane < cn && lane < dec_bad) {
                         if (dropped + ostart + tot > out_limit || (uint64_t)(ostart - block_out0) + tot > BLOCK_MAX) fail = 1;
                         else if (lit_incl > regen - lpos) fail = 2;
-                        else if ((uint64_t)ostart + tot > cap) fail = 3;
-                        else if ((SIZES ? (uint64_t)off > dropped + mstart : off > mstart) || off > window) fail = 4;  // beyond the frame's start, or beyond its window: the verdict must not
+                        else if (!TOKENS && (uint64_t)ostart + tot > cap) fail = 3;
+                        else if (TOKENS ? (ov > 3 && off >= 0x80000000u) : (SIZES ? (uint64_t)off > dropped + mstart : off > mstart) || off > window) fail = 4;  // beyond the frame's start, or beyond its window: the verdict must not
                                                                           // depend on how much history a streaming caller has let go (api.hip, dec_compact)
                     }
                     const uint64_t failm = __ballot(fail != 0);
@@ -1764,12 +1832,20 @@ next_frame:
                         ZFAIL(ZSTD_E_CORRUPTION);
                     }
                     const uint32_t LB = rdlane(lit_incl, 63), OB = rdlane(out_incl, 63);
+#if CHIP_ZSTD_TOKENS
+                    if (lane < cn) {
+                        uint32_t *const w = tk.tok + 3 * (tk.seq_base[u] + i0 + lane);
+                        w[0] = ll;
+                        w[1] = ml;
+                        w[2] = off;
+                    }
+#endif
                     // (LSYNC in both phases: the steps talk through LDS, and a wave's global stores are seen by its later loads in
                     // program order -- lanes of one wave share the CU's L1 --, so no step waits for its stores to be acknowledged)
                     // ---- phase A: all literal bytes of the chunk (their sources never depend on this chunk) ----
                     ZT_BEGIN(zt5);
 #ifndef CHIP_EXP_NOEXEC
-                    if (!SIZES && LB) {
+                    if (!SIZES && !TOKENS && LB) {
                         LSYNC();
                         L.xpar[2 * lane] = ostart;
                         L.xpar[2 * lane + 1] = lit_before;
@@ -1817,7 +1893,7 @@ next_frame:
                     ZT_END(5, zt5);
                     // ---- phase B: matches, several per step as long as none reads what the step writes ----------
                     ZT_BEGIN(zt6);
-                    if (!SIZES) {
+                    if (!SIZES && !TOKENS) {
                         const uint32_t mbi = wave_incl_scan(ml), mbx = mbi - ml;
                         const uint32_t srcend = mstart - off + (ml < off ? ml : off);
                         uint64_t mm = __ballot(ml != 0);
@@ -1910,21 +1986,33 @@ next_frame:
             const uint32_t restl = regen - lpos;
             if (dropped + opos + restl > out_limit) ZFAIL(70);
             if ((uint64_t)(opos - block_out0) + restl > BLOCK_MAX) ZFAIL(70);
-            if ((uint64_t)opos + restl > cap) {
+            if (!TOKENS && (uint64_t)opos + restl > cap) {
                 opos = block_out0;
                 status = CHIP_NEED_OUTPUT;
                 goto done;
             }
-            if (!SIZES) copy_literals(restl);
+            if (!SIZES && !TOKENS) copy_literals(restl);
             opos += restl;
             ip = bend;
             rewind_to = ~0u;
+#if CHIP_ZSTD_TOKENS
+            if (lane == 0) {  // where the block's literals lie, and the repeat offsets it hands on
+                uint32_t *const r = tk.res + 8 * u;
+                r[0] = rep0;
+                r[1] = rep1;
+                r[2] = rep2;
+                r[3] = lit_mode;
+                r[4] = lit_mode == 0 ? lit_in - B0 : lit_mode == 1 ? lit_rle : lit_out;
+                r[5] = regen;
+            }
+            blocks_done = true;
+#endif
         }
         if (SIZES) {  // the block is counted: the 32-bit cursor starts over
             dropped += opos;
             opos = 0;
         }
-        if (last) {
+        if (!TOKENS && last) {
             if (has_fcs && dropped + opos != fcs) ZFAIL(ZSTD_E_CORRUPTION);
             blocks_done = true;
         }
@@ -2022,7 +2110,9 @@ done:
 
 }  // namespace
 
-#if CHIP_ZSTD_MEMBERS && !defined(CHIP_ZSTD_SIZES_TU)
+#if CHIP_ZSTD_TOKENS
+// (the launch is zstd_tokens.hip's)
+#elif CHIP_ZSTD_MEMBERS && !defined(CHIP_ZSTD_SIZES_TU)
 hipError_t launch_zstd_members(const BatchArgs &a, int window_log_max, hipStream_t stream)
 {
     hipLaunchKernelGGL(zstd_members_kernel, dim3(a.n), dim3(64), 0, stream, a, window_log_max ? window_log_max : 27);

@@ -459,6 +459,128 @@ int chip_zstd_plan(const void *in_base, uint64_t len, uint64_t max_frames, uint6
 int chip_layout_units(size_t n, const uint64_t *out_size, uint64_t *out_off, uint32_t *out_cap, uint64_t *total, uint64_t *n_over,
                       void *stream);
 
+/* ---- one zstd frame: its blocks and their table sources (additive API) ----- */
+
+/*
+ * The plain `big.zst` is ONE frame of many blocks.  A block states its size in its 3-byte header, so where every block lies is
+ * found by the hop chip_zstd_plan makes, and what a block needs from the blocks in front of it -- the Huffman literal table a
+ * Treeless_Literals_Block reuses, the FSE tables Repeat_Mode reuses -- is stated in its section headers.  These calls describe the
+ * blocks of the FIRST frame of a buffer from headers alone: nothing is decoded.  It is the first pass of decoding one frame with a
+ * wave per block (sec. 4.19), and a cheap answer to "which blocks stand alone".  All integers are little endian.
+ * The walk of `len` bytes:
+ *     len < 4             -> TRUNCATED
+ *     LE32(0) != 0xFD2FB528 -> BAD_HEADER           (a skippable frame in front is not stepped over)
+ *     len < 5             -> TRUNCATED
+ *     fhd = byte(4);  f = fhd >> 6;  ss = (fhd >> 5) & 1;  d = fhd & 3
+ *     hs = 5 + (ss ? 0 : 1) + {0,1,2,4}[d] + (f == 0 ? ss : {-,2,4,8}[f])
+ *     len < hs            -> TRUNCATED
+ *     content_size = CHIP_ZBLOCKS_UNSIZED when f == 0 and ss == 0, else the field's value (the 2-byte form + 256)
+ *     window_size  = ss ? content_size : (1 << wl) + ((1 << wl) >> 3) * (wd & 7), wd = byte(5), wl = 10 + (wd >> 3)
+ *     q = hs;  n = 0
+ *     per block:  len - q < 3 -> TRUNCATED;  h = LE24(q);  type = (h >> 1) & 3;  type == 3 -> BAD_HEADER
+ *                 n + 1 > CHIP_ZPLAN_MAX_BLOCKS -> TOO_LARGE
+ *                 body = (type == 1) ? 1 : h >> 3;  body > len - q - 3 -> TRUNCATED
+ *                 block n:  offset = q, size = h >> 3, type, flags = h & 1 (CHIP_ZBLOCK_LAST)
+ *                 n++;  q += 3 + body;  stop after the block with h & 1
+ *     fhd & 4 (checksum):  len - q < 4 -> TRUNCATED;  q += 4
+ *     in_used = q, status OK
+ * A walk that stops early keeps the blocks it has counted (header and body present), with in_used = 0: the frame is not
+ * consumed.  The reserved bit, the dictionary ID and the window against a limit are for the decode to judge; `descriptor` is fhd
+ * and header_bytes is hs, so it can.
+ * A compressed block (type 2) is described from its literals section header and its sequences section header (RFC 8878
+ * 3.1.1.3.1.1, 3.1.1.3.2.1): lit_type (0 raw, 1 RLE, 2 compressed, 3 treeless), lit_regen (Regenerated_Size), lit_comp (the bytes
+ * the literals take behind their header: lit_regen, 1, or Compressed_Size), n_seq (Number_of_Sequences) and mode[3], the
+ * compression modes of LL, OF and ML (0 predefined, 1 RLE, 2 FSE, 3 repeat; all 0 when n_seq == 0, which has no modes byte).
+ * Where one of these headers reaches beyond the block's body, the block gets CHIP_ZBLOCK_MALFORMED, the fields from there on are
+ * 0, and it defines nothing.  Raw and RLE blocks have these fields 0.
+ * src[k] of block i is the nearest block j < i that DEFINED the table of kind k, or -1:
+ *     CHIP_ZSRC_HUF        a compressed block with lit_type == 2
+ *     CHIP_ZSRC_LL/OF/ML   a compressed block with n_seq > 0 whose mode of that kind is not 3 (predefined and RLE define a table;
+ *                          a block with no sequences defines nothing)
+ * src is filled for every block, whether it reuses a table or not: block i needs src[CHIP_ZSRC_HUF] when lit_type == 3 and
+ * src[CHIP_ZSRC_LL + k] when n_seq > 0 and mode[k] == 3, and a -1 there means the frame cannot be decoded.
+ * `blocks` receives the first min(n_blocks, max_blocks) blocks and nothing behind them is written: max_blocks = 0 with a NULL
+ * array counts, a second call fills.  CHIP_E_INVALID, checked before the device is looked for: summary NULL, a NULL buffer with
+ * len > 0, a NULL array with max_blocks > 0 (chip_zstd_blocks: in_base not 4-byte aligned, len > 2^40).
+ * The limits are chip_zstd_plan's (the same buffer goes to both): 2^40 bytes, and the alignment chip_zstd_parallel's token pass needs
+ * for its dword loads although the walk itself reads bytes; chip_zstd_parallel narrows len to 2^32 - 1.
+ * A consumer tests CHIP_ZBLOCK_MALFORMED first: the literals fields of such a block are kept when only the sequences header failed to
+ * fit.  The record does not say whether Huffman literals come in one stream or four (Size_Format 0 against 1 to 3 of the first body
+ * byte): the token pass parses that header itself.
+ * No reference counterpart: compu decodes a frame front to back.
+ */
+#define CHIP_ZBLOCKS_UNSIZED 0xFFFFFFFFFFFFFFFFull /* content_size of a frame without Frame_Content_Size */
+enum { CHIP_ZBLOCK_LAST = 1, CHIP_ZBLOCK_MALFORMED = 2 };
+enum { CHIP_ZSRC_HUF = 0, CHIP_ZSRC_LL = 1, CHIP_ZSRC_OF = 2, CHIP_ZSRC_ML = 3 };
+typedef struct {
+    uint64_t offset;    /* of the 3-byte block header in the buffer */
+    uint32_t size;      /* the Block_Size field: the body's bytes (raw, compressed) or the count of an RLE block */
+    uint32_t lit_regen, lit_comp, n_seq;
+    uint8_t type, flags, lit_type, mode[3], pad[2];
+    int32_t src[4];
+} chip_zstd_block;
+typedef struct {
+    uint64_t n_blocks, in_used, content_size, window_size;
+    int32_t status;     /* CHIP_ZPLAN_OK, _TRUNCATED, _BAD_HEADER, _TOO_LARGE */
+    uint32_t descriptor, header_bytes, pad;
+} chip_zstd_blocks_summary;
+
+/* On HOST memory: pure host arithmetic, no device needed. */
+int chip_zstd_blocks_host(const uint8_t *in, uint64_t len, uint64_t max_blocks, chip_zstd_block *blocks, chip_zstd_blocks_summary *summary);
+
+/* The same answer for a buffer in DEVICE memory, with the conventions of chip_zstd_plan: in_base and blocks are DEVICE pointers,
+ * summary is a HOST pointer; in_base 4-byte aligned, its allocation padded to a multiple of 4 bytes.  One lane hops over the
+ * block headers, then one lane per block reads its section headers and one workgroup scans for the sources.  SYNCHRONOUS on
+ * `stream`: it waits once behind the hop for the block count and once at the end.  A launch slot of its own (the summary only),
+ * released by chip_trim().  The calling thread's current device is left as it was. */
+int chip_zstd_blocks(const void *in_base, uint64_t len, uint64_t max_blocks, chip_zstd_block *blocks, chip_zstd_blocks_summary *summary,
+                     void *stream);
+
+/*
+ * ONE large zstd frame decoded by the whole GPU, with the conventions of chip_inflate_parallel: in_base and
+ * out_base are DEVICE pointers, in_base 4-byte aligned and its allocation padded to a multiple of 4; summary is a HOST pointer;
+ * SYNCHRONOUS on `stream`; scratch in a launch slot of its own, released by chip_trim(); the calling thread's device is left as it
+ * was.  window_log_max as in chip_decoder_opts (0 is 27).  Only the FIRST frame of the buffer is decoded; in_used says where it ended.
+ * The passes: chip_zstd_blocks; a token pass, one wave per block, that rebuilds the tables its block reuses from the blocks
+ * chip_zstd_blocks names, decodes the literals and stores the sequences with symbolic repeat offsets; the host's prefix sums and
+ * carried repeat offsets; one 32-bit word per content byte (a final byte or the position it copies), every offset checked; pointer
+ * jumping W[p] = W[W[p]] until no word is left (at most 32 rounds below 2^31 bytes; after CHIP_ZPAR_ROUNDS_MAX the serial path); the
+ * bytes, and XXH64 over them on one wave.
+ * A CLEAN frame of at least two blocks with total_out <= out_cap: path = CHIP_ZPAR_PARALLEL; the bytes, out_len, in_used and status
+ * (CHIP_FINISHED) are those of chip_decode_batch(CHIP_FMT_ZSTD, 1, ..) for that unit.  Clean: the buffer starts with the frame magic;
+ * the frame header is accepted (reserved bit, dictionary ID, the window against window_log_max); every block is present and of a
+ * legal type; the token pass fails in no block; every table reuse has a source; every offset lies within the content before it and
+ * the window; every block decodes to at most Block_Maximum_Size; the blocks add up to Frame_Content_Size where one is stated;
+ * total_out < 2^31; the content checksum matches if one is present and not waived.
+ * The same with total_out > out_cap: CHIP_NEED_OUTPUT, out_len = 0, total_out the exact size to come back with; nothing is written
+ * (the checksum is compared by the call that has the room).
+ * Anything else: path = CHIP_ZPAR_SERIAL and the answer is the one-unit batch decode's, which is the arbiter of every verdict -- if
+ * the frame fits a unit (out_cap <= 2^32 - 1 and at most 2^28 bytes of input: the first frame's own length where the block walk
+ * reaches its end, else len); else path = CHIP_ZPAR_REFUSED and nothing is written.  A clean frame is not bounded by 2^28: a wave of
+ * the token pass reads from the earliest block whose table its block reuses to the end of its block, and only that span must stay
+ * below 2^28 bytes (a reuse across more is "anything else").
+ * CHIP_ZPAR_NO_CHECKSUM: on the parallel path the checksum is read over, not compared (XXH64 is one serial chain: one wave hashes
+ * the whole content).  The one deliberate difference from the batch.  summary.check is 0.  Where the checksum is compared the bytes
+ * are delivered into scratch, hashed there and copied to out_base only when they match: a mismatch writes nothing before the
+ * serial decode does.
+ * CHIP_E_INVALID before the device is looked for: summary NULL, a NULL buffer with a length, in_base misaligned, unknown flag bits,
+ * len > 2^32 - 1.  The bytes and every summary field except `rounds` are a property of the frame.
+ * CHIP_ZPAR_TIMING in the environment (read on every call; a diagnostic): the call waits behind every phase and prints its time on
+ * stderr -- describe, tokens, place, each jump round with the words left, deliver, checksum, copy.
+ * Scratch: 4 bytes per content byte (5 where the checksum is compared), 12 per sequence, Regenerated_Size + 8 736 per block with Huffman literals, about 140 per block;
+ * CHIP_E_NOMEM if it cannot be had.
+ */
+enum { CHIP_ZPAR_SERIAL = 0, CHIP_ZPAR_PARALLEL = 1, CHIP_ZPAR_REFUSED = 2 };
+#define CHIP_ZPAR_NO_CHECKSUM 1u      /* flags: do not verify Content_Checksum */
+#define CHIP_ZPAR_ROUNDS_MAX 40
+typedef struct {
+    uint64_t n_blocks, n_sequences, out_len, in_used, total_out;
+    int32_t status;
+    uint32_t path, rounds, check;
+} chip_zstd_parallel_summary;
+int chip_zstd_parallel(const void *in_base, uint64_t len, void *out_base, uint64_t out_cap, int window_log_max, uint32_t flags,
+                       chip_zstd_parallel_summary *summary, void *stream);
+
 /* ---- gzip members: from a file to a batch (additive API) ------------------- */
 
 /*

@@ -373,6 +373,57 @@ pub unsafe fn zstd_plan_device(input: &crate::buffer::DeviceBuffer, len: usize, 
     if rc == sys::CHIP_OK { Ok(summary) } else { Err(rc) }
 }
 
+///The blocks of the first zstd frame of a buffer in host memory (`chip_zstd_blocks_host`): where each block lies, its type, a
+///compressed block's section headers and, per table kind, the nearest earlier block that defined the table it may reuse (-1: none);
+///and the summary of the walk.  Read from headers alone, nothing is decoded.  Pure host arithmetic.  No counterpart in this crate.
+pub fn zstd_blocks_host(input: &[u8]) -> Result<(alloc::vec::Vec<sys::chip_zstd_block>, sys::chip_zstd_blocks_summary), i32> {
+    let mut summary = sys::chip_zstd_blocks_summary::default();
+    let rc = unsafe { sys::chip_zstd_blocks_host(input.as_ptr(), input.len() as u64, 0, ptr::null_mut(), &mut summary) };
+    if rc != sys::CHIP_OK {
+        return Err(rc);
+    }
+    let n = summary.n_blocks as usize;
+    let mut blocks = alloc::vec![sys::chip_zstd_block::default(); n];
+    let rc = unsafe { sys::chip_zstd_blocks_host(input.as_ptr(), input.len() as u64, n as u64, blocks.as_mut_ptr(), &mut summary) };
+    if rc == sys::CHIP_OK { Ok((blocks, summary)) } else { Err(rc) }
+}
+
+///`chip_zstd_blocks` over the first `len` bytes of a device-resident buffer that begins with a zstd frame: fills `blocks` (device
+///memory, 48 bytes per `chip_zstd_block`) for the first `max_blocks` blocks and returns the summary of the whole walk (`max_blocks`
+///0 counts).  Synchronous on `stream`.
+///
+///# Safety
+///
+///As `decode_batch_device`; `input` must be 4-byte aligned and padded to a multiple of 4 bytes.
+pub unsafe fn zstd_blocks_device(input: &crate::buffer::DeviceBuffer, len: usize, max_blocks: usize, blocks: &mut crate::buffer::DeviceBuffer,
+                                 stream: *mut core::ffi::c_void) -> Result<sys::chip_zstd_blocks_summary, i32> {
+    if len > input.capacity() || blocks.capacity() < core::mem::size_of::<sys::chip_zstd_block>() * max_blocks {
+        return Err(-101);
+    }
+    let mut summary = sys::chip_zstd_blocks_summary::default();
+    let rc = sys::chip_zstd_blocks(input.as_ptr() as *const _, len as u64, max_blocks as u64, blocks.as_mut_ptr() as *mut sys::chip_zstd_block, &mut summary,
+                                   stream);
+    if rc == sys::CHIP_OK { Ok(summary) } else { Err(rc) }
+}
+
+///`chip_zstd_parallel`: the first zstd frame of the first `len` bytes of `input` decoded into `output` with a wave per block; the
+///summary carries the batch decode's `out_len`, `in_used` and `status`, the exact size on `NeedOutput` and the path taken.
+///`flags`: `CHIP_ZPAR_NO_CHECKSUM`.  Synchronous on `stream`.
+///
+///# Safety
+///
+///As `decode_batch_device`; `input` must be 4-byte aligned and padded to a multiple of 4 bytes.
+pub unsafe fn zstd_parallel_device(input: &crate::buffer::DeviceBuffer, len: usize, output: &mut crate::buffer::DeviceBuffer, window_log_max: i32, flags: u32,
+                                   stream: *mut core::ffi::c_void) -> Result<sys::chip_zstd_parallel_summary, i32> {
+    if len > input.capacity() {
+        return Err(-101);
+    }
+    let mut summary = sys::chip_zstd_parallel_summary::default();
+    let rc = sys::chip_zstd_parallel(input.as_ptr() as *const _, len as u64, output.as_mut_ptr() as *mut _, output.capacity() as u64, window_log_max, flags,
+                                     &mut summary, stream);
+    if rc == sys::CHIP_OK { Ok(summary) } else { Err(rc) }
+}
+
 ///`chip_gzip_plan` over the first `len` bytes of a device-resident buffer of gzip members (WARC records, `cat a.gz b.gz`, what
 ///`encode_file_device` writes for gzip): fills the four device arrays for the first `max_members` members -- what
 ///`decode_batch_device` takes with `BatchFormat::Zlib` in gzip mode -- and returns the summary of the whole walk (`max_members` 0 counts).

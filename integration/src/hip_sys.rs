@@ -116,6 +116,74 @@ pub struct chip_zstd_plan_summary {
     pub pad: u32,
 }
 
+///`content_size` of a frame without `Frame_Content_Size`
+pub const CHIP_ZBLOCKS_UNSIZED: u64 = u64::MAX;
+///`chip_zstd_block::flags`
+pub const CHIP_ZBLOCK_LAST: u8 = 1;
+pub const CHIP_ZBLOCK_MALFORMED: u8 = 2;
+///the columns of `chip_zstd_block::src`
+pub const CHIP_ZSRC_HUF: usize = 0;
+pub const CHIP_ZSRC_LL: usize = 1;
+pub const CHIP_ZSRC_OF: usize = 2;
+pub const CHIP_ZSRC_ML: usize = 3;
+
+///one block of a zstd frame as its headers describe it: where it lies, its type, a compressed block's literals and sequences section
+///headers, and per table kind the nearest earlier block that defined the table (-1: none)
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct chip_zstd_block {
+    pub offset: u64,
+    pub size: u32,
+    pub lit_regen: u32,
+    pub lit_comp: u32,
+    pub n_seq: u32,
+    pub r#type: u8,
+    pub flags: u8,
+    pub lit_type: u8,
+    pub mode: [u8; 3],
+    pub pad: [u8; 2],
+    pub src: [i32; 4],
+}
+
+///what the walk over one frame's block headers found: the blocks counted, the frame's end (0 when the walk stopped early), the
+///stated content size, the window, why it stopped (`CHIP_ZPLAN_*`), the frame header descriptor and the frame header's length
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct chip_zstd_blocks_summary {
+    pub n_blocks: u64,
+    pub in_used: u64,
+    pub content_size: u64,
+    pub window_size: u64,
+    pub status: i32,
+    pub descriptor: u32,
+    pub header_bytes: u32,
+    pub pad: u32,
+}
+
+///`chip_zstd_parallel_summary::path`
+pub const CHIP_ZPAR_SERIAL: u32 = 0;
+pub const CHIP_ZPAR_PARALLEL: u32 = 1;
+pub const CHIP_ZPAR_REFUSED: u32 = 2;
+///`chip_zstd_parallel` flag: do not verify `Content_Checksum`
+pub const CHIP_ZPAR_NO_CHECKSUM: u32 = 1;
+pub const CHIP_ZPAR_ROUNDS_MAX: u32 = 40;
+
+///what `chip_zstd_parallel` did: blocks and sequences of the frame, bytes written, input consumed, the exact size to come back with,
+///the batch decode's status, the path taken, the rounds of the jump pass
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct chip_zstd_parallel_summary {
+    pub n_blocks: u64,
+    pub n_sequences: u64,
+    pub out_len: u64,
+    pub in_used: u64,
+    pub total_out: u64,
+    pub status: i32,
+    pub path: u32,
+    pub rounds: u32,
+    pub check: u32,
+}
+
 ///`chip_gzip_plan_summary::status`
 pub const CHIP_GZPLAN_OK: i32 = 0;
 pub const CHIP_GZPLAN_TRUNCATED: i32 = 1;
@@ -330,6 +398,15 @@ extern "C" {
     ///the same answer for a buffer in device memory (device arrays, host summary); synchronous on `stream`
     pub fn chip_zstd_plan(in_base: *const c_void, len: u64, max_frames: u64, in_off: *mut u64, in_len: *mut u32, out_off: *mut u64, out_cap: *mut u32,
                           summary: *mut chip_zstd_plan_summary, stream: *mut c_void) -> c_int;
+    ///the blocks of the first frame of a host buffer and their table sources, from headers alone; pure host arithmetic
+    pub fn chip_zstd_blocks_host(input: *const u8, len: u64, max_blocks: u64, blocks: *mut chip_zstd_block, summary: *mut chip_zstd_blocks_summary) -> c_int;
+    ///the same answer for a buffer in device memory (device records, host summary); synchronous on `stream`
+    pub fn chip_zstd_blocks(in_base: *const c_void, len: u64, max_blocks: u64, blocks: *mut chip_zstd_block, summary: *mut chip_zstd_blocks_summary,
+                            stream: *mut c_void) -> c_int;
+    ///one large zstd frame decoded with a wave per block (token pass, placement, pointer jumping); anything not clean is the one-unit
+    ///batch decode's answer; synchronous on `stream`
+    pub fn chip_zstd_parallel(in_base: *const c_void, len: u64, out_base: *mut c_void, out_cap: u64, window_log_max: c_int, flags: u32,
+                              summary: *mut chip_zstd_parallel_summary, stream: *mut c_void) -> c_int;
     ///the member index of a device-resident buffer of gzip members: the size pass over every candidate start, then the chain from 0
     pub fn chip_gzip_plan(in_base: *const c_void, len: u64, max_members: u64, in_off: *mut u64, in_len: *mut u32, out_off: *mut u64, out_cap: *mut u32,
                           summary: *mut chip_gzip_plan_summary, stream: *mut c_void) -> c_int;
