@@ -67,6 +67,26 @@ class _ZstdParallelSummary(C.Structure):
                 ("status", C.c_int32), ("path", C.c_uint32), ("rounds", C.c_uint32), ("check", C.c_uint32)]
 
 
+class _Xxh64State(C.Structure):
+    _fields_ = [("acc", C.c_uint64 * 4), ("total", C.c_uint64), ("tail", C.c_uint8 * 32), ("tail_n", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class _ZstdCursor(C.Structure):
+    _fields_ = [("in_total", C.c_uint64), ("out_total", C.c_uint64), ("window_size", C.c_uint64), ("content_size", C.c_uint64),
+                ("hist", C.c_uint64), ("ring", C.c_uint64), ("carry_at", C.c_uint64 * 4), ("carry_len", C.c_uint32 * 4), ("rep", C.c_uint32 * 3),
+                ("phase", C.c_uint32), ("descriptor", C.c_uint32), ("waived", C.c_uint32), ("error", C.c_int32), ("pad", C.c_uint32),
+                ("xxh", _Xxh64State)]
+
+
+class _ZstdNextSummary(C.Structure):
+    _fields_ = [("in_used", C.c_uint64), ("out_len", C.c_uint64), ("need_out", C.c_uint64), ("need_state", C.c_uint64), ("n_blocks", C.c_uint64),
+                ("n_sequences", C.c_uint64), ("status", C.c_int32), ("rounds", C.c_uint32)]
+
+
+class _ZstdSlabSummary(C.Structure):
+    _fields_ = [("n_blocks", C.c_uint64), ("in_used", C.c_uint64), ("status", C.c_int32), ("last", C.c_uint32)]
+
+
 class _GzipPlanSummary(C.Structure):
     _fields_ = [("n_members", C.c_uint64), ("total_out", C.c_uint64), ("in_used", C.c_uint64), ("status", C.c_int32),
                 ("member_status", C.c_int32)]
@@ -205,6 +225,17 @@ def lib():
     L.chip_zstd_parallel.argtypes = [vp, C.c_uint64, vp, C.c_uint64, C.c_int, C.c_uint32, C.POINTER(_ZstdParallelSummary), vp]
     L.chip_zstd_blocks.restype = C.c_int
     L.chip_zstd_blocks.argtypes = [vp, C.c_uint64, C.c_uint64, vp, C.POINTER(_ZstdBlocksSummary), vp]
+    L.chip_zstd_parallel_next.restype = C.c_int
+    L.chip_zstd_parallel_next.argtypes = [C.POINTER(_ZstdCursor), vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, C.c_int, C.c_uint32,
+                                          C.POINTER(_ZstdNextSummary), vp]
+    L.chip_zstd_slab_blocks_host.restype = C.c_int
+    L.chip_zstd_slab_blocks_host.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint64, vp, C.POINTER(_ZstdSlabSummary)]
+    L.chip_zstd_cursor_header_host.restype = C.c_int
+    L.chip_zstd_cursor_header_host.argtypes = [C.POINTER(_ZstdCursor), vp, C.c_uint64, C.c_int, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
+    L.chip_xxh64_update_host.restype = C.c_int
+    L.chip_xxh64_update_host.argtypes = [C.POINTER(_Xxh64State), vp, C.c_uint64]
+    L.chip_xxh64_digest_host.restype = C.c_uint64
+    L.chip_xxh64_digest_host.argtypes = [C.POINTER(_Xxh64State)]
     L.chip_gzip_plan.restype = C.c_int
     L.chip_gzip_plan.argtypes = [vp, C.c_uint64, C.c_uint64, vp, vp, vp, vp, C.POINTER(_GzipPlanSummary), vp]
     L.chip_layout_units.restype = C.c_int
@@ -1428,6 +1459,257 @@ def zstd_parallel(in_buf, length, out_buf=None, window_log_max=0, checksum=True,
         else:
             call(out_buf)
     return out_buf[:int(raw.out_len)], ZstdParallelSummary(raw)
+
+
+ZCUR_HEADER, ZCUR_BLOCKS, ZCUR_CHECKSUM, ZCUR_DONE, ZCUR_ERROR = range(5)  # chip_zstd_cursor::phase
+ZCUR_SLOT_BYTES = 131088  # CHIP_ZCUR_SLOT_BYTES
+ZCUR_CARRY_BYTES = 4 * ZCUR_SLOT_BYTES  # CHIP_ZCUR_CARRY_BYTES
+
+
+class ZstdCursor:
+    """chip_zstd_cursor and its device state (the four carry slots and the window ring): where a slabbed decode of ONE zstd frame
+    stands.  A fresh one is the beginning of a frame; its state is allocated by zstd_parallel_next once the frame header has said
+    how large the window is (need_state).  The scalar fields read and write the C struct `raw`; copy() is an independent cursor at
+    the same place."""
+
+    FIELDS = ("in_total", "out_total", "window_size", "content_size", "hist", "ring", "phase", "descriptor", "waived", "error")
+
+    def __init__(self, device=None):
+        import torch
+
+        self.raw = _ZstdCursor()
+        self.device = torch.device(device if device is not None else "cuda")
+        self.state = torch.zeros(ZCUR_CARRY_BYTES, dtype=torch.uint8, device=self.device)
+
+    def __getattr__(self, name):
+        if name in ZstdCursor.FIELDS:
+            return int(getattr(self.raw, name))
+        raise AttributeError(name)
+
+    def __setattr__(self, name, value):
+        if name in ZstdCursor.FIELDS:
+            setattr(self.raw, name, int(value))
+        else:
+            object.__setattr__(self, name, value)
+
+    def copy(self):
+        other = ZstdCursor(self.device)
+        C.memmove(C.byref(other.raw), C.byref(self.raw), C.sizeof(_ZstdCursor))
+        other.state = self.state.clone()
+        return other
+
+    def __repr__(self):
+        return "ZstdCursor(" + ", ".join(f"{name}={getattr(self, name)}" for name in self.FIELDS) + f", rep={list(self.raw.rep)})"
+
+
+class ZstdNextSummary:
+    """chip_zstd_next_summary: in_used bytes of the slab lie in front of the new cursor, out_len bytes were delivered, need_out is the
+    decoded size of the block that did not fit, need_state the state bytes to come back with, n_blocks / n_sequences / rounds
+    describe the blocks taken, status says why the call stopped (a DecodeStatus value or a negative error)."""
+
+    FIELDS = tuple(name for name, _ in _ZstdNextSummary._fields_)
+
+    def __init__(self, raw):
+        for name in self.FIELDS:
+            setattr(self, name, int(getattr(raw, name)))
+
+    def __repr__(self):
+        return "ZstdNextSummary(" + ", ".join(f"{name}={getattr(self, name)}" for name in self.FIELDS) + ")"
+
+
+def zstd_parallel_next(cursor, in_buf, out_buf, window_log_max=0, checksum=True, stream=None, grow_state=True):
+    """chip_zstd_parallel_next: decode the next part of the frame `cursor` stands in.  in_buf (uint8 device tensor, any alignment)
+    holds the frame from byte cursor.in_total on, out_buf the room.  The cursor moves; the bytes are out_buf[:summary.out_len] and
+    the next slab begins summary.in_used bytes further.  grow_state: a call that stops behind the frame header because the state is
+    too small for the window (need_state) gets a state of that size and is made again over the rest of the slab, its in_used added.
+    Synchronous on `stream`."""
+    import torch
+
+    dev = _check_tensors([(in_buf, torch.uint8), (out_buf, torch.uint8), (cursor.state, torch.uint8)])
+    flags = 0 if checksum else ZPAR_NO_CHECKSUM
+    done = 0
+    while True:
+        raw = _ZstdNextSummary()
+        part = in_buf[done:]
+        with torch.cuda.device(dev):
+            rc = lib().chip_zstd_parallel_next(C.byref(cursor.raw), _dp(cursor.state), cursor.state.numel(), _dp(part) if part.numel() else None, part.numel(),
+                                               _dp(out_buf) if out_buf.numel() else None, out_buf.numel(), int(window_log_max), flags, C.byref(raw),
+                                               _stream_ptr(stream))
+        if rc != 0:
+            raise RuntimeError(f"chip_zstd_parallel_next failed: {rc}")
+        summ = ZstdNextSummary(raw)
+        summ.in_used += done
+        if not (grow_state and summ.need_state > cursor.state.numel()):
+            return summ
+        done = summ.in_used
+        state = torch.zeros(summ.need_state, dtype=torch.uint8, device=dev)
+        state[:ZCUR_CARRY_BYTES] = cursor.state[:ZCUR_CARRY_BYTES]
+        cursor.state = state
+
+
+class ZstdSlabSummary:
+    """chip_zstd_slab_summary: the whole blocks in front of where the walk from a block boundary stopped, their bytes, why it stopped
+    (ZstdPlanStatus; Truncated is a cut block, no error) and whether the frame's last block is among them."""
+
+    __slots__ = ("n_blocks", "in_used", "status", "last")
+
+    def __init__(self, raw):
+        self.n_blocks, self.in_used, self.status, self.last = int(raw.n_blocks), int(raw.in_used), ZstdPlanStatus(raw.status), int(raw.last)
+
+    def as_tuple(self):
+        return (self.n_blocks, self.in_used, int(self.status), self.last)
+
+    def __repr__(self):
+        return f"ZstdSlabSummary(n_blocks={self.n_blocks}, in_used={self.in_used}, status={self.status.name}, last={self.last})"
+
+
+def zstd_slab_blocks_host(data, block_max=131072):
+    """chip_zstd_slab_blocks_host over bytes that begin at a block boundary of a frame whose Block_Maximum_Size is block_max:
+    (blocks, summary), the records as zstd_blocks_host's with slab-relative offsets and sources."""
+    import numpy as np
+
+    buf = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8)
+    raw = _ZstdSlabSummary()
+    p = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None  # noqa: E731
+    call = lib().chip_zstd_slab_blocks_host
+    rc = call(p(buf), buf.size, int(block_max), 0, None, C.byref(raw))
+    if rc != 0:
+        raise RuntimeError(f"chip_zstd_slab_blocks_host failed: {rc}")
+    m = int(raw.n_blocks)
+    blocks = np.zeros(m, zstd_block_dtype())
+    rc = call(p(buf), buf.size, int(block_max), m, p(blocks), C.byref(raw))
+    if rc != 0:
+        raise RuntimeError(f"chip_zstd_slab_blocks_host failed: {rc}")
+    return blocks, ZstdSlabSummary(raw)
+
+
+def zstd_cursor_header_host(data, window_log_max=0, checksum=True):
+    """chip_zstd_cursor_header_host on the first bytes of a frame in host memory: (status, raw cursor, header_bytes, need_state).
+    status is DecodeStatus.Finished with the cursor at the first block, NeedInput for a cut header, or the negative code."""
+    import numpy as np
+
+    buf = np.frombuffer(bytes(data), dtype=np.uint8)
+    cur, hb, need = _ZstdCursor(), C.c_uint32(0), C.c_uint64(0)
+    rc = lib().chip_zstd_cursor_header_host(C.byref(cur), buf.ctypes.data_as(C.c_void_p) if buf.size else None, buf.size, int(window_log_max),
+                                            0 if checksum else ZPAR_NO_CHECKSUM, C.byref(hb), C.byref(need))
+    return rc, cur, int(hb.value), int(need.value)
+
+
+class Xxh64:
+    """A running XXH64 (seed 0) over chip_xxh64_state: update(bytes), digest(), copy()."""
+
+    def __init__(self):
+        self.raw = _Xxh64State()
+
+    def update(self, data):
+        import numpy as np
+
+        buf = np.frombuffer(bytes(data), dtype=np.uint8)
+        rc = lib().chip_xxh64_update_host(C.byref(self.raw), buf.ctypes.data_as(C.c_void_p) if buf.size else None, buf.size)
+        if rc != 0:
+            raise RuntimeError(f"chip_xxh64_update_host failed: {rc}")
+        return self
+
+    def digest(self):
+        return int(lib().chip_xxh64_digest_host(C.byref(self.raw)))
+
+    def copy(self):
+        other = Xxh64()
+        C.memmove(C.byref(other.raw), C.byref(self.raw), C.sizeof(_Xxh64State))
+        return other
+
+
+def zstd_parallel_stream(source, sink=None, slab_bytes=64 << 20, out_bytes=256 << 20, frames=False, checksum=True, window_log_max=0, device=None):
+    """One zstd frame of ANY length through zstd_parallel_next: `source` (bytes-like, or a binary file object) is uploaded slab after
+    slab, every call's bytes are downloaded and written to `sink` (a binary file object; None: they are returned as bytes).  The
+    slab doubles when a call finds no whole block in it, the room goes to need_out when the next block does not fit, the state is
+    allocated from need_state.  frames=True: behind a finished frame the loop goes on while a zstd or skippable magic follows, as
+    `zstd -d` does, and steps over skippable frames itself.  Raises DecodeError(code) on an error in the frame and EOFError when
+    the source ends inside it.  Returns the bytes, or with a sink the number of bytes written."""
+    import numpy as np
+    import torch
+
+    dev = torch.device(device if device is not None else "cuda")
+    read = source.read if hasattr(source, "read") else None
+    view, taken = (None, 0) if read else (memoryview(source).cast("B"), 0)
+    pending, eof = bytearray(), False
+    slab, room = max(int(slab_bytes), 1), max(int(out_bytes), 1)
+    parts, written = [], 0
+    cur = ZstdCursor(dev)
+    d_in, d_out = None, None
+
+    def fill(want):
+        nonlocal eof, taken
+        while not eof and len(pending) < want:
+            if read:
+                piece = read(want - len(pending))
+            else:
+                piece = view[taken : taken + want - len(pending)]
+                taken += len(piece)
+            if not len(piece):
+                eof = True
+            pending.extend(piece)
+
+    while True:
+        slab, room = min(slab, 1 << 31), min(room, (1 << 31) - 1)
+        fill(slab)
+        n = min(len(pending), slab)  # (below the slab only where the source has ended: the buffers are as large as what there is)
+        left = cur.content_size - cur.out_total if cur.phase and cur.content_size != ZBLOCKS_UNSIZED else ZBLOCKS_UNSIZED
+        if not cur.phase:  # a new frame: what its header says of its size, so that a small frame gets a small room
+            rc, head, _, _ = zstd_cursor_header_host(pending[:18], 31)
+            left = int(head.content_size) if rc == int(DecodeStatus.Finished) else ZBLOCKS_UNSIZED
+        room_now = min(room, max(left, 1)) if 0 <= left < ZBLOCKS_UNSIZED else room
+        if d_in is None or d_in.numel() < n:
+            d_in = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+        if d_out is None or d_out.numel() < room_now:
+            d_out = torch.empty(room_now, dtype=torch.uint8, device=dev)
+        if n:  # straight from the pending bytes (the copy from pageable memory has ended when copy_ returns)
+            host = torch.from_numpy(np.frombuffer(pending, dtype=np.uint8, count=n))
+            d_in[:n].copy_(host)
+            del host  # (it holds the bytearray's buffer, which is cut below)
+        s = zstd_parallel_next(cur, d_in[:n], d_out[:room_now], window_log_max, checksum)
+        if s.out_len:
+            got = d_out[: s.out_len].cpu().numpy().tobytes()
+            written += len(got)
+            if sink is None:
+                parts.append(got)
+            else:
+                sink.write(got)
+        del pending[: s.in_used]
+        if s.status == int(DecodeStatus.Finished):
+            again = False
+            while frames:
+                fill(8)
+                magic = int.from_bytes(bytes(pending[:4]), "little") if len(pending) >= 4 else 0
+                if magic & 0xFFFFFFF0 == 0x184D2A50:  # a skippable frame: 8 bytes and what they announce
+                    if len(pending) < 8:
+                        raise EOFError("the source ends inside a skippable frame")
+                    size = 8 + int.from_bytes(bytes(pending[4:8]), "little")
+                    fill(size)
+                    if len(pending) < size:
+                        raise EOFError("the source ends inside a skippable frame")
+                    del pending[:size]
+                    continue
+                again = magic == 0xFD2FB528
+                break
+            if again:
+                cur = ZstdCursor(dev)
+                continue
+            break
+        if s.status not in (int(DecodeStatus.NeedInput), int(DecodeStatus.NeedOutput)):
+            raise DecodeError(s.status)
+        if s.in_used == 0 and s.out_len == 0:
+            if s.status == int(DecodeStatus.NeedOutput):
+                if s.need_out > (1 << 31) - 1:
+                    raise DecodeError(-5)
+                room = max(room, s.need_out)
+            elif n < len(pending) or not eof:
+                if slab >= 1 << 31:
+                    raise DecodeError(-5)  # a block beyond a call's slab
+                slab *= 2
+            else:
+                raise EOFError("the source ends inside the frame")
+    return b"".join(parts) if sink is None else written
 
 
 def layout_units(out_size, stream=None):

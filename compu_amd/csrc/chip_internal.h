@@ -76,6 +76,8 @@ constexpr uint32_t ZTOK_SLOT_SLACK = 8736;  // a literal slot is Regenerated_Siz
 hipError_t launch_zstd_tokens(const BatchArgs &a, const ZTokArgs &tk, hipStream_t stream);
 // (zstd_tokens.hip) XXH64 of n bytes on one wave, its low 32 bits to *got
 hipError_t launch_zstd_xxh(const uint8_t *p, uint32_t n, uint32_t *got, hipStream_t stream);
+// (zstd_tokens.hip) the running XXH64 `st` brought forward over n bytes on one wave, the new state to *out (device memory)
+hipError_t launch_zstd_xxh_update(const uint8_t *p, uint32_t n, const chip_xxh64_state &st, chip_xxh64_state *out, hipStream_t stream);
 constexpr uint32_t F_COMPU_STATUS = 1u;  // = CHIP_F_COMPU_STATUS
 constexpr uint32_t F_MEMBERS = 2u;       // = CHIP_F_MEMBERS
 

@@ -627,6 +627,20 @@ public:
         if (rc == CHIP_OK) cursor_ += summary.out_len;
         return rc;
     }
+    // chip_zstd_parallel_next into this buffer's spare capacity: the next part of ONE zstd frame of any length.  `slab` holds `len` bytes of
+    // the frame from byte cur.in_total on (from offset `from` of the buffer: the caller keeps what a call did not consume and moves on by
+    // summary.in_used), `state` is the cursor's DEVICE memory: CHIP_ZCUR_CARRY_BYTES and the window (summary.need_state says how much when
+    // it is too small).  The cursor of this buffer moves by summary.out_len; summary.status says why the call stopped.  Synchronous on `stream`.
+    int zstd_parallel_next(chip_zstd_cursor &cur, DeviceBuffer &state, const DeviceBuffer &slab, uint64_t from, uint64_t len, int window_log_max,
+                           uint32_t flags, chip_zstd_next_summary &summary, void *stream = nullptr)
+    {
+        if (from > slab.len() || len > slab.len() - from) return CHIP_E_INVALID;
+        const size_t room = cap_ - cursor_;
+        const int rc = chip_zstd_parallel_next(&cur, state.buf_, state.cap_, slab.data() + from, len, buf_ + cursor_, room < 0x7FFFFFFFu ? room : 0x7FFFFFFFu,
+                                               window_log_max, flags, &summary, stream);
+        if (rc == CHIP_OK) cursor_ += summary.out_len;
+        return rc;
+    }
     // chip_select_units: the index step of read_ranges alone (DEVICE arrays, HOST summary), for a caller that decodes the sub-batch
     // sel_in_off / sel_in_len / sel_out_off / sel_out_cap into summary.scratch_bytes of its own.  max_sel 0 with null sel arrays
     // counts.  Synchronous on `stream`.
@@ -679,6 +693,19 @@ inline int zstd_plan_host(const uint8_t *in, uint64_t len, uint64_t max_frames, 
 {
     return chip_zstd_plan_host(in, len, max_frames, in_off, in_len, out_off, out_cap, &summary);
 }
+// The host twins of chip_zstd_parallel_next's steps (no device needed): the walk from a block boundary, the header step, the running XXH64.
+inline int zstd_slab_blocks_host(const uint8_t *in, uint64_t len, uint64_t block_max, uint64_t max_blocks, chip_zstd_block *blocks,
+                                 chip_zstd_slab_summary &summary)
+{
+    return chip_zstd_slab_blocks_host(in, len, block_max, max_blocks, blocks, &summary);
+}
+inline int zstd_cursor_header_host(chip_zstd_cursor &cur, const uint8_t *in, uint64_t len, int window_log_max, uint32_t flags, uint32_t &header_bytes,
+                                   uint64_t &need_state)
+{
+    return chip_zstd_cursor_header_host(&cur, in, len, window_log_max, flags, &header_bytes, &need_state);
+}
+inline int xxh64_update_host(chip_xxh64_state &st, const uint8_t *data, uint64_t len) { return chip_xxh64_update_host(&st, data, len); }
+inline uint64_t xxh64_digest_host(const chip_xxh64_state &st) { return chip_xxh64_digest_host(&st); }
 // htslib's 28-byte EOF marker, to be written behind the last block of a file made with chip_encode_batch(CHIP_FMT_BGZF, ..) (DeviceBuffer::
 // bgzf_write does all of it)
 inline const uint8_t *bgzf_eof_block(size_t &len) { return chip_bgzf_eof_block(&len); }

@@ -581,6 +581,119 @@ typedef struct {
 int chip_zstd_parallel(const void *in_base, uint64_t len, void *out_base, uint64_t out_cap, int window_log_max, uint32_t flags,
                        chip_zstd_parallel_summary *summary, void *stream);
 
+/*
+ * chip_zstd_parallel_next: the NEXT PART of one zstd frame of any length, by the passes of chip_zstd_parallel over a SLAB of it
+ * (DESIGN.md sec. 4.20).  The caller owns a CURSOR, plain host data that may be copied and saved (all zero = the beginning of a
+ * frame), and beside it `state`, state_cap bytes of DEVICE memory which a copy of the cursor needs a copy of:
+ *     [0, CHIP_ZCUR_CARRY_BYTES)   four slots of CHIP_ZCUR_SLOT_BYTES, one per table kind (CHIP_ZSRC_*): the bytes, 3-byte header and
+ *                                  body, of the nearest block in front of the cursor that defined the table (cur->carry_len[k] of them)
+ *     behind them                  the window, cur->window_size bytes, as a ring: content byte j of the frame lies at j mod window_size
+ * in_base is a device pointer to frame byte cur->in_total and len the bytes of the frame that stand there, at most 2^31.  in_base
+ * needs no alignment and no padding: the slab is staged behind the carried blocks in scratch.  out_cap is below 2^31.  Positions
+ * inside a call are slab-relative, the totals of the cursor are 64-bit: neither bound limits the frame.  window_log_max as in
+ * chip_decoder_opts (0 is 27, at most 31); flags: CHIP_ZPAR_NO_CHECKSUM, the same in every call of a frame.  SYNCHRONOUS on `stream`.
+ * The header step (phase = CHIP_ZCUR_HEADER) reads the frame header and judges it with the batch decode's codes: the magic (-10), the
+ * reserved bit (-14), the window against window_log_max (-16), a dictionary ID other than 0 (-32).  A header that is not whole in the
+ * slab is CHIP_NEED_INPUT without progress.  It fills the cursor and moves to CHIP_ZCUR_BLOCKS.  When state_cap is below
+ * CHIP_ZCUR_CARRY_BYTES + window_size the call stops there: in_used = the header's bytes, out_len = 0, status = CHIP_NEED_OUTPUT and
+ * need_state = the bytes to come back with (a call at phase BLOCKS with too small a state answers the same with in_used = 0; at
+ * phase CHECKSUM the state is not read any more and its size is not looked at).
+ * Otherwise it goes straight on.
+ * Where a call ends: it moves the cursor from a block boundary to a later block boundary, or through the checksum, and delivers
+ * exactly the content of the whole blocks between the two at out_base[0 .. out_len); nothing behind out_len is written.  It appends
+ * those bytes to the window ring (only the last window_size of a call are moved), copies the nearest definer of each table kind
+ * into its carry slot, brings cur->xxh up to out_total, and answers in_used: the next slab begins at in_base + in_used.
+ *   - CHIP_FINISHED: the last block and, where the frame has one, the 4 checksum bytes were in the slab; Frame_Content_Size was
+ *     compared with out_total in 64 bits and the checksum was compared unless waived.  phase = CHIP_ZCUR_DONE; in_used counts through
+ *     the frame and nothing behind it.
+ *   - CHIP_NEED_INPUT: everything whole was delivered.  in_used == 0 && out_len == 0: the slab holds no whole block (or not the
+ *     whole checksum); come back with a longer slab.  A block cut by the slab's end is dropped and read again by the next call.
+ *   - CHIP_NEED_OUTPUT: the next block was whole in the slab and did not fit the room left; need_out is its exact decoded size.
+ *   - a negative code: sticky; phase = CHIP_ZCUR_ERROR, cur->error keeps it and every later call answers it.  out_len counts the
+ *     whole blocks of true content delivered in front of the failing block.
+ * Progress: a slab with one whole block behind the cursor and room for that block's bytes always advances the cursor.
+ * There is NO serial path: the passes are a complete decoder for clean blocks, and a block that is not clean is an error with the
+ * code of the one-unit batch decode for the same damage: -20 for everything inside a block (the token pass is that kernel's text),
+ * for a reserved block type, a block above Block_Maximum_Size, a reuse of a table without a source, an offset beyond the content or
+ * the window, and content that does not add up to Frame_Content_Size; -22 for a wrong checksum -- which is found when ALL content
+ * has already been delivered: a slabbed decode cannot hold content back as chip_zstd_parallel does.
+ * The passes per call: the block walk from the cursor (chip_zstd_slab_blocks_host is its text); the token pass over
+ * [carried definers | slab], the carried blocks being replay-only records in front of the slab's; the host's prefix sums from the
+ * cursor's repeat offsets, as many leading blocks as fit out_cap; place, where a source in front of the slab's first byte is read
+ * from the window ring as a final byte (an offset is legal when off <= hist + position and off <= window_size) and the FIRST block
+ * with a bad offset is found; jump and deliver over the blocks in front of it; the window, the carry, the checksum.
+ * A wave of the token pass reads one range from the earliest block whose table its block reuses to its block's end; a call takes
+ * blocks only while that range stays below 2^28 bytes (the next call has the definer in its carry), and at most
+ * CHIP_ZPLAN_MAX_BLOCKS blocks.
+ * CHIP_E_INVALID, before a device is looked for: cur, state, summary NULL; in_base NULL with len > 0; out_base NULL with out_cap > 0;
+ * len > 2^31; out_cap >= 2^31; unknown flags; window_log_max outside 0..31; a cursor no call has left (an unknown phase,
+ * hist != min(out_total, window_size), ring != out_total mod window_size, a carry length above the slot or below 3, xxh.tail_n > 31
+ * or xxh.total != out_total of a frame whose checksum is compared, a repeat offset of 0 behind the header); the flag changed
+ * mid-frame.  CHIP_E_NOMEM / CHIP_E_LAUNCH: the cursor is as it was, the state may not be: the decode cannot go on.
+ * Scratch per (device, stream), in chip_zstd_parallel's launch slot, released by chip_trim(): 4 bytes per byte delivered in the
+ * call, 12 per sequence of the slab, Regenerated_Size + 8 736 per block of the slab with Huffman literals, the staged slab and
+ * carry, about 200 bytes per block.  It does not depend on the frame's length.
+ * CHIP_ZPAR_TIMING as chip_zstd_parallel: walk, tokens, place, each jump round, deliver, checksum, window.
+ */
+enum { CHIP_ZCUR_HEADER = 0, CHIP_ZCUR_BLOCKS = 1, CHIP_ZCUR_CHECKSUM = 2, CHIP_ZCUR_DONE = 3, CHIP_ZCUR_ERROR = 4 };
+#define CHIP_ZCUR_SLOT_BYTES 131088u                          /* Block_Maximum_Size + 3, rounded up to 16 */
+#define CHIP_ZCUR_CARRY_BYTES (4u * CHIP_ZCUR_SLOT_BYTES)     /* 524 352 */
+/* A running XXH64 (seed 0): the four accumulators, the bytes covered, the bytes behind the last whole 32-byte stripe.  All zero =
+ * nothing hashed yet (the accumulators are started by the first update).  One definition for the kernel and the host functions. */
+typedef struct {
+    uint64_t acc[4];
+    uint64_t total;
+    uint8_t tail[32];
+    uint32_t tail_n, pad;
+} chip_xxh64_state;
+typedef struct {
+    uint64_t in_total;     /* bytes of the frame in front of the next call's first byte */
+    uint64_t out_total;    /* bytes delivered so far */
+    uint64_t window_size;  /* from the frame header (Single_Segment: the content size) */
+    uint64_t content_size; /* Frame_Content_Size, or CHIP_ZBLOCKS_UNSIZED */
+    uint64_t hist;         /* valid bytes of the window: min(out_total, window_size) */
+    uint64_t ring;         /* where the next content byte goes in the ring: out_total mod window_size */
+    uint64_t carry_at[4];  /* frame offset of the carried definer of each kind (orders their replay) */
+    uint32_t carry_len[4]; /* its bytes in the slot, header and body; 0 = none */
+    uint32_t rep[3];       /* the repeat offsets at the cursor */
+    uint32_t phase;        /* CHIP_ZCUR_* */
+    uint32_t descriptor;   /* Frame_Header_Descriptor (bit 2: the frame has a checksum) */
+    uint32_t waived;       /* 1: the frame is decoded with CHIP_ZPAR_NO_CHECKSUM */
+    int32_t error;         /* the sticky status once phase == ERROR */
+    uint32_t pad;
+    chip_xxh64_state xxh;  /* over out_total bytes (untouched while waived) */
+} chip_zstd_cursor;        /* all zero = the beginning of a frame */
+typedef struct {
+    uint64_t in_used, out_len, need_out, need_state, n_blocks, n_sequences;
+    int32_t status; /* why the call stopped */
+    uint32_t rounds;
+} chip_zstd_next_summary;
+int chip_zstd_parallel_next(chip_zstd_cursor *cur, void *state, uint64_t state_cap, const void *in_base, uint64_t len, void *out_base,
+                            uint64_t out_cap, int window_log_max, uint32_t flags, chip_zstd_next_summary *summary, void *stream);
+
+/* The host twins of its steps: pure host arithmetic on HOST memory, no device needed.
+ * chip_zstd_slab_blocks_host: the walk from a block boundary.  `in` points at a block header, block_max is the frame's
+ * Block_Maximum_Size (min(window_size, 131072)).  Per block: len - q < 3 or a body beyond len -> the walk stops, status
+ * CHIP_ZPLAN_TRUNCATED (a cut block is never an error); type 3 or Block_Size > block_max -> CHIP_ZPLAN_BAD_HEADER; more than
+ * CHIP_ZPLAN_MAX_BLOCKS -> CHIP_ZPLAN_TOO_LARGE; behind the block with the last-block flag: CHIP_ZPLAN_OK, last = 1.  n_blocks counts
+ * the whole blocks in front of where it stopped and in_used their bytes, whatever the status.  The records are chip_zstd_blocks_host's
+ * with slab-relative offsets; src names the nearest definer INSIDE the slab, -1 where it lies in front of it.
+ * chip_zstd_cursor_header_host: the header step on the first `len` bytes of a frame.  Returns CHIP_FINISHED with the cursor filled
+ * (phase BLOCKS, in_total = *header_bytes) and *need_state set; CHIP_NEED_INPUT (nothing changed) for a cut header; else the negative
+ * code, which it also makes the cursor's sticky error.
+ * chip_xxh64_update_host / chip_xxh64_digest_host: the running XXH64 over a chip_xxh64_state; the digest leaves the state usable. */
+typedef struct {
+    uint64_t n_blocks, in_used;
+    int32_t status; /* CHIP_ZPLAN_* */
+    uint32_t last;  /* 1: the frame's last block is block n_blocks - 1 */
+} chip_zstd_slab_summary;
+int chip_zstd_slab_blocks_host(const uint8_t *in, uint64_t len, uint64_t block_max, uint64_t max_blocks, chip_zstd_block *blocks,
+                               chip_zstd_slab_summary *summary);
+int chip_zstd_cursor_header_host(chip_zstd_cursor *cur, const uint8_t *in, uint64_t len, int window_log_max, uint32_t flags,
+                                 uint32_t *header_bytes, uint64_t *need_state);
+int chip_xxh64_update_host(chip_xxh64_state *st, const uint8_t *data, uint64_t len);
+uint64_t chip_xxh64_digest_host(const chip_xxh64_state *st);
+
 /* ---- gzip members: from a file to a batch (additive API) ------------------- */
 
 /*

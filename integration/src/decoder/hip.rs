@@ -424,6 +424,29 @@ pub unsafe fn zstd_parallel_device(input: &crate::buffer::DeviceBuffer, len: usi
     if rc == sys::CHIP_OK { Ok(summary) } else { Err(rc) }
 }
 
+///`chip_zstd_parallel_next`: decodes the next part of one zstd frame of any length.  `slab` holds `len` bytes of the frame from byte
+///`cursor.in_total` on, `state` the carried table definers and the window ring (`summary.need_state` says how large it must be once
+///the frame header is read); the call delivers whole blocks into `output` while they fit, moves the cursor to a later block boundary
+///(or through the checksum) and says in the summary how many bytes of the slab lie in front of the new cursor, how many bytes it
+///delivered and why it stopped.  `flags`: `CHIP_ZPAR_NO_CHECKSUM`, the same in every call of a frame.  Synchronous on `stream`.
+///No counterpart in this crate.
+///
+///# Safety
+///
+///As `decode_batch_device`; `state` must be the one the cursor was left with.
+pub unsafe fn zstd_parallel_next_device(cursor: &mut sys::chip_zstd_cursor, state: &mut crate::buffer::DeviceBuffer, slab: &crate::buffer::DeviceBuffer,
+                                        len: usize, output: &mut crate::buffer::DeviceBuffer, window_log_max: i32, flags: u32,
+                                        stream: *mut core::ffi::c_void) -> Result<sys::chip_zstd_next_summary, i32> {
+    if len > slab.capacity() || state.capacity() < sys::CHIP_ZCUR_CARRY_BYTES {
+        return Err(-101);
+    }
+    let mut summary = sys::chip_zstd_next_summary::default();
+    let cap = core::cmp::min(output.capacity() as u64, (1u64 << 31) - 1);
+    let rc = sys::chip_zstd_parallel_next(cursor, state.as_mut_ptr() as *mut _, state.capacity() as u64, slab.as_ptr() as *const _, len as u64,
+                                          output.as_mut_ptr() as *mut _, cap, window_log_max, flags, &mut summary, stream);
+    if rc == sys::CHIP_OK { Ok(summary) } else { Err(rc) }
+}
+
 ///`chip_gzip_plan` over the first `len` bytes of a device-resident buffer of gzip members (WARC records, `cat a.gz b.gz`, what
 ///`encode_file_device` writes for gzip): fills the four device arrays for the first `max_members` members -- what
 ///`decode_batch_device` takes with `BatchFormat::Zlib` in gzip mode -- and returns the summary of the whole walk (`max_members` 0 counts).

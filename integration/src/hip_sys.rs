@@ -335,6 +335,70 @@ pub struct chip_inflate_next_summary {
     pub path: u32,
 }
 
+///`chip_zstd_cursor::phase`
+pub const CHIP_ZCUR_HEADER: u32 = 0;
+pub const CHIP_ZCUR_BLOCKS: u32 = 1;
+pub const CHIP_ZCUR_CHECKSUM: u32 = 2;
+pub const CHIP_ZCUR_DONE: u32 = 3;
+pub const CHIP_ZCUR_ERROR: u32 = 4;
+///one carry slot of a `chip_zstd_cursor`'s device state, and the four of them in front of the window
+pub const CHIP_ZCUR_SLOT_BYTES: usize = 131088;
+pub const CHIP_ZCUR_CARRY_BYTES: usize = 4 * CHIP_ZCUR_SLOT_BYTES;
+///a running XXH64 (seed 0): accumulators, bytes covered, the bytes behind the last whole stripe; all zero = nothing hashed
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct chip_xxh64_state {
+    pub acc: [u64; 4],
+    pub total: u64,
+    pub tail: [u8; 32],
+    pub tail_n: u32,
+    pub pad: u32,
+}
+///where a slabbed decode of one zstd frame stands (`chip_zstd_parallel_next`): plain host data, all zero = the beginning of a
+///frame; the carried table definers and the window ring live in device memory beside it
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct chip_zstd_cursor {
+    pub in_total: u64,
+    pub out_total: u64,
+    pub window_size: u64,
+    pub content_size: u64,
+    pub hist: u64,
+    pub ring: u64,
+    pub carry_at: [u64; 4],
+    pub carry_len: [u32; 4],
+    pub rep: [u32; 3],
+    pub phase: u32,
+    pub descriptor: u32,
+    pub waived: u32,
+    pub error: i32,
+    pub pad: u32,
+    pub xxh: chip_xxh64_state,
+}
+///what one `chip_zstd_parallel_next` call answers: the bytes it consumed and delivered, the size of the block that did not fit
+///(`need_out`), the state bytes to come back with (`need_state`), the blocks and sequences taken, why it stopped, the jump rounds
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct chip_zstd_next_summary {
+    pub in_used: u64,
+    pub out_len: u64,
+    pub need_out: u64,
+    pub need_state: u64,
+    pub n_blocks: u64,
+    pub n_sequences: u64,
+    pub status: i32,
+    pub rounds: u32,
+}
+///what the walk from a block boundary found (`chip_zstd_slab_blocks_host`)
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct chip_zstd_slab_summary {
+    pub n_blocks: u64,
+    pub in_used: u64,
+    pub status: i32,
+    pub last: u32,
+}
+
 pub type chip_malloc_fn = unsafe extern "C" fn(opaque: *mut c_void, size: usize) -> *mut c_void;
 pub type chip_free_fn = unsafe extern "C" fn(opaque: *mut c_void, ptr: *mut c_void);
 
@@ -407,6 +471,17 @@ extern "C" {
     ///batch decode's answer; synchronous on `stream`
     pub fn chip_zstd_parallel(in_base: *const c_void, len: u64, out_base: *mut c_void, out_cap: u64, window_log_max: c_int, flags: u32,
                               summary: *mut chip_zstd_parallel_summary, stream: *mut c_void) -> c_int;
+    ///the next part of one zstd frame of any length: the same passes over a slab, from a carried cursor and its device state;
+    ///synchronous on `stream`
+    pub fn chip_zstd_parallel_next(cur: *mut chip_zstd_cursor, state: *mut c_void, state_cap: u64, in_base: *const c_void, len: u64, out_base: *mut c_void,
+                                   out_cap: u64, window_log_max: c_int, flags: u32, summary: *mut chip_zstd_next_summary, stream: *mut c_void) -> c_int;
+    ///its steps on host memory (no device needed): the walk from a block boundary, the header step, the running XXH64
+    pub fn chip_zstd_slab_blocks_host(input: *const u8, len: u64, block_max: u64, max_blocks: u64, blocks: *mut chip_zstd_block,
+                                      summary: *mut chip_zstd_slab_summary) -> c_int;
+    pub fn chip_zstd_cursor_header_host(cur: *mut chip_zstd_cursor, input: *const u8, len: u64, window_log_max: c_int, flags: u32, header_bytes: *mut u32,
+                                        need_state: *mut u64) -> c_int;
+    pub fn chip_xxh64_update_host(st: *mut chip_xxh64_state, data: *const u8, len: u64) -> c_int;
+    pub fn chip_xxh64_digest_host(st: *const chip_xxh64_state) -> u64;
     ///the member index of a device-resident buffer of gzip members: the size pass over every candidate start, then the chain from 0
     pub fn chip_gzip_plan(in_base: *const c_void, len: u64, max_members: u64, in_off: *mut u64, in_len: *mut u32, out_off: *mut u64, out_cap: *mut u32,
                           summary: *mut chip_gzip_plan_summary, stream: *mut c_void) -> c_int;
