@@ -92,6 +92,22 @@ class _GzipPlanSummary(C.Structure):
                 ("member_status", C.c_int32)]
 
 
+class _ZipEntry(C.Structure):
+    _fields_ = [("header_off", C.c_uint64), ("data_off", C.c_uint64), ("comp_size", C.c_uint64), ("size", C.c_uint64), ("name_off", C.c_uint64),
+                ("crc32", C.c_uint32), ("name_len", C.c_uint16), ("method", C.c_uint16), ("flags", C.c_uint16), ("pad", C.c_uint16),
+                ("status", C.c_int32)]
+
+
+class _ZipPlanSummary(C.Structure):
+    _fields_ = [("n_entries", C.c_uint64), ("n_ok", C.c_uint64), ("total_size", C.c_uint64), ("cd_off", C.c_uint64), ("cd_size", C.c_uint64),
+                ("eocd_off", C.c_uint64), ("bad_index", C.c_uint64), ("status", C.c_int32), ("zip64", C.c_int32)]
+
+
+class _ZipDecodeSummary(C.Structure):
+    _fields_ = [("n_sel", C.c_uint64), ("n_ok", C.c_uint64), ("n_bad", C.c_uint64), ("first_bad", C.c_uint64), ("total_out", C.c_uint64),
+                ("status", C.c_int32), ("pad", C.c_int32)]
+
+
 class _FileSummary(C.Structure):
     _fields_ = [("n_units", C.c_uint64), ("out_len", C.c_uint64), ("table_off", C.c_uint64), ("status", C.c_int32), ("pad", C.c_uint32)]
 
@@ -238,6 +254,14 @@ def lib():
     L.chip_xxh64_digest_host.argtypes = [C.POINTER(_Xxh64State)]
     L.chip_gzip_plan.restype = C.c_int
     L.chip_gzip_plan.argtypes = [vp, C.c_uint64, C.c_uint64, vp, vp, vp, vp, C.POINTER(_GzipPlanSummary), vp]
+    L.chip_zip_plan_host.restype = C.c_int
+    L.chip_zip_plan_host.argtypes = [vp, C.c_uint64, C.c_uint64, vp, C.POINTER(_ZipPlanSummary)]
+    L.chip_zip_plan.restype = C.c_int
+    L.chip_zip_plan.argtypes = [vp, C.c_uint64, C.c_uint64, vp, C.POINTER(_ZipPlanSummary), vp]
+    L.chip_crc32_batch.restype = C.c_int
+    L.chip_crc32_batch.argtypes = [sz, vp, vp, vp, vp, vp]
+    L.chip_zip_decode.restype = C.c_int
+    L.chip_zip_decode.argtypes = [vp, C.c_uint64, vp, C.c_uint64, C.c_uint64, vp, vp, C.c_uint64, vp, vp, C.POINTER(_ZipDecodeSummary), vp]
     L.chip_layout_units.restype = C.c_int
     L.chip_layout_units.argtypes = [sz, vp, vp, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), vp]
     L.chip_pack_units.restype = C.c_int
@@ -2260,6 +2284,226 @@ def gzip_index_read(index, in_buf, ranges, stream=None):
     lo, ln = _ranges_to_device(ranges, in_buf.device)
     out, dst_off, status, rs = inflate_index_read(index, in_buf, lo, ln, stream=stream)
     return _read_checked("gzip_index_read", out, status, rs), dst_off
+
+
+# ---- ZIP archives (include/compu_hip.h, "ZIP archives") ---------------------------------------------
+
+
+class ZipStatus(enum.IntEnum):
+    Ok = 0
+    NoEocd = 1
+    BadDirectory = 2
+    Unsupported = 3
+
+
+class ZipEntryStatus(enum.IntEnum):
+    """chip_zip_entry.status, and what zip_decode answers beside the decode statuses (DecodeStatus, negative codec errors)."""
+
+    Ok = 0
+    Unsupported = 16
+    Encrypted = 17
+    BadLocal = 18
+    TooLarge = 19
+    BadSize = 20
+    BadCrc = 21
+    BadIndex = 22
+
+
+CRC_PIECE = 65536  # CHIP_CRC_PIECE: the piece a range of crc32_batch is cut into
+
+
+def zip_entry_dtype():
+    """chip_zip_entry as a numpy record: header_off, data_off, comp_size, size, name_off, crc32, name_len, method, flags, pad, status."""
+    import numpy as np
+
+    dt = np.dtype([("header_off", "<u8"), ("data_off", "<u8"), ("comp_size", "<u8"), ("size", "<u8"), ("name_off", "<u8"), ("crc32", "<u4"),
+                   ("name_len", "<u2"), ("method", "<u2"), ("flags", "<u2"), ("pad", "<u2"), ("status", "<i4")])
+    assert dt.itemsize == C.sizeof(_ZipEntry) == 56
+    return dt
+
+
+class ZipPlanSummary:
+    """chip_zip_plan_summary: n_entries, n_ok and total_size (decoded bytes of the OK entries) of the whole walk, the directory's
+    place (cd_off, cd_size), the end record's (eocd_off), bad_index (the entry a BadDirectory walk stopped at), status, zip64."""
+
+    __slots__ = ("n_entries", "n_ok", "total_size", "cd_off", "cd_size", "eocd_off", "bad_index", "status", "zip64")
+
+    def __init__(self, raw):
+        self.n_entries, self.n_ok, self.total_size = int(raw.n_entries), int(raw.n_ok), int(raw.total_size)
+        self.cd_off, self.cd_size, self.eocd_off, self.bad_index = int(raw.cd_off), int(raw.cd_size), int(raw.eocd_off), int(raw.bad_index)
+        self.status, self.zip64 = ZipStatus(raw.status), int(raw.zip64)
+
+    def as_tuple(self):
+        return (self.n_entries, self.n_ok, self.total_size, self.cd_off, self.cd_size, self.eocd_off, self.bad_index, int(self.status), self.zip64)
+
+    def __repr__(self):
+        return (f"ZipPlanSummary(n_entries={self.n_entries}, n_ok={self.n_ok}, total_size={self.total_size}, cd_off={self.cd_off}, "
+                f"cd_size={self.cd_size}, eocd_off={self.eocd_off}, bad_index={self.bad_index}, status={self.status.name}, zip64={self.zip64})")
+
+
+class ZipDecodeSummary:
+    """chip_zip_decode_summary: n_sel, n_ok (entries that are Finished), n_bad, first_bad (position in the selection), total_out,
+    status (ReadStatus.Ok or NeedOutput)."""
+
+    __slots__ = ("n_sel", "n_ok", "n_bad", "first_bad", "total_out", "status")
+
+    def __init__(self, raw):
+        self.n_sel, self.n_ok, self.n_bad, self.first_bad = int(raw.n_sel), int(raw.n_ok), int(raw.n_bad), int(raw.first_bad)
+        self.total_out, self.status = int(raw.total_out), ReadStatus(raw.status)
+
+    def as_tuple(self):
+        return (self.n_sel, self.n_ok, self.n_bad, self.first_bad, self.total_out, int(self.status))
+
+    def __repr__(self):
+        return (f"ZipDecodeSummary(n_sel={self.n_sel}, n_ok={self.n_ok}, n_bad={self.n_bad}, first_bad={self.first_bad}, "
+                f"total_out={self.total_out}, status={self.status.name})")
+
+
+def zip_plan_host(data, max_entries=None):
+    """chip_zip_plan_host over bytes / a uint8 numpy array in host memory: (entries, summary), entries a numpy record array
+    (zip_entry_dtype) of the first min(n_entries, max_entries) entries (None = all of them: one call to count, one to fill).  Read
+    from the directory and the local headers alone; nothing is decoded."""
+    import numpy as np
+
+    buf = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8)
+    raw = _ZipPlanSummary()
+    p = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None  # noqa: E731
+    call = lib().chip_zip_plan_host
+    if max_entries is None:
+        rc = call(p(buf), buf.size, 0, None, C.byref(raw))
+        if rc != 0:
+            raise RuntimeError(f"chip_zip_plan_host failed: {rc}")
+        max_entries = int(raw.n_entries)
+    m = int(max_entries)
+    entries = np.zeros(m, zip_entry_dtype())
+    rc = call(p(buf), buf.size, m, p(entries), C.byref(raw))
+    if rc != 0:
+        raise RuntimeError(f"chip_zip_plan_host failed: {rc}")
+    return entries[:min(m, int(raw.n_entries))], ZipPlanSummary(raw)
+
+
+def zip_plan(in_buf, length, stream=None, max_entries=None):
+    """chip_zip_plan over a uint8 device tensor holding a ZIP archive of `length` bytes (4-byte aligned, padded to a multiple of 4):
+    (entries, summary), entries a uint8 device tensor of shape (k, 56) holding the chip_zip_entry records of the first
+    k = min(n_entries, max_entries) entries (`.cpu().numpy().view(zip_entry_dtype())` reads them; zip_decode takes the tensor).
+    Synchronous on `stream`.  max_entries None: all of them (one call to count, one to fill)."""
+    import torch
+
+    dev = _check_tensors(((in_buf, torch.uint8),))
+    length = int(length)
+    if length < 0 or length > in_buf.numel():
+        raise ValueError(f"length {length} outside the buffer of {in_buf.numel()} bytes")
+    raw = _ZipPlanSummary()
+    base, sp = (_dp(in_buf) if length else None), _stream_ptr(stream)
+    call = lib().chip_zip_plan
+    with torch.cuda.device(dev):
+        if max_entries is None:  # count, then fill
+            rc = call(base, length, 0, None, C.byref(raw), sp)
+            if rc != 0:
+                raise RuntimeError(f"chip_zip_plan failed: {rc}")
+            max_entries = int(raw.n_entries)
+        m = int(max_entries)
+        entries = torch.empty((m, C.sizeof(_ZipEntry)), dtype=torch.uint8, device=dev)
+        rc = call(base, length, m, _dp(entries) if m else None, C.byref(raw), sp)
+    if rc != 0:
+        raise RuntimeError(f"chip_zip_plan failed: {rc}")
+    return entries[:min(m, int(raw.n_entries))], ZipPlanSummary(raw)
+
+
+def zip_names(entries, summary, directory):
+    """The names of a plan's entries, as bytes: `entries` the records (the numpy record array of zip_plan_host, or the device
+    tensor of zip_plan, which is copied to the host), `directory` a bytes copy of the archive's
+    [summary.cd_off, summary.cd_off + summary.cd_size), which is where the names lie."""
+    import numpy as np
+
+    if not isinstance(entries, np.ndarray):
+        entries = entries.cpu().numpy().reshape(-1).view(zip_entry_dtype())
+    directory = bytes(directory)
+    if len(directory) != summary.cd_size:
+        raise ValueError(f"the directory has {summary.cd_size} bytes, got {len(directory)}")
+    names = []
+    for e in entries:
+        at = int(e["name_off"]) - summary.cd_off
+        names.append(directory[at:at + int(e["name_len"])])
+    return names
+
+
+def crc32_batch(buf, off, length, stream=None):
+    """chip_crc32_batch on device tensors: the CRC-32 (zlib.crc32) of buf[off[i] : off[i] + length[i]] for every i.  buf uint8, off and
+    length int64 (read as u64).  Returns an int32 device tensor (read it as u32: `& 0xFFFFFFFF`).  Enqueues on `stream`; waits once
+    in between to size its scratch, not for the result."""
+    import torch
+
+    dev = _check_tensors(((buf, torch.uint8), (off, torch.int64), (length, torch.int64)))
+    n = off.numel()
+    if length.numel() != n:
+        raise ValueError("off and length must have one length")
+    crc = torch.empty(n, dtype=torch.int32, device=dev)
+    if n == 0:
+        return crc
+    with torch.cuda.device(dev):
+        rc = lib().chip_crc32_batch(n, _dp(buf), _dp(off), _dp(length), _dp(crc), _stream_ptr(stream))
+    if rc != 0:
+        raise RuntimeError(f"chip_crc32_batch failed: {rc}")
+    return crc
+
+
+def zip_decode(in_buf, length, names_or_indices=None, stream=None):
+    """Entries of a ZIP archive in device memory, planned by chip_zip_plan and decoded, copied and verified by chip_zip_decode.
+    in_buf is a uint8 device tensor holding the archive's `length` bytes (4-byte aligned, padded to a multiple of 4).
+    names_or_indices: None for every entry in order, else a sequence of entry indices and / or names (str, matched as UTF-8, or
+    bytes; the LAST entry of that name, as zipfile does; the names are read from a host copy of the directory), or an int32 device
+    tensor of indices (read as u32).  The output tensor is allocated here: one call for total_out, one to decode.
+    Raises ValueError when the archive's directory is refused (the summary says why), KeyError for an unknown name.  Damaged
+    entries do not raise: returns (out, out_off int64, sizes int64, status int32, summary), device tensors of one row per selected
+    entry; status is DecodeStatus.Finished (2) for an entry whose bytes are out[out_off : out_off + size] and verified; sizes is the
+    room each entry takes in `out`, 0 for one that did not take part (its plan status says why).  Waits for the result."""
+    import numpy as np
+    import torch
+
+    dev = _check_tensors(((in_buf, torch.uint8),))
+    length = int(length)
+    entries, summ = zip_plan(in_buf, length, stream=stream)
+    if summ.status != ZipStatus.Ok:
+        raise ValueError(f"not a ZIP archive this library reads: {summ!r}")
+    n_entries = entries.shape[0]
+    sel = None
+    if names_or_indices is None:
+        n_sel = n_entries
+    elif isinstance(names_or_indices, torch.Tensor):
+        sel = names_or_indices
+        _check_tensors(((in_buf, torch.uint8), (sel, torch.int32)))
+        n_sel = sel.numel()
+    else:
+        wanted = list(names_or_indices)
+        if any(not isinstance(w, (int, np.integer)) for w in wanted):
+            directory = in_buf[summ.cd_off:summ.cd_off + summ.cd_size].cpu().numpy().tobytes()
+            index = {name: i for i, name in enumerate(zip_names(entries, summ, directory))}
+            wanted = [w if isinstance(w, (int, np.integer)) else index[w.encode("utf-8") if isinstance(w, str) else bytes(w)] for w in wanted]
+        sel = torch.tensor(np.asarray(wanted, dtype=np.int64).astype(np.uint32).view(np.int32), dtype=torch.int32, device=dev)
+        n_sel = len(wanted)
+    out_off = torch.empty(n_sel, dtype=torch.int64, device=dev)
+    status = torch.empty(n_sel, dtype=torch.int32, device=dev)
+    raw = _ZipDecodeSummary()
+    sp = _stream_ptr(stream)
+
+    def call(o):
+        with torch.cuda.device(dev):
+            rc = lib().chip_zip_decode(_dp(in_buf) if length else None, length, _dp(entries) if n_entries else None, n_entries, n_sel,
+                                       _dp(sel) if sel is not None and n_sel else None, _dp(o) if o.numel() else None, o.numel(),
+                                       _dp(out_off) if n_sel else None, _dp(status) if n_sel else None, C.byref(raw), sp)
+        if rc != 0:
+            raise RuntimeError(f"chip_zip_decode failed: {rc}")
+
+    out = torch.empty(0, dtype=torch.uint8, device=dev)
+    call(out)  # sizes only: NeedOutput with the exact total, or an empty result
+    if raw.status == ReadStatus.NeedOutput:
+        out = torch.empty(int(raw.total_out), dtype=torch.uint8, device=dev)
+        call(out)
+    summary = ZipDecodeSummary(raw)
+    # the sizes of the entries that took part: the differences of the layout
+    ends = torch.cat((out_off[1:], torch.tensor([summary.total_out], dtype=torch.int64, device=dev))) if n_sel else out_off
+    return out, out_off, ends - out_off, status, summary
 
 
 # ---- one large stream: block starts (include/compu_hip.h, "block starts") -------------------------

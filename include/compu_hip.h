@@ -758,6 +758,154 @@ typedef struct {
 int chip_gzip_plan(const void *in_base, uint64_t len, uint64_t max_members, uint64_t *in_off, uint32_t *in_len,
                    uint64_t *out_off, uint32_t *out_cap, chip_gzip_plan_summary *summary, void *stream);
 
+/* ---- ZIP archives: directory plan, entry decode, CRC-32 (additive API) ------ */
+
+/*
+ * A ZIP archive (.zip, .npz, .jar, .apk, .docx / .xlsx, .whl, .epub) states in its central directory, per entry, where the data
+ * lies, its compressed size, its decoded size and its CRC-32; entries are independent raw-DEFLATE (method 8) or stored (method 0)
+ * streams.  chip_zip_plan[_host] turns the directory into an array of chip_zip_entry records, chip_zip_decode decodes, copies and
+ * verifies selected entries, chip_crc32_batch is the check on its own.
+ * The plan of `len` bytes is DEFINED by this walk (all integers little endian; a status ends the walk):
+ *   End record.  Positions p with max(0, len - 22 - 65535) <= p <= len - 22 qualify when the bytes at p are 50 4b 05 06 and
+ *     p + 22 + LE16(p + 20) == len: the comment reaches exactly to the end.  The highest qualifying p wins.  None, or len < 22:
+ *     CHIP_ZIP_NO_EOCD.  So trailing bytes behind the archive refuse it, and a comment that spells an end record whose length
+ *     field reaches the end IS the end record.
+ *   ZIP64.  When p >= 20 and the bytes at p - 20 are 50 4b 06 07 (the locator): e = LE64(p - 12) needs e + 56 <= p - 20 and the
+ *     bytes 50 4b 06 06 at e, else CHIP_ZIP_BAD_DIRECTORY; n = LE64(e + 32), cd_size = LE64(e + 40), cd_off = LE64(e + 48),
+ *     zip64 = 1.  Without a locator n = LE16(p + 10), cd_size = LE32(p + 12), cd_off = LE32(p + 16).
+ *   Spanning.  LE16(p + 4) != 0, LE16(p + 6) != 0, LE16(p + 8) != LE16(p + 10); with ZIP64 also LE32(p - 16) != 0 (the locator's
+ *     disk), LE32(p - 4) != 1 (its total), LE32(e + 16) != 0, LE32(e + 20) != 0, LE64(e + 24) != n: CHIP_ZIP_UNSUPPORTED.
+ *   Bounds.  cd_off + cd_size (formed without wrapping) must not exceed e with ZIP64, p without, and n <= 2^32 - 1; else
+ *     CHIP_ZIP_BAD_DIRECTORY.  Offsets are taken as stated: an archive with prepended bytes (a self-extractor) is not re-based.
+ *   Directory.  q = cd_off; for i = 0 .. n:
+ *     the 46 bytes at q lie inside [cd_off, cd_off + cd_size) and start with 50 4b 01 02, else CHIP_ZIP_BAD_DIRECTORY, bad_index = i
+ *     flags = LE16(+8), method = LE16(+10), crc = LE32(+16), csize = LE32(+20), usize = LE32(+24), nlen = LE16(+28),
+ *     xlen = LE16(+30), clen = LE16(+32), disk = LE16(+34), lho = LE32(+42)
+ *     the record of 46 + nlen + xlen + clen bytes lies inside the directory, else stop as above
+ *     the extra field's subfields (id:u16 size:u16 data) are walked; a subfield that reaches out of the extra field ends the chain.
+ *       The first subfield with id 1 supplies 64-bit values in this order: usize if it was 0xFFFFFFFF, then csize if it was
+ *       0xFFFFFFFF, then lho if it was 0xFFFFFFFF, each from the bytes that lie in both the subfield and the extra field.  A
+ *       0xFFFFFFFF field with no value for it: stop as above.  What the chain holds behind the needed values is not looked at
+ *       (the 32-bit disk number an id-1 subfield may carry included).
+ *     entry i (below); q += 46 + nlen + xlen + clen
+ *     What lies in the directory behind the n-th record is not looked at.
+ * Entry i is a chip_zip_entry.  status is the first of these that applies:
+ *   CHIP_ZIPENT_UNSUPPORTED  disk != 0 (and not 0xFFFF with an id-1 subfield present), or a method other than 0 and 8 (zstd-in-ZIP,
+ *                            method 93, included)
+ *   CHIP_ZIPENT_ENCRYPTED    flag bit 0, 6 or 13
+ *   CHIP_ZIPENT_BAD_LOCAL    the local header: header_off + 30 <= cd_off; the bytes 50 4b 03 04 at header_off;
+ *                            data_off = header_off + 30 + LE16(header_off + 26) + LE16(header_off + 28);
+ *                            data_off + comp_size <= cd_off (formed without wrapping); method 0 needs comp_size == size.
+ *                            If any of these fails data_off is 0 (whatever the status), else it is that sum.
+ *   CHIP_ZIPENT_TOO_LARGE    method 8 with comp_size > 2^29 - 64 or size > 2^32 - 2, the limits of a unit.  data_off / comp_size of
+ *                            such an entry are what chip_inflate_parallel_next takes with CHIP_FMT_DEFLATE.
+ *   CHIP_ZIPENT_OK
+ * The local header's own sizes, CRC and name are not looked at: with a data descriptor (flag bit 3) they are zero, the directory
+ * is the authority.  The name of entry i is the name_len bytes at name_off, in the directory.
+ * summary: n_entries, n_ok and total_size (sum of `size` over the OK entries, modulo 2^64) are those of the WHOLE walk; a walk that
+ * stops at entry i keeps entries 0 .. i with n_entries = i.  eocd_off = p, cd_off, cd_size and zip64 as read (0 where the walk
+ * stopped before reading them).  The array receives the first min(n_entries, max_entries) records and nothing behind them is
+ * written: max_entries = 0 with a NULL array counts, a second call fills.
+ * chip_zip_plan: conventions of chip_zstd_plan.  in_base and `entries` are DEVICE pointers, summary is a HOST pointer; in_base
+ * 4-byte aligned, its allocation padded to a multiple of 4 bytes; len <= 2^40.  SYNCHRONOUS on `stream`: it waits for the end record,
+ * for the number of candidates and at the end.  CHIP_E_INVALID, checked before the device is looked for: summary NULL, a NULL buffer
+ * with len > 0, a NULL array with max_entries > 0, in_base not 4-byte aligned, len > 2^40.  len == 0 is CHIP_OK with an all-zero
+ * summary except status = CHIP_ZIP_NO_EOCD.  More than 2^31 - 1 candidates: CHIP_E_NOMEM.  Input that changes during the call:
+ * CHIP_E_LAUNCH, nothing is written out of range.  A candidate is a position of the directory whose four bytes are 50 4b 01 02.
+ * Scratch per (device, stream), a launch slot of its own, kept between calls and released by chip_trim(): 16 bytes per 16 KiB of
+ * directory and 36 + 4 * ceil(log2(candidates + 1)) bytes per candidate.
+ * No reference counterpart: compu has no container formats.
+ */
+enum { CHIP_ZIP_OK = 0, CHIP_ZIP_NO_EOCD = 1, CHIP_ZIP_BAD_DIRECTORY = 2, CHIP_ZIP_UNSUPPORTED = 3 };
+/* Entry statuses.  All but CHIP_ZIPENT_OK, which chip_zip_decode never writes into its status array, are numbers no decode status
+ * has. */
+enum {
+    CHIP_ZIPENT_OK = 0,
+    CHIP_ZIPENT_UNSUPPORTED = 16,
+    CHIP_ZIPENT_ENCRYPTED = 17,
+    CHIP_ZIPENT_BAD_LOCAL = 18,
+    CHIP_ZIPENT_TOO_LARGE = 19,
+    CHIP_ZIPENT_BAD_SIZE = 20,  /* chip_zip_decode: the stream finished with another length than `size` */
+    CHIP_ZIPENT_BAD_CRC = 21,   /* chip_zip_decode: the bytes' CRC-32 is not the directory's */
+    CHIP_ZIPENT_BAD_INDEX = 22  /* chip_zip_decode: sel[k] >= n_entries */
+};
+typedef struct {       /* 56 bytes, no implicit padding */
+    uint64_t header_off; /* the local header offset */
+    uint64_t data_off;   /* first byte of the entry's data; 0 when the local header's checks fail */
+    uint64_t comp_size;
+    uint64_t size;       /* decoded size */
+    uint64_t name_off;   /* the name's place in the directory */
+    uint32_t crc32;
+    uint16_t name_len, method, flags, pad;
+    int32_t status;      /* CHIP_ZIPENT_* */
+} chip_zip_entry;
+typedef struct {
+    uint64_t n_entries, n_ok, total_size, cd_off, cd_size, eocd_off, bad_index;
+    int32_t status; /* CHIP_ZIP_* */
+    int32_t zip64;
+} chip_zip_plan_summary;
+int chip_zip_plan_host(const uint8_t *in, uint64_t len, uint64_t max_entries, chip_zip_entry *entries, chip_zip_plan_summary *summary);
+int chip_zip_plan(const void *in_base, uint64_t len, uint64_t max_entries, chip_zip_entry *entries, chip_zip_plan_summary *summary,
+                  void *stream);
+
+/*
+ * CRC-32 of many device ranges: crc[i] = the RFC 1952 CRC-32 (zlib's crc32) of base[off[i] .. + len[i]); len[i] == 0 gives 0.  All
+ * four arrays and base are DEVICE pointers, off[i] at any alignment.  A range is cut into pieces of CHIP_CRC_PIECE bytes,
+ * right-aligned: only the first piece of a range is short.  One wave does each piece; a second kernel folds the pieces of each
+ * range on the device, crc = multmodp(x^(8 * CHIP_CRC_PIECE), crc) ^ piece_crc, one wave per range.  So one 4 GiB range and a
+ * million 100-byte ranges both fill the card.  The call enqueues on `stream` and waits ONCE in between, for the number of pieces,
+ * to size its scratch; the results are in device memory when the stream reaches them, not when the call returns.
+ * CHIP_E_INVALID, before the device is looked for: a NULL array or base with n > 0; n > 2^32 - 1.  n == 0: CHIP_OK, the device is
+ * not touched.  More than 2^31 - 1 pieces: CHIP_E_NOMEM.  Scratch per (device, stream), a launch slot of its own released by
+ * chip_trim(): 16 bytes per range and 4 bytes per piece.
+ * No reference counterpart.
+ */
+#define CHIP_CRC_PIECE 65536u
+int chip_crc32_batch(size_t n, const void *base, const uint64_t *off, const uint64_t *len, uint32_t *crc, void *stream);
+
+/*
+ * Selected entries of a planned archive, decoded, copied and verified in DEVICE memory.  in_base / len are the archive the plan
+ * was made of (alignment and padding as for chip_zip_plan), `entries` the plan's records (DEVICE memory) and n_entries their
+ * number; sel is a DEVICE array of n_sel entry indices in any order, repeats allowed; sel NULL means entries 0 .. n_sel in order.
+ * out_off (u64) and status (i32) are DEVICE arrays of n_sel entries; summary is a HOST pointer.
+ * The records are read as the caller hands them over.  An entry takes part when its record's status is CHIP_ZIPENT_OK and the
+ * record passes the checks every load depends on: method 0 or 8, data_off + comp_size <= len, method 0 with comp_size == size,
+ * method 8 within a unit's limits; a record with status OK that fails them is CHIP_ZIPENT_BAD_LOCAL.  So no load is out of range,
+ * whatever the records hold.
+ *   out_off[k]  the exclusive 64-bit sum over the selection of `size` of the entries that take part; every other entry contributes 0
+ *   total_out   the sum of them all.  total_out > out_cap: summary status CHIP_READ_NEED_OUTPUT, total_out exact, out_off answered,
+ *               status[k] is CHIP_NEED_OUTPUT for an entry that would take part and the verdict below for one that would not,
+ *               nothing is decoded and no byte of out_base is written.
+ * With enough room (summary status CHIP_READ_OK): the method 8 entries go as one batch to chip_decode_batch(CHIP_FMT_DEFLATE) with
+ * in_off = data_off, in_len = comp_size, out_cap = size; the method 0 entries are copied with chip_pack_units' discipline (a
+ * destination byte is written once, by a store no wider than the bytes that belong to it); one chip_crc32_batch pass runs over all
+ * of them.  status[k] is then
+ *   the record's status, or CHIP_ZIPENT_BAD_LOCAL as above, or CHIP_ZIPENT_BAD_INDEX for sel[k] >= n_entries: nothing is written for it
+ *   the decode's own status when that is not CHIP_FINISHED: CHIP_NEED_INPUT (the stream is cut), CHIP_NEED_OUTPUT (it holds more
+ *     than `size`), -3
+ *   CHIP_ZIPENT_BAD_SIZE when it finished with fewer than `size` bytes
+ *   CHIP_ZIPENT_BAD_CRC
+ *   CHIP_FINISHED: out_base[out_off[k] .. + size) is the entry.
+ * The bytes of an entry that is not CHIP_FINISHED are unspecified inside its own range.  Nothing outside out_base[0 .. total_out)
+ * is ever written.  summary: n_sel; n_ok the entries that are CHIP_FINISHED, n_bad the others, first_bad the lowest k that is not
+ * (0 without one); total_out; status CHIP_READ_OK or CHIP_READ_NEED_OUTPUT.  out_base must not overlap in_base.
+ * SYNCHRONOUS on `stream`: it waits once for total_out and the number of deflated entries and once at the end.
+ * CHIP_E_INVALID, before the device is looked for: summary NULL; in_base NULL with len > 0, not 4-byte aligned, len > 2^40; entries
+ * NULL with n_entries > 0; out_off or status NULL with n_sel > 0; out_base NULL with out_cap > 0; n_entries or n_sel above
+ * 2^31 - 1.  n_sel == 0: CHIP_OK, an all-zero summary, the device is not touched.
+ * Scratch per (device, stream), a launch slot of its own released by chip_trim(): 112 bytes per selected entry and 4 bytes per
+ * CHIP_CRC_PIECE bytes of output; the decode runs on the inflate slot of that stream, as chip_decode_batch does.
+ * No reference counterpart.
+ */
+typedef struct {
+    uint64_t n_sel, n_ok, n_bad, first_bad, total_out;
+    int32_t status; /* CHIP_READ_OK, CHIP_READ_NEED_OUTPUT */
+    int32_t pad;
+} chip_zip_decode_summary;
+int chip_zip_decode(const void *in_base, uint64_t len, const chip_zip_entry *entries, uint64_t n_entries, uint64_t n_sel,
+                    const uint32_t *sel, void *out_base, uint64_t out_cap, uint64_t *out_off, int32_t *status,
+                    chip_zip_decode_summary *summary, void *stream);
+
 /* ---- encoder: mirrors encoder::Interface, src/encoder/mod.rs:52-57 ---------------------------- */
 
 typedef struct chip_encoder chip_encoder;

@@ -205,6 +205,70 @@ pub struct chip_gzip_plan_summary {
     pub member_status: i32,
 }
 
+///`chip_zip_plan_summary::status`
+pub const CHIP_ZIP_OK: i32 = 0;
+pub const CHIP_ZIP_NO_EOCD: i32 = 1;
+pub const CHIP_ZIP_BAD_DIRECTORY: i32 = 2;
+pub const CHIP_ZIP_UNSUPPORTED: i32 = 3;
+///`chip_zip_entry::status`, and what `chip_zip_decode` answers beside the decode statuses
+pub const CHIP_ZIPENT_OK: i32 = 0;
+pub const CHIP_ZIPENT_UNSUPPORTED: i32 = 16;
+pub const CHIP_ZIPENT_ENCRYPTED: i32 = 17;
+pub const CHIP_ZIPENT_BAD_LOCAL: i32 = 18;
+pub const CHIP_ZIPENT_TOO_LARGE: i32 = 19;
+pub const CHIP_ZIPENT_BAD_SIZE: i32 = 20;
+pub const CHIP_ZIPENT_BAD_CRC: i32 = 21;
+pub const CHIP_ZIPENT_BAD_INDEX: i32 = 22;
+///bytes of a piece of a `chip_crc32_batch` range
+pub const CHIP_CRC_PIECE: u32 = 65536;
+
+///one entry of a ZIP archive's directory as `chip_zip_plan` lists it (56 bytes, no implicit padding)
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct chip_zip_entry {
+    pub header_off: u64,
+    pub data_off: u64,
+    pub comp_size: u64,
+    pub size: u64,
+    pub name_off: u64,
+    pub crc32: u32,
+    pub name_len: u16,
+    pub method: u16,
+    pub flags: u16,
+    pub pad: u16,
+    pub status: i32,
+}
+
+///what the directory walk found: entries, OK entries and their decoded bytes of the whole walk, where the directory and the end
+///record lie, the entry a `CHIP_ZIP_BAD_DIRECTORY` walk stopped at, why it stopped, whether ZIP64 records were read
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct chip_zip_plan_summary {
+    pub n_entries: u64,
+    pub n_ok: u64,
+    pub total_size: u64,
+    pub cd_off: u64,
+    pub cd_size: u64,
+    pub eocd_off: u64,
+    pub bad_index: u64,
+    pub status: i32,
+    pub zip64: i32,
+}
+
+///what `chip_zip_decode` did: entries selected, those that are `CHIP_FINISHED`, the others, the lowest position of one of those,
+///the bytes of the layout (the exact size needed on `CHIP_READ_NEED_OUTPUT`)
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct chip_zip_decode_summary {
+    pub n_sel: u64,
+    pub n_ok: u64,
+    pub n_bad: u64,
+    pub first_bad: u64,
+    pub total_out: u64,
+    pub status: i32,
+    pub pad: i32,
+}
+
 ///`chip_encode_file` flag: the seek table of zstd's seekable format follows the last frame (`CHIP_FMT_ZSTD` only)
 pub const CHIP_W_SEEK_TABLE: u32 = 1;
 ///`chip_file_summary::status`
@@ -485,6 +549,17 @@ extern "C" {
     ///the member index of a device-resident buffer of gzip members: the size pass over every candidate start, then the chain from 0
     pub fn chip_gzip_plan(in_base: *const c_void, len: u64, max_members: u64, in_off: *mut u64, in_len: *mut u32, out_off: *mut u64, out_cap: *mut u32,
                           summary: *mut chip_gzip_plan_summary, stream: *mut c_void) -> c_int;
+    ///the directory of a ZIP archive in host memory as entry records: the walk that defines the plan
+    pub fn chip_zip_plan_host(input: *const u8, len: u64, max_entries: u64, entries: *mut chip_zip_entry, summary: *mut chip_zip_plan_summary) -> c_int;
+    ///the same over a device-resident archive: end record search, record chain by pointer doubling, one lane per local header
+    pub fn chip_zip_plan(in_base: *const c_void, len: u64, max_entries: u64, entries: *mut chip_zip_entry, summary: *mut chip_zip_plan_summary,
+                         stream: *mut c_void) -> c_int;
+    ///CRC-32 of many device ranges: one wave per `CHIP_CRC_PIECE` bytes, folded per range on the device
+    pub fn chip_crc32_batch(n: usize, base: *const c_void, off: *const u64, len: *const u64, crc: *mut u32, stream: *mut c_void) -> c_int;
+    ///selected entries of a planned archive decoded (method 8), copied (method 0) and verified against the directory's CRC-32
+    pub fn chip_zip_decode(in_base: *const c_void, len: u64, entries: *const chip_zip_entry, n_entries: u64, n_sel: u64, sel: *const u32,
+                           out_base: *mut c_void, out_cap: u64, out_off: *mut u64, status: *mut i32, summary: *mut chip_zip_decode_summary,
+                           stream: *mut c_void) -> c_int;
     ///from a size pass to a decode on the device: offsets (exclusive sum) and clipped capacities of `out_size`; host `total` / `n_over`
     pub fn chip_layout_units(n: usize, out_size: *const u64, out_off: *mut u64, out_cap: *mut u32, total: *mut u64, n_over: *mut u64,
                              stream: *mut c_void) -> c_int;
