@@ -108,6 +108,16 @@ class _ZipDecodeSummary(C.Structure):
                 ("status", C.c_int32), ("pad", C.c_int32)]
 
 
+class _ZipSource(C.Structure):
+    _fields_ = [("data_off", C.c_uint64), ("size", C.c_uint64), ("name_off", C.c_uint64), ("name_len", C.c_uint16), ("method", C.c_uint16),
+                ("dos_time", C.c_uint16), ("dos_date", C.c_uint16)]
+
+
+class _ZipWriteSummary(C.Structure):
+    _fields_ = [("n_entries", C.c_uint64), ("n_deflated", C.c_uint64), ("out_len", C.c_uint64), ("cd_off", C.c_uint64), ("cd_size", C.c_uint64),
+                ("eocd_off", C.c_uint64), ("bad_index", C.c_uint64), ("status", C.c_int32), ("zip64", C.c_int32)]
+
+
 class _FileSummary(C.Structure):
     _fields_ = [("n_units", C.c_uint64), ("out_len", C.c_uint64), ("table_off", C.c_uint64), ("status", C.c_int32), ("pad", C.c_uint32)]
 
@@ -262,6 +272,15 @@ def lib():
     L.chip_crc32_batch.argtypes = [sz, vp, vp, vp, vp, vp]
     L.chip_zip_decode.restype = C.c_int
     L.chip_zip_decode.argtypes = [vp, C.c_uint64, vp, C.c_uint64, C.c_uint64, vp, vp, C.c_uint64, vp, vp, C.POINTER(_ZipDecodeSummary), vp]
+    u64, zws = C.c_uint64, C.POINTER(_ZipWriteSummary)
+    L.chip_zip_assemble_host.restype = C.c_int
+    L.chip_zip_assemble_host.argtypes = [u64, vp, vp, u64, vp, u64, vp, u64, vp, vp, vp, C.c_uint32, vp, u64, vp, zws]
+    L.chip_zip_assemble.restype = C.c_int
+    L.chip_zip_assemble.argtypes = [u64, vp, vp, u64, vp, u64, vp, u64, vp, vp, vp, C.c_uint32, vp, u64, vp, zws, vp]
+    L.chip_zip_write.restype = C.c_int
+    L.chip_zip_write.argtypes = [C.c_int, C.c_uint32, u64, vp, vp, u64, vp, u64, vp, u64, vp, zws, vp]
+    L.chip_zip_write_bound.restype = C.c_uint64
+    L.chip_zip_write_bound.argtypes = [u64, u64, u64]
     L.chip_layout_units.restype = C.c_int
     L.chip_layout_units.argtypes = [sz, vp, vp, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), vp]
     L.chip_pack_units.restype = C.c_int
@@ -2504,6 +2523,215 @@ def zip_decode(in_buf, length, names_or_indices=None, stream=None):
     # the sizes of the entries that took part: the differences of the layout
     ends = torch.cat((out_off[1:], torch.tensor([summary.total_out], dtype=torch.int64, device=dev))) if n_sel else out_off
     return out, out_off, ends - out_off, status, summary
+
+
+# ---- ZIP archives: writing (include/compu_hip.h, "ZIP archives: writing") ---------------------------
+
+ZIP_STORE, ZIP_DEFLATE = 0, 8  # CHIP_ZIP_STORE, CHIP_ZIP_DEFLATE: chip_zip_source.method
+ZW_ZIP64, ZW_UTF8 = 1, 2  # CHIP_ZW_ZIP64 (every record in its ZIP64 form), CHIP_ZW_UTF8 (gp flag bit 11: the names are UTF-8)
+ZIPW_DEFLATE_MAX = 1 << 30  # CHIP_ZIPW_DEFLATE_MAX: zip_write stores a larger entry
+
+
+class ZipWriteStatus(enum.IntEnum):
+    Ok = 0
+    NeedOutput = 1
+    BadSource = 2
+
+
+def zip_source_dtype():
+    """chip_zip_source as a numpy record: data_off, size, name_off, name_len, method, dos_time, dos_date."""
+    import numpy as np
+
+    dt = np.dtype([("data_off", "<u8"), ("size", "<u8"), ("name_off", "<u8"), ("name_len", "<u2"), ("method", "<u2"), ("dos_time", "<u2"),
+                   ("dos_date", "<u2")])
+    assert dt.itemsize == C.sizeof(_ZipSource) == 32
+    return dt
+
+
+class ZipWriteSummary:
+    """chip_zip_write_summary: n_entries, n_deflated (entries written with method 8), out_len (the archive's length; the exact room
+    to come back with on NeedOutput), the directory's place (cd_off, cd_size), the end record's (eocd_off), bad_index (the lowest
+    bad record on BadSource), status, zip64."""
+
+    __slots__ = ("n_entries", "n_deflated", "out_len", "cd_off", "cd_size", "eocd_off", "bad_index", "status", "zip64")
+
+    def __init__(self, raw):
+        self.n_entries, self.n_deflated, self.out_len = int(raw.n_entries), int(raw.n_deflated), int(raw.out_len)
+        self.cd_off, self.cd_size, self.eocd_off, self.bad_index = int(raw.cd_off), int(raw.cd_size), int(raw.eocd_off), int(raw.bad_index)
+        self.status, self.zip64 = ZipWriteStatus(raw.status), int(raw.zip64)
+
+    def as_tuple(self):
+        return (self.n_entries, self.n_deflated, self.out_len, self.cd_off, self.cd_size, self.eocd_off, self.bad_index, int(self.status), self.zip64)
+
+    def __repr__(self):
+        return (f"ZipWriteSummary(n_entries={self.n_entries}, n_deflated={self.n_deflated}, out_len={self.out_len}, cd_off={self.cd_off}, "
+                f"cd_size={self.cd_size}, eocd_off={self.eocd_off}, bad_index={self.bad_index}, status={self.status.name}, zip64={self.zip64})")
+
+
+def zip_write_bound(n, names_total, content_total):
+    """chip_zip_write_bound: the room that is always enough for n entries with names_total bytes of names and content_total bytes of
+    content; 0 when it overflows 64 bits."""
+    return int(lib().chip_zip_write_bound(int(n), int(names_total), int(content_total)))
+
+
+def zip_assemble_host(sources, names, content, crc, comp=None, comp_off=None, comp_len=None, flags=0, out_cap=None, content_len=None):
+    """chip_zip_assemble_host: `sources` a numpy record array (zip_source_dtype), names / content / comp bytes or uint8 arrays, crc a
+    uint32 array, comp_off uint64 and comp_len uint32 arrays (comp, comp_off, comp_len all None: every entry is stored).  out_cap
+    None: one call for the size, one to write.  content_len overrides len(content) for a call that only sizes (out_cap smaller than
+    the archive: the content is never read).  Returns (the archive as bytes -- b"" unless status is Ok --, entries as a numpy record
+    array of zip_entry_dtype, ZipWriteSummary)."""
+    import numpy as np
+
+    u8 = lambda b: None if b is None else (np.ascontiguousarray(b, dtype=np.uint8) if isinstance(b, np.ndarray) else np.frombuffer(bytes(b), np.uint8))  # noqa: E731
+    src = np.ascontiguousarray(sources, dtype=zip_source_dtype())
+    n = src.size
+    names, content, comp = u8(names), u8(content), u8(comp)
+    crc = np.ascontiguousarray(crc, dtype=np.uint32)
+    if crc.size != n:
+        raise ValueError("one CRC per source")
+    if comp is not None:
+        comp_off, comp_len = np.ascontiguousarray(comp_off, dtype=np.uint64), np.ascontiguousarray(comp_len, dtype=np.uint32)
+        if comp_off.size != n or comp_len.size != n:
+            raise ValueError("one comp_off and one comp_len per source")
+        comp_all = comp.size
+        if comp.size == 0:
+            comp = np.zeros(1, np.uint8)  # (an empty stream buffer still has an address)
+    else:
+        comp_off = comp_len = None
+        comp_all = 0
+    p = lambda a: None if a is None or a.size == 0 else a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    pc = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    clen = content.size if content_len is None else int(content_len)
+    raw = _ZipWriteSummary()
+    entries = np.zeros(n, zip_entry_dtype())
+
+    def call(out, cap):
+        rc = lib().chip_zip_assemble_host(n, p(src), p(names), names.size, pc(content) if clen else None, clen, pc(comp), comp_all, pc(comp_off), pc(comp_len),
+                                          p(crc), flags, p(out), cap, p(entries), C.byref(raw))
+        if rc != 0:
+            raise RuntimeError(f"chip_zip_assemble_host failed: {rc}")
+
+    out = np.zeros(0 if out_cap is None else int(out_cap), np.uint8)
+    call(out, out.size)
+    if out_cap is None and raw.status == ZipWriteStatus.NeedOutput:
+        out = np.zeros(int(raw.out_len), np.uint8)
+        call(out, out.size)
+    summ = ZipWriteSummary(raw)
+    return (out[:summ.out_len].tobytes() if summ.status == ZipWriteStatus.Ok else b""), entries, summ
+
+
+def _zip_device_call(what, call, n, dev, out, stream):
+    """the two-call protocol of zip_assemble / zip_write: `out` None allocates the exact room after a sizing call"""
+    import torch
+
+    raw = _ZipWriteSummary()
+    entries = torch.empty((n, C.sizeof(_ZipEntry)), dtype=torch.uint8, device=dev)
+
+    def once(o):
+        with torch.cuda.device(dev):
+            rc = call(_dp(o) if o.numel() else None, o.numel(), _dp(entries) if n else None, C.byref(raw), _stream_ptr(stream))
+        if rc != 0:
+            raise RuntimeError(f"{what} failed: {rc}")
+
+    if out is None:
+        out = torch.empty(0, dtype=torch.uint8, device=dev)
+        once(out)
+        if raw.status == ZipWriteStatus.NeedOutput:
+            out = torch.empty(int(raw.out_len), dtype=torch.uint8, device=dev)
+            once(out)
+    else:
+        once(out)
+    summ = ZipWriteSummary(raw)
+    return (out[:summ.out_len] if summ.status == ZipWriteStatus.Ok else out[:0]), entries, summ
+
+
+def zip_assemble(sources, names, content, crc, comp=None, comp_off=None, comp_len=None, flags=0, out=None, stream=None):
+    """chip_zip_assemble on device tensors: sources uint8 of shape (n, 32) holding chip_zip_source records
+    (`torch.from_numpy(records.view(np.uint8).reshape(-1, 32)).cuda()`), names / content / comp uint8, crc int32 (read as u32), comp_off
+    int64, comp_len int32 (comp, comp_off, comp_len all None: every entry is stored).  out None: the exact room is allocated after a
+    sizing call; else a uint8 tensor, and too little room is status NeedOutput with nothing written.  Returns (the archive: a view of
+    `out`, empty unless status is Ok; entries: uint8 of shape (n, 56), what zip_plan would answer; ZipWriteSummary).  Synchronous on
+    `stream`."""
+    import torch
+
+    pairs = [(sources, torch.uint8), (names, torch.uint8), (content, torch.uint8), (crc, torch.int32)]
+    if comp is not None or comp_off is not None or comp_len is not None:
+        pairs += [(comp, torch.uint8), (comp_off, torch.int64), (comp_len, torch.int32)]
+    if out is not None:
+        pairs.append((out, torch.uint8))
+    dev = _check_tensors(pairs)
+    n = sources.numel() // C.sizeof(_ZipSource)
+    if sources.numel() != n * C.sizeof(_ZipSource) or crc.numel() != n or (comp is not None and (comp_off.numel() != n or comp_len.numel() != n)):
+        raise ValueError("sources holds 32-byte records; crc, comp_off and comp_len one value per record")
+    q = lambda t: _dp(t) if t is not None and t.numel() else None  # noqa: E731
+    have = comp is not None
+    if have and comp.numel() == 0:
+        comp = torch.zeros(16, dtype=torch.uint8, device=dev)  # (an empty stream buffer still has an address)
+        comp_all = 0
+    else:
+        comp_all = comp.numel() if have else 0
+
+    def call(o, cap, ent, raw, sp):
+        return lib().chip_zip_assemble(n, q(sources), q(names), names.numel(), q(content), content.numel(), _dp(comp) if have else None, comp_all,
+                                       _dp(comp_off) if have else None, _dp(comp_len) if have else None, q(crc), flags, o, cap, ent, raw, sp)
+
+    return _zip_device_call("chip_zip_assemble", call, n, dev, out, stream)
+
+
+def zip_write(sources, names, content, level=6, flags=0, out=None, stream=None):
+    """chip_zip_write on device tensors: content to archive in one call -- the CRC-32 of every entry, the deflate-eligible entries
+    encoded at `level` (one wave each), the assembly.  sources / names / out as for zip_assemble; content a uint8 tensor, 4-byte aligned
+    and padded to a multiple of 4, the sources' data_off at any alignment.  Returns (archive, entries, ZipWriteSummary) as
+    zip_assemble does.  Synchronous on `stream`."""
+    import torch
+
+    pairs = [(sources, torch.uint8), (names, torch.uint8), (content, torch.uint8)] + ([(out, torch.uint8)] if out is not None else [])
+    dev = _check_tensors(pairs)
+    n = sources.numel() // C.sizeof(_ZipSource)
+    if sources.numel() != n * C.sizeof(_ZipSource):
+        raise ValueError("sources holds 32-byte records")
+    q = lambda t: _dp(t) if t.numel() else None  # noqa: E731
+
+    def call(o, cap, ent, raw, sp):
+        return lib().chip_zip_write(level, flags, n, q(sources), q(names), names.numel(), q(content), content.numel(), o, cap, ent, raw, sp)
+
+    return _zip_device_call("chip_zip_write", call, n, dev, out, stream)
+
+
+def zip_write_items(items, level=6, flags=0, stream=None, device=None):
+    """A ZIP archive of (name, content) pairs on the device.  name: str (encoded as UTF-8, and ZW_UTF8 is set for the archive) or
+    bytes; content: bytes-like, or a uint8 device tensor.  Every entry asks for method 8 (zip_write stores what does not shrink);
+    the contents land at 4-byte aligned offsets of one device buffer, the DOS date is 1980-01-01.  Returns (the archive as a uint8
+    device tensor, entries, ZipWriteSummary) as zip_write does."""
+    import numpy as np
+    import torch
+
+    items = list(items)
+    tensors = [c for _, c in items if isinstance(c, torch.Tensor)]
+    dev = tensors[0].device if tensors else torch.device("cuda" if device is None else device)
+    src = np.zeros(len(items), zip_source_dtype())
+    names, at = bytearray(), 0
+    for i, (name, c) in enumerate(items):
+        if isinstance(name, str):
+            name, flags = name.encode("utf-8"), flags | ZW_UTF8
+        if len(name) > 65535:
+            raise ValueError("a name has at most 65535 bytes")
+        size = c.numel() if isinstance(c, torch.Tensor) else len(memoryview(c).cast("B"))
+        src[i] = (at, size, len(names), len(name), ZIP_DEFLATE, 0, 0x21)
+        names += name
+        at += (size + 3) // 4 * 4
+    content = torch.zeros(at, dtype=torch.uint8, device=dev)
+    for row, (_, c) in zip(src, items):
+        o, size = int(row["data_off"]), int(row["size"])
+        if size:
+            if isinstance(c, torch.Tensor):
+                _check_tensors(((content, torch.uint8), (c, torch.uint8)))
+                content[o:o + size] = c.reshape(-1)
+            else:
+                content[o:o + size] = torch.from_numpy(np.frombuffer(memoryview(c).cast("B"), np.uint8).copy()).to(dev)
+    d_src = torch.from_numpy(src.view(np.uint8).reshape(-1, 32).copy()).to(dev)
+    d_names = torch.from_numpy(np.frombuffer(bytes(names), np.uint8).copy()).to(dev)
+    return zip_write(d_src, d_names, content, level=level, flags=flags, stream=stream)
 
 
 # ---- one large stream: block starts (include/compu_hip.h, "block starts") -------------------------

@@ -906,6 +906,102 @@ int chip_zip_decode(const void *in_base, uint64_t len, const chip_zip_entry *ent
                     const uint32_t *sel, void *out_base, uint64_t out_cap, uint64_t *out_off, int32_t *status,
                     chip_zip_decode_summary *summary, void *stream);
 
+/* ---- ZIP archives: writing ------------------------------------------------- */
+
+/*
+ * The archive chip_zip_plan reads back, made on the device.  Sizes and CRC-32 are known before the first byte is placed, so the
+ * archive has no data descriptors: every header states its true sizes and CRC.  Entry i is a chip_zip_source: its content is
+ * content[data_off .. + size), its name names[name_off .. + name_len) (any bytes, may be empty), `method` what the caller asks for.
+ *   chip_zip_assemble_host  the whole assembly on the host from streams that are already encoded: comp_off (u64) and comp_len (u32)
+ *                           give entry i's raw deflate stream inside comp[0 .. comp_all), crc[i] is the CRC-32 of the content.  comp,
+ *                           comp_off and comp_len may all be NULL: every entry is then stored.
+ *   chip_zip_assemble       the same with every array and buffer in DEVICE memory, summary on the HOST, and a stream: for a caller
+ *                           with encoder settings of its own (chip_encode_batch_ex), or one that re-bundles deflated entries of
+ *                           another archive without recompressing them (chip_zip_plan's data_off / comp_size / crc32 are its inputs).
+ *   chip_zip_write          content to archive in one call: chip_crc32_batch over every entry's content, then
+ *                           chip_encode_batch(CHIP_FMT_DEFLATE, level, ..) over the deflate-eligible entries -- method 8 with
+ *                           0 < size <= CHIP_ZIPW_DEFLATE_MAX -- each one unit and one wave, into scratch slots of
+ *                           up16(chip_encode_bound(CHIP_FMT_DEFLATE, size)) bytes that a kernel lays out with a scan; then the
+ *                           assembly of chip_zip_assemble.  level as for chip_encode_batch (-1 .. 9).  in_base is 4-byte aligned and
+ *                           its allocation padded to a multiple of 4, as the encoder requires; data_off may have any alignment.
+ *   chip_zip_write_bound    content_total + 2 * names_total + 124 * n + 98, or 0 when that overflows 64 bits: always enough, because
+ *                           an entry is only written deflated when that is smaller.
+ * The archive is DEFINED by these rules (all integers little endian; M32 = 0xFFFFFFFF; FORCE = flags & CHIP_ZW_ZIP64):
+ *   Method.  Entry i is written deflated (method 8, c_i = comp_len[i]) when its source asks for 8, a stream is given and
+ *     0 < comp_len[i] < size; otherwise stored (method 0, c_i = size).  So an empty entry such as "dir/", an incompressible one, one
+ *     above CHIP_ZIPW_DEFLATE_MAX and level 0 (stored blocks never shrink) are all stored.
+ *   Local part of entry i at header_off_i; the entries follow each other in order with no gaps, header_off_0 = 0:
+ *     50 4b 03 04 | version v_i | gp flags (0x0800 with CHIP_ZW_UTF8, else 0) | method | dos_time | dos_date | crc | csize | usize |
+ *     name_len | xlen | the name | the extra field | the data.
+ *     zs_i = FORCE || size >= M32 || c_i >= M32.  With zs_i both size fields are M32 and the extra field is
+ *     01 00 10 00 LE64(size) LE64(c_i) (20 bytes); without it xlen is 0.
+ *   Central record of entry i; the records follow each other from cd_off, the end of the last entry's data:
+ *     50 4b 01 02 | made-by v_i | version v_i | the same seven fields as the local header | name_len | xlen | comment length 0 |
+ *     disk 0 | internal attributes 0 | external attributes 0 | lho | the name | the extra field.
+ *     zl_i = FORCE || header_off_i >= M32.  The extra field is one id-1 subfield holding, in this order, size and c_i (both, when
+ *     zs_i) and then header_off_i (when zl_i): 0, 12, 20 or 28 bytes with its 4-byte header.  The fields it replaces are M32.
+ *     v_i = 45 when the central record has the subfield, else 20 for method 8 and 10 for method 0; the local header has the same v_i.
+ *   End.  z = FORCE || n >= 0xFFFF || cd_size >= M32 || cd_off >= M32.  With z the 56-byte ZIP64 end record comes first:
+ *     50 4b 06 06 | LE64 44 | LE16 45 | LE16 45 | LE32 0 | LE32 0 | n | n | cd_size | cd_off; then the 20-byte locator:
+ *     50 4b 06 07 | LE32 0 | LE64 the record's offset | LE32 1.  Then the 22-byte end record with min(n, 0xFFFF) twice,
+ *     min(cd_size, M32), min(cd_off, M32) and comment length 0; eocd_off is its place, zip64 = z.  n == 0 gives 22 bytes (98 with
+ *     FORCE).  There are no data descriptors, comments, timestamp subfields or alignment padding.
+ *   entries[i] (may be NULL) is the chip_zip_entry chip_zip_plan produces for entry i of the written archive: header_off, data_off,
+ *     comp_size, size, name_off (inside the directory), crc32, name_len, the written method, flags, pad 0, status CHIP_ZIPENT_OK --
+ *     CHIP_ZIPENT_TOO_LARGE, as the plan says, for a deflated entry beyond a unit's limits, which only the assemble calls can be
+ *     handed.  The caller holds the index of what it wrote without planning it again.
+ * summary: n_entries = n, n_deflated the entries written with method 8, out_len, cd_off, cd_size, eocd_off, zip64, status:
+ *   CHIP_ZIPW_BAD_SOURCE   bad_index = the LOWEST i whose record fails one of: method not 0 or 8; data_off + size > content_len,
+ *                          formed without wrapping; name_off + name_len > names_len, likewise; for an entry that would be written
+ *                          deflated in the assemble calls, comp_off + comp_len > comp_all.  Nothing but the summary is written; its
+ *                          other fields are 0 except n_entries.
+ *   CHIP_ZIPW_NEED_OUTPUT  out_len > out_cap: out_len is exact, entries and the summary are answered, no byte of `out` is written and
+ *                          no byte of content / comp is read.  The host form is then pure arithmetic on the records.
+ *   CHIP_ZIPW_OK           nothing outside out[0 .. out_len) is written; `out` may have any alignment; every byte is written exactly
+ *                          once, by a store that covers only bytes of its own record or range (chip_pack_units' discipline).
+ * `out` must not overlap the inputs.
+ * CHIP_E_INVALID, before a device is looked for: summary NULL; src NULL with n > 0, names NULL with names_len > 0, content (in_base)
+ * NULL with content_len > 0, crc NULL with n > 0; out NULL with out_cap > 0; exactly one or two of the three comp arrays NULL;
+ * n > 2^31 - 1; unknown flag bits; level out of range and in_base not 4-byte aligned (chip_zip_write); and arguments that allow an
+ * archive of 2^63 bytes or more: content_len >= 2^62, or n * (content_len + 131 194) > 2^63 - 98.
+ * n == 0 is answered by the host without touching the device, with or without room: the end records alone, placed with one copy
+ * on `stream` that is waited for (chip_zip_assemble_host: written directly).
+ * The device calls are SYNCHRONOUS on `stream`.  chip_zip_assemble waits twice: for out_len against the room, and at the end.
+ * chip_zip_write waits four times: for the scratch sizes (the slot bytes and the number of deflate-eligible entries), once inside
+ * chip_crc32_batch (its pieces), for out_len, and at the end.
+ * Scratch per (device, stream), a launch slot of its own released by chip_trim(): 160 bytes per entry for the assembly (and 24
+ * bytes per 1024 entries); chip_zip_write adds 84 bytes per entry and the slot area, the sum of up16(chip_encode_bound(CHIP_FMT_DEFLATE, size)) over the
+ * deflate-eligible entries -- a little more than their content -- each allocation with a quarter of headroom; the CRC pass and the
+ * encoder run on their own slots of that stream.  CHIP_E_NOMEM: the scratch could not be allocated.  CHIP_E_LAUNCH: a launch
+ * failed, the inputs changed during the call, or a unit did not end CHIP_ENC_FINISHED (which the slots rule out).
+ * No reference counterpart: compu has no container formats.
+ */
+enum { CHIP_ZIP_STORE = 0, CHIP_ZIP_DEFLATE = 8 };
+enum { CHIP_ZW_ZIP64 = 1, CHIP_ZW_UTF8 = 2 };                 /* call flags */
+enum { CHIP_ZIPW_OK = 0, CHIP_ZIPW_NEED_OUTPUT = 1, CHIP_ZIPW_BAD_SOURCE = 2 };
+#define CHIP_ZIPW_DEFLATE_MAX (1u << 30)                      /* chip_encode_file's unit limit */
+typedef struct {            /* 32 bytes, no implicit padding */
+    uint64_t data_off, size;          /* the content: content[data_off .. + size) */
+    uint64_t name_off;                /* the name: names[name_off .. + name_len), any bytes, may be empty */
+    uint16_t name_len, method, dos_time, dos_date;   /* method: what the caller asks for, 0 or 8 */
+} chip_zip_source;
+typedef struct {            /* 64 bytes */
+    uint64_t n_entries, n_deflated, out_len, cd_off, cd_size, eocd_off, bad_index;
+    int32_t status, zip64;
+} chip_zip_write_summary;
+int chip_zip_assemble_host(uint64_t n, const chip_zip_source *src, const uint8_t *names, uint64_t names_len, const uint8_t *content,
+                           uint64_t content_len, const uint8_t *comp, uint64_t comp_all, const uint64_t *comp_off, const uint32_t *comp_len,
+                           const uint32_t *crc, uint32_t flags, uint8_t *out, uint64_t out_cap, chip_zip_entry *entries,
+                           chip_zip_write_summary *summary);
+int chip_zip_assemble(uint64_t n, const chip_zip_source *src, const void *names, uint64_t names_len, const void *content,
+                      uint64_t content_len, const void *comp, uint64_t comp_all, const uint64_t *comp_off, const uint32_t *comp_len,
+                      const uint32_t *crc, uint32_t flags, void *out, uint64_t out_cap, chip_zip_entry *entries,
+                      chip_zip_write_summary *summary, void *stream);
+int chip_zip_write(int level, uint32_t flags, uint64_t n, const chip_zip_source *src, const void *names, uint64_t names_len,
+                   const void *in_base, uint64_t in_len, void *out_base, uint64_t out_cap, chip_zip_entry *entries,
+                   chip_zip_write_summary *summary, void *stream);
+uint64_t chip_zip_write_bound(uint64_t n, uint64_t names_total, uint64_t content_total);
+
 /* ---- encoder: mirrors encoder::Interface, src/encoder/mod.rs:52-57 ---------------------------- */
 
 typedef struct chip_encoder chip_encoder;

@@ -269,6 +269,49 @@ pub struct chip_zip_decode_summary {
     pub pad: i32,
 }
 
+///`chip_zip_source::method`
+pub const CHIP_ZIP_STORE: u16 = 0;
+pub const CHIP_ZIP_DEFLATE: u16 = 8;
+///flags of the ZIP writer's calls: every record in its ZIP64 form; general purpose bit 11, the names are UTF-8
+pub const CHIP_ZW_ZIP64: u32 = 1;
+pub const CHIP_ZW_UTF8: u32 = 2;
+///`chip_zip_write_summary::status`
+pub const CHIP_ZIPW_OK: i32 = 0;
+pub const CHIP_ZIPW_NEED_OUTPUT: i32 = 1;
+pub const CHIP_ZIPW_BAD_SOURCE: i32 = 2;
+///`chip_zip_write` stores an entry above this size: the limit of a unit of `chip_encode_file`
+pub const CHIP_ZIPW_DEFLATE_MAX: u32 = 1 << 30;
+
+///one entry to be written into a ZIP archive (32 bytes, no implicit padding): where its content and its name lie, the method asked
+///for, the DOS time stamp
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct chip_zip_source {
+    pub data_off: u64,
+    pub size: u64,
+    pub name_off: u64,
+    pub name_len: u16,
+    pub method: u16,
+    pub dos_time: u16,
+    pub dos_date: u16,
+}
+
+///what the ZIP writer made: entries, those written deflated, the archive's length (the exact room needed on
+///`CHIP_ZIPW_NEED_OUTPUT`), the directory's and the end record's place, the lowest bad record on `CHIP_ZIPW_BAD_SOURCE`
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct chip_zip_write_summary {
+    pub n_entries: u64,
+    pub n_deflated: u64,
+    pub out_len: u64,
+    pub cd_off: u64,
+    pub cd_size: u64,
+    pub eocd_off: u64,
+    pub bad_index: u64,
+    pub status: i32,
+    pub zip64: i32,
+}
+
 ///`chip_encode_file` flag: the seek table of zstd's seekable format follows the last frame (`CHIP_FMT_ZSTD` only)
 pub const CHIP_W_SEEK_TABLE: u32 = 1;
 ///`chip_file_summary::status`
@@ -560,6 +603,21 @@ extern "C" {
     pub fn chip_zip_decode(in_base: *const c_void, len: u64, entries: *const chip_zip_entry, n_entries: u64, n_sel: u64, sel: *const u32,
                            out_base: *mut c_void, out_cap: u64, out_off: *mut u64, status: *mut i32, summary: *mut chip_zip_decode_summary,
                            stream: *mut c_void) -> c_int;
+    ///a ZIP archive assembled on the host from contents, names and already encoded raw deflate streams: the rules that define the writer
+    pub fn chip_zip_assemble_host(n: u64, src: *const chip_zip_source, names: *const u8, names_len: u64, content: *const u8, content_len: u64,
+                                  comp: *const u8, comp_all: u64, comp_off: *const u64, comp_len: *const u32, crc: *const u32, flags: u32,
+                                  out: *mut u8, out_cap: u64, entries: *mut chip_zip_entry, summary: *mut chip_zip_write_summary) -> c_int;
+    ///the same with every array and buffer in device memory (host `summary`): layout by two scans, records, destination-driven copies
+    pub fn chip_zip_assemble(n: u64, src: *const chip_zip_source, names: *const c_void, names_len: u64, content: *const c_void, content_len: u64,
+                             comp: *const c_void, comp_all: u64, comp_off: *const u64, comp_len: *const u32, crc: *const u32, flags: u32,
+                             out: *mut c_void, out_cap: u64, entries: *mut chip_zip_entry, summary: *mut chip_zip_write_summary,
+                             stream: *mut c_void) -> c_int;
+    ///content to archive in one call: CRC-32, deflate of the eligible entries (one wave each), assembly; synchronous on `stream`
+    pub fn chip_zip_write(level: c_int, flags: u32, n: u64, src: *const chip_zip_source, names: *const c_void, names_len: u64,
+                          in_base: *const c_void, in_len: u64, out_base: *mut c_void, out_cap: u64, entries: *mut chip_zip_entry,
+                          summary: *mut chip_zip_write_summary, stream: *mut c_void) -> c_int;
+    ///the room that is always enough for `chip_zip_write`; 0 when it overflows 64 bits
+    pub fn chip_zip_write_bound(n: u64, names_total: u64, content_total: u64) -> u64;
     ///from a size pass to a decode on the device: offsets (exclusive sum) and clipped capacities of `out_size`; host `total` / `n_over`
     pub fn chip_layout_units(n: usize, out_size: *const u64, out_off: *mut u64, out_cap: *mut u32, total: *mut u64, n_over: *mut u64,
                              stream: *mut c_void) -> c_int;
