@@ -181,7 +181,7 @@ int chip_decode_batch_ex(int format, uint32_t flags, size_t n, const void *in_ba
     case CHIP_FMT_ZLIB:
     case CHIP_FMT_GZIP:
     case CHIP_FMT_AUTO: e = launch_inflate(a, nullptr, (hipStream_t)stream); break;
-    case CHIP_FMT_ZSTD: e = launch_zstd_decode(a, 0, (hipStream_t)stream); break;
+    case CHIP_FMT_ZSTD: e = launch_zstd(a, nullptr, 0, (hipStream_t)stream); break;
     case CHIP_FMT_BROTLI: e = launch_brotli_decode(a, (hipStream_t)stream); break;  // CHIP_F_COMPU_STATUS changes nothing
     case CHIP_FMT_DETECT:
         // Detection::detect routes every unit: one pass buckets the batch by format, then each decoder runs over its own
@@ -215,7 +215,7 @@ int chip_decode_batch_sizes(int format, uint32_t flags, size_t n, const void *in
     BatchArgs a = batch_args(format, n, in_base, in_off, in_len, nullptr, nullptr, nullptr, nullptr, in_used, status);
     a.flags = flags;
     hipError_t e;
-    if (format == CHIP_FMT_ZSTD) e = launch_zstd_sizes(a, out_size, 0, (hipStream_t)stream);
+    if (format == CHIP_FMT_ZSTD) e = launch_zstd(a, out_size, 0, (hipStream_t)stream);
     else if (format == CHIP_FMT_DETECT) e = launch_routed(a, out_size, (hipStream_t)stream);  // routed as a decode batch is
     else e = launch_inflate(a, out_size, (hipStream_t)stream);
     return e == hipSuccess ? CHIP_OK : CHIP_E_LAUNCH;
@@ -804,7 +804,7 @@ struct chip_decoder {
     uint32_t resume[RESUME_WORDS];  // inflate: last block boundary the kernel reached, running check (BatchArgs::resume); zeros = from the start
     size_t in_dropped;    // input bytes dropped in front of the buffer so far
     uint32_t last_ck;     // resume[0] + 8 * input bytes dropped so far: tells whether a run reached a new block boundary
-    uint32_t *d_zres;     // zstd: device blob with the kernel's block checkpoint (header + decode tables), see zstd.hip
+    uint32_t *d_zres;     // zstd: device blob with the kernel's block checkpoint (header + decode tables), see zstd_unit.h
     uint32_t *h_zhdr;     // zstd: host copy of the checkpoint's ZRES_HDR header words (pinned, behind h_meta)
 };
 
@@ -870,7 +870,7 @@ bool dec_run(chip_decoder *d)
         a.resume = inflate ? dm->resume : d->d_zres;
         hipError_t e = inflate  ? launch_inflate(a, nullptr, d->stream)
                        : brotli ? launch_brotli_decode(a, d->stream)
-                                : launch_zstd_decode(a, d->window_log_max, d->stream);
+                                : launch_zstd(a, nullptr, d->window_log_max, d->stream);
         if (e != hipSuccess) return false;
         if (hipMemcpyAsync(d->h_meta, d->d_meta, sizeof(Meta), hipMemcpyDeviceToHost, d->stream) != hipSuccess) return false;
         if (!inflate && hipMemcpyAsync(d->h_zhdr, d->d_zres, ZRES_HDR * 4, hipMemcpyDeviceToHost, d->stream) != hipSuccess) return false;
@@ -916,14 +916,14 @@ bool dec_move_down(chip_decoder *d, size_t from, size_t n)
 // Between calls of a stream that goes on: drop the input in front of the last block boundary and the output that has been
 // handed on and that no later block can reach -- inflate: in front of the 32 KiB window of that boundary (BatchArgs::resume
 // says how the kernel is told); zstd: in front of the frame's window, and never behind what the running XXH64 covers (the
-// checkpoint header, zstd.hip).  A single-segment zstd frame's window is its content size: nothing is dropped for it, as libzstd
+// checkpoint header, zstd_unit.h).  A single-segment zstd frame's window is its content size: nothing is dropped for it, as libzstd
 // keeps it whole (src/decoder/zstd.rs:98-136 sits on ZSTD_decompressStream).
 bool dec_compact(chip_decoder *d)
 {
     if (!d->decoded) return true;
     if (d->k_status != CHIP_NEED_INPUT && d->k_status != CHIP_NEED_OUTPUT) return true;
     if (d->format == CHIP_FMT_BROTLI || d->format == CHIP_FMT_ZSTD) {
-        // the checkpoint header (zstd.hip; brotli's metablock checkpoint: chip_internal.h, BRES_WORDS): input in front of the
+        // the checkpoint header (zstd_unit.h; brotli's metablock checkpoint: chip_internal.h, BRES_WORDS): input in front of the
         // boundary's byte, output in front of the window of the boundary that has been handed on.  zh[0] is 1 + the boundary's
         // offset in the input, in bits for brotli and in bytes for zstd.
         const bool brotli = d->format == CHIP_FMT_BROTLI;

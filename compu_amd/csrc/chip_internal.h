@@ -28,7 +28,7 @@ constexpr int32_t ZSTD_E_DICT_WRONG = 32;
 constexpr uint32_t RESUME_WORDS = 6;
 
 // The streaming zstd decoder's checkpoint in device memory (written by zstd_kernel, sized by api.hip): a header of ZRES_HDR words, then the
-// first ZSAVE_WORDS words of the kernel's LDS state (its decode tables; zstd.hip asserts that this is where `weights` starts), then slack.
+// first ZSAVE_WORDS words of the kernel's LDS state (its decode tables; zstd_unit.h asserts that this is where `weights` starts), then slack.
 constexpr uint32_t ZRES_HDR = 24;
 constexpr uint32_t ZSAVE_WORDS = 2312;
 constexpr size_t ZRES_BYTES = (size_t)(ZRES_HDR + ZSAVE_WORDS) * 4 + 64;
@@ -63,7 +63,7 @@ struct BatchArgs {
     const uint32_t *sel_n = nullptr;
     uint32_t flags = 0;  // CHIP_F_* of chip_decode_batch_ex (include/compu_hip.h)
 };
-// What zstd_tokens_kernel (zstd.hip compiled with CHIP_ZSTD_TOKENS; zstd_tokens.hip) takes beside a BatchArgs whose units are the blocks
+// What zstd_tokens_kernel (zstd_unit.h compiled with CHIP_ZSTD_TOKENS; zstd_tokens.hip) takes beside a BatchArgs whose units are the blocks
 // of ONE frame: in_off 0 and in_len the frame's for every unit, out_off / out_cap the block's literal slot in scratch.
 struct ZTokArgs {
     const chip_zstd_block *blocks;  // chip_zstd_blocks' records
@@ -72,7 +72,7 @@ struct ZTokArgs {
     uint32_t *res;                  // 8 words per block: rep0..2 handed on, literal mode (0 input, 1 RLE, 2 slot), its place / byte, Regenerated_Size
     uint64_t window;
 };
-constexpr uint32_t ZTOK_SLOT_SLACK = 8736;  // a literal slot is Regenerated_Size + this: the Huffman walk's scratch rows (zstd.hip asserts it)
+constexpr uint32_t ZTOK_SLOT_SLACK = 8736;  // a literal slot is Regenerated_Size + this: the Huffman walk's scratch rows (zstd_unit.h asserts it)
 hipError_t launch_zstd_tokens(const BatchArgs &a, const ZTokArgs &tk, hipStream_t stream);
 // (zstd_tokens.hip) XXH64 of n bytes on one wave, its low 32 bits to *got
 hipError_t launch_zstd_xxh(const uint8_t *p, uint32_t n, uint32_t *got, hipStream_t stream);
@@ -93,15 +93,16 @@ hipError_t enqueue_inflate_members(const BatchArgs &a, uint64_t *out_size, uint3
 // that begin at bit bit0[u] of their first input byte and write 16-bit elements; a.out_off counts bytes, a.out_cap and a.out_len
 // elements; `blocks` waves with SCRATCH_WORDS of token rows each)
 hipError_t enqueue_inflate_markers(const BatchArgs &a, const uint32_t *bit0, uint32_t *scratch, uint32_t *counter, uint32_t blocks, hipStream_t stream);
-// zstd_sizes.hip: the zstd size pass
-hipError_t launch_zstd_sizes(const BatchArgs &a, uint64_t *out_size, int window_log_max, hipStream_t stream);
-// (zstd_members.hip, zstd_members_sizes.hip: the CHIP_F_MEMBERS kernels behind launch_zstd_decode / launch_zstd_sizes)
-hipError_t launch_zstd_members(const BatchArgs &a, int window_log_max, hipStream_t stream);
-hipError_t launch_zstd_members_sizes(const BatchArgs &a, uint64_t *out_size, int window_log_max, hipStream_t stream);
+// zstd.hip: out_size == nullptr decodes the batch, else the size pass, as launch_inflate; window_log_max 0 = 27
+hipError_t launch_zstd(const BatchArgs &a, uint64_t *out_size, int window_log_max, hipStream_t stream);
+// (zstd_sizes.hip: the size pass's launch itself, for launch_zstd; wlog_max is the limit itself, never 0)
+hipError_t enqueue_zstd_sizes(const BatchArgs &a, uint64_t *out_size, int wlog_max, hipStream_t stream);
+// (zstd_members.hip, zstd_members_sizes.hip: the same for a CHIP_F_MEMBERS batch, decoder and size pass)
+hipError_t enqueue_zstd_members(const BatchArgs &a, int wlog_max, hipStream_t stream);
+hipError_t enqueue_zstd_members_sizes(const BatchArgs &a, uint64_t *out_size, int wlog_max, hipStream_t stream);
 // launch_slots.hip: the cached launch scratch of every codec ("Launch slots")
 hipError_t release_scratch();                 // every slot of the current device, after a device sync
 void release_scratch_of(hipStream_t stream);  // the slots of one (drained) stream of the current device
-hipError_t launch_zstd_decode(const BatchArgs &a, int window_log_max, hipStream_t stream);
 // Detection-driven router of a mixed batch: appends the index of every gzip / zlib unit to sel_inflate and of every zstd
 // frame to sel_zstd (counts[0], counts[1], zeroed by the call) and answers units that are neither at once (their length to
 // out_size, the size pass's array, when that is given).

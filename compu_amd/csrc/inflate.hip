@@ -132,7 +132,7 @@ hipError_t launch_routed(const BatchArgs &a, uint64_t *out_size, hipStream_t str
     az.sel = sel_z;
     az.sel_n = counts + 1;
     if (e == hipSuccess) e = launch_inflate_locked(ai, out_size, stream);
-    if (e == hipSuccess) e = out_size ? launch_zstd_sizes(az, out_size, 0, stream) : launch_zstd_decode(az, 0, stream);
+    if (e == hipSuccess) e = launch_zstd(az, out_size, 0, stream);
     return e;
 }
 

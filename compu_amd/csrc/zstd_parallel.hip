@@ -1,6 +1,6 @@
 // One large zstd frame, block by block: chip_zstd_parallel and its launches, and the first pass on its own,
 // the description of the frame's blocks: chip_zstd_blocks_host on the host and chip_zstd_blocks on the GPU.  The token pass is
-// zstd.hip's kernel body in zstd_tokens.hip; place, jump and deliver are below, behind the description.
+// zstd_unit.h's kernel body in zstd_tokens.hip; place, jump and deliver are below, behind the description.
 //
 // The description of a buffer is DEFINED by the walk of include/compu_hip.h.  walk_blocks, describe_block and defines below are
 // its one text for host and device.
@@ -476,7 +476,7 @@ hipError_t zpar_serial(ZparSlot &sl, const ZparCall &c, uint64_t unit_len, hipSt
     a.status = &d->status;
     a.n = 1;
     a.format = CHIP_FMT_ZSTD;
-    if ((e = launch_zstd_decode(a, c.wlog_max, s)) != hipSuccess) return e;
+    if ((e = launch_zstd(a, nullptr, c.wlog_max, s)) != hipSuccess) return e;
     if ((e = hipMemcpyAsync(&h, d, sizeof h, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
     if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;
     o.out_len = o.total_out = h.out_len;

@@ -1,10 +1,14 @@
 // The token pass of chip_zstd_parallel: zstd_tokens_kernel and its launch, and the XXH64 of the delivered content.
 //
-// The kernel is zstd.hip's kernel body compiled with CHIP_ZSTD_TOKENS set (see there): headers, table builds, literal decode and the
-// FSE state chain are that file's source, not a copy.  It has a translation unit of its own for the reason zstd_sizes.hip has one.
-// zpar_xxh_kernel is here because xxh_stripes / xxh_finish are that file's too.
+// The kernel is zstd_unit.h's kernel body compiled with CHIP_ZSTD_TOKENS set (see there): headers, table builds, literal decode and the
+// FSE state chain are that header's source, not a copy.  It has a translation unit of its own for the reason zstd_sizes.hip has one.
+// zpar_xxh_kernel and zpar_xxh_update_kernel stay here, with their launchers, though zstd_parallel.hip is what launches them: they use
+// the header's xxh_stripes / xxh_finish, and zstd_tokens_kernel's inlining depends on sharing its translation unit with them -- with the
+// XXH64 functions in a header of their own and the two kernels in zstd_parallel.hip, tools/kernel_diff.py reports zstd_tokens_kernel and
+// wave_xxh64_low32 DIFF.
+#define CHIP_ZSTD_KERNEL zstd_tokens_kernel
 #define CHIP_ZSTD_TOKENS 1
-#include "zstd.hip"
+#include "zstd_unit.h"
 
 namespace chip {
 

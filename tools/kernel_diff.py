@@ -2,6 +2,7 @@
 flags of tools/spill_audit.py) and prints SAME or DIFF per function; exit status 1 on any DIFF or any function on one side only.
 
   python tools/kernel_diff.py A B   # A, B: the root of a source tree, or a git revision of this repository (HEAD, a hash)
+  python tools/kernel_diff.py A B -- -DCHIP_STATS ...   # what follows `--` is appended to every compile of both trees
 
 Compared per function: the lines between `; -- Begin function NAME` and `; -- End function` without comments, without the
 .section / .file / .loc / .ident / .p2align lines, local labels reduced to their number within the function; and per kernel its
@@ -19,8 +20,9 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 META = ("vgpr_count", "agpr_count", "sgpr_count", "vgpr_spill_count", "sgpr_spill_count", "group_segment_fixed_size", "private_segment_fixed_size")
 
 
-def compile_tree(arg, tmp):
-    """(file, assembly text) of every .hip of a source tree or git revision; brotli.hip's generated include (build.sh) is made here"""
+def compile_tree(arg, tmp, extra):
+    """(file, assembly text) of every .hip of a source tree or git revision, compiled with the flags `extra` as well; brotli.hip's
+    generated include (build.sh) is made here"""
     if not os.path.isdir(arg):
         tar = subprocess.run(["git", "-C", ROOT, "archive", arg, "compu_amd/csrc", "include"], check=True, capture_output=True).stdout
         subprocess.run(["tar", "-x", "-C", tmp], input=tar, check=True)
@@ -33,7 +35,7 @@ def compile_tree(arg, tmp):
     def one(f):
         out = os.path.join(tmp, "asm", f[:-4] + ".s")
         subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", "-I", os.path.join(tmp, "asm"), "-o", out,
-                        os.path.join(src, f)], check=True, stderr=subprocess.DEVNULL)
+                        os.path.join(src, f)] + extra, check=True, stderr=subprocess.DEVNULL)
         return f, open(out).read()
 
     with ThreadPoolExecutor(8) as pool:
@@ -61,10 +63,11 @@ def functions(units):
 
 
 def main():
-    if len(sys.argv) != 3:
+    extra = sys.argv[4:] if sys.argv[3:4] == ["--"] else []
+    if len(sys.argv) != 3 and sys.argv[3:4] != ["--"]:
         sys.exit(__doc__)
     with tempfile.TemporaryDirectory() as ta, tempfile.TemporaryDirectory() as tb:
-        a, b = functions(compile_tree(sys.argv[1], ta)), functions(compile_tree(sys.argv[2], tb))
+        a, b = functions(compile_tree(sys.argv[1], ta, extra)), functions(compile_tree(sys.argv[2], tb, extra))
     keys = sorted(set(a) | set(b))
     plain = subprocess.run(["c++filt"], input="\n".join(n for n, _ in keys), capture_output=True, text=True).stdout.splitlines()
     bad = 0

@@ -3,7 +3,7 @@ python tools/time_sizes.py [units] [launches]
 hipEvent timing of `launches` (default 20) launches of each after two warm-up launches; prints the median and the fastest per kind
 (dynamic, fixed, stored, zstd, mixed = gzip + zstd through CHIP_FMT_DETECT: synthetic 64 KiB units as bench.py builds them) and the ratio size pass / decode.
 With SSTATS=1 and a -DCHIP_STATS build (COMPU_HIP_LIB=compu_amd/libcompu_hip_stats.so) it also prints the kernels' own cycle counters per
-unit, decode beside size pass (inflate_unit.h's stat slots; zstd.hip's ZT_* / ZC); the timings of that build are not the product's."""
+unit, decode beside size pass (inflate_unit.h's stat slots; zstd_unit.h's ZT_* / ZC); the timings of that build are not the product's."""
 import os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -1,6 +1,6 @@
 """Timing of the zstd kernel alone on synthetic 64 KiB frames: python tools/time_zstd.py [units]
 With ZSTATS=1 and a -DCHIP_STATS build (COMPU_HIP_LIB=compu_amd/libcompu_hip_stats.so) it also prints the kernel's own cycle counters
-per frame (phases and trip counts; zstd.hip, ZT_* / ZC)."""
+per frame (phases and trip counts; zstd_unit.h, ZT_* / ZC)."""
 import os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
