@@ -118,6 +118,17 @@ class _ZipWriteSummary(C.Structure):
                 ("eocd_off", C.c_uint64), ("bad_index", C.c_uint64), ("status", C.c_int32), ("zip64", C.c_int32)]
 
 
+class _TarEntry(C.Structure):
+    _fields_ = [("group_off", C.c_uint64), ("header_off", C.c_uint64), ("data_off", C.c_uint64), ("size", C.c_uint64), ("name_off", C.c_uint64),
+                ("link_off", C.c_uint64), ("mtime", C.c_int64), ("name_len", C.c_uint32), ("link_len", C.c_uint32), ("mode", C.c_uint32),
+                ("prefix_len", C.c_uint16), ("typeflag", C.c_uint8), ("flags", C.c_uint8)]
+
+
+class _TarPlanSummary(C.Structure):
+    _fields_ = [("n_entries", C.c_uint64), ("n_global", C.c_uint64), ("total_size", C.c_uint64), ("stop_off", C.c_uint64), ("bad_off", C.c_uint64),
+                ("status", C.c_int32), ("zero_blocks", C.c_int32)]
+
+
 class _FileSummary(C.Structure):
     _fields_ = [("n_units", C.c_uint64), ("out_len", C.c_uint64), ("table_off", C.c_uint64), ("status", C.c_int32), ("pad", C.c_uint32)]
 
@@ -281,6 +292,10 @@ def lib():
     L.chip_zip_write.argtypes = [C.c_int, C.c_uint32, u64, vp, vp, u64, vp, u64, vp, u64, vp, zws, vp]
     L.chip_zip_write_bound.restype = C.c_uint64
     L.chip_zip_write_bound.argtypes = [u64, u64, u64]
+    L.chip_tar_plan_host.restype = C.c_int
+    L.chip_tar_plan_host.argtypes = [vp, u64, u64, vp, C.POINTER(_TarPlanSummary)]
+    L.chip_tar_plan.restype = C.c_int
+    L.chip_tar_plan.argtypes = [vp, u64, u64, vp, C.POINTER(_TarPlanSummary), vp]
     L.chip_layout_units.restype = C.c_int
     L.chip_layout_units.argtypes = [sz, vp, vp, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), vp]
     L.chip_pack_units.restype = C.c_int
@@ -2985,3 +3000,194 @@ def inflate_parallel_stream(source, sink=None, slab_bytes=64 << 20, out_bytes=25
             else:
                 raise EOFError("the source ends inside the stream")
     return b"".join(parts) if sink is None else written
+
+
+# ---- tar archives (include/compu_hip.h, "tar archives") ---------------------------------------------
+
+
+class TarStatus(enum.IntEnum):
+    Ok = 0
+    Truncated = 1
+    BadHeader = 2
+    Unsupported = 3
+
+
+TAR_EXT_MAX, TAR_EXT_BYTES = 16, 1 << 20  # CHIP_TAR_EXT_MAX, CHIP_TAR_EXT_BYTES
+TARF_NAME_GNU, TARF_NAME_PAX, TARF_LINK_GNU, TARF_LINK_PAX, TARF_SIZE_PAX, TARF_SIZE_BASE256 = 1, 2, 4, 8, 16, 32  # CHIP_TARF_*
+
+
+def tar_entry_dtype():
+    """chip_tar_entry as a numpy record: group_off, header_off, data_off, size, name_off, link_off, mtime, name_len, link_len, mode,
+    prefix_len, typeflag, flags."""
+    import numpy as np
+
+    dt = np.dtype([("group_off", "<u8"), ("header_off", "<u8"), ("data_off", "<u8"), ("size", "<u8"), ("name_off", "<u8"), ("link_off", "<u8"),
+                   ("mtime", "<i8"), ("name_len", "<u4"), ("link_len", "<u4"), ("mode", "<u4"), ("prefix_len", "<u2"), ("typeflag", "u1"),
+                   ("flags", "u1")])
+    assert dt.itemsize == C.sizeof(_TarEntry) == 72
+    return dt
+
+
+class TarPlanSummary:
+    """chip_tar_plan_summary: n_entries (members), n_global (global pax headers stepped over) and total_size (the members' sizes) of
+    the whole walk, stop_off (the group or position where the walk stopped), bad_off (the offending header), status, zero_blocks
+    (the all-zero blocks seen at the stop: 0, 1 or 2)."""
+
+    __slots__ = ("n_entries", "n_global", "total_size", "stop_off", "bad_off", "status", "zero_blocks")
+
+    def __init__(self, raw):
+        self.n_entries, self.n_global, self.total_size = int(raw.n_entries), int(raw.n_global), int(raw.total_size)
+        self.stop_off, self.bad_off, self.status, self.zero_blocks = int(raw.stop_off), int(raw.bad_off), TarStatus(raw.status), int(raw.zero_blocks)
+
+    def as_tuple(self):
+        return (self.n_entries, self.n_global, self.total_size, self.stop_off, self.bad_off, int(self.status), self.zero_blocks)
+
+    def __repr__(self):
+        return (f"TarPlanSummary(n_entries={self.n_entries}, n_global={self.n_global}, total_size={self.total_size}, stop_off={self.stop_off}, "
+                f"bad_off={self.bad_off}, status={self.status.name}, zero_blocks={self.zero_blocks})")
+
+
+def tar_plan_host(data, max_entries=None):
+    """chip_tar_plan_host over bytes / a uint8 numpy array in host memory holding a tar image: (entries, summary), entries a numpy
+    record array (tar_entry_dtype) of the first min(n_entries, max_entries) members (None = all of them: one call to count, one to
+    fill).  Nothing is copied or decoded: the records say where content and names lie in the image."""
+    import numpy as np
+
+    buf = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8)
+    raw = _TarPlanSummary()
+    p = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None  # noqa: E731
+    call = lib().chip_tar_plan_host
+    if max_entries is None:
+        rc = call(p(buf), buf.size, 0, None, C.byref(raw))
+        if rc != 0:
+            raise RuntimeError(f"chip_tar_plan_host failed: {rc}")
+        max_entries = int(raw.n_entries)
+    m = int(max_entries)
+    entries = np.zeros(m, tar_entry_dtype())
+    rc = call(p(buf), buf.size, m, p(entries), C.byref(raw))
+    if rc != 0:
+        raise RuntimeError(f"chip_tar_plan_host failed: {rc}")
+    return entries[:min(m, int(raw.n_entries))], TarPlanSummary(raw)
+
+
+def tar_plan(in_buf, length, stream=None, max_entries=None):
+    """chip_tar_plan over a uint8 device tensor holding a tar image of `length` bytes (4-byte aligned, padded to a multiple of 4):
+    (entries, summary), entries a uint8 device tensor of shape (k, 72) holding the chip_tar_entry records of the first
+    k = min(n_entries, max_entries) members (`.cpu().numpy().view(tar_entry_dtype())` reads them).  Synchronous on `stream`.
+    max_entries None: all of them (one call to count, one to fill)."""
+    import torch
+
+    dev = _check_tensors(((in_buf, torch.uint8),))
+    length = int(length)
+    if length < 0 or length > in_buf.numel():
+        raise ValueError(f"length {length} outside the buffer of {in_buf.numel()} bytes")
+    raw = _TarPlanSummary()
+    base, sp = (_dp(in_buf) if length else None), _stream_ptr(stream)
+    call = lib().chip_tar_plan
+    with torch.cuda.device(dev):
+        if max_entries is None:  # count, then fill
+            rc = call(base, length, 0, None, C.byref(raw), sp)
+            if rc != 0:
+                raise RuntimeError(f"chip_tar_plan failed: {rc}")
+            max_entries = int(raw.n_entries)
+        m = int(max_entries)
+        entries = torch.empty((m, C.sizeof(_TarEntry)), dtype=torch.uint8, device=dev)
+        rc = call(base, length, m, _dp(entries) if m else None, C.byref(raw), sp)
+    if rc != 0:
+        raise RuntimeError(f"chip_tar_plan failed: {rc}")
+    return entries[:min(m, int(raw.n_entries))], TarPlanSummary(raw)
+
+
+def tar_names(entries, source, stream=None):
+    """The full names of a plan's members, as a list of bytes (prefix + b"/" + name where the header has a prefix): `entries` the
+    records (the numpy record array of tar_plan_host, or the device tensor of tar_plan, which is copied to the host), `source` the
+    tar image as host bytes, or the uint8 device tensor it lies in: the prefix and name bytes of all members then come over in ONE
+    packed copy (chip_pack_units), not in a copy per member."""
+    import numpy as np
+
+    if not isinstance(entries, np.ndarray):
+        entries = entries.cpu().numpy().reshape(-1).view(tar_entry_dtype())
+    n = len(entries)
+    pre_off = entries["header_off"].astype(np.int64) + 345
+    pre_len, name_off, name_len = entries["prefix_len"].astype(np.int64), entries["name_off"].astype(np.int64), entries["name_len"].astype(np.int64)
+    if isinstance(source, (bytes, bytearray, memoryview, np.ndarray)):
+        image = bytes(source)
+        pick = lambda off, ln: image[off:off + ln]  # noqa: E731
+        pre = [pick(int(o), int(k)) for o, k in zip(pre_off, pre_len)]
+        name = [pick(int(o), int(k)) for o, k in zip(name_off, name_len)]
+    else:
+        import torch
+
+        # unit 2 i is member i's prefix, unit 2 i + 1 its name
+        off, ln = np.empty(2 * n, np.int64), np.empty(2 * n, np.int64)
+        off[0::2], off[1::2], ln[0::2], ln[1::2] = pre_off, name_off, pre_len, name_len
+        d_off = torch.from_numpy(off).to(source.device)
+        d_len = torch.from_numpy(ln.astype(np.int32)).to(source.device)
+        packed, _, total = pack_units(source, d_off, d_len, stream=stream)
+        flat = packed.cpu().numpy().tobytes()
+        at = np.concatenate(([0], np.cumsum(ln)))
+        assert int(at[-1]) == total == len(flat)
+        pre = [flat[at[2 * i]:at[2 * i + 1]] for i in range(n)]
+        name = [flat[at[2 * i + 1]:at[2 * i + 2]] for i in range(n)]
+    return [p + b"/" + m if p else m for p, m in zip(pre, name)]
+
+
+class TarArchive:
+    """A tar archive in device memory, planned: `content` the tar image (a uint8 device tensor), `entries` the members' records on
+    the host (tar_entry_dtype), `summary` the plan's, `names` the members' full names (bytes)."""
+
+    def __init__(self, content, entries, summary, names):
+        self.content, self.entries, self.summary, self.names = content, entries, summary, names
+        self._index = {name: i for i, name in enumerate(names)}  # a repeated name: its last member, as tarfile.extract resolves it
+
+    def __len__(self):
+        return len(self.entries)
+
+    def member(self, index_or_name):
+        """The content of one member, content[data_off : data_off + size], as a zero-copy uint8 view.  A name (str, matched as UTF-8,
+        or bytes) resolves to the LAST member of that name; KeyError for an unknown one, IndexError for an index out of range."""
+        if isinstance(index_or_name, (str, bytes, bytearray)):
+            i = self._index[index_or_name.encode("utf-8") if isinstance(index_or_name, str) else bytes(index_or_name)]
+        else:
+            i = int(index_or_name)
+            if not 0 <= i < len(self.entries):
+                raise IndexError(f"member {i} of {len(self.entries)}")
+        e = self.entries[i]
+        return self.content[int(e["data_off"]):int(e["data_off"]) + int(e["size"])]
+
+
+def tar_open(in_buf, length, fmt=None, stream=None):
+    """A .tar, .tar.gz or .tar.zst in device memory (in_buf a uint8 device tensor holding its `length` bytes, 4-byte aligned and
+    padded to a multiple of 4) as a TarArchive: decoded on the device where it is compressed, planned by chip_tar_plan, the names
+    fetched in one packed copy.  fmt None sniffs the first bytes (chip_detect): gzip and zlib go through inflate_parallel, zstd
+    through zstd_parallel, anything else is taken as a plain tar image (which then stays in in_buf: no copy).  A zlib verdict rests
+    on two bytes, which a plain tar's first member name can spell ("XG", "HK", "x^"): it is trusted only when bytes 257..261 are not
+    `ustar`.  fmt may also be given, and is then not questioned: Detection.Gzip / Zlib / Zstd / Unknown (= plain).
+    Limits are those of the one-shot decodes: a gzip / zlib stream of at most 2^29 - 64 bytes that decodes to at most 2^32 - 16; a
+    zstd frame of at most 2^32 - 1 bytes, below 2^31 decoded bytes on the parallel path and within a unit (2^28 input bytes) on the
+    serial one.  A larger archive belongs to the slab loops (inflate_parallel_stream, zstd_parallel_stream).
+    Raises ValueError when the decode does not finish (the message carries its status and in_used) or when the plan's status is
+    not Ok (the message carries the status, stop_off and bad_off).  Waits for the result."""
+    length = int(length)
+    if fmt is None:
+        head = in_buf[:min(length, 262)].cpu().numpy().tobytes()
+        fmt = Detection.detect(head[:4])
+        if fmt == Detection.Zlib and head[257:262] == b"ustar":
+            fmt = Detection.Unknown  # a member name that begins like a zlib header ("XGBoost-1.0/": 58 47), not a zlib stream
+    content, n = in_buf, length
+    if fmt in (Detection.Gzip, Detection.Zlib):
+        content, s = inflate_parallel(ZlibMode.Gzip if fmt == Detection.Gzip else ZlibMode.Zlib, in_buf, length, stream=stream)
+        if s.status != int(DecodeStatus.Finished):
+            raise ValueError(f"tar_open: the {Detection(fmt).name} stream did not finish: status {s.status} at input byte {s.in_used}")
+        n = s.out_len
+    elif fmt == Detection.Zstd:
+        content, s = zstd_parallel(in_buf, length, stream=stream)
+        if s.status != int(DecodeStatus.Finished):
+            raise ValueError(f"tar_open: the zstd frame did not finish: status {s.status} at input byte {s.in_used}")
+        n = s.out_len
+    entries, summ = tar_plan(content, n, stream=stream)
+    if summ.status != TarStatus.Ok:
+        raise ValueError(f"tar_open: not a tar image this library reads: status {summ.status.name} at stop_off {summ.stop_off} "
+                         f"(bad_off {summ.bad_off}); {summ!r}")
+    host = entries.cpu().numpy().reshape(-1).view(tar_entry_dtype())
+    return TarArchive(content[:n], host, summ, tar_names(host, content, stream=stream))

@@ -1002,6 +1002,84 @@ int chip_zip_write(int level, uint32_t flags, uint64_t n, const chip_zip_source 
                    chip_zip_write_summary *summary, void *stream);
 uint64_t chip_zip_write_bound(uint64_t n, uint64_t names_total, uint64_t content_total);
 
+/* ---- tar archives: the member plan (additive API) --------------------------- */
+
+/*
+ * A tar image (what chip_inflate_parallel or chip_zstd_parallel leaves of a .tar.gz / .tar.zst, or a plain .tar) has no directory:
+ * every 512-byte header says where the next one is, and a member's content may hold valid headers of its own (a tar in a tar).
+ * chip_tar_plan[_host] turns the image into an array of chip_tar_entry records, one per member, in file order.  Nothing is copied:
+ * member i's content is in[data_off .. data_off + size), its name in[name_off .. name_off + name_len), behind the prefix
+ * in[header_off + 345 .. + prefix_len) and a '/' when prefix_len > 0.  Formats: POSIX ustar, GNU (L / K long names, base-256
+ * numbers) and pax (x headers: path, linkpath, size).  Not read: v7 archives without the `ustar` magic, old-GNU and pax sparse
+ * members, multi-volume archives.
+ *
+ * The plan of `len` bytes (any value, not only a multiple of 512) is DEFINED by this walk; all offsets are into the image.
+ *   A number field (size, chksum, mode, mtime).  First byte 0x80: the remaining bytes are a big-endian base-256 value, invalid when
+ *     it is >= 2^63.  First byte 0xFF: invalid.  Else: leading spaces are skipped, octal digits read, and the byte behind the digits,
+ *     if the field has one, must be NUL or space (else invalid); no digits is 0.
+ *   is_header(p): p % 512 == 0 and p + 512 <= len; bytes 257..261 are `ustar` (the POSIX magic "ustar\0" and the GNU magic "ustar "
+ *     alike); size and chksum are valid; chksum equals the sum of the 512 bytes with bytes 148..155 taken as spaces, the bytes
+ *     summed unsigned or signed (both accepted, as Python's tarfile does).
+ *   The walk starts at e = 0 and repeats: e == len: stop, CHIP_TAR_OK.  len - e < 512: stop, CHIP_TAR_TRUNCATED.  The 512 bytes at e
+ *     all zero: stop, CHIP_TAR_OK, zero_blocks = 2 if the next block lies inside len and is all zero too, else 1; nothing behind
+ *     them is looked at.  is_header(e) false: stop, CHIP_TAR_BAD_HEADER.  Else the group at e is read and e becomes its end.
+ *   A group is a run of extension headers and the member header they modify.  From q = e, by the typeflag (byte 156) of the header
+ *   at q, s its size field:
+ *     L, K, x  More than CHIP_TAR_EXT_MAX extension headers in the group or s > CHIP_TAR_EXT_BYTES: CHIP_TAR_UNSUPPORTED, bad_off = q.
+ *              q2 = q + 512 + roundup512(s); q2 + 512 > len: CHIP_TAR_TRUNCATED, bad_off = q; is_header(q2) false:
+ *              CHIP_TAR_BAD_HEADER, bad_off = q2.  L sets the name to the data in[q + 512 .. + s) up to its first NUL (or all of it),
+ *              K the link name likewise.  x holds records "<decimal length> <key>=<value>\n": the length has 1 to 10 digits and a
+ *              space behind them, counts the whole record, must end on the record's '\n' inside the data, and the record must hold
+ *              a '='; the records fill the s bytes.  Key `path` sets the name, `linkpath` the link name, `size` (1 to 19 decimal
+ *              digits) the size; a key that begins with `GNU.sparse.`: CHIP_TAR_UNSUPPORTED, bad_off = q; a malformed record or size
+ *              value: CHIP_TAR_BAD_HEADER, bad_off = q (the first record out of order decides).  Other keys (mtime among them) are
+ *              not applied.  When two extension headers set the same thing the later one wins.  Continue at q = q2.
+ *     g        Legal only with q == e (else CHIP_TAR_BAD_HEADER, bad_off = q): a group of its own, counted in n_global, that ends
+ *              at q + 512 + roundup512(s) (above len: CHIP_TAR_TRUNCATED, bad_off = q).  Its records are NOT parsed and NOT
+ *              applied to the members behind it.
+ *     S, M     CHIP_TAR_UNSUPPORTED, bad_off = q.
+ *     else     the member.  size = the pax override, else the field; 0 for the types '1'..'6', which carry no data (tarfile's
+ *              rule).  data_off = q + 512, the group ends at data_off + roundup512(size) (above len: CHIP_TAR_TRUNCATED,
+ *              bad_off = q).  Without a name override the name is bytes 0..99 up to the first NUL and prefix_len the length of bytes
+ *              345..499 up to the first NUL (the full name is prefix + "/" + name, as tarfile builds it); with one prefix_len = 0.
+ *              Without a link override the link name is bytes 157..256 up to the first NUL.  flags says where name, link name and
+ *              size came from (CHIP_TARF_*: for each the extension header that won; SIZE_BASE256: the field in its base-256 form).
+ * A walk that stops keeps the members in front of the stop.  stop_off = the start of the group, or the position, where the walk
+ * stopped; bad_off = the offending header (= stop_off unless stated above).  n_entries, n_global and total_size (the sum of the
+ * members' sizes) are those of the whole walk whatever max_entries is.
+ *
+ * chip_tar_plan: conventions of chip_zip_plan.  in_base and `entries` are DEVICE pointers, summary is a HOST pointer; in_base
+ * 4-byte aligned and its allocation padded to a multiple of 4 bytes; len <= 2^40 (both forms).  max_entries = 0 with entries NULL
+ * only counts.  Nothing is written behind min(n_entries, max_entries) records.  CHIP_E_INVALID (a NULL summary, a NULL buffer with
+ * len > 0, a NULL array with max_entries > 0, a misaligned in_base, len > 2^40) is answered before the device is looked for.
+ * len == 0: CHIP_OK with an all-zero summary.  More than 2^31 - 1 candidates: CHIP_E_NOMEM.  Input that changes during the call:
+ * CHIP_E_LAUNCH, and nothing is written out of range.  SYNCHRONOUS on `stream` (waits twice: the candidate count, the summary).
+ * Scratch in a launch slot of its own per (device, stream), released by chip_trim(): 16 bytes per 128 KiB of input, and per
+ * candidate -- a 512-aligned position whose bytes 257..261 are `ustar`, headers inside member data included -- 128 + 4 * levels
+ * bytes (levels = ceil(log2(candidates + 1))): 72 of them the candidate's record.
+ */
+enum { CHIP_TAR_OK = 0, CHIP_TAR_TRUNCATED = 1, CHIP_TAR_BAD_HEADER = 2, CHIP_TAR_UNSUPPORTED = 3 };
+#define CHIP_TAR_EXT_MAX 16u
+#define CHIP_TAR_EXT_BYTES (1u << 20)
+enum { CHIP_TARF_NAME_GNU = 1, CHIP_TARF_NAME_PAX = 2, CHIP_TARF_LINK_GNU = 4, CHIP_TARF_LINK_PAX = 8,
+       CHIP_TARF_SIZE_PAX = 16, CHIP_TARF_SIZE_BASE256 = 32 };
+typedef struct {            /* 72 bytes, no implicit padding */
+    uint64_t group_off;     /* first header of the group (== header_off without extension headers) */
+    uint64_t header_off, data_off, size, name_off, link_off;
+    int64_t  mtime;         /* header field; an invalid field is 0 (pax mtime is not applied) */
+    uint32_t name_len, link_len, mode;   /* mode: header field, invalid is 0 */
+    uint16_t prefix_len;    /* prefix bytes at header_off + 345 */
+    uint8_t  typeflag, flags;            /* CHIP_TARF_* */
+} chip_tar_entry;
+typedef struct {
+    uint64_t n_entries, n_global, total_size, stop_off, bad_off;
+    int32_t status;         /* CHIP_TAR_* */
+    int32_t zero_blocks;
+} chip_tar_plan_summary;
+int chip_tar_plan_host(const uint8_t *in, uint64_t len, uint64_t max_entries, chip_tar_entry *entries, chip_tar_plan_summary *summary);
+int chip_tar_plan(const void *in_base, uint64_t len, uint64_t max_entries, chip_tar_entry *entries, chip_tar_plan_summary *summary,
+                  void *stream);
+
 /* ---- encoder: mirrors encoder::Interface, src/encoder/mod.rs:52-57 ---------------------------- */
 
 typedef struct chip_encoder chip_encoder;

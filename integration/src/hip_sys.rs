@@ -312,6 +312,55 @@ pub struct chip_zip_write_summary {
     pub zip64: i32,
 }
 
+///`chip_tar_plan_summary::status`
+pub const CHIP_TAR_OK: i32 = 0;
+pub const CHIP_TAR_TRUNCATED: i32 = 1;
+pub const CHIP_TAR_BAD_HEADER: i32 = 2;
+pub const CHIP_TAR_UNSUPPORTED: i32 = 3;
+///extension headers a group may hold, and the bytes of data one of them may have
+pub const CHIP_TAR_EXT_MAX: u32 = 16;
+pub const CHIP_TAR_EXT_BYTES: u32 = 1 << 20;
+///`chip_tar_entry::flags`: where name, link name and size came from
+pub const CHIP_TARF_NAME_GNU: u8 = 1;
+pub const CHIP_TARF_NAME_PAX: u8 = 2;
+pub const CHIP_TARF_LINK_GNU: u8 = 4;
+pub const CHIP_TARF_LINK_PAX: u8 = 8;
+pub const CHIP_TARF_SIZE_PAX: u8 = 16;
+pub const CHIP_TARF_SIZE_BASE256: u8 = 32;
+
+///one member of a tar image as `chip_tar_plan` lists it (72 bytes, no implicit padding): offsets into the image
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct chip_tar_entry {
+    pub group_off: u64,
+    pub header_off: u64,
+    pub data_off: u64,
+    pub size: u64,
+    pub name_off: u64,
+    pub link_off: u64,
+    pub mtime: i64,
+    pub name_len: u32,
+    pub link_len: u32,
+    pub mode: u32,
+    pub prefix_len: u16,
+    pub typeflag: u8,
+    pub flags: u8,
+}
+
+///what the tar walk found: members, global headers and content bytes of the whole walk, where it stopped, the offending header,
+///why, and the all-zero blocks at the stop
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct chip_tar_plan_summary {
+    pub n_entries: u64,
+    pub n_global: u64,
+    pub total_size: u64,
+    pub stop_off: u64,
+    pub bad_off: u64,
+    pub status: i32,
+    pub zero_blocks: i32,
+}
+
 ///`chip_encode_file` flag: the seek table of zstd's seekable format follows the last frame (`CHIP_FMT_ZSTD` only)
 pub const CHIP_W_SEEK_TABLE: u32 = 1;
 ///`chip_file_summary::status`
@@ -618,6 +667,12 @@ extern "C" {
                           summary: *mut chip_zip_write_summary, stream: *mut c_void) -> c_int;
     ///the room that is always enough for `chip_zip_write`; 0 when it overflows 64 bits
     pub fn chip_zip_write_bound(n: u64, names_total: u64, content_total: u64) -> u64;
+    ///the members of a tar image in host memory as entry records: the walk that defines the plan (no reference counterpart)
+    pub fn chip_tar_plan_host(input: *const u8, len: u64, max_entries: u64, entries: *mut chip_tar_entry, summary: *mut chip_tar_plan_summary) -> c_int;
+    ///the same over a device-resident image: one lane per 512-byte block finds the headers, one per header reads its group, the chain
+    ///from 0 is marked by pointer doubling
+    pub fn chip_tar_plan(in_base: *const c_void, len: u64, max_entries: u64, entries: *mut chip_tar_entry, summary: *mut chip_tar_plan_summary,
+                         stream: *mut c_void) -> c_int;
     ///from a size pass to a decode on the device: offsets (exclusive sum) and clipped capacities of `out_size`; host `total` / `n_over`
     pub fn chip_layout_units(n: usize, out_size: *const u64, out_off: *mut u64, out_cap: *mut u32, total: *mut u64, n_over: *mut u64,
                              stream: *mut c_void) -> c_int;
