@@ -129,6 +129,17 @@ class _TarPlanSummary(C.Structure):
                 ("status", C.c_int32), ("zero_blocks", C.c_int32)]
 
 
+class _TarSource(C.Structure):
+    _fields_ = [("data_off", C.c_uint64), ("size", C.c_uint64), ("name_off", C.c_uint64), ("link_off", C.c_uint64), ("mtime", C.c_int64),
+                ("name_len", C.c_uint32), ("link_len", C.c_uint32), ("mode", C.c_uint32), ("uid", C.c_uint32), ("gid", C.c_uint32),
+                ("typeflag", C.c_uint8), ("pad", C.c_uint8 * 3)]
+
+
+class _TarWriteSummary(C.Structure):
+    _fields_ = [("n_entries", C.c_uint64), ("n_ext", C.c_uint64), ("out_len", C.c_uint64), ("end_off", C.c_uint64), ("total_size", C.c_uint64),
+                ("bad_index", C.c_uint64), ("status", C.c_int32), ("pad", C.c_int32)]
+
+
 class _FileSummary(C.Structure):
     _fields_ = [("n_units", C.c_uint64), ("out_len", C.c_uint64), ("table_off", C.c_uint64), ("status", C.c_int32), ("pad", C.c_uint32)]
 
@@ -296,6 +307,13 @@ def lib():
     L.chip_tar_plan_host.argtypes = [vp, u64, u64, vp, C.POINTER(_TarPlanSummary)]
     L.chip_tar_plan.restype = C.c_int
     L.chip_tar_plan.argtypes = [vp, u64, u64, vp, C.POINTER(_TarPlanSummary), vp]
+    tws = C.POINTER(_TarWriteSummary)
+    L.chip_tar_write_host.restype = C.c_int
+    L.chip_tar_write_host.argtypes = [u64, vp, vp, u64, vp, u64, C.c_uint32, C.c_uint32, vp, u64, vp, tws]
+    L.chip_tar_write.restype = C.c_int
+    L.chip_tar_write.argtypes = [u64, vp, vp, u64, vp, u64, C.c_uint32, C.c_uint32, vp, u64, vp, tws, vp]
+    L.chip_tar_write_bound.restype = C.c_uint64
+    L.chip_tar_write_bound.argtypes = [u64, u64, u64, C.c_uint32]
     L.chip_layout_units.restype = C.c_int
     L.chip_layout_units.argtypes = [sz, vp, vp, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), vp]
     L.chip_pack_units.restype = C.c_int
@@ -3191,3 +3209,161 @@ def tar_open(in_buf, length, fmt=None, stream=None):
                          f"(bad_off {summ.bad_off}); {summ!r}")
     host = entries.cpu().numpy().reshape(-1).view(tar_entry_dtype())
     return TarArchive(content[:n], host, summ, tar_names(host, content, stream=stream))
+
+
+# ---- tar archives: writing (include/compu_hip.h, "tar archives: writing") ----------------------------
+
+
+class TarWriteStatus(enum.IntEnum):
+    Ok = 0
+    NeedOutput = 1
+    BadSource = 2
+
+
+TW_GNU, TW_FORCE_EXT = 1, 2  # CHIP_TW_GNU (L / K headers and base-256 sizes instead of pax records), CHIP_TW_FORCE_EXT (every size goes the long way)
+TARW_NAME_MAX = 65535        # CHIP_TARW_NAME_MAX
+
+
+def tar_source_dtype():
+    """chip_tar_source as a numpy record: data_off, size, name_off, link_off, mtime, name_len, link_len, mode, uid, gid, typeflag
+    (the character's code, ord("0") for a file), pad (three bytes, 0)."""
+    import numpy as np
+
+    dt = np.dtype([("data_off", "<u8"), ("size", "<u8"), ("name_off", "<u8"), ("link_off", "<u8"), ("mtime", "<i8"), ("name_len", "<u4"),
+                   ("link_len", "<u4"), ("mode", "<u4"), ("uid", "<u4"), ("gid", "<u4"), ("typeflag", "u1"), ("pad", "u1", (3,))])
+    assert dt.itemsize == C.sizeof(_TarSource) == 64
+    return dt
+
+
+class TarWriteSummary:
+    """chip_tar_write_summary: n_entries, n_ext (extension headers written), out_len (the whole image; the exact room to come back
+    with on NeedOutput), end_off (where the two zero blocks start), total_size (the sum of the sizes), bad_index (the lowest bad
+    record on BadSource), status."""
+
+    __slots__ = ("n_entries", "n_ext", "out_len", "end_off", "total_size", "bad_index", "status")
+
+    def __init__(self, raw):
+        self.n_entries, self.n_ext, self.out_len, self.end_off = int(raw.n_entries), int(raw.n_ext), int(raw.out_len), int(raw.end_off)
+        self.total_size, self.bad_index, self.status = int(raw.total_size), int(raw.bad_index), TarWriteStatus(raw.status)
+
+    def as_tuple(self):
+        return (self.n_entries, self.n_ext, self.out_len, self.end_off, self.total_size, self.bad_index, int(self.status))
+
+    def __repr__(self):
+        return (f"TarWriteSummary(n_entries={self.n_entries}, n_ext={self.n_ext}, out_len={self.out_len}, end_off={self.end_off}, "
+                f"total_size={self.total_size}, bad_index={self.bad_index}, status={self.status.name})")
+
+
+def tar_write_bound(n, names_total, content_total, record_bytes=0):
+    """chip_tar_write_bound: the room that is always enough for n members with names_total bytes of names and link names and
+    content_total bytes of content; 0 when it overflows 64 bits or record_bytes is refused."""
+    return int(lib().chip_tar_write_bound(int(n), int(names_total), int(content_total), int(record_bytes)))
+
+
+def tar_write_host(sources, names, content, flags=0, record_bytes=0, out_cap=None, content_len=None):
+    """chip_tar_write_host: `sources` a numpy record array (tar_source_dtype), names / content bytes or uint8 arrays.  out_cap None:
+    one call for the size, one to write.  content_len overrides len(content) for a call that only sizes (out_cap smaller than the
+    image: the content is never read).  Returns (the image as bytes -- b"" unless status is Ok --, entries as a numpy record array
+    of tar_entry_dtype, TarWriteSummary)."""
+    import numpy as np
+
+    u8 = lambda b: np.ascontiguousarray(b, dtype=np.uint8) if isinstance(b, np.ndarray) else np.frombuffer(bytes(b), np.uint8)  # noqa: E731
+    src = np.ascontiguousarray(sources, dtype=tar_source_dtype())
+    n = src.size
+    names, content = u8(names), u8(content)
+    p = lambda a: None if a.size == 0 else a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    clen = content.size if content_len is None else int(content_len)
+    raw = _TarWriteSummary()
+    entries = np.zeros(n, tar_entry_dtype())
+
+    def call(out, cap):
+        rc = lib().chip_tar_write_host(n, p(src), p(names), names.size, content.ctypes.data_as(C.c_void_p) if clen else None, clen, flags, record_bytes,
+                                       p(out), cap, p(entries), C.byref(raw))
+        if rc != 0:
+            raise RuntimeError(f"chip_tar_write_host failed: {rc}")
+
+    out = np.zeros(0 if out_cap is None else int(out_cap), np.uint8)
+    call(out, out.size)
+    if out_cap is None and raw.status == TarWriteStatus.NeedOutput:
+        out = np.zeros(int(raw.out_len), np.uint8)
+        call(out, out.size)
+    summ = TarWriteSummary(raw)
+    return (out[:summ.out_len].tobytes() if summ.status == TarWriteStatus.Ok else b""), entries, summ
+
+
+def tar_write(sources, names, content, flags=0, record_bytes=0, out=None, stream=None):
+    """chip_tar_write on device tensors: sources uint8 of shape (n, 64) holding chip_tar_source records
+    (`torch.from_numpy(records.view(np.uint8).reshape(-1, 64)).cuda()`), names / content uint8.  out None: the exact room is allocated
+    after a sizing call; else a uint8 tensor, and too little room is status NeedOutput with nothing written.  Returns (the image: a
+    view of `out`, empty unless status is Ok; entries: uint8 of shape (n, 72), what tar_plan would answer; TarWriteSummary).
+    Synchronous on `stream`."""
+    import torch
+
+    pairs = [(sources, torch.uint8), (names, torch.uint8), (content, torch.uint8)] + ([(out, torch.uint8)] if out is not None else [])
+    dev = _check_tensors(pairs)
+    n = sources.numel() // C.sizeof(_TarSource)
+    if sources.numel() != n * C.sizeof(_TarSource):
+        raise ValueError("sources holds 64-byte records")
+    q = lambda t: _dp(t) if t.numel() else None  # noqa: E731
+    raw = _TarWriteSummary()
+    entries = torch.empty((n, C.sizeof(_TarEntry)), dtype=torch.uint8, device=dev)
+
+    def once(o):
+        with torch.cuda.device(dev):
+            rc = lib().chip_tar_write(n, q(sources), q(names), names.numel(), q(content), content.numel(), flags, record_bytes, q(o), o.numel(),
+                                      _dp(entries) if n else None, C.byref(raw), _stream_ptr(stream))
+        if rc != 0:
+            raise RuntimeError(f"chip_tar_write failed: {rc}")
+
+    if out is None:
+        out = torch.empty(0, dtype=torch.uint8, device=dev)
+        once(out)
+        if raw.status == TarWriteStatus.NeedOutput:
+            out = torch.empty(int(raw.out_len), dtype=torch.uint8, device=dev)
+            once(out)
+    else:
+        once(out)
+    summ = TarWriteSummary(raw)
+    return (out[:summ.out_len] if summ.status == TarWriteStatus.Ok else out[:0]), entries, summ
+
+
+def tar_write_items(items, flags=0, stream=None, device=None):
+    """A tar image of (name, content[, mode, mtime]) items on the device, the counterpart of zip_write_items.  name: str (encoded as
+    UTF-8) or bytes, a name that ends in "/" is a directory (typeflag 5, its content must be empty); content: bytes-like, or a uint8
+    device tensor; mode defaults to 0644 (0755 for a directory), mtime to 0.  The contents land at 16-byte aligned offsets of one
+    device buffer.  Returns (the image as a uint8 device tensor, entries, TarWriteSummary) as tar_write does; tar_open reads it back."""
+    import numpy as np
+    import torch
+
+    items = [tuple(it) for it in items]
+    tensors = [it[1] for it in items if isinstance(it[1], torch.Tensor)]
+    dev = tensors[0].device if tensors else torch.device("cuda" if device is None else device)
+    src = np.zeros(len(items), tar_source_dtype())
+    names, at = bytearray(), 0
+    for i, it in enumerate(items):
+        name, c = it[0], it[1]
+        if isinstance(name, str):
+            name = name.encode("utf-8")
+        if not 1 <= len(name) <= TARW_NAME_MAX:
+            raise ValueError("a name has 1 to 65535 bytes")
+        size = c.numel() if isinstance(c, torch.Tensor) else len(memoryview(c).cast("B"))
+        is_dir = name.endswith(b"/")
+        if is_dir and size:
+            raise ValueError("a directory has no content")
+        mode = int(it[2]) if len(it) > 2 and it[2] is not None else (0o755 if is_dir else 0o644)
+        mtime = int(it[3]) if len(it) > 3 and it[3] is not None else 0
+        src[i] = (at, size, len(names), 0, mtime, len(name), 0, mode, 0, 0, ord("5") if is_dir else ord("0"), (0, 0, 0))
+        names += name
+        at += (size + 15) // 16 * 16
+    content = torch.zeros(at, dtype=torch.uint8, device=dev)
+    for row, it in zip(src, items):
+        o, size, c = int(row["data_off"]), int(row["size"]), it[1]
+        if size:
+            if isinstance(c, torch.Tensor):
+                _check_tensors(((content, torch.uint8), (c, torch.uint8)))
+                content[o:o + size] = c.reshape(-1)
+            else:
+                content[o:o + size] = torch.from_numpy(np.frombuffer(memoryview(c).cast("B"), np.uint8).copy()).to(dev)
+    d_src = torch.from_numpy(src.view(np.uint8).reshape(-1, 64).copy()).to(dev)
+    d_names = torch.from_numpy(np.frombuffer(bytes(names), np.uint8).copy()).to(dev)
+    return tar_write(d_src, d_names, content, flags=flags, stream=stream)

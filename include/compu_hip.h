@@ -1080,6 +1080,85 @@ int chip_tar_plan_host(const uint8_t *in, uint64_t len, uint64_t max_entries, ch
 int chip_tar_plan(const void *in_base, uint64_t len, uint64_t max_entries, chip_tar_entry *entries, chip_tar_plan_summary *summary,
                   void *stream);
 
+/* ---- tar archives: writing (additive API) ----------------------------------- */
+
+/*
+ * The image chip_tar_plan, Python's tarfile and GNU tar read back, made on the device: the counterpart of chip_zip_write.  Member i
+ * is a chip_tar_source: its content is content[data_off .. + size), its name names[name_off .. + name_len), its link name
+ * names[link_off .. + link_len) (may be empty).  The image is not compressed; chip_encode_file makes the .tar.zst or .tar.gz.
+ *   chip_tar_write_host   the whole image on the host; the definition.
+ *   chip_tar_write        the same with every array and buffer in DEVICE memory, summary on the HOST, and a stream.
+ *   chip_tar_write_bound  up(content_total + 2 * names_total + 3072 * n + 1024, record), or 0 when that overflows 64 bits or
+ *                         record_bytes is refused: always enough.  A group is 512 + up512(size) and, per name above 100 bytes, at
+ *                         most 512 + up512(len + 1) <= 822 + 2 * len, so 2667 bytes above size + 2 * names bound it.
+ * The image is DEFINED by these rules.  GNU = flags & CHIP_TW_GNU, else the image is pax.
+ *   Accepted sources; anything else is CHIP_TARW_BAD_SOURCE with bad_index the LOWEST offender, nothing but the summary is written
+ *     and its other fields are 0 except n_entries: typeflag '0'..'7'; size == 0 for '1'..'6'; 1 <= name_len <= CHIP_TARW_NAME_MAX,
+ *     link_len <= CHIP_TARW_NAME_MAX; no NUL byte in the name or the link name; name_off + name_len and link_off + link_len inside
+ *     names_len, data_off + size inside content_len, the sums formed without wrapping; mode <= 07777777; uid, gid < 8^7;
+ *     0 <= mtime < 8^11; pad == 0.
+ *   A header block, 512 bytes, zero where nothing is said: 0 name (up to 100 bytes) | 100, 108, 116 mode, uid, gid as %07o NUL |
+ *     124 size as %011o NUL, or base-256: 80 and 11 big-endian bytes | 136 mtime as %011o NUL | 148 chksum as %06o NUL space: the
+ *     unsigned sum of the block with this field taken as spaces | 156 typeflag | 157 link name (up to 100 bytes) | 257 "ustar" NUL
+ *     "00", GNU: "ustar" two spaces NUL | 265, 297 uname, gname: empty | 329, 337 devmajor, devminor: "0000000" NUL | 345 prefix (up
+ *     to 155 bytes).  A field that is exactly full has no NUL behind it.
+ *   The group of member i; the groups follow each other from offset 0 with no gaps.  BIG = size >= 8^11 or CHIP_TW_FORCE_EXT.
+ *     pax   A name of at most 100 bytes goes into the name field.  A longer one is split at the LARGEST p with name[p] == '/',
+ *           1 <= p <= 155 and 1 <= name_len - p - 1 <= 100: prefix = name[0 .. p), name field = name[p + 1 ..).  Without such a p a
+ *           `path` record carries the name and the field holds its first 100 bytes.  A link name above 100 bytes gets a `linkpath`
+ *           record and the field its first 100 bytes.  BIG gets a `size` record in decimal; the size field is the size when it is
+ *           below 8^11, else 0.  With at least one record ONE x header precedes the member header: name "././@PaxHeader", mode
+ *           0644, uid and gid 0, the member's mtime, size = the records' length; the records follow in the order path, linkpath,
+ *           size, zero-padded to 512.  A record is "<L> <key>=<value>\n", L the smallest decimal number that counts the whole
+ *           record, its own digits included.
+ *     GNU   No prefix split.  A link name above 100 bytes gets a K header, a name above 100 bytes an L header, K first: name
+ *           "././@LongLink", mode, uid, gid and mtime 0, size = len + 1; the data is the bytes and one NUL, zero-padded to 512.
+ *           The member header holds the first 100 bytes of each.  BIG writes the size field in base-256.
+ *     Then the member header and the content, zero-padded to 512.
+ *   The end: two zero blocks at end_off, then zeros up to the next multiple of record_bytes (a multiple of 512, at most 2^20;
+ *     0 means 10 240, the default of tar and tarfile).
+ *   entries[i] (may be NULL) is the chip_tar_entry chip_tar_plan produces for member i of the written image: the offsets,
+ *     prefix_len, and the flags NAME_PAX / NAME_GNU / LINK_* / SIZE_PAX / SIZE_BASE256.
+ * summary: n_entries = n, n_ext the extension headers written, out_len the whole image, end_off, total_size the sum of the sizes.
+ *   CHIP_TARW_NEED_OUTPUT  out_len > out_cap: out_len is exact, entries and the summary are answered, no byte of `out` is written and
+ *                          no byte of content is read.  Names are read: the layout depends on them.
+ *   CHIP_TARW_OK           every byte of out[0 .. out_len) is written exactly once, by a store that covers only bytes of its own
+ *                          block or range (chip_pack_units' discipline): the padding, the end blocks and the record padding are
+ *                          bytes of the image and are written as zeros.  Nothing outside is written; `out` may have any alignment.
+ * `out` must not overlap the inputs.
+ * CHIP_E_INVALID, before a device is looked for: summary NULL; src NULL with n > 0, names NULL with names_len > 0, content NULL
+ * with content_len > 0, out NULL with out_cap > 0; unknown flag bits; record_bytes no multiple of 512 or above 2^20; n > 2^31 - 1;
+ * and arguments that allow an image of 2^63 bytes or more: content_len >= 2^62, or n * (content_len + 134 144) > 2^63 - 2^20 - 1024.
+ * n == 0 is answered by the host: the end blocks alone, zeroed with one memset on `stream` that is waited for.
+ * chip_tar_write is SYNCHRONOUS on `stream` and waits twice: for the groups' total against the room, and at the end.  Scratch per
+ * (device, stream), a launch slot of its own released by chip_trim(): 284 bytes per entry (64 the kept record, 24 the scan, 196 the
+ * seven pieces of the copy) and 24 bytes per 1024 entries, with a quarter of headroom.  CHIP_E_NOMEM: the scratch could not be
+ * allocated.  CHIP_E_LAUNCH: a launch failed, or the inputs changed during the call; nothing is ever written out of range.
+ * Not written: uname and gname, device numbers, pax mtime / uid records, sparse members, global headers.
+ * No reference counterpart: compu has no container formats.
+ */
+enum { CHIP_TW_GNU = 1, CHIP_TW_FORCE_EXT = 2 };                       /* call flags */
+enum { CHIP_TARW_OK = 0, CHIP_TARW_NEED_OUTPUT = 1, CHIP_TARW_BAD_SOURCE = 2 };
+#define CHIP_TARW_NAME_MAX 65535u
+typedef struct {            /* 64 bytes, no implicit padding */
+    uint64_t data_off, size;        /* content[data_off .. + size) */
+    uint64_t name_off, link_off;    /* names[name_off .. + name_len), names[link_off .. + link_len) */
+    int64_t  mtime;
+    uint32_t name_len, link_len, mode, uid, gid;
+    uint8_t  typeflag, pad[3];      /* pad must be 0 */
+} chip_tar_source;
+typedef struct {            /* 56 bytes */
+    uint64_t n_entries, n_ext, out_len, end_off, total_size, bad_index;
+    int32_t status, pad;
+} chip_tar_write_summary;
+int chip_tar_write_host(uint64_t n, const chip_tar_source *src, const uint8_t *names, uint64_t names_len, const uint8_t *content,
+                        uint64_t content_len, uint32_t flags, uint32_t record_bytes, uint8_t *out, uint64_t out_cap,
+                        chip_tar_entry *entries, chip_tar_write_summary *summary);
+int chip_tar_write(uint64_t n, const chip_tar_source *src, const void *names, uint64_t names_len, const void *content,
+                   uint64_t content_len, uint32_t flags, uint32_t record_bytes, void *out, uint64_t out_cap,
+                   chip_tar_entry *entries, chip_tar_write_summary *summary, void *stream);
+uint64_t chip_tar_write_bound(uint64_t n, uint64_t names_total, uint64_t content_total, uint32_t record_bytes);
+
 /* ---- encoder: mirrors encoder::Interface, src/encoder/mod.rs:52-57 ---------------------------- */
 
 typedef struct chip_encoder chip_encoder;

@@ -361,6 +361,50 @@ pub struct chip_tar_plan_summary {
     pub zero_blocks: i32,
 }
 
+///flags of the tar writer's calls: GNU long-name headers and base-256 sizes instead of pax records; every size the long way
+pub const CHIP_TW_GNU: u32 = 1;
+pub const CHIP_TW_FORCE_EXT: u32 = 2;
+///`chip_tar_write_summary::status`
+pub const CHIP_TARW_OK: i32 = 0;
+pub const CHIP_TARW_NEED_OUTPUT: i32 = 1;
+pub const CHIP_TARW_BAD_SOURCE: i32 = 2;
+///the longest name or link name of a source
+pub const CHIP_TARW_NAME_MAX: u32 = 65535;
+
+///one member to be written into a tar image (64 bytes, no implicit padding): where its content, its name and its link name lie,
+///and the numbers of its header
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct chip_tar_source {
+    pub data_off: u64,
+    pub size: u64,
+    pub name_off: u64,
+    pub link_off: u64,
+    pub mtime: i64,
+    pub name_len: u32,
+    pub link_len: u32,
+    pub mode: u32,
+    pub uid: u32,
+    pub gid: u32,
+    pub typeflag: u8,
+    pub pad: [u8; 3],
+}
+
+///what the tar writer made: members, extension headers, the image's length, where the end blocks start, the sum of the sizes,
+///the lowest bad record, why
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct chip_tar_write_summary {
+    pub n_entries: u64,
+    pub n_ext: u64,
+    pub out_len: u64,
+    pub end_off: u64,
+    pub total_size: u64,
+    pub bad_index: u64,
+    pub status: i32,
+    pub pad: i32,
+}
+
 ///`chip_encode_file` flag: the seek table of zstd's seekable format follows the last frame (`CHIP_FMT_ZSTD` only)
 pub const CHIP_W_SEEK_TABLE: u32 = 1;
 ///`chip_file_summary::status`
@@ -673,6 +717,17 @@ extern "C" {
     ///from 0 is marked by pointer doubling
     pub fn chip_tar_plan(in_base: *const c_void, len: u64, max_entries: u64, entries: *mut chip_tar_entry, summary: *mut chip_tar_plan_summary,
                          stream: *mut c_void) -> c_int;
+    ///a tar image (pax or GNU) written on the host from contents, names and link names: the rules that define the writer
+    pub fn chip_tar_write_host(n: u64, src: *const chip_tar_source, names: *const u8, names_len: u64, content: *const u8, content_len: u64,
+                               flags: u32, record_bytes: u32, out: *mut u8, out_cap: u64, entries: *mut chip_tar_entry,
+                               summary: *mut chip_tar_write_summary) -> c_int;
+    ///the same with every array and buffer in device memory (host `summary`): check, scan, header blocks by a wave, a copy that
+    ///zero-fills; synchronous on `stream`
+    pub fn chip_tar_write(n: u64, src: *const chip_tar_source, names: *const c_void, names_len: u64, content: *const c_void, content_len: u64,
+                          flags: u32, record_bytes: u32, out: *mut c_void, out_cap: u64, entries: *mut chip_tar_entry,
+                          summary: *mut chip_tar_write_summary, stream: *mut c_void) -> c_int;
+    ///the room that is always enough for `chip_tar_write`; 0 when it overflows 64 bits or `record_bytes` is refused
+    pub fn chip_tar_write_bound(n: u64, names_total: u64, content_total: u64, record_bytes: u32) -> u64;
     ///from a size pass to a decode on the device: offsets (exclusive sum) and clipped capacities of `out_size`; host `total` / `n_over`
     pub fn chip_layout_units(n: usize, out_size: *const u64, out_off: *mut u64, out_cap: *mut u32, total: *mut u64, n_over: *mut u64,
                              stream: *mut c_void) -> c_int;
