@@ -955,12 +955,11 @@ __device__ CHIP_PHASE_FN bool flush_tokens(WaveLds &L, const uint32_t *grow_, ui
     uint32_t nfirst = 0;       // first stream index of piece `before` (0xffffffff: there is none; piece 0 starts at 0)
     uint32_t dcur = 0;         // pdelta of piece before - 1
     uint32_t gnext = 0;        // stream index the next fetch() asks for
-    uint32_t slot_w = 0;       // ring slot the next fetch() fills
     const uint32_t tok_lds = rdfirst((uint32_t)(uintptr_t)(LDS_AS uint32_t *)C.tok);  // LDS byte address of the ring
     // The load goes straight into LDS (global_load_lds_dword: LDS address = M0 + 4 * lane): no register is held while it
     // is in flight, and the compiler does not wait for it -- issue() and the explicit vmcnt wait in front of a slot's
     // first read keep the count: a slot's load is complete once at most TOK_RING - 1 younger loads are outstanding.
-    auto fetch = [&]() {
+    auto fetch = [&](const uint32_t slot_w) {
         const uint32_t g = gnext;
         uint32_t d = dcur;
         while (nfirst - g < 64u) {  // (nfirst >= g; "none" is far above any g)
@@ -980,119 +979,165 @@ __device__ CHIP_PHASE_FN bool flush_tokens(WaveLds &L, const uint32_t *grow_, ui
                      : "=&s"(keep)
                      : "v"(src), "s"(dst)
                      : "memory");
-        slot_w = (slot_w + 1u) & (TOK_RING - 1u);
     };
     WSYNC();  // the piece descriptions are in LDS; whatever used the chunk state's place before is done
-    uint32_t c0 = 0;      // tokens executed so far
-    uint32_t slot_r = 0;  // ring slot of the group at c0
+    uint32_t c0 = 0;  // tokens executed so far
+    // Ring slot of the group at c0.  Whenever a group is taken whole, fetch() refills the slot just read with the group TOK_RING
+    // ahead, and a partly taken group starts the ring over: the slot that is read next is always the slot that is filled next,
+    // and one counter serves both.
+    uint32_t slot_r = 0;
 #pragma unroll
-    for (uint32_t k = 0; k < TOK_RING; k++) fetch();
-    // ---- chunk state (every piece of code below exists once: no closures, everything stays in registers)
-    bool fresh = true;  // a chunk starts with the next group
-    uint32_t mis = 0, run = 0, nq = 0, qh = 0, prod0 = 0, cstart = 0;
-    uint8_t *base = gout;
-    bool glob_ok = false, inflight = false;
-    Round R;
-    for (;;) {
-        if (fresh) {
-            STAT_ADD(13, 1);
-            mis = (uint32_t)((uintptr_t)(gout + opos) & 3u);
-            base = gout + opos - mis;  // byte x of the chunk lives at base[x]; base is dword aligned
-            glob_ok = cap - opos >= 16u;
-            run = mis;
-            prod0 = opos - mis;  // output bytes in front of offset 0
-            nq = qh = 0;
-            cstart = c0;
-            fresh = false;
-        }
-        static_assert(TOK_RING == 4, "the wait below counts three younger ring loads");
-        asm volatile("s_waitcnt vmcnt(3)" ::: "memory");  // the load into slot_r has landed
-        const uint32_t t = C.tok[64u * slot_r + lane];
+    for (uint32_t k = 0; k < TOK_RING; k++) fetch(k);
+    for (;;) {  // one trip per chunk
+        STAT_ADD(13, 1);
+        const uint32_t mis = (uint32_t)((uintptr_t)(gout + opos) & 3u);
+        uint8_t *const base = gout + opos - mis;  // byte x of the chunk lives at base[x]; base is dword aligned
+        const bool glob_ok = cap - opos >= 16u;
+        const uint32_t prod0 = opos - mis;  // output bytes in front of offset 0
+        const uint32_t cstart = c0;
+        uint32_t run = mis, nq = 0, qh = 0;
+        Round R;
+        bool inflight = false;  // R's loads are under way
+        uint64_t globm = 0;     // R.glob by lane, as a scalar (a flag per lane carried around a loop costs three mask operations a trip)
+        // ---- the group at c0: token, lengths, wave prefix sum
         // token: [8:0] literal byte or match length, [9] match, [25:10] distance - 1; a literal pair: [31], second byte in [23:16]
         // (a literal's byte is the token's low byte as it stands; length and distance are only formed where a match is queued)
-        const bool ismatch = (t & 512u) != 0;
-        const uint32_t len = ismatch ? t & 0x1ffu : 0u;
-        const uint32_t val = ismatch ? __builtin_amdgcn_ubfe(t, 10, 16) + 1u : t;  // distance, or the literal (low byte)
-        const uint32_t left = ntok - c0;
-        const bool pair = (int32_t)t < 0;
-        uint32_t olen = ismatch ? len : 1u + (t >> 31);
-        olen = lane < left ? olen : 0u;  // (only the last group of a batch has lanes behind the end)
-        const uint32_t incl = wave_incl_scan(olen);
-        const uint32_t start = run + incl - olen;
-        const uint32_t total = rdlane(incl, 63u);
-        const uint64_t lenm = __ballot(len != 0);
-        uint32_t nacc;
-        bool ending, too_far = false;
-        // The common group: 64 tokens that all fit the chunk, no distance reaching in front of the output's first byte.
-        // (a distance cannot reach in front of the output once 32 KiB of it exist)
-        // (the distance test is one compare in every lane, masked by the match lanes: a literal's `val` is below 256.  It is
-        // skipped by the chunk's first output position, not by prod0: prod0 = opos - mis wraps below zero for a unit whose first
-        // byte is not dword aligned, and the sum prod0 + start is right all the same)
-        if (left >= 64u && run + total <= CHUNK_BYTES && (opos >= 32768u || (__ballot(val > prod0 + start) & lenm) == 0)) {
-            asm volatile("; the common group" ::: "memory");  // (keeps the compiler from folding this path into the general one below)
-            // every lane makes both stores, one of them to the trash: two selects instead of two exec-mask regions
-            const uint32_t qi = __builtin_amdgcn_mbcnt_hi((uint32_t)(lenm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)lenm, nq)) & (MQ_CAP - 1u);
-            *(len == 0 ? img + start : C.trash) = (uint8_t)val;
-            *(pair ? img + start + 1u : C.trash) = (uint8_t)(t >> 16);
-            *(len != 0 ? &C.mq[qi] : (uint2 *)(uint8_t *)C.trash) = make_uint2(start, len | (val << 16));
-            nq += (uint32_t)__popcll(lenm);
-            c0 += 64u;
-            run += total;
-            nacc = 64u;
-            ending = c0 >= ntok;
-        } else {
-            const uint32_t nvalid = left < 64u ? left : 64u;
-            // stops: the first token that does not fit the chunk, or with an "invalid distance too far back" (the distance
-            // reaches before the first output byte)
-            const uint64_t validm = nvalid == 64u ? ~0ull : (1ull << nvalid) - 1ull;
-            const uint64_t nofit = __ballot(incl > CHUNK_BYTES - run) & validm;
-            const uint64_t badm = __ballot(val > prod0 + start) & lenm & validm;
-            const uint64_t stopm = nofit | badm;
-            nacc = stopm ? (uint32_t)__ffsll((long long)stopm) - 1u : nvalid;
-            // a group that does not fit is left whole to the next chunk (the prefetched group stays the right one) unless the
-            // chunk is empty (long matches: 64 tokens can be 16 KB) or the stop is an error
-            too_far = stopm != 0 && ((badm & ~nofit) >> nacc) & 1ull;
-            if (stopm && !too_far && run != mis) nacc = 0;
-            // (a pair whose second byte does not fit the chunk is a token that does not fit: it goes whole to the next chunk)
-            if (lane < nacc && len == 0) img[start] = (uint8_t)val;
-            if (lane < nacc && pair) img[start + 1u] = (uint8_t)(t >> 16);
-            const uint64_t mm = lenm & (nacc == 64u ? ~0ull : (1ull << nacc) - 1ull);
-            if (lane < nacc && len != 0) {
-                const uint32_t qi = __builtin_amdgcn_mbcnt_hi((uint32_t)(mm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mm, nq)) & (MQ_CAP - 1u);
-                C.mq[qi] = make_uint2(start, len | (val << 16));
+        uint32_t t, len, val, left, incl, start, total;
+        bool pair;
+        uint64_t lenm;
+        auto group = [&]() __attribute__((always_inline)) {
+            static_assert(TOK_RING == 4, "the wait below counts three younger ring loads");
+            asm volatile("s_waitcnt vmcnt(3)" ::: "memory");  // the load into slot_r has landed
+            t = C.tok[64u * slot_r + lane];
+            const bool ismatch = (t & 512u) != 0;
+            len = ismatch ? t & 0x1ffu : 0u;
+            val = ismatch ? __builtin_amdgcn_ubfe(t, 10, 16) + 1u : t;  // distance, or the literal (low byte)
+            left = ntok - c0;
+            pair = (int32_t)t < 0;
+            uint32_t olen = ismatch ? len : 1u + (t >> 31);
+            olen = lane < left ? olen : 0u;  // (only the last group of a batch has lanes behind the end)
+            incl = wave_incl_scan(olen);
+            start = run + incl - olen;
+            total = rdlane(incl, 63u);
+            lenm = __ballot(len != 0);
+        };
+        // ---- The steady loop: common groups and nothing else.  A common group is 64 tokens that all fit the chunk, no distance
+        // reaching in front of the output's first byte.  It carries no flag of the chunk's end, no count of accepted tokens and no
+        // stop mask: the first group that is not common leaves the loop as it stands in the registers, for the general code below.
+        // (a distance cannot reach in front of the output once 32 KiB of it exist: dist_test is a constant of the chunk.  The
+        // test is one compare in every lane, masked by the match lanes: a literal's `val` is below 256.  It goes by the chunk's
+        // first output position, not by prod0: prod0 = opos - mis wraps below zero for a unit whose first byte is not dword
+        // aligned, and the sum prod0 + start is right all the same)
+        auto steady = [&](const bool dist_test) __attribute__((always_inline)) {
+            // No round outlives its chunk, so R holds nothing here.  (The empty statements say so to the compiler, loop by loop:
+            // left alone it carries R's eleven lane registers around the chunk loop in a second set, copies them at both ends of
+            // each steady loop behind a wait for every load in flight, and runs out of lane registers elsewhere in the kernel.)
+            {
+                uint32_t u[11];
+#pragma unroll
+                for (int k = 0; k < 11; k++) asm volatile("" : "=v"(u[k]));
+                R.x = u[0], R.len = u[1], R.dist = u[2], R.glob = false;
+                R.v0 = U128u{u[3], u[4], u[5], u[6]};
+                R.v1 = U128u{u[7], u[8], u[9], u[10]};
             }
-            nq += (uint32_t)__popcll(mm);
-            c0 += nacc;
-            if (stopm) {
-                if (nacc) run = rdlane(start, nacc);
-            } else {
+            for (;;) {
+                group();
+                if (left < 64u || run + total > CHUNK_BYTES) break;
+                if (dist_test && (__ballot(val > prod0 + start) & lenm) != 0) break;
+                // (the markers keep the compiler from folding the loops into each other or into the general group)
+                if (dist_test)
+                    asm volatile("; a steady group, distances tested" ::: "memory");
+                else
+                    asm volatile("; a steady group" ::: "memory");
+                // every lane makes all three stores, those it has nothing for to the trash: selects instead of exec-mask regions
+                const uint32_t qi = __builtin_amdgcn_mbcnt_hi((uint32_t)(lenm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)lenm, nq)) & (MQ_CAP - 1u);
+                *(len == 0 ? img + start : C.trash) = (uint8_t)val;
+                *(pair ? img + start + 1u : C.trash) = (uint8_t)(t >> 16);
+                *(len != 0 ? &C.mq[qi] : (uint2 *)(uint8_t *)C.trash) = make_uint2(start, len | (val << 16));
+                nq += (uint32_t)__popcll(lenm);
+                c0 += 64u;
                 run += total;
-            }
-            ending = stopm != 0 || c0 >= ntok;  // the chunk ends with this group
-        }
-        LSYNC();  // literals and queue entries are in LDS; the slot's tokens are in registers
-        STAT_ACC(16);
-        // ---- match rounds.  A round's source loads are started as soon as 64 matches are queued and it is finished
-        // when the next 64 are (about three token groups later: the loads have landed by then), or at the chunk's end.
-        if (nq - qh >= 64u || ending) {
-            do {
-                if (inflight) {
-                    round_finish(R, C, base, mis STAT_ARG);
-                    inflight = false;
-                }
-                const uint32_t pq = nq - qh;
-                if (pq >= 64u || (ending && pq != 0)) {
-                    const uint32_t nr = pq < 64u ? pq : 64u;
-                    round_issue(R, C, base, mis, qh, nr, glob_ok);
-                    qh += nr;
+                LSYNC();  // literals and queue entries are in LDS; the slot's tokens are in registers
+                STAT_ACC(16);
+                // A round's source loads are started as soon as 64 matches are queued and it is finished when the next 64 are
+                // (about three token groups later: the loads have landed by then), or at the chunk's end.
+                if (nq - qh >= 64u) {
+                    if (inflight) {
+                        R.glob = __builtin_amdgcn_inverse_ballot_w64(globm);
+                        round_finish(R, C, base, mis STAT_ARG);
+                    }
+                    round_issue(R, C, base, mis, qh, 64u, glob_ok);
+                    globm = __ballot(R.glob);
+                    qh += 64u;
                     inflight = true;
                 }
-            } while (ending && inflight);
+                STAT_ACC(17);
+                // (behind the round: its waits do not hold a ring load that was only just issued)
+                fetch(slot_r);
+                slot_r = (slot_r + 1u) & (TOK_RING - 1u);
+            }
+        };
+        // Two loops: opos only grows, so half the chunks of a 64 KiB unit run the one without the test.  (One loop with the flag
+        // tested per trip was built too: the compiler splits it in two by itself and then carries R through the trip in a second
+        // set of registers, eighteen copies per group.)
+        if (opos < 32768u)
+            steady(true);
+        else
+            steady(false);
+        // ---- The general group, which ends the chunk: the batch's last tokens (fewer than 64, or none when the batch ended with
+        // a steady group), a group that does not fit, or one with a distance too far back.
+        const uint32_t nvalid = left < 64u ? left : 64u;
+        // stops: the first token that does not fit the chunk, or with an "invalid distance too far back" (the distance
+        // reaches before the first output byte)
+        const uint64_t validm = nvalid == 64u ? ~0ull : (1ull << nvalid) - 1ull;
+        const uint64_t nofit = __ballot(incl > CHUNK_BYTES - run) & validm;
+        const uint64_t badm = __ballot(val > prod0 + start) & lenm & validm;
+        const uint64_t stopm = nofit | badm;
+        uint32_t nacc = stopm ? (uint32_t)__ffsll((long long)stopm) - 1u : nvalid;
+        // a group that does not fit is left whole to the next chunk (the prefetched group stays the right one) unless the
+        // chunk is empty (long matches: 64 tokens can be 16 KB) or the stop is an error
+        const bool too_far = stopm != 0 && ((badm & ~nofit) >> nacc) & 1ull;
+        if (stopm && !too_far && run != mis) nacc = 0;
+        // (a pair whose second byte does not fit the chunk is a token that does not fit: it goes whole to the next chunk)
+        if (lane < nacc && len == 0) img[start] = (uint8_t)val;
+        if (lane < nacc && pair) img[start + 1u] = (uint8_t)(t >> 16);
+        const uint64_t mm = lenm & (nacc == 64u ? ~0ull : (1ull << nacc) - 1ull);
+        if (lane < nacc && len != 0) {
+            const uint32_t qi = __builtin_amdgcn_mbcnt_hi((uint32_t)(mm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mm, nq)) & (MQ_CAP - 1u);
+            C.mq[qi] = make_uint2(start, len | (val << 16));
         }
+        nq += (uint32_t)__popcll(mm);
+        c0 += nacc;
+        if (stopm) {
+            if (nacc) run = rdlane(start, nacc);
+        } else {
+            run += total;
+        }
+        LSYNC();
+        STAT_ACC(16);
+        // ---- the chunk's last rounds: the one in flight, then what is left in the queue
+        for (;;) {
+            if (inflight) {
+                R.glob = __builtin_amdgcn_inverse_ballot_w64(globm);
+                round_finish(R, C, base, mis STAT_ARG);
+                inflight = false;
+            }
+            const uint32_t pq = nq - qh;
+            if (pq == 0) break;
+            const uint32_t nr = pq < 64u ? pq : 64u;
+            round_issue(R, C, base, mis, qh, nr, glob_ok);
+            globm = __ballot(R.glob);
+            qh += nr;
+            inflight = true;
+        }
+        // (To the compiler a round may still be loading into R: round_finish() does not read v0 and v1 on every path.  R is read
+        // here for nothing, so that the compiler's wait for those loads stands here, where the ring's loads are a group old or
+        // older, and not in front of the first reuse of the registers below, where it would wait for the loads issued there.)
+        asm volatile("" ::"v"(R.v0.x), "v"(R.v0.y), "v"(R.v0.z), "v"(R.v0.w), "v"(R.v1.x), "v"(R.v1.y), "v"(R.v1.z), "v"(R.v1.w));
         STAT_ACC(17);
-        // ---- the token ring (behind the rounds: their waits do not hold a ring load that was only just issued)
+        // ---- the token ring
         if (nacc == 64u) {
-            fetch();  // refills the slot just read: the group TOK_RING ahead
+            fetch(slot_r);
             slot_r = (slot_r + 1u) & (TOK_RING - 1u);
         } else if (nacc != 0 && c0 < ntok) {  // a partly taken group: the stream moves by less than a group, the ring starts over
             gnext = c0;
@@ -1103,11 +1148,10 @@ __device__ CHIP_PHASE_FN bool flush_tokens(WaveLds &L, const uint32_t *grow_, ui
                 nfirst = before < npieces ? nx : 0xffffffffu;
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // no load of the old ring is left to land on the new one
-            slot_r = slot_w = 0;
+            slot_r = 0;
 #pragma unroll
-            for (uint32_t k = 0; k < TOK_RING; k++) fetch();
+            for (uint32_t k = 0; k < TOK_RING; k++) fetch(k);
         }
-        if (!ending) continue;
         // ---- the finished chunk: offsets [mis, min(run, capacity)) of the LDS image go to HBM
         const uint32_t xcap = cap - (opos - mis);
         {
@@ -1139,7 +1183,6 @@ __device__ CHIP_PHASE_FN bool flush_tokens(WaveLds &L, const uint32_t *grow_, ui
             return false;
         }
         if (c0 >= ntok) return true;
-        fresh = true;
     }
 }
 // ---- the walk of a super-round -----------------------------------------------------------------------------
