@@ -154,6 +154,11 @@ class _ReadSummary(C.Structure):
                 ("first_bad", C.c_uint64), ("bad_index", C.c_uint64), ("status", C.c_int32), ("bad_status", C.c_int32)]
 
 
+class _ZstdSeekSummary(C.Structure):
+    _fields_ = [("n_frames", C.c_uint64), ("table_bytes", C.c_uint64), ("frames_bytes", C.c_uint64), ("total_out", C.c_uint64),
+                ("bad_index", C.c_uint64), ("status", C.c_int32), ("checksums", C.c_uint32)]
+
+
 class _InflateIndexSummary(C.Structure):
     _fields_ = [("n_points", C.c_uint64), ("out_len", C.c_uint64), ("in_used", C.c_uint64), ("end_bit", C.c_uint64), ("status", C.c_int32),
                 ("wrap", C.c_uint32), ("check", C.c_uint32), ("pad", C.c_uint32)]
@@ -328,6 +333,19 @@ def lib():
     L.chip_select_units.argtypes = [sz, vp, vp, vp, vp, sz, vp, vp, C.c_uint64] + [vp] * 8 + [C.POINTER(_SelectSummary), vp]
     L.chip_read_ranges.restype = C.c_int
     L.chip_read_ranges.argtypes = [C.c_int, sz, vp, vp, vp, vp, vp, sz, vp, vp, vp, C.c_uint64, vp, vp, C.POINTER(_ReadSummary), vp]
+    zss = C.POINTER(_ZstdSeekSummary)
+    L.chip_zstd_seek_plan_host.restype = C.c_int
+    L.chip_zstd_seek_plan_host.argtypes = [vp, u64, u64, u64, vp, vp, vp, vp, vp, zss]
+    L.chip_zstd_seek_plan.restype = C.c_int
+    L.chip_zstd_seek_plan.argtypes = [vp, u64, u64, u64, vp, vp, vp, vp, vp, zss, vp]
+    L.chip_zstd_seek_table_write_host.restype = C.c_int
+    L.chip_zstd_seek_table_write_host.argtypes = [u64, vp, vp, vp, vp, u64, C.POINTER(u64)]
+    L.chip_zstd_seek_table_write.restype = C.c_int
+    L.chip_zstd_seek_table_write.argtypes = [u64, vp, vp, vp, vp, u64, C.POINTER(u64), vp]
+    L.chip_xxh64_batch.restype = C.c_int
+    L.chip_xxh64_batch.argtypes = [sz, vp, vp, vp, vp, vp]
+    L.chip_zstd_seek_read.restype = C.c_int
+    L.chip_zstd_seek_read.argtypes = [sz, vp, vp, vp, vp, vp, vp, sz, vp, vp, vp, u64, vp, vp, C.POINTER(_ReadSummary), vp]
     L.chip_inflate_index_build.restype = C.c_int
     L.chip_inflate_index_build.argtypes = [C.c_int, vp, C.c_uint64, vp, C.c_uint64, C.c_uint32, C.c_uint64, vp, vp, vp, vp,
                                            C.POINTER(_InflateIndexSummary), vp]
@@ -2194,6 +2212,336 @@ def gzip_members_read(in_buf, length, ranges, stream=None):
     read_ranges(ZlibMode.Gzip).  Returns (the uint8 tensor of the ranges end to end, dst_off int64).  Waits for the result."""
     return _plan_read("gzip_members_read", gzip_plan, GzipPlanStatus.Ok, "not a whole series of gzip members", ZlibMode.Gzip, in_buf, length, ranges,
                       stream)
+
+
+# ---- seekable zstd files: the seek table as a plan (include/compu_hip.h, "seekable zstd files") ---
+
+
+class ZstdSeekStatus(enum.IntEnum):
+    Ok = 0
+    NoTable = 1
+    NeedTail = 2
+    BadTable = 3
+    TooLarge = 4
+    BadLayout = 5
+
+
+class ZstdSeekSummary:
+    """chip_zstd_seek_summary: n_frames entries in a table of table_bytes (on NeedTail: the tail to come back with), frames_bytes
+    and total_out the sums of the compressed and content sizes, bad_index the lowest entry without a size on TooLarge, checksums
+    whether the entries carry them, status."""
+
+    __slots__ = ("n_frames", "table_bytes", "frames_bytes", "total_out", "bad_index", "status", "checksums")
+
+    def __init__(self, raw):
+        self.n_frames, self.table_bytes, self.frames_bytes = int(raw.n_frames), int(raw.table_bytes), int(raw.frames_bytes)
+        self.total_out, self.bad_index = int(raw.total_out), int(raw.bad_index)
+        self.status, self.checksums = ZstdSeekStatus(raw.status), int(raw.checksums)
+
+    def as_tuple(self):
+        return (self.n_frames, self.table_bytes, self.frames_bytes, self.total_out, self.bad_index, int(self.status), self.checksums)
+
+    def __repr__(self):
+        return (f"ZstdSeekSummary(n_frames={self.n_frames}, table_bytes={self.table_bytes}, frames_bytes={self.frames_bytes}, "
+                f"total_out={self.total_out}, bad_index={self.bad_index}, status={self.status.name}, checksums={self.checksums})")
+
+
+def zstd_seek_plan_host(tail, file_len=None, max_frames=None):
+    """chip_zstd_seek_plan_host over bytes / a uint8 numpy array holding the last bytes of a file of file_len bytes (None: the
+    tail is the file): (in_off u64, in_len u32, out_off u64, out_cap u32, checksum u32, summary) of the first min(n_frames,
+    max_frames) entries (None = all of them: one call to count, one to fill).  With a status other than Ok the arrays are empty."""
+    import numpy as np
+
+    buf = np.frombuffer(tail, dtype=np.uint8) if not isinstance(tail, np.ndarray) else np.ascontiguousarray(tail, dtype=np.uint8)
+    file_len = buf.size if file_len is None else int(file_len)
+    raw = _ZstdSeekSummary()
+    p = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None  # noqa: E731
+    if max_frames is None:
+        rc = lib().chip_zstd_seek_plan_host(p(buf), buf.size, file_len, 0, None, None, None, None, None, C.byref(raw))
+        if rc != 0:
+            raise RuntimeError(f"chip_zstd_seek_plan_host failed: {rc}")
+        max_frames = int(raw.n_frames) if raw.status == int(ZstdSeekStatus.Ok) else 0
+    m = int(max_frames)
+    in_off, in_len, out_off, out_cap = np.zeros(m, np.uint64), np.zeros(m, np.uint32), np.zeros(m, np.uint64), np.zeros(m, np.uint32)
+    checksum = np.zeros(m, np.uint32)
+    rc = lib().chip_zstd_seek_plan_host(p(buf), buf.size, file_len, m, p(in_off), p(in_len), p(out_off), p(out_cap), p(checksum), C.byref(raw))
+    if rc != 0:
+        raise RuntimeError(f"chip_zstd_seek_plan_host failed: {rc}")
+    k = min(m, int(raw.n_frames)) if raw.status == int(ZstdSeekStatus.Ok) else 0
+    return in_off[:k], in_len[:k], out_off[:k], out_cap[:k], checksum[:k], ZstdSeekSummary(raw)
+
+
+def zstd_seek_plan(tail, file_len=None, stream=None, max_frames=None):
+    """chip_zstd_seek_plan over a uint8 device tensor (a view at any alignment) holding the last bytes of a file of file_len bytes
+    (None: the tail is the file): (in_off int64, in_len int32, out_off int64, out_cap int32, checksum int32, summary), device
+    tensors of the first min(n_frames, max_frames) entries (None = all of them: one call to count, one to fill), in_off in FILE
+    coordinates.  With a status other than Ok the tensors are empty.  Synchronous on `stream`."""
+    import torch
+
+    dev = _check_tensors(((tail, torch.uint8),))
+    tail_len = tail.numel()
+    file_len = tail_len if file_len is None else int(file_len)
+    raw = _ZstdSeekSummary()
+    base, sp = (_dp(tail) if tail_len else None), _stream_ptr(stream)
+    call = lib().chip_zstd_seek_plan
+    with torch.cuda.device(dev):
+        if max_frames is None:
+            rc = call(base, tail_len, file_len, 0, None, None, None, None, None, C.byref(raw), sp)
+            if rc != 0:
+                raise RuntimeError(f"chip_zstd_seek_plan failed: {rc}")
+            max_frames = int(raw.n_frames) if raw.status == int(ZstdSeekStatus.Ok) else 0
+        m = int(max_frames)
+        in_off, out_off = torch.empty(m, dtype=torch.int64, device=dev), torch.empty(m, dtype=torch.int64, device=dev)
+        in_len, out_cap, checksum = (torch.empty(m, dtype=torch.int32, device=dev) for _ in range(3))
+        q = lambda t: _dp(t) if m else None  # noqa: E731
+        rc = call(base, tail_len, file_len, m, q(in_off), q(in_len), q(out_off), q(out_cap), q(checksum), C.byref(raw), sp)
+    if rc != 0:
+        raise RuntimeError(f"chip_zstd_seek_plan failed: {rc}")
+    k = min(m, int(raw.n_frames)) if raw.status == int(ZstdSeekStatus.Ok) else 0
+    return in_off[:k], in_len[:k], out_off[:k], out_cap[:k], checksum[:k], ZstdSeekSummary(raw)
+
+
+def zstd_seek_table_write_host(c_len, d_len, checksum=None):
+    """chip_zstd_seek_table_write_host: the seek table of the entries (c_len[i], d_len[i][, checksum[i]]) as bytes."""
+    import numpy as np
+
+    arr = lambda a: np.ascontiguousarray(a, dtype=np.uint32)  # noqa: E731
+    c_len, d_len = arr(c_len), arr(d_len)
+    n = int(c_len.size)
+    if d_len.size != n or (checksum is not None and arr(checksum).size != n):
+        raise ValueError("the entries' arrays must have one length")
+    # (an empty checksum array still means 12-byte entries: a one-word stand-in keeps the pointer non-NULL)
+    cs = None if checksum is None else (arr(checksum) if n else np.zeros(1, np.uint32))
+    p = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None  # noqa: E731
+    size = C.c_uint64(0)
+    out = np.zeros(17 + (8 if cs is None else 12) * n, np.uint8)
+    rc = lib().chip_zstd_seek_table_write_host(n, p(c_len), p(d_len), p(cs), p(out), out.size, C.byref(size))
+    if rc != 0 or size.value != out.size:
+        raise RuntimeError(f"chip_zstd_seek_table_write_host failed: {rc}")
+    return out.tobytes()
+
+
+def zstd_seek_table_write(c_len, d_len, checksum=None, out=None, stream=None):
+    """chip_zstd_seek_table_write on device tensors (int32 read as u32): the table goes to `out` (a uint8 device tensor, a view at
+    any alignment; None: a tensor of exactly the table's size).  Returns (out trimmed to the table -- None when `out` is too small,
+    nothing is written then --, table_bytes).  Only enqueues on `stream`."""
+    import torch
+
+    pairs = [(c_len, torch.int32), (d_len, torch.int32)] + ([(checksum, torch.int32)] if checksum is not None else [])
+    dev = _check_tensors(pairs + ([(out, torch.uint8)] if out is not None else []))
+    n = c_len.numel()
+    if d_len.numel() != n or (checksum is not None and checksum.numel() != n):
+        raise ValueError("the entries' arrays must have one length")
+    if out is None:
+        out = torch.empty(17 + (8 if checksum is None else 12) * n, dtype=torch.uint8, device=dev)
+    cs = None if checksum is None else (checksum if n else torch.zeros(1, dtype=torch.int32, device=dev))
+    size = C.c_uint64(0)
+    with torch.cuda.device(dev):
+        rc = lib().chip_zstd_seek_table_write(n, _dp_or_none(c_len), _dp_or_none(d_len), _dp_or_none(cs), _dp_or_none(out), out.numel(),
+                                              C.byref(size), _stream_ptr(stream))
+    if rc != 0:
+        raise RuntimeError(f"chip_zstd_seek_table_write failed: {rc}")
+    return (out[: size.value] if size.value <= out.numel() else None), int(size.value)
+
+
+def xxh64_batch(buf, off, length, stream=None):
+    """chip_xxh64_batch on device tensors: XXH64 (seed 0) of buf[off[i] : off[i] + length[i]] for every i.  buf uint8, off int64
+    (read as u64), length int32 (read as u32).  Returns an int64 device tensor (read it as u64; a seek table's entry is its low
+    32 bits).  One wave per range.  Only enqueues on `stream`."""
+    import torch
+
+    dev = _check_tensors(((buf, torch.uint8), (off, torch.int64), (length, torch.int32)))
+    n = off.numel()
+    if length.numel() != n:
+        raise ValueError("off and length must have one length")
+    digest = torch.empty(n, dtype=torch.int64, device=dev)
+    if n == 0:
+        return digest
+    with torch.cuda.device(dev):
+        rc = lib().chip_xxh64_batch(n, _dp(buf), _dp(off), _dp(length), _dp(digest), _stream_ptr(stream))
+    if rc != 0:
+        raise RuntimeError(f"chip_xxh64_batch failed: {rc}")
+    return digest
+
+
+def zstd_seek_read(in_buf, in_off, in_len, out_off, out_cap, checksum, range_lo, range_len, dst=None, stream=None):
+    """chip_zstd_seek_read on device tensors: read_ranges(FMT_ZSTD, ..) over the plan of a seek table, with the low 32 bits of
+    every selected unit's XXH64 compared with checksum[unit] (int32 read as u32; None: read_ranges itself).  A unit that differs
+    is a bad unit with bad_status -22.  Returns what read_ranges returns.  Synchronous on `stream`."""
+    import torch
+
+    pairs = [(in_buf, torch.uint8), (in_off, torch.int64), (in_len, torch.int32), (out_off, torch.int64), (out_cap, torch.int32),
+             (range_lo, torch.int64), (range_len, torch.int32)] + ([(checksum, torch.int32)] if checksum is not None else [])
+    n, m = out_cap.numel(), range_len.numel()
+    mismatch = (not (in_off.numel() == in_len.numel() == out_off.numel() == n) or range_lo.numel() != m
+                or (checksum is not None and checksum.numel() != n))
+    q = _dp_or_none
+    return _read_call("chip_zstd_seek_read", pairs, mismatch and "the plan's arrays, and the ranges' arrays, must have one length each", m, dst, stream,
+                      lambda *out: lib().chip_zstd_seek_read(n, q(in_buf) if n else None, q(in_off), q(in_len), q(out_off), q(out_cap), q(checksum),
+                                                             m, q(range_lo), q(range_len), *out))
+
+
+def seekable_write(data, length, level=3, unit_bytes=0, checksums=True, out=None, stream=None):
+    """A seekable zstd file of the first `length` bytes of the uint8 device tensor `data` (4-byte aligned, padded to a multiple
+    of 4), with the seek table behind the last frame and, with `checksums`, the low 32 bits of every frame's content XXH64 in it:
+    xxh64_batch over the chunks, encode_file(FMT_ZSTD, flags=0), zstd_plan of the frames for their sizes, zstd_seek_table_write.
+    unit_bytes 0: 262144.  out None: a tensor of the bound is allocated.  Returns (the file as a uint8 device tensor -- None when
+    `out` is too small --, FileSummary with n_units, out_len, table_off and the status)."""
+    import torch
+
+    dev = _check_tensors(((data, torch.uint8),) + (((out, torch.uint8),) if out is not None else ()))
+    length, unit = int(length), int(unit_bytes) or 262144
+    n = max(1, -(-length // unit))
+    table = 17 + (12 if checksums else 8) * n
+    if out is None:
+        bound = encode_file_bound(FMT_ZSTD, length, unit, 0)
+        if bound == 0:
+            raise ValueError(f"seekable_write refuses unit_bytes {unit_bytes}, length {length}")
+        out = torch.empty(bound + table, dtype=torch.uint8, device=dev)
+    low = None
+    with torch.cuda.device(dev):
+        if checksums and length == 0:  # (no buffer to hash: the one frame of empty content)
+            low = torch.tensor([0x51D8E999], dtype=torch.int32, device=dev)
+        elif checksums:
+            off = torch.arange(n, dtype=torch.int64, device=dev) * unit
+            ln = torch.clamp(length - off, min=0, max=unit).to(torch.int32)
+            low = xxh64_batch(data, off, ln, stream=stream).view(torch.int32)[::2].contiguous()  # (little endian: the low words)
+    frames, summ = encode_file(FMT_ZSTD, level, data, length, unit, 0, stream=stream, out=out)
+    raw = _FileSummary(summ.n_units, summ.out_len + table, summ.out_len, int(summ.status), 0)
+    if frames is None or summ.out_len + table > out.numel():
+        raw.status = int(FileStatus.NeedOutput)
+        return None, FileSummary(raw)
+    _, c_len, _, d_len, plan = zstd_plan(out, summ.out_len, stream=stream)
+    if plan.status != ZstdPlanStatus.Ok or plan.n_frames != n or plan.n_unsized:
+        raise RuntimeError(f"seekable_write: the frames just written do not plan as {n} sized frames: {plan!r}")
+    _, size = zstd_seek_table_write(c_len, d_len, low, out=out[summ.out_len:], stream=stream)
+    assert size == table
+    return out[: summ.out_len + table], FileSummary(raw)
+
+
+def _read_exact(f, pos, view):
+    """seek + readinto until `view` (a writable memoryview of bytes) is full; EOFError when the source ends first"""
+    f.seek(pos)
+    got = 0
+    while got < len(view):
+        k = f.readinto(view[got:])
+        if not k:
+            raise EOFError(f"the source ended {len(view) - got} bytes short at {pos + got}")
+        got += k
+
+
+class SeekableZstd:
+    """A reader of seekable zstd files that fetches the table and the frames its ranges touch, nothing else.
+    open() plans the table; n_frames, size (the content's length), has_checksums and the plan (in_off, in_len, out_off, out_cap,
+    checksum: numpy arrays, in_off in file coordinates) are its attributes; bytes_fetched counts what was read from the source."""
+
+    def __init__(self, src, file_len, plan, summary, bytes_fetched, device_plan=None):
+        self._src, self.file_len, self.summary, self.bytes_fetched = src, file_len, summary, bytes_fetched
+        self.in_off, self.in_len, self.out_off, self.out_cap, self.checksum = plan
+        self.n_frames, self.size, self.has_checksums = summary.n_frames, summary.total_out, bool(summary.checksums)
+        self._dev = device_plan  # the plan as device tensors, once a read has needed it
+
+    @classmethod
+    def open(cls, src, length=None, tail_bytes=65536):
+        """src: bytes, a seekable binary file object, or a uint8 device tensor holding the file (4-byte aligned, padded to a
+        multiple of 4).  length: the file's length (None: all of src).  The last min(length, tail_bytes) bytes are read and
+        planned (bytes and files: on the host; a tensor: on the device); a table that is larger costs a second read of exactly
+        table_bytes.  ValueError, naming the status, for every status but Ok."""
+        import io
+
+        try:
+            import torch
+
+            on_device = isinstance(src, torch.Tensor)
+        except ImportError:  # pragma: no cover - the host walk needs no torch
+            on_device = False
+        if on_device:
+            file_len = src.numel() if length is None else int(length)
+            if file_len < 0 or file_len > src.numel():
+                raise ValueError(f"length {file_len} outside the buffer of {src.numel()} bytes")
+            plan_of = lambda k: zstd_seek_plan(src[file_len - k:file_len], file_len)  # noqa: E731
+        else:
+            if isinstance(src, (bytes, bytearray, memoryview)):
+                src = io.BytesIO(src)
+            file_len = src.seek(0, 2) if length is None else int(length)
+            fetched = [0]
+
+            def plan_of(k):
+                tail = bytearray(k)
+                if k:
+                    _read_exact(src, file_len - k, memoryview(tail))
+                fetched[0] += k
+                return zstd_seek_plan_host(tail, file_len)
+
+        planned = plan_of(min(file_len, max(0, int(tail_bytes))))
+        if planned[5].status == ZstdSeekStatus.NeedTail and planned[5].table_bytes <= file_len:
+            planned = plan_of(planned[5].table_bytes)
+        summ = planned[5]
+        if summ.status != ZstdSeekStatus.Ok:
+            raise ValueError(f"no usable seek table ({summ.status.name}): {summ!r}")
+        if on_device:
+            import numpy as np
+
+            host = tuple(t.cpu().numpy().view(dt) for t, dt in zip(planned[:5], (np.uint64, np.uint32, np.uint64, np.uint32, np.uint32)))
+            return cls(src, file_len, host, summ, 0, device_plan=planned[:5])
+        return cls(src, file_len, planned[:5], summ, fetched[0])
+
+    def _device_plan(self, dev):
+        import numpy as np
+        import torch
+
+        if self._dev is None or self._dev[1].device != dev:
+            up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a).view(dt)).to(dev)  # noqa: E731
+            self._dev = (up(self.in_off, np.int64), up(self.in_len, np.int32), up(self.out_off, np.int64), up(self.out_cap, np.int32),
+                         up(self.checksum, np.int32))
+        return self._dev
+
+    def read(self, ranges, verify=True, stream=None):
+        """The bytes of `ranges`, a sequence of (lo, len) pairs in content coordinates: (the uint8 device tensor of the ranges end
+        to end, dst_off int64).  From a file or bytes, the frames the ranges touch are read -- runs of frames that are adjacent in
+        the file with one seek + readinto each, into pinned memory -- and uploaded; zstd_seek_read decodes them, with the table's
+        checksums verified unless `verify` is false or the table has none.  Raises ValueError for a range outside the content,
+        RuntimeError with the first bad frame's index and status (-22: its checksum) when a frame does not decode to its entry."""
+        import numpy as np
+        import torch
+
+        ranges = [(int(lo), int(ln)) for lo, ln in ranges]
+        if isinstance(self._src, torch.Tensor):
+            dev = self._src.device
+            in_off, in_len, out_off, out_cap, checksum = self._device_plan(dev)
+            buf = self._src
+        else:
+            dev = torch.device("cuda", torch.cuda.current_device())
+            _, in_len, out_off, out_cap, checksum = self._device_plan(dev)
+            sel = select_units_host(self.in_off, self.in_len, self.out_off, self.out_cap, [r[0] for r in ranges], [r[1] for r in ranges])
+            units, s_off, s_len = sel[0], sel[1], sel[2]
+            runs, at = [], 0  # (file offset, bytes, offset in the buffer) of every run of adjacent frames
+            rebased = np.zeros(self.n_frames, np.int64)
+            for u, o, ln in zip(units.tolist(), s_off.tolist(), s_len.tolist()):
+                if runs and runs[-1][0] + runs[-1][1] == o:
+                    runs[-1][1] += ln
+                else:
+                    runs.append([o, ln, at])
+                rebased[u] = at
+                at += ln
+            if at > self.file_len or any(o + ln > self.file_len for o, ln, _ in runs):
+                raise ValueError("the seek table names bytes behind the end of the file")
+            pinned = torch.zeros(max(4, (at + 3) // 4 * 4), dtype=torch.uint8).pin_memory()
+            view = memoryview(pinned.numpy())
+            for o, ln, b in runs:
+                _read_exact(self._src, o, view[b:b + ln])
+            self.bytes_fetched += at
+            buf = pinned.to(dev)
+            in_off = torch.from_numpy(rebased).to(dev)
+        lo, ln = _ranges_to_device(ranges, dev)
+        cs = checksum if verify and self.has_checksums else None
+        out, dst_off, status, summ = zstd_seek_read(buf, in_off, in_len, out_off, out_cap, cs, lo, ln, stream=stream)
+        return _read_checked("SeekableZstd.read", out, status, summ), dst_off
+
+    def read_bytes(self, lo, n, verify=True):
+        """bytes [lo, lo + n) of the content, as bytes"""
+        out, _ = self.read([(lo, n)], verify=verify)
+        return bytes(out.cpu().numpy())
 
 
 # ---- one large stream: the checkpoint index (include/compu_hip.h, "one large stream") ------------

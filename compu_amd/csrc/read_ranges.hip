@@ -1,9 +1,9 @@
 // Reading ranges: random access on a plan.  Given the four arrays of a plan and many byte ranges of the
 // decoded content, chip_select_units[_host] names the units the ranges touch and where each range lies in their decoded image;
 // a read decodes exactly those units once and lands the ranges end to end.  The definition is in include/compu_hip.h; the host
-// walk and the kernels below implement it.  One driver, read_locked<Source>(), serves two sources of units: the caller's plan
-// (chip_read_ranges, PlanSource) and the chunks of a checkpoint index (chip_inflate_index_read, sec. 4.16, IndexSource).  The
-// phases on the device, in stream order:
+// walk and the kernels below implement it.  One driver, read_locked<Source>(), serves three sources of units: the caller's plan
+// (chip_read_ranges, PlanSource), the chunks of a checkpoint index (chip_inflate_index_read, sec. 4.16, IndexSource) and a plan
+// with a checksum per unit (chip_zstd_seek_read, sec. 4.25, SeekSource).  The phases on the device, in stream order:
 //   0. units    Source::carve and units: an index fills the four arrays of its units, arrays of its own in buffer ARRAYS; a plan
 //               brings them
 //   1. link     one lane per unit: out_off[i] + out_cap[i] == out_off[i + 1], no unsized cap, no wrap; the lowest failing link wins
@@ -29,6 +29,7 @@
 #include "launch_slots.h"
 #include "pack_copy.h"
 #include "plan_common.h"
+#include "wave_checksums.h"
 
 namespace chip {
 
@@ -507,6 +508,41 @@ struct IndexSource {
     }
 };
 
+// ---- reading through a seek table with per-frame checksums ------------------------------------------------
+// The units are a plan's, decoded and verified as PlanSource does it.  Behind that, phase 7 goes on: one wave per selected unit that
+// is not bad already hashes the unit's image (XXH64, wave_checksums.h); a unit whose low 32 bits differ from the table's entry is a
+// bad unit with the decoder's own status for a wrong content checksum.
+__global__ __launch_bounds__(64) void rr_hash_kernel(const uint8_t *image, const uint64_t *sel_out_off, const uint32_t *sel_cap, const uint32_t *sel_unit,
+                                                     const uint32_t *checksum, Cnt32 *flag, DevSummary *ds)
+{
+    __shared__ uint64_t stage[512];
+    const uint32_t k = blockIdx.x;
+    if (flag[k].v) return;  // (uniform) counted by rr_verify_kernel
+    const uint32_t unit = sel_unit[k];
+    const uint32_t got = wave_xxh64_low32(stage, image + sel_out_off[k], sel_cap[k]);
+    if (lane_id() != 0 || got == checksum[unit]) return;
+    flag[k] = Cnt32{1u};
+    atomicAdd((unsigned long long *)&ds->n_bad, 1ull);
+    atomicMax((unsigned long long *)&ds->bad_key, ((unsigned long long)(uint32_t)~unit << 32) | (uint32_t)-ZSTD_E_CHECKSUM_WRONG);
+}
+
+struct SeekSource {
+    const uint32_t *checksum;  // per unit of the plan
+
+    void carve(Carve &) {}
+    void units(uint8_t *, SelectArgs &, hipStream_t) {}
+    static constexpr uint64_t LINK_BACK = PlanSource::LINK_BACK;
+    static size_t area(const chip_select_summary &s) { return PlanSource::area(s); }
+    hipError_t decode(const BatchArgs &ba, const uint32_t *unit, Cnt32 *flag, DevSummary *ds, hipStream_t stream) const
+    {
+        const hipError_t e = PlanSource::decode(ba, unit, flag, ds, stream);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(rr_hash_kernel, dim3(ba.n), dim3(64), 0, stream, (const uint8_t *)ba.out_base, ba.out_off, ba.out_cap, unit, checksum, flag, ds);
+        return hipSuccess;
+    }
+    static const uint8_t *image(const BatchArgs &ba, uint64_t scratch_bytes, hipStream_t stream) { return PlanSource::image(ba, scratch_bytes, stream); }
+};
+
 SlotCache<ReadSlot> g_index_read_cache;
 
 constexpr chip_select_summary SELECT_NOTHING{0, 0, 0, 0, 0, CHIP_READ_OK, 0};
@@ -673,6 +709,21 @@ int chip_read_ranges(int format, size_t n_units, const void *in_base, const uint
     const SelectArgs g{n_units, n_ranges, in_off,  in_len,  out_off, out_cap, range_lo, range_len,   0,
                        nullptr, nullptr,  nullptr, nullptr, nullptr, nullptr, dst_off,  range_status};
     return read_with_slot(g_read_cache, PlanSource{}, format, in_base, g, dst_base, dst_cap, summary, stream);
+}
+
+int chip_zstd_seek_read(size_t n_units, const void *in_base, const uint64_t *in_off, const uint32_t *in_len, const uint64_t *out_off,
+                        const uint32_t *out_cap, const uint32_t *checksum, size_t n_ranges, const uint64_t *range_lo, const uint32_t *range_len,
+                        void *dst_base, uint64_t dst_cap, uint64_t *dst_off, int32_t *range_status, chip_read_summary *summary, void *stream)
+{
+    if (!checksum)
+        return chip_read_ranges(CHIP_FMT_ZSTD, n_units, in_base, in_off, in_len, out_off, out_cap, n_ranges, range_lo, range_len, dst_base, dst_cap,
+                                dst_off, range_status, summary, stream);
+    if (!summary || !plan_args_ok(n_units, in_off, in_len, out_off, out_cap, n_ranges, range_lo, range_len) || (n_units && !in_base) ||
+        ((uintptr_t)in_base & 3u) || (dst_cap && !dst_base))
+        return CHIP_E_INVALID;
+    const SelectArgs g{n_units, n_ranges, in_off,  in_len,  out_off, out_cap, range_lo, range_len,   0,
+                       nullptr, nullptr,  nullptr, nullptr, nullptr, nullptr, dst_off,  range_status};
+    return read_with_slot(g_read_cache, SeekSource{checksum}, CHIP_FMT_ZSTD, in_base, g, dst_base, dst_cap, summary, stream);
 }
 
 int chip_inflate_index_units_host(int format, uint64_t len, uint64_t n_points, const uint64_t *pt_bit, const uint64_t *pt_out,

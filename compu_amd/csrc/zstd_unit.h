@@ -19,6 +19,7 @@
 #include <cstddef>
 
 #include "chip_internal.h"
+#include "wave_checksums.h"  // the wave XXH64: xxh_init, xxh_stripes, xxh_finish, wave_xxh64_low32
 
 namespace chip {
 
@@ -812,132 +813,6 @@ __device__ int huf_read(ZLds &L, const Bits &b, uint32_t p0, uint32_t n ZSTAT_PA
     if (huf_build(L, nw)) return -1;
     ZT_END(17, zt17);
     return (int)used;
-}
-
-// XXH64 (seed 0), lanes 0..3 own the four accumulators.  Three steps so that the streaming decoder can carry the state
-// from block to block: xxh_init(), xxh_stripes() over whole 32-byte stripes, xxh_finish() with the bytes behind the last stripe.
-// `stage`: 4 * stage_stripes qwords of LDS scratch.
-__device__ __forceinline__ uint64_t xxh_init()
-{
-    constexpr uint64_t P1 = 11400714785074694791ULL, P2 = 14029467366897019727ULL;
-    const uint32_t lane = lane_id();
-    return lane == 0 ? P1 + P2 : lane == 1 ? P2 : lane == 2 ? 0ULL : 0ULL - P1;
-}
-
-struct XxhView {  // aligned dword view of a byte range; reads stay inside dwords that hold bytes of it
-    const uint32_t *p32;
-    uint32_t pmis;
-    __device__ __forceinline__ explicit XxhView(const uint8_t *p) : p32((const uint32_t *)(p - ((uintptr_t)p & 3u))), pmis((uint32_t)((uintptr_t)p & 3u)) {}
-    __device__ __forceinline__ uint64_t rd64(uint32_t off) const
-    {
-        const uint32_t i = (pmis + off) >> 2, sh = ((pmis + off) & 3u) * 8u;
-        const uint32_t d0 = p32[i], d1 = p32[i + 1], d2 = sh ? p32[i + 2] : 0u;
-        return (uint64_t)__builtin_amdgcn_alignbit(d1, d0, sh) | ((uint64_t)__builtin_amdgcn_alignbit(d2, d1, sh) << 32);
-    }
-};
-
-// (out of line; the pointers carry their address spaces, else every access here is a flat one that counts on both wait counters)
-__device__ void xxh_stripes(uint64_t *stage_, const uint32_t stage_stripes, const uint8_t *p_, uint32_t stripes, uint64_t &acc)
-{
-    LDS_AS uint64_t *const stage = (LDS_AS uint64_t *)stage_;
-    const GAS uint8_t *const p = (const GAS uint8_t *)p_;
-    constexpr uint64_t P1 = 11400714785074694791ULL, P2 = 14029467366897019727ULL;
-    auto rotl = [](uint64_t x, int r) { return (x << r) | (x >> (64 - r)); };
-    const uint32_t lane = lane_id();
-    // The accumulator recurrence acc = rotl(acc + in * P2, 31) * P1 is serial per 8-byte column, but the products
-    // in * P2 are not: all 64 lanes form them for up to 128 stripes at a time into `stage` (4 KB of LDS), then lanes 0..3
-    // run their columns over the staged products -- one multiplication per dependent step instead of two, and no
-    // address arithmetic or loads on the chain.
-    for (uint32_t s0 = 0; s0 < stripes; s0 += stage_stripes) {
-        const uint32_t ns = stripes - s0 < stage_stripes ? stripes - s0 : stage_stripes;
-        WSYNC();
-        // one 8-byte load at any alignment per product (gfx950 takes them), all eight of a lane requested before the first is
-        // used: no branch around a load (a lane past the batch's end re-reads its last qword and stores nothing)
-        struct __attribute__((packed, aligned(1))) U64u {
-            uint64_t v;
-        };
-        uint64_t in[8];
-#pragma unroll
-        for (uint32_t k = 0; k < 8; k++) {
-            const uint32_t q = 64u * k + lane;  // qword of the batch: stripe q / 4, column q % 4
-            const uint32_t qq = q < 4u * ns ? q : 4u * ns - 1u;
-            in[k] = ((const GAS U64u *)(p + 32u * s0 + 8u * qq))->v;
-        }
-#pragma unroll
-        for (uint32_t k = 0; k < 8; k++) {
-            const uint32_t q = 64u * k + lane;
-            if (q < 4u * ns) stage[q] = in[k] * P2;
-        }
-        WSYNC();
-        if (lane < 4) {
-            uint32_t i = 0;
-            for (; i + 8 <= ns; i += 8) {
-                uint64_t in[8];
-#pragma unroll
-                for (uint32_t k = 0; k < 8; k++) in[k] = stage[4u * (i + k) + lane];
-#pragma unroll
-                for (uint32_t k = 0; k < 8; k++) acc = rotl(acc + in[k], 31) * P1;
-            }
-            for (; i < ns; i++) acc = rotl(acc + stage[4u * i + lane], 31) * P1;
-        }
-    }
-    WSYNC();
-}
-
-// total: bytes hashed altogether (stripes and tail); tail[0..tail_n): the bytes behind the last whole stripe (< 32).  Low 32 bits.
-__device__ uint32_t xxh_finish(uint64_t acc, uint64_t total, const uint8_t *tail, uint32_t tail_n)
-{
-    constexpr uint64_t P1 = 11400714785074694791ULL, P2 = 14029467366897019727ULL, P3 = 1609587929392839161ULL,
-                       P4 = 9650029242287828579ULL, P5 = 2870177450012600261ULL;
-    auto rotl = [](uint64_t x, int r) { return (x << r) | (x >> (64 - r)); };
-    auto round1 = [&](uint64_t a, uint64_t in) { return rotl(a + in * P2, 31) * P1; };
-    const XxhView V(tail);
-    uint64_t h;
-    if (total >= 32) {
-        uint64_t v[4];
-        for (int k = 0; k < 4; k++) {
-            uint32_t lo = rdlane((uint32_t)acc, (uint32_t)k), hi = rdlane((uint32_t)(acc >> 32), (uint32_t)k);
-            v[k] = ((uint64_t)hi << 32) | lo;
-        }
-        h = rotl(v[0], 1) + rotl(v[1], 7) + rotl(v[2], 12) + rotl(v[3], 18);
-        for (int k = 0; k < 4; k++) h = (h ^ round1(0, v[k])) * P1 + P4;
-    } else {
-        h = P5;
-    }
-    h += total;
-    uint32_t off = 0;
-    while (off + 8 <= tail_n) {
-        h ^= round1(0, V.rd64(off));
-        h = rotl(h, 27) * P1 + P4;
-        off += 8;
-    }
-    if (off + 4 <= tail_n) {
-        uint64_t v = 0;
-        for (int k = 3; k >= 0; k--) v = (v << 8) | tail[off + (uint32_t)k];
-        h ^= v * P1;
-        h = rotl(h, 23) * P2 + P3;
-        off += 4;
-    }
-    while (off < tail_n) {
-        h ^= (uint64_t)tail[off] * P5;
-        h = rotl(h, 11) * P1;
-        off++;
-    }
-    h ^= h >> 33;
-    h *= P2;
-    h ^= h >> 29;
-    h *= P3;
-    h ^= h >> 32;
-    return (uint32_t)h;
-}
-
-// XXH64 (seed 0) of p[0..n) in one go.  `stage`: 512 qwords of LDS scratch (anything that is dead once the frame's blocks are done).
-__device__ uint32_t wave_xxh64_low32(uint64_t *stage, const uint8_t *p, uint32_t n)
-{
-    uint64_t acc = xxh_init();
-    const uint32_t stripes = n >> 5;
-    if (stripes) xxh_stripes(stage, 128, p, stripes, acc);
-    return xxh_finish(acc, n, p + (stripes << 5), n & 31u);
 }
 
 // wave-cooperative forward copy of n bytes; dst and src may overlap with dst - src = period >= 1

@@ -1386,6 +1386,112 @@ int chip_read_ranges(int format, size_t n_units, const void *in_base, const uint
                      const uint32_t *out_cap, size_t n_ranges, const uint64_t *range_lo, const uint32_t *range_len, void *dst_base,
                      uint64_t dst_cap, uint64_t *dst_off, int32_t *range_status, chip_read_summary *summary, void *stream);
 
+/* ---- seekable zstd files: the seek table as a plan (additive API) ------------ */
+
+/*
+ * zstd's seekable format (contrib/seekable_format) ends a series of frames with a skippable frame that lists every frame's
+ * compressed size, content size and, optionally, the low 32 bits of the content's XXH64.  A reader takes the last few KiB of the
+ * file, knows where every frame lies, and fetches and decodes only the frames its ranges touch.  These calls read such a table as
+ * a plan (the four arrays of chip_zstd_plan, plus the checksums), write one, make the checksums, and read ranges with the
+ * checksums verified on the device.  The table is untrusted input: its sizes are checked by the decode (a frame that does not end
+ * CHIP_FINISHED at exactly out_cap bytes is a bad unit), its checksums by chip_zstd_seek_read.
+ *
+ * `tail` is the last tail_len bytes of a file of file_len bytes: byte j of tail is byte file_len - tail_len + j of the file.  All
+ * integers are little endian.  The answer is defined by this walk (host and device implement the same one):
+ *   file_len < 17                                   -> CHIP_ZSEEK_NO_TABLE
+ *   tail_len < 17                                   -> CHIP_ZSEEK_NEED_TAIL, table_bytes = 17
+ *   LE32(tail_len - 4) != 0x8F92EAB1                -> CHIP_ZSEEK_NO_TABLE
+ *   desc = byte(tail_len - 5);  desc & 0x7C         -> CHIP_ZSEEK_BAD_TABLE   (reserved bits; the two low bits are ignored)
+ *   cs = desc >> 7;  es = 8 + 4 * cs;  n = LE32(tail_len - 9)
+ *   n > 0x8000000                                   -> CHIP_ZSEEK_BAD_TABLE
+ *   T = 17 + es * n;  T > file_len                  -> CHIP_ZSEEK_BAD_TABLE
+ *      from here on the summary has n_frames = n, table_bytes = T, checksums = cs
+ *   tail_len < T                                    -> CHIP_ZSEEK_NEED_TAIL   (come back with the last T bytes)
+ *   LE32(tail_len - T) != 0x184D2A5E, or LE32(tail_len - T + 4) != T - 8      -> CHIP_ZSEEK_BAD_TABLE
+ *   entry i at tail_len - T + 8 + es * i:  c_i = LE32, d_i = LE32, x_i = LE32 when cs (else 0)
+ *      some d_i == 0xFFFFFFFF (CHIP_ZPLAN_UNSIZED is taken)  -> CHIP_ZSEEK_TOO_LARGE, bad_index = the lowest such i
+ *      in_off[i] = c_0 + .. + c_(i-1)  (FILE coordinates, 64-bit),  in_len[i] = c_i,
+ *      out_off[i] = d_0 + .. + d_(i-1),  out_cap[i] = d_i,  checksum[i] = x_i
+ *   C = sum of c_i;  C > file_len - T               -> CHIP_ZSEEK_BAD_LAYOUT  (C < file_len - T is accepted: foreign skippable
+ *                                                                             frames may sit in front of the table)
+ *   CHIP_ZSEEK_OK: frames_bytes = C, total_out = sum of d_i
+ * Every field of the summary that the walk has not set by the line it stops at is 0.  The arrays receive the first
+ * min(n, max_frames) entries and nothing behind them is written: max_frames = 0 with NULL arrays counts, a second call fills.
+ * `checksum` may be NULL (not wanted).  With a status other than CHIP_ZSEEK_OK the arrays' contents are unspecified.
+ * The plan judges only the table.  An entry is taken to be one zstd frame: an entry that is several frames, or a skippable frame
+ * with d_i > 0, surfaces as a bad unit at decode; entries with d_i == 0 are never selected by a read.
+ * CHIP_E_INVALID: summary NULL, tail NULL with tail_len > 0, tail_len > file_len, file_len > 2^40, or one of in_off, in_len,
+ * out_off, out_cap NULL with max_frames > 0.
+ */
+enum { CHIP_ZSEEK_OK = 0, CHIP_ZSEEK_NO_TABLE = 1, CHIP_ZSEEK_NEED_TAIL = 2, CHIP_ZSEEK_BAD_TABLE = 3, CHIP_ZSEEK_TOO_LARGE = 4,
+       CHIP_ZSEEK_BAD_LAYOUT = 5 };
+typedef struct {
+    uint64_t n_frames, table_bytes, frames_bytes, total_out, bad_index;
+    int32_t status;     /* CHIP_ZSEEK_* */
+    uint32_t checksums; /* 1: the entries carry checksums */
+} chip_zstd_seek_summary;
+
+/* The walk on HOST memory: pure host arithmetic, no device needed. */
+int chip_zstd_seek_plan_host(const uint8_t *tail, uint64_t tail_len, uint64_t file_len, uint64_t max_frames, uint64_t *in_off,
+                             uint32_t *in_len, uint64_t *out_off, uint32_t *out_cap, uint32_t *checksum, chip_zstd_seek_summary *summary);
+
+/* The same answer for a tail in DEVICE memory: tail and the five arrays are DEVICE pointers, summary is a HOST pointer.  tail may
+ * have any alignment (a file's table starts wherever it starts); reads stay inside the aligned dwords that hold bytes of the tail.
+ * Arguments are checked before the device is looked for, and a walk that stops before a byte is read (file_len or tail_len below
+ * 17) is answered on the host.  SYNCHRONOUS on `stream`: it waits once for the footer and the table's header (the grid is sized
+ * from n), once for the sums.  One lane per entry reads its 8 or 12 bytes; the offsets are two 64-bit exclusive scans.  Every byte
+ * of the tail is read once and every position follows from the n the host holds, so input that changes during the call changes
+ * the answer and never where something is read or written; CHIP_E_LAUNCH: a launch failed, or what came back from the device
+ * contradicts itself.  CHIP_E_NOMEM: the scratch could not be allocated.  Scratch per (device, stream), a launch slot of its own,
+ * kept between calls and released by chip_trim(): 16 bytes per entry, with a quarter of headroom.  The calling thread's current
+ * device is left as it was.  No reference counterpart: compu has no container formats. */
+int chip_zstd_seek_plan(const void *tail, uint64_t tail_len, uint64_t file_len, uint64_t max_frames, uint64_t *in_off, uint32_t *in_len,
+                        uint64_t *out_off, uint32_t *out_cap, uint32_t *checksum, chip_zstd_seek_summary *summary, void *stream);
+
+/*
+ * Writing a table: 17 + (checksum ? 12 : 8) * n bytes at dst,
+ *   LE32 0x184D2A5E | LE32 size - 8 | n x { LE32 c_len[i], LE32 d_len[i] [, LE32 checksum[i]] } | LE32 n | u8 (checksum ? 0x80 : 0) |
+ *   LE32 0x8F92EAB1
+ * The entries go out as they are handed in.  With checksum == NULL the bytes are the ones chip_encode_file(.., CHIP_W_SEEK_TABLE)
+ * writes for the same lengths.  *table_bytes (HOST) is always the exact size; when it exceeds dst_cap nothing is written.
+ * CHIP_E_INVALID: table_bytes NULL, n > 0x8000000 (the format's limit), c_len or d_len NULL with n > 0, dst NULL with dst_cap > 0.
+ * chip_zstd_seek_table_write: the three arrays and dst are DEVICE pointers; dst may have any alignment, each destination byte is
+ * written once, by a store that covers only bytes of the table.  It only enqueues on `stream` (no wait, no scratch); arguments are
+ * checked before the device is looked for, and a table that does not fit does not touch it.  No reference counterpart.
+ */
+int chip_zstd_seek_table_write_host(uint64_t n, const uint32_t *c_len, const uint32_t *d_len, const uint32_t *checksum, void *dst,
+                                    uint64_t dst_cap, uint64_t *table_bytes);
+int chip_zstd_seek_table_write(uint64_t n, const uint32_t *c_len, const uint32_t *d_len, const uint32_t *checksum, void *dst,
+                               uint64_t dst_cap, uint64_t *table_bytes, void *stream);
+
+/*
+ * XXH64 of many ranges of DEVICE memory: digest[i] = XXH64, seed 0, of base[off[i] .. + len[i]), all 64 bits (a table's entry
+ * holds the low 32); len[i] == 0 gives 0xEF46DB3751D8E999.  Every pointer is a DEVICE pointer.  off[i] may have any alignment;
+ * loads stay inside the aligned dwords that hold bytes of the range.  len is 32-bit so that a plan's out_off / out_cap go in
+ * unchanged.  It only enqueues on `stream`: no wait, no scratch.
+ * One wave hashes one range.  XXH64 is a serial chain per range: many ranges fill the card, one huge range runs at one wave's
+ * rate (1.1 GB/s) -- that is the limit of this form.
+ * CHIP_E_INVALID, before the device is looked for: a NULL array or base with n > 0, n > 2^31 - 1.  n == 0: CHIP_OK, the device is
+ * not touched.  CHIP_E_LAUNCH: the launch failed.  No reference counterpart.
+ */
+int chip_xxh64_batch(size_t n, const void *base, const uint64_t *off, const uint32_t *len, uint64_t *digest, void *stream);
+
+/*
+ * chip_read_ranges(CHIP_FMT_ZSTD, ..) over the plan of a seek table, with the table's checksums verified on the device.
+ * With checksum == NULL it IS that call, to the byte and to the summary.  With checksum (a DEVICE array of n_units entries):
+ * behind the decode and its check of status and length, one wave hashes the decoded image of each selected unit that is not
+ * already bad; a unit whose XXH64's low 32 bits differ from checksum[unit] becomes a bad unit with bad_status -22, the decoder's
+ * own code for a wrong content checksum.  n_bad counts a unit once; ranges whose span holds a bad unit get CHIP_RANGE_BAD_UNIT.
+ * The rest of chip_read_ranges' contract holds word for word: the argument checks (the format is fixed), the two waits, the
+ * scratch and its slot, and "units no range touches are never decoded, damaged or not" -- nor are their checksums or in_off looked
+ * at.  in_off are whatever the caller hands over: a reader that holds only part of the file rebases the selected units' offsets
+ * to its own buffer.  No reference counterpart.
+ */
+int chip_zstd_seek_read(size_t n_units, const void *in_base, const uint64_t *in_off, const uint32_t *in_len, const uint64_t *out_off,
+                        const uint32_t *out_cap, const uint32_t *checksum, size_t n_ranges, const uint64_t *range_lo,
+                        const uint32_t *range_len, void *dst_base, uint64_t dst_cap, uint64_t *dst_off, int32_t *range_status,
+                        chip_read_summary *summary, void *stream);
+
 /* ---- one large stream: the checkpoint index (additive API) ------------------ */
 
 /*

@@ -461,6 +461,29 @@ pub struct chip_read_summary {
     pub bad_status: i32,
 }
 
+///`chip_zstd_seek_summary::status`
+pub const CHIP_ZSEEK_OK: i32 = 0;
+pub const CHIP_ZSEEK_NO_TABLE: i32 = 1;
+pub const CHIP_ZSEEK_NEED_TAIL: i32 = 2;
+pub const CHIP_ZSEEK_BAD_TABLE: i32 = 3;
+pub const CHIP_ZSEEK_TOO_LARGE: i32 = 4;
+pub const CHIP_ZSEEK_BAD_LAYOUT: i32 = 5;
+
+///what the walk over a seek table found: entries, the table's size (on `CHIP_ZSEEK_NEED_TAIL` the tail to come back with), the
+///sums of the compressed and the content sizes, the lowest entry without a size on `CHIP_ZSEEK_TOO_LARGE`, whether the entries
+///carry checksums
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct chip_zstd_seek_summary {
+    pub n_frames: u64,
+    pub table_bytes: u64,
+    pub frames_bytes: u64,
+    pub total_out: u64,
+    pub bad_index: u64,
+    pub status: i32,
+    pub checksums: u32,
+}
+
 ///what `chip_inflate_index_build` found: points of the whole walk; `out_len`, `in_used`, `status` as `chip_decode_batch` answers
 ///them for the unit; `wrap` 0 raw / 1 zlib / 2 gzip; with `CHIP_FINISHED`, `check` the content's CRC-32 / Adler-32 and `end_bit`
 ///the bit behind the final block
@@ -777,6 +800,30 @@ extern "C" {
     pub fn chip_read_ranges(format: c_int, n_units: usize, in_base: *const c_void, in_off: *const u64, in_len: *const u32, out_off: *const u64,
                             out_cap: *const u32, n_ranges: usize, range_lo: *const u64, range_len: *const u32, dst_base: *mut c_void, dst_cap: u64,
                             dst_off: *mut u64, range_status: *mut i32, summary: *mut chip_read_summary, stream: *mut c_void) -> c_int;
+
+    // ---- seekable zstd files: the seek table as a plan (no reference counterpart)
+    ///the seek table at the end of `tail` (the last `tail_len` bytes of a file of `file_len`) as a plan: pure host arithmetic;
+    ///`max_frames` 0 with null arrays counts, `checksum` may be null
+    pub fn chip_zstd_seek_plan_host(tail: *const u8, tail_len: u64, file_len: u64, max_frames: u64, in_off: *mut u64, in_len: *mut u32,
+                                    out_off: *mut u64, out_cap: *mut u32, checksum: *mut u32, summary: *mut chip_zstd_seek_summary) -> c_int;
+    ///the same for a tail in device memory at any alignment (device arrays, host summary); synchronous on `stream`
+    pub fn chip_zstd_seek_plan(tail: *const c_void, tail_len: u64, file_len: u64, max_frames: u64, in_off: *mut u64, in_len: *mut u32,
+                               out_off: *mut u64, out_cap: *mut u32, checksum: *mut u32, summary: *mut chip_zstd_seek_summary,
+                               stream: *mut c_void) -> c_int;
+    ///a seek table of `n` entries into host memory (`checksum` null: 8-byte entries); `table_bytes` is always the exact size
+    pub fn chip_zstd_seek_table_write_host(n: u64, c_len: *const u32, d_len: *const u32, checksum: *const u32, dst: *mut c_void, dst_cap: u64,
+                                           table_bytes: *mut u64) -> c_int;
+    ///the same from device arrays into device memory at any alignment (`table_bytes` a host pointer); only enqueues
+    pub fn chip_zstd_seek_table_write(n: u64, c_len: *const u32, d_len: *const u32, checksum: *const u32, dst: *mut c_void, dst_cap: u64,
+                                      table_bytes: *mut u64, stream: *mut c_void) -> c_int;
+    ///XXH64 (seed 0, all 64 bits) of `n` ranges of device memory, one wave per range; only enqueues
+    pub fn chip_xxh64_batch(n: usize, base: *const c_void, off: *const u64, len: *const u32, digest: *mut u64, stream: *mut c_void) -> c_int;
+    ///`chip_read_ranges(CHIP_FMT_ZSTD, ..)` with the seek table's per-unit checksums verified on the device (`checksum` null: that
+    ///call itself); synchronous on `stream`
+    pub fn chip_zstd_seek_read(n_units: usize, in_base: *const c_void, in_off: *const u64, in_len: *const u32, out_off: *const u64,
+                               out_cap: *const u32, checksum: *const u32, n_ranges: usize, range_lo: *const u64, range_len: *const u32,
+                               dst_base: *mut c_void, dst_cap: u64, dst_off: *mut u64, range_status: *mut i32, summary: *mut chip_read_summary,
+                               stream: *mut c_void) -> c_int;
 
     // ---- one large stream: the checkpoint index of a gzip / zlib / raw deflate stream (no reference counterpart)
     ///decode the one unit and record a point every `spacing` decoded bytes (0 = 1 MiB): device buffers and arrays, host summary;
