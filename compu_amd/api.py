@@ -167,6 +167,20 @@ class _InflateIndexSummary(C.Structure):
 _lib = None
 
 
+class _Lz4Block(C.Structure):
+    _fields_ = [("offset", C.c_uint64), ("size", C.c_uint32), ("flags", C.c_uint32), ("checksum", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class _Lz4BlocksSummary(C.Structure):
+    _fields_ = [("n_blocks", C.c_uint64), ("in_used", C.c_uint64), ("content_size", C.c_uint64), ("block_max", C.c_uint32), ("flg", C.c_uint32),
+                ("bd", C.c_uint32), ("header_bytes", C.c_uint32), ("content_checksum", C.c_uint32), ("status", C.c_int32)]
+
+
+class _Lz4ParallelSummary(C.Structure):
+    _fields_ = [("n_blocks", C.c_uint64), ("out_len", C.c_uint64), ("in_used", C.c_uint64), ("total_out", C.c_uint64), ("status", C.c_int32),
+                ("path", C.c_uint32), ("check", C.c_uint32), ("pad", C.c_uint32)]
+
+
 class _InflateParallelSummary(C.Structure):
     _fields_ = [("n_points", C.c_uint64), ("out_len", C.c_uint64), ("in_used", C.c_uint64), ("end_bit", C.c_uint64), ("total_out", C.c_uint64),
                 ("n_starts", C.c_uint64), ("n_false", C.c_uint64), ("status", C.c_int32), ("wrap", C.c_uint32), ("check", C.c_uint32),
@@ -344,6 +358,16 @@ def lib():
     L.chip_zstd_seek_table_write.argtypes = [u64, vp, vp, vp, vp, u64, C.POINTER(u64), vp]
     L.chip_xxh64_batch.restype = C.c_int
     L.chip_xxh64_batch.argtypes = [sz, vp, vp, vp, vp, vp]
+    L.chip_xxh32_batch.restype = C.c_int
+    L.chip_xxh32_batch.argtypes = [sz, vp, vp, vp, C.c_uint32, vp, vp]
+    L.chip_lz4_block_decode_host.restype = C.c_int
+    L.chip_lz4_block_decode_host.argtypes = [vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64)]
+    L.chip_lz4_blocks_host.restype = C.c_int
+    L.chip_lz4_blocks_host.argtypes = [vp, u64, u64, vp, C.POINTER(_Lz4BlocksSummary)]
+    L.chip_lz4_blocks.restype = C.c_int
+    L.chip_lz4_blocks.argtypes = [vp, u64, u64, vp, C.POINTER(_Lz4BlocksSummary), vp]
+    L.chip_lz4_parallel.restype = C.c_int
+    L.chip_lz4_parallel.argtypes = [vp, u64, vp, u64, C.c_uint32, C.POINTER(_Lz4ParallelSummary), vp]
     L.chip_zstd_seek_read.restype = C.c_int
     L.chip_zstd_seek_read.argtypes = [sz, vp, vp, vp, vp, vp, vp, sz, vp, vp, vp, u64, vp, vp, C.POINTER(_ReadSummary), vp]
     L.chip_inflate_index_build.restype = C.c_int
@@ -432,6 +456,8 @@ class ZlibMode(enum.IntEnum):
 
 FMT_ZSTD = 100
 FMT_BROTLI = 101  # Interface::brotli_c decoder and encoder
+FMT_LZ4_BLOCK = 102  # CHIP_FMT_LZ4_BLOCK: one raw LZ4 block per unit (the batch calls only; decode only)
+FMT_LZ4 = 103  # CHIP_FMT_LZ4: one LZ4 frame per unit (the batch calls only; decode only)
 
 
 class ZstdOptions:
@@ -3528,7 +3554,9 @@ def tar_open(in_buf, length, fmt=None, stream=None):
     fetched in one packed copy.  fmt None sniffs the first bytes (chip_detect): gzip and zlib go through inflate_parallel, zstd
     through zstd_parallel, anything else is taken as a plain tar image (which then stays in in_buf: no copy).  A zlib verdict rests
     on two bytes, which a plain tar's first member name can spell ("XG", "HK", "x^"): it is trusted only when bytes 257..261 are not
-    `ustar`.  fmt may also be given, and is then not questioned: Detection.Gzip / Zlib / Zstd / Unknown (= plain).
+    `ustar`.  A .tar.lz4 is known by the LZ4 frame magic (the sniff is made here: chip_detect knows no LZ4) and goes through
+    lz4_parallel: its first frame is the archive.  fmt may also be given, and is then not questioned: Detection.Gzip / Zlib / Zstd /
+    Unknown (= plain), or the string "lz4".
     Limits are those of the one-shot decodes: a gzip / zlib stream of at most 2^29 - 64 bytes that decodes to at most 2^32 - 16; a
     zstd frame of at most 2^32 - 1 bytes, below 2^31 decoded bytes on the parallel path and within a unit (2^28 input bytes) on the
     serial one.  A larger archive belongs to the slab loops (inflate_parallel_stream, zstd_parallel_stream).
@@ -3540,8 +3568,15 @@ def tar_open(in_buf, length, fmt=None, stream=None):
         fmt = Detection.detect(head[:4])
         if fmt == Detection.Zlib and head[257:262] == b"ustar":
             fmt = Detection.Unknown  # a member name that begins like a zlib header ("XGBoost-1.0/": 58 47), not a zlib stream
+        if head[:4] == LZ4_MAGIC.to_bytes(4, "little"):
+            fmt = "lz4"  # (chip_detect knows no LZ4: the sniff is made here; no member name begins with 04 22 4d 18)
     content, n = in_buf, length
-    if fmt in (Detection.Gzip, Detection.Zlib):
+    if fmt == "lz4":
+        content, s = lz4_parallel(in_buf, length, stream=stream)
+        if s.status != int(DecodeStatus.Finished):
+            raise ValueError(f"tar_open: the LZ4 frame did not finish: status {s.status} at input byte {s.in_used}")
+        n = s.out_len
+    elif fmt in (Detection.Gzip, Detection.Zlib):
         content, s = inflate_parallel(ZlibMode.Gzip if fmt == Detection.Gzip else ZlibMode.Zlib, in_buf, length, stream=stream)
         if s.status != int(DecodeStatus.Finished):
             raise ValueError(f"tar_open: the {Detection(fmt).name} stream did not finish: status {s.status} at input byte {s.in_used}")
@@ -3715,3 +3750,230 @@ def tar_write_items(items, flags=0, stream=None, device=None):
     d_src = torch.from_numpy(src.view(np.uint8).reshape(-1, 64).copy()).to(dev)
     d_names = torch.from_numpy(np.frombuffer(bytes(names), np.uint8).copy()).to(dev)
     return tar_write(d_src, d_names, content, flags=flags, stream=stream)
+
+
+# ---- LZ4: blocks and frames (include/compu_hip.h, "LZ4: blocks and frames"; decode only) ---------------
+
+
+LZ4_E_HEADER, LZ4_E_DICT, LZ4_E_BLOCK_SIZE, LZ4_E_BLOCK = -200, -201, -202, -203  # CHIP_LZ4_E_*
+LZ4_E_OFFSET, LZ4_E_BLOCK_CHECKSUM, LZ4_E_CONTENT_SIZE, LZ4_E_CONTENT_CHECKSUM = -204, -205, -206, -207
+LZ4BLOCKS_UNSIZED = 0xFFFFFFFFFFFFFFFF  # CHIP_LZ4BLOCKS_UNSIZED: content_size of a frame without C.Size
+LZ4BLOCK_STORED, LZ4BLOCK_LAST = 1, 2  # chip_lz4_block.flags
+LZ4PAR_SERIAL, LZ4PAR_PARALLEL, LZ4PAR_REFUSED = 0, 1, 2  # chip_lz4_parallel_summary.path
+LZ4PAR_NO_CHECKSUM = 1  # CHIP_LZ4PAR_NO_CHECKSUM
+LZ4_MAGIC = 0x184D2204
+
+
+def lz4_block_dtype():
+    """chip_lz4_block as a numpy record: offset (of the 4-byte block header), size, flags (LZ4BLOCK_*), checksum."""
+    import numpy as np
+
+    dt = np.dtype([("offset", "<u8"), ("size", "<u4"), ("flags", "<u4"), ("checksum", "<u4"), ("pad", "<u4")])
+    assert dt.itemsize == C.sizeof(_Lz4Block)
+    return dt
+
+
+class Lz4BlocksSummary:
+    """chip_lz4_blocks_summary: n_blocks the walk counted, in_used (the frame's end, 0 when the walk stopped early), content_size
+    (LZ4BLOCKS_UNSIZED without C.Size), block_max, the FLG and BD bytes, the header's length, the stored content checksum, status."""
+
+    __slots__ = ("n_blocks", "in_used", "content_size", "block_max", "flg", "bd", "header_bytes", "content_checksum", "status")
+
+    def __init__(self, raw):
+        self.n_blocks, self.in_used, self.content_size = int(raw.n_blocks), int(raw.in_used), int(raw.content_size)
+        self.block_max, self.flg, self.bd, self.header_bytes = int(raw.block_max), int(raw.flg), int(raw.bd), int(raw.header_bytes)
+        self.content_checksum, self.status = int(raw.content_checksum), ZstdPlanStatus(raw.status)
+
+    def as_tuple(self):
+        return (self.n_blocks, self.in_used, self.content_size, self.block_max, self.flg, self.bd, self.header_bytes, self.content_checksum,
+                int(self.status))
+
+    def __repr__(self):
+        return (f"Lz4BlocksSummary(n_blocks={self.n_blocks}, in_used={self.in_used}, content_size={self.content_size}, block_max={self.block_max}, "
+                f"flg={self.flg:#x}, bd={self.bd:#x}, header_bytes={self.header_bytes}, content_checksum={self.content_checksum:#x}, "
+                f"status={self.status.name})")
+
+
+def lz4_block_decode_host(data, out_cap):
+    """chip_lz4_block_decode_host: one raw LZ4 block (bytes-like) decoded on the host into out_cap bytes of room: (out bytes --
+    the first out_len --, in_used, status).  The definition of the block rules."""
+    import numpy as np
+
+    buf = np.frombuffer(bytes(data), dtype=np.uint8)
+    out = np.zeros(int(out_cap), np.uint8)
+    ol, iu = C.c_uint64(0), C.c_uint64(0)
+    p = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None  # noqa: E731
+    st = lib().chip_lz4_block_decode_host(p(buf), buf.size, p(out), out.size, C.byref(ol), C.byref(iu))
+    if st == -101:
+        raise ValueError("chip_lz4_block_decode_host refused its arguments")
+    return out[:ol.value].tobytes(), int(iu.value), int(st)
+
+
+def lz4_blocks_host(data, max_blocks=None):
+    """chip_lz4_blocks_host over bytes / a uint8 numpy array in host memory: (blocks, summary) of the FIRST frame -- blocks a numpy
+    record array (lz4_block_dtype) of the first min(n_blocks, max_blocks) blocks (None = all of them: one call to count, one to
+    fill).  Read from headers alone; nothing is decoded."""
+    import numpy as np
+
+    buf = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8)
+    raw = _Lz4BlocksSummary()
+    p = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None  # noqa: E731
+    call = lib().chip_lz4_blocks_host
+    if max_blocks is None:
+        rc = call(p(buf), buf.size, 0, None, C.byref(raw))
+        if rc != 0:
+            raise RuntimeError(f"chip_lz4_blocks_host failed: {rc}")
+        max_blocks = int(raw.n_blocks)
+    m = int(max_blocks)
+    blocks = np.zeros(m, lz4_block_dtype())
+    rc = call(p(buf), buf.size, m, p(blocks), C.byref(raw))
+    if rc != 0:
+        raise RuntimeError(f"chip_lz4_blocks_host failed: {rc}")
+    return blocks[:min(m, int(raw.n_blocks))], Lz4BlocksSummary(raw)
+
+
+def lz4_blocks(in_buf, length, stream=None, max_blocks=None):
+    """chip_lz4_blocks over a uint8 device tensor holding `length` bytes that begin with an LZ4 frame (4-byte aligned, padded to a
+    multiple of 4): (blocks, summary), blocks a uint8 device tensor of shape (k, 24) holding the chip_lz4_block records of the first
+    k = min(n_blocks, max_blocks) blocks (`.cpu().numpy().view(lz4_block_dtype())` reads them).  Synchronous on `stream`.
+    max_blocks None: all of them (one call to count, one to fill)."""
+    import torch
+
+    dev = _check_tensors(((in_buf, torch.uint8),))
+    length = int(length)
+    if length < 0 or length > in_buf.numel():
+        raise ValueError(f"length {length} outside the buffer of {in_buf.numel()} bytes")
+    raw = _Lz4BlocksSummary()
+    base, sp = (_dp(in_buf) if length else None), _stream_ptr(stream)
+    call = lib().chip_lz4_blocks
+    with torch.cuda.device(dev):
+        if max_blocks is None:  # count, then fill
+            rc = call(base, length, 0, None, C.byref(raw), sp)
+            if rc != 0:
+                raise RuntimeError(f"chip_lz4_blocks failed: {rc}")
+            max_blocks = int(raw.n_blocks)
+        m = int(max_blocks)
+        blocks = torch.zeros((m, C.sizeof(_Lz4Block)), dtype=torch.uint8, device=dev)
+        rc = call(base, length, m, _dp(blocks) if m else None, C.byref(raw), sp)
+    if rc != 0:
+        raise RuntimeError(f"chip_lz4_blocks failed: {rc}")
+    return blocks[:min(m, int(raw.n_blocks))], Lz4BlocksSummary(raw)
+
+
+def xxh32_batch(buf, off, length, seed=0, stream=None):
+    """chip_xxh32_batch on device tensors: XXH32 with `seed` of buf[off[i] : off[i] + length[i]] for every i.  buf uint8, off int64
+    (read as u64), length int32 (read as u32).  Returns an int32 device tensor (read it as u32).  One wave per range.  Only
+    enqueues on `stream`."""
+    import torch
+
+    dev = _check_tensors(((buf, torch.uint8), (off, torch.int64), (length, torch.int32)))
+    n = off.numel()
+    if length.numel() != n:
+        raise ValueError("off and length must have one length")
+    digest = torch.empty(n, dtype=torch.int32, device=dev)
+    if n == 0:
+        return digest
+    with torch.cuda.device(dev):
+        rc = lib().chip_xxh32_batch(n, _dp(buf), _dp(off), _dp(length), int(seed) & 0xFFFFFFFF, _dp(digest), _stream_ptr(stream))
+    if rc != 0:
+        raise RuntimeError(f"chip_xxh32_batch failed: {rc}")
+    return digest
+
+
+class Lz4ParallelSummary:
+    """chip_lz4_parallel_summary: n_blocks of the frame, out_len, in_used, total_out (the size to come back with on NeedOutput),
+    status, path (LZ4PAR_*), check (the content checksum computed on the parallel path)."""
+
+    __slots__ = ("n_blocks", "out_len", "in_used", "total_out", "status", "path", "check")
+
+    def __init__(self, raw):
+        self.n_blocks, self.out_len, self.in_used, self.total_out = int(raw.n_blocks), int(raw.out_len), int(raw.in_used), int(raw.total_out)
+        self.status, self.path, self.check = int(raw.status), int(raw.path), int(raw.check)
+
+    def as_tuple(self):
+        return (self.n_blocks, self.out_len, self.in_used, self.total_out, self.status, self.path, self.check)
+
+    def __repr__(self):
+        return (f"Lz4ParallelSummary(n_blocks={self.n_blocks}, out_len={self.out_len}, in_used={self.in_used}, total_out={self.total_out}, "
+                f"status={self.status}, path={self.path}, check={self.check:#x})")
+
+
+def lz4_parallel(in_buf, length, out_buf=None, checksum=True, stream=None):
+    """chip_lz4_parallel over a uint8 device tensor holding `length` bytes that begin with ONE LZ4 frame (4-byte aligned, padded to a
+    multiple of 4): (out, summary).  With `out_buf` (a uint8 device tensor) the content goes there and `out` is its first out_len
+    bytes.  Without, the call is made with no room first, then with a new tensor of total_out bytes; a frame that takes the serial
+    path states no size that way, so it is sized by decode_batch_sizes as one unit and decoded with that room -- a frame that is
+    refused, or in error, comes back as the empty tensor and its summary.  checksum=False waives the comparison of the content
+    checksum on the parallel path.  Synchronous on `stream`."""
+    import torch
+
+    dev = _check_tensors(((in_buf, torch.uint8),) + (((out_buf, torch.uint8),) if out_buf is not None else ()))
+    length = int(length)
+    if length < 0 or length > in_buf.numel():
+        raise ValueError(f"length {length} outside the buffer of {in_buf.numel()} bytes")
+    raw = _Lz4ParallelSummary()
+    flags = 0 if checksum else LZ4PAR_NO_CHECKSUM
+    base, sp = (_dp(in_buf) if length else None), _stream_ptr(stream)
+
+    def call(out):
+        cap = out.numel() if out is not None else 0
+        rc = lib().chip_lz4_parallel(base, length, _dp(out) if cap else None, cap, flags, C.byref(raw), sp)
+        if rc != 0:
+            raise RuntimeError(f"chip_lz4_parallel failed: {rc}")
+
+    with torch.cuda.device(dev):
+        if out_buf is None:
+            call(None)
+            need = int(raw.total_out) if raw.status == int(DecodeStatus.NeedOutput) and raw.path == LZ4PAR_PARALLEL else 0
+            if raw.status == int(DecodeStatus.NeedOutput) and raw.path == LZ4PAR_SERIAL and length <= 0xFFFFFFFF:
+                one = lambda v, dt: torch.tensor([v], dtype=torch.int64, device=dev).to(dt)  # noqa: E731
+                size, _, st = decode_batch_sizes(FMT_LZ4, in_buf, one(0, torch.int64), one(length, torch.int32), stream=stream)
+                need = int(size[0]) if int(st[0]) == int(DecodeStatus.Finished) and int(size[0]) <= 0xFFFFFFFF else 0
+            out_buf = torch.empty(need, dtype=torch.uint8, device=dev)
+            if need:
+                call(out_buf)
+        else:
+            call(out_buf)
+    return out_buf[:int(raw.out_len)], Lz4ParallelSummary(raw)
+
+
+def lz4_decode(data, checksum=True, device=None, stream=None):
+    """The contents of a whole .lz4 file (bytes-like): concatenated frames are decoded one behind the other, each by lz4_parallel,
+    and skippable frames (magic 0x184D2A50 .. 5F, a 4-byte length) are stepped over on the host.  Returns a uint8 device tensor.
+    Raises ValueError where a frame does not finish (the message carries its offset, status and in_used), where bytes that are
+    no frame follow a frame, and on a legacy frame (magic 0x184C2102), which this library does not read.  Waits for the result."""
+    import numpy as np
+    import torch
+
+    data = bytes(data)
+    dev = torch.device("cuda" if device is None else device)
+    parts, p, n = [], 0, len(data)
+    while p < n:
+        if n - p < 4:
+            raise ValueError(f"lz4_decode: {n - p} stray bytes at offset {p}")
+        magic = int.from_bytes(data[p:p + 4], "little")
+        if 0x184D2A50 <= magic <= 0x184D2A5F:
+            if n - p < 8:
+                raise ValueError(f"lz4_decode: a skippable frame is cut off at offset {p}")
+            size = int.from_bytes(data[p + 4:p + 8], "little")
+            if n - p - 8 < size:
+                raise ValueError(f"lz4_decode: a skippable frame is cut off at offset {p}")
+            p += 8 + size
+            continue
+        if magic != LZ4_MAGIC:
+            raise ValueError(f"lz4_decode: no LZ4 frame at offset {p} (magic {magic:#010x})")
+        rest = np.frombuffer(data, np.uint8, offset=p)
+        _, walk = lz4_blocks_host(rest, 0)  # the frame's own bytes go up, where its headers say how many they are
+        if walk.status == ZstdPlanStatus.Ok:
+            rest = rest[:walk.in_used]
+        padded = np.zeros((rest.size + 3) // 4 * 4, np.uint8)
+        padded[:rest.size] = rest
+        d_in = torch.from_numpy(padded).to(dev)
+        out, s = lz4_parallel(d_in, rest.size, checksum=checksum, stream=stream)
+        if s.status != int(DecodeStatus.Finished):
+            raise ValueError(f"lz4_decode: the frame at offset {p} did not finish: status {s.status} at input byte {s.in_used}")
+        parts.append(out)
+        p += s.in_used
+    if not parts:
+        return torch.empty(0, dtype=torch.uint8, device=dev)
+    return parts[0] if len(parts) == 1 else torch.cat(parts)

@@ -100,6 +100,10 @@ hipError_t enqueue_zstd_sizes(const BatchArgs &a, uint64_t *out_size, int wlog_m
 // (zstd_members.hip, zstd_members_sizes.hip: the same for a CHIP_F_MEMBERS batch, decoder and size pass)
 hipError_t enqueue_zstd_members(const BatchArgs &a, int wlog_max, hipStream_t stream);
 hipError_t enqueue_zstd_members_sizes(const BatchArgs &a, uint64_t *out_size, int wlog_max, hipStream_t stream);
+// lz4.hip: CHIP_FMT_LZ4_BLOCK / CHIP_FMT_LZ4 (a.format), out_size == nullptr decodes the batch, else the size pass; no scratch
+hipError_t launch_lz4(const BatchArgs &a, uint64_t *out_size, hipStream_t stream);
+// (lz4.hip) XXH32, seed 0, of n bytes on one wave, to *got (device memory)
+hipError_t launch_lz4_xxh(const uint8_t *p, uint64_t n, uint32_t *got, hipStream_t stream);
 // launch_slots.hip: the cached launch scratch of every codec ("Launch slots")
 hipError_t release_scratch();                 // every slot of the current device, after a device sync
 void release_scratch_of(hipStream_t stream);  // the slots of one (drained) stream of the current device

@@ -48,6 +48,11 @@ enum {
      * BROTLI_DECODER_PARAM_LARGE_WINDOW), no shared dictionaries; not part of CHIP_FMT_DETECT routing (compu cannot detect
      * brotli) */
     CHIP_FMT_BROTLI = 101,
+    /* LZ4 (decode only; "LZ4: blocks and frames" below): one raw block of the LZ4 block format, delimited by in_len[i], and one
+     * frame of the LZ4 frame format.  The batch calls only (device, host and multi); not part of CHIP_FMT_DETECT routing, not with
+     * CHIP_F_COMPU_STATUS or CHIP_F_MEMBERS, and the streaming chip_decoder_new does not take them (compu has no LZ4). */
+    CHIP_FMT_LZ4_BLOCK = 102,
+    CHIP_FMT_LZ4 = 103,
     /* chip_encode_batch / _ex / _host and chip_encode_bound only: every unit becomes one BGZF block (below).  Decoding takes
      * CHIP_FMT_GZIP with the arrays of chip_bgzf_plan; the streaming chip_encoder_new does not take this tag. */
     CHIP_FMT_BGZF = 131,
@@ -199,7 +204,8 @@ int chip_decode_batch(int format, size_t n, const void *in_base, const uint64_t 
  * that owns the unit, as gzip -d and ZSTD_decompress do.  For CHIP_FMT_GZIP, CHIP_FMT_AUTO, CHIP_FMT_ZSTD and CHIP_FMT_DETECT (routed:
  * gzip / zlib units and zstd units each go to their member kernel, units that are neither are answered as without the flag).
  * CHIP_E_INVALID, before the device is looked for, with CHIP_FMT_DEFLATE, CHIP_FMT_ZLIB and CHIP_FMT_BROTLI (no concatenation
- * convention) and together with CHIP_F_COMPU_STATUS (compu has no multi-member decode to mirror).  No reference counterpart, and
+ * convention), with the LZ4 tags (concatenated frames are the caller's loop) and together with CHIP_F_COMPU_STATUS (compu has
+ * no multi-member decode to mirror).  No reference counterpart, and
  * batch only: the streaming decoders do not take it (compu's caller sees Finished, calls reset and goes on), nor do
  * chip_decode_batch_host / _multi, which have no flags word.
  * The contract.  decode1(p, room) is what a unit without the flag answers for the input in[p .. len) and `room` bytes of output:
@@ -253,7 +259,8 @@ int chip_decode_batch_ex(int format, uint32_t flags, size_t n, const void *in_ba
  * with the same flag; out_size[i] is the series' total and may exceed 2^32.
  * `format`: CHIP_FMT_DEFLATE, CHIP_FMT_ZLIB, CHIP_FMT_GZIP, CHIP_FMT_AUTO, CHIP_FMT_ZSTD (window_log_max: the default, as
  * chip_decode_batch), and CHIP_FMT_DETECT, routed exactly as a CHIP_FMT_DETECT decode batch is (units that are neither get
- * CHIP_UNKNOWN_FORMAT / CHIP_NEED_INPUT).  CHIP_FMT_BROTLI is CHIP_E_INVALID: brotli's literal context is the two previous
+ * CHIP_UNKNOWN_FORMAT / CHIP_NEED_INPUT), and CHIP_FMT_LZ4_BLOCK / CHIP_FMT_LZ4 (flags 0 only; "LZ4: blocks and frames" below says
+ * what the pass checks).  CHIP_FMT_BROTLI is CHIP_E_INVALID: brotli's literal context is the two previous
  * BYTES, so a brotli size pass is a full decode (it would decode into a ring) -- a different design.  Arguments are checked
  * before the device is looked for (as chip_decode_batch_ex does).
  * The contract:
@@ -1491,6 +1498,168 @@ int chip_zstd_seek_read(size_t n_units, const void *in_base, const uint64_t *in_
                         const uint32_t *out_cap, const uint32_t *checksum, size_t n_ranges, const uint64_t *range_lo,
                         const uint32_t *range_len, void *dst_base, uint64_t dst_cap, uint64_t *dst_off, int32_t *range_status,
                         chip_read_summary *summary, void *stream);
+
+/* ---- LZ4: blocks and frames (additive API, decode only) ------------------- */
+
+/*
+ * CHIP_FMT_LZ4_BLOCK (102): a unit is ONE raw block of the LZ4 block format, delimited by in_len[i]; no prefix, no dictionary.
+ * CHIP_FMT_LZ4 (103): a unit is ONE frame of the LZ4 frame format 1.6.x (magic 0x184D2204).
+ * Both go to chip_decode_batch / _ex / _sizes / _host / _multi, one wave per unit.  CHIP_F_COMPU_STATUS and CHIP_F_MEMBERS with
+ * either tag: CHIP_E_INVALID before the device is looked for (compu has no LZ4 to mirror; concatenated frames are the caller's
+ * loop).  chip_detect / CHIP_FMT_DETECT never route to them, the streaming decoders do not take them.  No reference counterpart.
+ *
+ * THE BLOCK RULES, which chip_lz4_block_decode_host defines (p: input cursor, o: bytes produced, len = in_len, cap = out_cap):
+ *   sequence:  t = p (the token's offset)
+ *     p == len                                   -> CHIP_NEED_INPUT      (so in_len == 0 is CHIP_NEED_INPUT)
+ *     token = in[p++];  L = token >> 4;  if L == 15: add bytes while the byte just added was 255 (p == len there: CHIP_NEED_INPUT)
+ *     L > len - p                                -> CHIP_NEED_INPUT      (the input is looked at before the room)
+ *     L > cap - o                                -> CHIP_NEED_OUTPUT
+ *     copy L literals;  o += L;  p += L
+ *     p == len                                   -> CHIP_FINISHED        (the low nibble of this last token is not looked at)
+ *     len - p < 2                                -> CHIP_NEED_INPUT
+ *     offset = LE16(p);  p += 2
+ *     offset == 0 or offset > o                  -> CHIP_LZ4_E_OFFSET    (before the match length's extension bytes are read)
+ *     M = token & 15;  if M == 15: extension bytes as above (CHIP_NEED_INPUT where they end with the input);  M += 4
+ *     M > cap - o                                -> CHIP_NEED_OUTPUT
+ *     copy M bytes from o - offset, byte by byte in effect (offset < M repeats a period);  o += M
+ * Lengths accumulate in 64 bits: no run of extension bytes wraps anything.  The end-of-block restrictions of the format document
+ * (the last five bytes are literals, the last match starts 12 bytes before the end) are duties of encoders and are NOT enforced;
+ * offsets are checked strictly.  The one-byte block 00 decodes to nothing.
+ * On CHIP_FINISHED in_used == in_len.  On every other status in_used = t, the offset of the token of the sequence in which
+ * decoding stopped, and out_len = o, the complete literal runs and matches in front of the run that stopped it (a literal run
+ * that was copied counts, although its sequence did not finish).  Bytes between out_len and out_cap may have been used; nothing
+ * beyond out_cap is touched.
+ *
+ * THE FRAME RULES, in the order of the checks (q: input cursor; every offset below is relative to the unit's first byte):
+ *   len < 7                                      -> CHIP_NEED_INPUT
+ *   LE32(0) != 0x184D2204                        -> CHIP_LZ4_E_HEADER    (the legacy magic 0x184C2102 and the skippable magics
+ *                                                                         0x184D2A50..5F included: one unit is one frame)
+ *   FLG = in[4], BD = in[5]:  version (FLG >> 6) != 1, FLG bit 1, BD bit 7 or BD bits 0..3 set, block maximum code
+ *   (BD >> 4) & 7 outside 4..7                   -> CHIP_LZ4_E_HEADER
+ *   hs = 7 + (C.Size ? 8 : 0) + (DictID ? 4 : 0);  len < hs -> CHIP_NEED_INPUT
+ *   in[hs - 1] != (XXH32(in[4 .. hs - 1), 0) >> 8) & 0xff   -> CHIP_LZ4_E_HEADER
+ *   DictID flag (FLG bit 0)                      -> CHIP_LZ4_E_DICT      (there are no dictionaries here)
+ *   block maximum = 64 KiB, 256 KiB, 1 MiB, 4 MiB for the codes 4..7;  q = hs
+ *   per block, b = q:
+ *     len - q < 4                                -> CHIP_NEED_INPUT
+ *     w = LE32(q);  w == 0: the EndMark, q += 4, the blocks are done
+ *     size = w & 0x7fffffff > block maximum      -> CHIP_LZ4_E_BLOCK_SIZE  (compressed or stored)
+ *     len - q - 4 < size + (B.Checksum ? 4 : 0)  -> CHIP_NEED_INPUT
+ *     stored (w bit 31): size > cap - o -> CHIP_NEED_OUTPUT; the bytes are copied
+ *     compressed: the block rules over in[q + 4 .. + size), where an offset may reach as far as the block's own first byte
+ *       (B.Indep) or the frame's first byte (linked blocks; at most 65 535 back, the field's range), with these changes:
+ *       a literal run or match that takes the block beyond the block maximum -> CHIP_LZ4_E_BLOCK_SIZE (looked at before the
+ *       room), and what is CHIP_NEED_INPUT for a lone block is CHIP_LZ4_E_BLOCK here (the block's bytes are all present)
+ *     B.Checksum: LE32 behind the block != XXH32(the block's `size` bytes as they lie in the file, 0) -> CHIP_LZ4_E_BLOCK_CHECKSUM
+ *     q += 4 + size (+ 4)
+ *   C.Checksum and len - q < 4                   -> CHIP_NEED_INPUT
+ *   C.Size and the stated size != o              -> CHIP_LZ4_E_CONTENT_SIZE
+ *   C.Checksum and LE32(q) != XXH32(content, 0)  -> CHIP_LZ4_E_CONTENT_CHECKSUM
+ *   CHIP_FINISHED, in_used = the frame's length; bytes behind the frame are trailing bytes and are not counted.
+ * Where the issue is one element's, the checks of that element run in the order written, elements front to back: a frame whose
+ * second block is damaged and whose fourth is cut off answers for the second.
+ * out_len: the content in front of the error -- on CHIP_NEED_OUTPUT, CHIP_LZ4_E_BLOCK, _OFFSET and _BLOCK_SIZE inside a block the
+ * complete runs and matches in front of the one that failed (earlier blocks in full); on CHIP_LZ4_E_BLOCK_CHECKSUM the blocks in
+ * front of the block whose checksum is wrong; on CHIP_LZ4_E_CONTENT_SIZE and CHIP_LZ4_E_CONTENT_CHECKSUM the whole content.
+ * in_used on anything but CHIP_FINISHED: the offset of the element in which decoding stopped -- 0 for the frame header, b for a
+ * block (its 4-byte header; the EndMark's offset when the content checksum behind it is cut off), and the frame's length for
+ * CHIP_LZ4_E_CONTENT_SIZE and CHIP_LZ4_E_CONTENT_CHECKSUM, which are found behind its last byte.
+ * The size pass (chip_decode_batch_sizes) keeps its four contract rules: every check above except the two XXH32 comparisons of
+ * blocks and content (the header checksum IS checked); a stated content size is not trusted, the blocks are walked.
+ */
+enum {
+    CHIP_LZ4_E_HEADER = -200,
+    CHIP_LZ4_E_DICT = -201,
+    CHIP_LZ4_E_BLOCK_SIZE = -202,
+    CHIP_LZ4_E_BLOCK = -203,
+    CHIP_LZ4_E_OFFSET = -204,
+    CHIP_LZ4_E_BLOCK_CHECKSUM = -205,
+    CHIP_LZ4_E_CONTENT_SIZE = -206,
+    CHIP_LZ4_E_CONTENT_CHECKSUM = -207
+};
+
+/* The block rules on HOST memory, and their definition: returns the status (CHIP_FINISHED, CHIP_NEED_INPUT, CHIP_NEED_OUTPUT,
+ * CHIP_LZ4_E_OFFSET), or CHIP_E_INVALID for a NULL out_len / in_used, a NULL `in` with len > 0 or a NULL `out` with cap > 0.
+ * len and cap are at most 2^32 - 1 (CHIP_E_INVALID), as a unit's are.  Pure host arithmetic. */
+int chip_lz4_block_decode_host(const uint8_t *in, uint64_t len, uint8_t *out, uint64_t cap, uint64_t *out_len, uint64_t *in_used);
+
+/*
+ * The blocks of the FIRST frame of a buffer, from its headers alone, with chip_zstd_blocks' conventions.  The walk of `len` bytes:
+ *     len < 7 -> TRUNCATED;  the header checks of the frame rules: CHIP_LZ4_E_HEADER and CHIP_LZ4_E_DICT -> BAD_HEADER,
+ *     CHIP_NEED_INPUT -> TRUNCATED;  q = hs;  n = 0
+ *     per block:  len - q < 4 -> TRUNCATED;  w = LE32(q);  w == 0 -> the EndMark: the block before it gets CHIP_LZ4BLOCK_LAST, q += 4
+ *                 size = w & 0x7fffffff > block_max -> BAD_HEADER;  n + 1 > CHIP_ZPLAN_MAX_BLOCKS -> TOO_LARGE
+ *                 len - q - 4 < size + (B.Checksum ? 4 : 0) -> TRUNCATED
+ *                 block n: offset = q, size, flags = (w >> 31) ? CHIP_LZ4BLOCK_STORED : 0, checksum = the LE32 behind it or 0
+ *                 n++;  q += 4 + size (+ 4)
+ *     C.Checksum: len - q < 4 -> TRUNCATED;  content_checksum = LE32(q);  q += 4
+ *     in_used = q, status CHIP_ZPLAN_OK
+ * A walk that stops early keeps the blocks it has counted, with in_used = 0.  Nothing is decoded, no checksum but the header's is
+ * compared.  `blocks` receives the first min(n_blocks, max_blocks) records: max_blocks = 0 with a NULL array counts, a second call
+ * fills (CHIP_LZ4BLOCK_LAST is set only on a record that is written).  status: CHIP_ZPLAN_OK, _TRUNCATED, _BAD_HEADER, _TOO_LARGE.
+ * flg, bd, header_bytes (hs), block_max and content_size are filled once the header has been accepted, else 0 /
+ * CHIP_LZ4BLOCKS_UNSIZED.  CHIP_E_INVALID, before the device is looked for: summary NULL, a NULL buffer with len > 0, a NULL array
+ * with max_blocks > 0 (chip_lz4_blocks: in_base not 4-byte aligned, len > 2^40).
+ */
+#define CHIP_LZ4BLOCKS_UNSIZED 0xFFFFFFFFFFFFFFFFull /* content_size of a frame without C.Size */
+enum { CHIP_LZ4BLOCK_STORED = 1, CHIP_LZ4BLOCK_LAST = 2 };
+typedef struct {
+    uint64_t offset;   /* of the block's 4-byte header in the buffer */
+    uint32_t size;     /* the bytes behind the header: compressed, or stored as they are */
+    uint32_t flags;    /* CHIP_LZ4BLOCK_* */
+    uint32_t checksum; /* the stored block checksum (B.Checksum), else 0 */
+    uint32_t pad;
+} chip_lz4_block;
+typedef struct {
+    uint64_t n_blocks, in_used, content_size;
+    uint32_t block_max, flg, bd, header_bytes;
+    uint32_t content_checksum; /* the stored one (C.Checksum, status OK), else 0 */
+    int32_t status;
+} chip_lz4_blocks_summary;
+int chip_lz4_blocks_host(const uint8_t *in, uint64_t len, uint64_t max_blocks, chip_lz4_block *blocks, chip_lz4_blocks_summary *summary);
+/* The same for DEVICE memory: in_base and blocks are DEVICE pointers, summary is a HOST pointer; in_base 4-byte aligned, its
+ * allocation padded to a multiple of 4.  One lane hops over the block headers.  SYNCHRONOUS on `stream` (one wait); a launch
+ * slot of its own (the summary only), released by chip_trim(). */
+int chip_lz4_blocks(const void *in_base, uint64_t len, uint64_t max_blocks, chip_lz4_block *blocks, chip_lz4_blocks_summary *summary,
+                    void *stream);
+
+/* XXH32 of many ranges of DEVICE memory, chip_xxh64_batch's sibling: digest[i] = XXH32 with `seed` of base[off[i] .. + len[i]).
+ * Every pointer is a DEVICE pointer, off[i] may have any alignment; it only enqueues on `stream`: no wait, no scratch.  One wave
+ * hashes one range, and XXH32 is one serial chain per range.  CHIP_E_INVALID, before the device is looked for: a NULL array or
+ * base with n > 0, n > 2^31 - 1.  n == 0: CHIP_OK, the device is not touched. */
+int chip_xxh32_batch(size_t n, const void *base, const uint64_t *off, const uint32_t *len, uint32_t seed, uint32_t *digest, void *stream);
+
+/*
+ * ONE large LZ4 frame decoded by the whole GPU, a wave per block, with chip_zstd_parallel's conventions: in_base and out_base are
+ * DEVICE pointers, in_base 4-byte aligned and its allocation padded to a multiple of 4; summary is a HOST pointer; SYNCHRONOUS on
+ * `stream`; scratch in a launch slot of its own (80 bytes per block: its record and its unit arrays), released by chip_trim().  Only the
+ * FIRST frame of the buffer is decoded; in_used says where it ended.
+ * path = CHIP_LZ4PAR_PARALLEL when: the walk (chip_lz4_blocks) is OK; B.Indep is set; the frame has at least two blocks; the size
+ * pass over the compressed blocks (a CHIP_FMT_LZ4_BLOCK batch) answers CHIP_FINISHED for each with at most block_max bytes; a
+ * stated content size equals the counted one; every block checksum and the content checksum match (the latter unless waived).  The passes: the walk; the size pass; a device scan for the layout (chip_layout_units); the block batch straight
+ * into out_base; stored blocks placed by the file writer's copy; the block checksums by the XXH32 batch; the content checksum on
+ * one wave.  The bytes, out_len, in_used and status (CHIP_FINISHED) are those of chip_decode_batch(CHIP_FMT_LZ4, 1, ..).
+ * The same with total_out > out_cap: CHIP_NEED_OUTPUT, out_len = 0, total_out the exact size to come back with; nothing is
+ * written and no checksum is compared (the call that has the room compares them).
+ * Anything else, a linked-block frame and a checksum mismatch included: path = CHIP_LZ4PAR_SERIAL and the answer is the one-unit
+ * CHIP_FMT_LZ4 decode's, status and out_len included -- that decode is the arbiter of every verdict (after a mismatch it writes
+ * the bytes again) -- if a unit can hold the frame (len and out_cap at most 2^32 - 1); else path = CHIP_LZ4PAR_REFUSED and nothing
+ * is written.
+ * CHIP_LZ4PAR_NO_CHECKSUM: on the parallel path the content checksum is read over, not compared (XXH32 is one serial chain: one
+ * wave hashes the whole content); block checksums are still compared.  The one deliberate difference from the batch.
+ * summary.check: the content checksum computed on the parallel path, else 0.
+ * CHIP_E_INVALID before the device is looked for: summary NULL, a NULL buffer with a length, in_base misaligned, unknown flag
+ * bits, len > 2^40.
+ */
+enum { CHIP_LZ4PAR_SERIAL = 0, CHIP_LZ4PAR_PARALLEL = 1, CHIP_LZ4PAR_REFUSED = 2 };
+#define CHIP_LZ4PAR_NO_CHECKSUM 1u /* flags: do not verify the content checksum on the parallel path */
+typedef struct {
+    uint64_t n_blocks, out_len, in_used, total_out;
+    int32_t status;
+    uint32_t path, check, pad;
+} chip_lz4_parallel_summary;
+int chip_lz4_parallel(const void *in_base, uint64_t len, void *out_base, uint64_t out_cap, uint32_t flags,
+                      chip_lz4_parallel_summary *summary, void *stream);
 
 /* ---- one large stream: the checkpoint index (additive API) ------------------ */
 

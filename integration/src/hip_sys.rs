@@ -184,6 +184,72 @@ pub struct chip_zstd_parallel_summary {
     pub check: u32,
 }
 
+///LZ4 (decode only, the batch calls only; no compu counterpart): one raw block per unit, one frame per unit
+pub const CHIP_FMT_LZ4_BLOCK: c_int = 102;
+pub const CHIP_FMT_LZ4: c_int = 103;
+///per-unit status of an LZ4 unit, beside `CHIP_NEED_INPUT` / `CHIP_NEED_OUTPUT` / `CHIP_FINISHED`
+pub const CHIP_LZ4_E_HEADER: i32 = -200;
+pub const CHIP_LZ4_E_DICT: i32 = -201;
+pub const CHIP_LZ4_E_BLOCK_SIZE: i32 = -202;
+pub const CHIP_LZ4_E_BLOCK: i32 = -203;
+pub const CHIP_LZ4_E_OFFSET: i32 = -204;
+pub const CHIP_LZ4_E_BLOCK_CHECKSUM: i32 = -205;
+pub const CHIP_LZ4_E_CONTENT_SIZE: i32 = -206;
+pub const CHIP_LZ4_E_CONTENT_CHECKSUM: i32 = -207;
+///`chip_lz4_blocks_summary::content_size` of a frame without C.Size
+pub const CHIP_LZ4BLOCKS_UNSIZED: u64 = u64::MAX;
+///`chip_lz4_block::flags`
+pub const CHIP_LZ4BLOCK_STORED: u32 = 1;
+pub const CHIP_LZ4BLOCK_LAST: u32 = 2;
+
+///one block of an LZ4 frame as `chip_lz4_blocks` describes it: where its 4-byte header lies, its size, flags, stored checksum
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct chip_lz4_block {
+    pub offset: u64,
+    pub size: u32,
+    pub flags: u32,
+    pub checksum: u32,
+    pub pad: u32,
+}
+
+///what the walk over an LZ4 frame's block headers found; `status` is a `CHIP_ZPLAN_*` value
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct chip_lz4_blocks_summary {
+    pub n_blocks: u64,
+    pub in_used: u64,
+    pub content_size: u64,
+    pub block_max: u32,
+    pub flg: u32,
+    pub bd: u32,
+    pub header_bytes: u32,
+    pub content_checksum: u32,
+    pub status: i32,
+}
+
+///`chip_lz4_parallel_summary::path`
+pub const CHIP_LZ4PAR_SERIAL: u32 = 0;
+pub const CHIP_LZ4PAR_PARALLEL: u32 = 1;
+pub const CHIP_LZ4PAR_REFUSED: u32 = 2;
+///`chip_lz4_parallel` flag: do not verify the content checksum on the parallel path
+pub const CHIP_LZ4PAR_NO_CHECKSUM: u32 = 1;
+
+///what `chip_lz4_parallel` did: blocks of the frame, bytes written, input consumed, the exact size to come back with, the one-unit
+///decode's status, the path taken, the content checksum computed on the parallel path
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct chip_lz4_parallel_summary {
+    pub n_blocks: u64,
+    pub out_len: u64,
+    pub in_used: u64,
+    pub total_out: u64,
+    pub status: i32,
+    pub path: u32,
+    pub check: u32,
+    pub pad: u32,
+}
+
 ///`chip_gzip_plan_summary::status`
 pub const CHIP_GZPLAN_OK: i32 = 0;
 pub const CHIP_GZPLAN_TRUNCATED: i32 = 1;
@@ -818,6 +884,21 @@ extern "C" {
                                       table_bytes: *mut u64, stream: *mut c_void) -> c_int;
     ///XXH64 (seed 0, all 64 bits) of `n` ranges of device memory, one wave per range; only enqueues
     pub fn chip_xxh64_batch(n: usize, base: *const c_void, off: *const u64, len: *const u32, digest: *mut u64, stream: *mut c_void) -> c_int;
+
+    // ---- LZ4: blocks and frames, decode only (no reference counterpart); the batch calls take CHIP_FMT_LZ4_BLOCK / CHIP_FMT_LZ4
+    ///the block rules on host memory, and their definition; returns the unit's status
+    pub fn chip_lz4_block_decode_host(input: *const u8, len: u64, out: *mut u8, cap: u64, out_len: *mut u64, in_used: *mut u64) -> c_int;
+    ///the blocks of the first LZ4 frame of a host buffer, from headers alone; pure host arithmetic
+    pub fn chip_lz4_blocks_host(input: *const u8, len: u64, max_blocks: u64, blocks: *mut chip_lz4_block, summary: *mut chip_lz4_blocks_summary) -> c_int;
+    ///the same answer for a buffer in device memory (device records, host summary); synchronous on `stream`
+    pub fn chip_lz4_blocks(in_base: *const c_void, len: u64, max_blocks: u64, blocks: *mut chip_lz4_block, summary: *mut chip_lz4_blocks_summary,
+                           stream: *mut c_void) -> c_int;
+    ///XXH32 with `seed` of many device ranges, one wave per range; only enqueues
+    pub fn chip_xxh32_batch(n: usize, base: *const c_void, off: *const u64, len: *const u32, seed: u32, digest: *mut u32, stream: *mut c_void) -> c_int;
+    ///one large LZ4 frame of independent blocks decoded with a wave per block; anything not clean is the one-unit decode's answer;
+    ///synchronous on `stream`
+    pub fn chip_lz4_parallel(in_base: *const c_void, len: u64, out_base: *mut c_void, out_cap: u64, flags: u32, summary: *mut chip_lz4_parallel_summary,
+                             stream: *mut c_void) -> c_int;
     ///`chip_read_ranges(CHIP_FMT_ZSTD, ..)` with the seek table's per-unit checksums verified on the device (`checksum` null: that
     ///call itself); synchronous on `stream`
     pub fn chip_zstd_seek_read(n_units: usize, in_base: *const c_void, in_off: *const u64, in_len: *const u32, out_off: *const u64,
