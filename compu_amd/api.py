@@ -368,6 +368,10 @@ def lib():
     L.chip_lz4_blocks.argtypes = [vp, u64, u64, vp, C.POINTER(_Lz4BlocksSummary), vp]
     L.chip_lz4_parallel.restype = C.c_int
     L.chip_lz4_parallel.argtypes = [vp, u64, vp, u64, C.c_uint32, C.POINTER(_Lz4ParallelSummary), vp]
+    L.chip_lz4_block_encode_host.restype = C.c_int
+    L.chip_lz4_block_encode_host.argtypes = [vp, u64, C.c_int, vp, u64, C.POINTER(u64)]
+    L.chip_lz4_frame_encode_host.restype = C.c_int
+    L.chip_lz4_frame_encode_host.argtypes = [vp, u64, C.c_int, C.c_int, vp, u64, C.POINTER(u64)]
     L.chip_zstd_seek_read.restype = C.c_int
     L.chip_zstd_seek_read.argtypes = [sz, vp, vp, vp, vp, vp, vp, sz, vp, vp, vp, u64, vp, vp, C.POINTER(_ReadSummary), vp]
     L.chip_inflate_index_build.restype = C.c_int
@@ -456,8 +460,8 @@ class ZlibMode(enum.IntEnum):
 
 FMT_ZSTD = 100
 FMT_BROTLI = 101  # Interface::brotli_c decoder and encoder
-FMT_LZ4_BLOCK = 102  # CHIP_FMT_LZ4_BLOCK: one raw LZ4 block per unit (the batch calls only; decode only)
-FMT_LZ4 = 103  # CHIP_FMT_LZ4: one LZ4 frame per unit (the batch calls only; decode only)
+FMT_LZ4_BLOCK = 102  # CHIP_FMT_LZ4_BLOCK: one raw LZ4 block per unit (the batch calls, decode and encode)
+FMT_LZ4 = 103  # CHIP_FMT_LZ4: one LZ4 frame per unit (the batch calls, decode and encode; encode_file writes one frame)
 
 
 class ZstdOptions:
@@ -1230,7 +1234,8 @@ def encode_bound(fmt, in_len):
 def encode_batch(fmt, level, in_buf, in_off, in_len, out_buf, out_off, out_cap, out_len=None, status=None, stream=None, strategy=0):
     """chip_encode_batch_ex over device tensors: level 0 stored, 1 fixed Huffman, 2..9 (-1 = 6) dynamic Huffman blocks; FMT_ZSTD:
     zstd levels and ZstdStrategy values; FMT_BROTLI: level = quality 0..11 (0 = 11), strategy = mode 0..3, lgwin 22; FMT_BGZF: levels and
-    strategies as ZlibMode.Gzip, one BGZF block per unit, a unit above 65280 bytes is EncodeStatus.Error with out_len 0."""
+    strategies as ZlibMode.Gzip, one BGZF block per unit, a unit above 65280 bytes is EncodeStatus.Error with out_len 0;
+    FMT_LZ4_BLOCK / FMT_LZ4: levels -1 .. 12, one raw block / one frame per unit, strategy 0 for blocks and LZ4_S_* bits for frames."""
     import torch
 
     n = in_len.numel()
@@ -1985,6 +1990,8 @@ def encode_file(fmt, level, in_buf, length, unit_bytes=0, flags=0, stream=None, 
     """chip_encode_file over a uint8 device tensor holding `length` bytes (4-byte aligned, padded to a multiple of 4): cut into
     units of unit_bytes (0: 65280 for FMT_BGZF, 262144 for ZlibMode.Gzip and FMT_ZSTD), encoded, packed, trailer appended -- a
     BGZF file, a file of gzip members, a file of zstd frames (flags W_SEEK_TABLE: with the seekable format's seek table).
+    FMT_LZ4: ONE LZ4 frame with a block per unit (unit_bytes 0 = 65536, or 65536, 262144, 1048576, 4194304; levels -1 .. 12; flags
+    W_LZ4_CONTENT_CHECKSUM, W_LZ4_BLOCK_CHECKSUM), the file lz4_parallel reads with a wave per block.
     out None: a tensor of encode_file_bound bytes is allocated and the result is a view of its first out_len bytes.  With an
     `out` that is too small the summary says NeedOutput with the exact out_len and nothing is written.  Returns (the uint8
     output tensor trimmed to out_len -- None on NeedOutput --, summary).  Synchronous on `stream`."""
@@ -3752,7 +3759,7 @@ def tar_write_items(items, flags=0, stream=None, device=None):
     return tar_write(d_src, d_names, content, flags=flags, stream=stream)
 
 
-# ---- LZ4: blocks and frames (include/compu_hip.h, "LZ4: blocks and frames"; decode only) ---------------
+# ---- LZ4: blocks and frames (include/compu_hip.h, "LZ4: blocks and frames" and "LZ4: encoding") --------
 
 
 LZ4_E_HEADER, LZ4_E_DICT, LZ4_E_BLOCK_SIZE, LZ4_E_BLOCK = -200, -201, -202, -203  # CHIP_LZ4_E_*
@@ -3977,3 +3984,56 @@ def lz4_decode(data, checksum=True, device=None, stream=None):
     if not parts:
         return torch.empty(0, dtype=torch.uint8, device=dev)
     return parts[0] if len(parts) == 1 else torch.cat(parts)
+
+
+# ---- LZ4: encoding (include/compu_hip.h, "LZ4: encoding") -------------------------------------------------
+
+LZ4_S_BLOCK_CHECKSUM, LZ4_S_NO_CONTENT_CHECKSUM, LZ4_S_BLOCK_ID_SHIFT = 1, 2, 4  # CHIP_LZ4_S_*: encode_batch's strategy for FMT_LZ4
+W_LZ4_CONTENT_CHECKSUM, W_LZ4_BLOCK_CHECKSUM = 2, 4  # CHIP_W_LZ4_*: encode_file's flags for FMT_LZ4
+
+
+def _lz4_encode_host(what, call, data, out_cap, bound_fmt):
+    import numpy as np
+
+    buf = np.frombuffer(bytes(data), dtype=np.uint8)
+    cap = int(lib().chip_encode_bound(bound_fmt, buf.size)) if out_cap is None else int(out_cap)
+    out = np.zeros(cap, np.uint8)
+    ol = C.c_uint64(0)
+    p = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None  # noqa: E731
+    st = call(p(buf), buf.size, p(out), out.size, C.byref(ol))
+    if st == -101:
+        raise ValueError(f"{what} refused its arguments")
+    return out[:ol.value].tobytes(), int(st)
+
+
+def lz4_block_encode_host(data, level=1, out_cap=None):
+    """chip_lz4_block_encode_host: bytes-like -> (one raw LZ4 block, status) with out_cap bytes of room (None: encode_bound).  The
+    definition of the bytes the kernel writes.  status EncodeStatus.Finished, or NeedOutput / Error with an empty block."""
+    call = lambda i, n, o, c, ol: lib().chip_lz4_block_encode_host(i, n, int(level), o, c, ol)  # noqa: E731
+    return _lz4_encode_host("chip_lz4_block_encode_host", call, data, out_cap, FMT_LZ4_BLOCK)
+
+
+def lz4_frame_encode_host(data, level=1, strategy=0, out_cap=None):
+    """chip_lz4_frame_encode_host: bytes-like -> (one LZ4 frame, status); strategy carries the LZ4_S_* option bits."""
+    call = lambda i, n, o, c, ol: lib().chip_lz4_frame_encode_host(i, n, int(level), int(strategy), o, c, ol)  # noqa: E731
+    return _lz4_encode_host("chip_lz4_frame_encode_host", call, data, out_cap, FMT_LZ4)
+
+
+def lz4_encode(data, level=1, block_bytes=0, content_checksum=False, block_checksum=False, device=None, stream=None):
+    """A whole .lz4 file (bytes) of `data` (bytes-like or a uint8 device tensor): ONE frame with a block per block_bytes (0 = 65536,
+    or 65536, 262144, 1048576, 4194304) through encode_file(FMT_LZ4, ..), every block encoded by its own wave.  What the `lz4`
+    command writes and lz4_decode / lz4_parallel read back.  Waits for the result."""
+    import numpy as np
+    import torch
+
+    if isinstance(data, torch.Tensor):
+        d_in, length = data, data.numel()
+    else:
+        raw = np.frombuffer(bytes(data), np.uint8)
+        length = raw.size
+        padded = np.zeros((length + 3) // 4 * 4, np.uint8)
+        padded[:length] = raw
+        d_in = torch.from_numpy(padded).to(torch.device("cuda" if device is None else device))
+    flags = (W_LZ4_CONTENT_CHECKSUM if content_checksum else 0) | (W_LZ4_BLOCK_CHECKSUM if block_checksum else 0)
+    out, _ = encode_file(FMT_LZ4, level, d_in, length, unit_bytes=block_bytes, flags=flags, stream=stream)
+    return out.cpu().numpy().tobytes()

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "chip_internal.h"
+#include "lz4_enc_core.h"
 
 using namespace chip;
 
@@ -1253,6 +1254,9 @@ size_t chip_encode_bound(int format, size_t in_len)
     // brotli: uncompressed metablocks of 128 KiB (the first header shares its bytes with the WBITS field: at most 4 bytes, then 3
     // each), the closing empty last metablock (1 byte) -- 4 bytes per metablock and 2 more are a safe margin
     if (format == CHIP_FMT_BROTLI) return in_len + 4 * (in_len ? (in_len + (128u << 10) - 1) / (128u << 10) : 1) + 2;
+    // LZ4: the block format's own worst case; a frame of stored 64 KiB blocks with every checksum
+    if (format == CHIP_FMT_LZ4_BLOCK) return (size_t)lz4enc::block_bound(in_len);
+    if (format == CHIP_FMT_LZ4) return (size_t)lz4enc::frame_bound(in_len);
     size_t blocks = in_len ? (in_len + 65534) / 65535 : 1;
     size_t wrap = format == CHIP_FMT_BGZF ? 26 : format == CHIP_FMT_GZIP ? 18 : format == CHIP_FMT_ZLIB ? 6 : 0;  // header + trailer
     // dynamic levels: a block holds at least 65472 tokens and costs at most 6 bytes more than its stored form
@@ -1280,6 +1284,10 @@ int chip_encode_batch_ex(int format, int level, int strategy, size_t n, const vo
     case CHIP_FMT_BROTLI:  // level = quality 0..11 (0 = libbrotlienc's default 11), strategy = compu's mode byte 0..3 (recorded only)
         if (level < 0 || level > 11 || strategy < 0 || strategy > 3) return CHIP_E_INVALID;
         break;
+    case CHIP_FMT_LZ4_BLOCK:
+    case CHIP_FMT_LZ4:  // level -1 .. 12 (the lz4 command's range), strategy = CHIP_LZ4_S_* bits (frames only)
+        if (!lz4_encode_args_ok(format, level, strategy)) return CHIP_E_INVALID;
+        break;
     case CHIP_FMT_DEFLATE:
     case CHIP_FMT_ZLIB:
     case CHIP_FMT_GZIP:
@@ -1295,6 +1303,7 @@ int chip_encode_batch_ex(int format, int level, int strategy, size_t n, const vo
     hipError_t e;
     if (format == CHIP_FMT_ZSTD) e = launch_zstd_encode(a, level, strategy, wl, wl, ZF_FIRST | ZF_LAST | ZF_ONESHOT, nullptr, (hipStream_t)stream);
     else if (format == CHIP_FMT_BROTLI) e = launch_brotli_encode(a, level, 22, ZF_FIRST | ZF_LAST, nullptr, (hipStream_t)stream);
+    else if (format == CHIP_FMT_LZ4_BLOCK || format == CHIP_FMT_LZ4) e = launch_lz4_encode(a, level, strategy, (hipStream_t)stream);
     else e = launch_deflate_l1(a, level, 7u | ((uint32_t)strategy << 8), format == CHIP_FMT_ZLIB ? 1u : 0u, 0, nullptr, (hipStream_t)stream);
     return e == hipSuccess ? CHIP_OK : CHIP_E_LAUNCH;
 }

@@ -104,6 +104,10 @@ hipError_t enqueue_zstd_members_sizes(const BatchArgs &a, uint64_t *out_size, in
 hipError_t launch_lz4(const BatchArgs &a, uint64_t *out_size, hipStream_t stream);
 // (lz4.hip) XXH32, seed 0, of n bytes on one wave, to *got (device memory)
 hipError_t launch_lz4_xxh(const uint8_t *p, uint64_t n, uint32_t *got, hipStream_t stream);
+// lz4_enc.hip: the batch encoder of CHIP_FMT_LZ4_BLOCK / CHIP_FMT_LZ4 (a.format); lz4_encode_args_ok is the refusal that needs no
+// device: level -1 .. 12, strategy 0 for blocks and CHIP_LZ4_S_* bits for frames
+bool lz4_encode_args_ok(int format, int level, int strategy);
+hipError_t launch_lz4_encode(const BatchArgs &a, int level, int strategy, hipStream_t stream);
 // launch_slots.hip: the cached launch scratch of every codec ("Launch slots")
 hipError_t release_scratch();                 // every slot of the current device, after a device sync
 void release_scratch_of(hipStream_t stream);  // the slots of one (drained) stream of the current device

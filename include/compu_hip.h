@@ -48,7 +48,7 @@ enum {
      * BROTLI_DECODER_PARAM_LARGE_WINDOW), no shared dictionaries; not part of CHIP_FMT_DETECT routing (compu cannot detect
      * brotli) */
     CHIP_FMT_BROTLI = 101,
-    /* LZ4 (decode only; "LZ4: blocks and frames" below): one raw block of the LZ4 block format, delimited by in_len[i], and one
+    /* LZ4 ("LZ4: blocks and frames" and "LZ4: encoding" below): one raw block of the LZ4 block format, delimited by in_len[i], and one
      * frame of the LZ4 frame format.  The batch calls only (device, host and multi); not part of CHIP_FMT_DETECT routing, not with
      * CHIP_F_COMPU_STATUS or CHIP_F_MEMBERS, and the streaming chip_decoder_new does not take them (compu has no LZ4). */
     CHIP_FMT_LZ4_BLOCK = 102,
@@ -1499,7 +1499,7 @@ int chip_zstd_seek_read(size_t n_units, const void *in_base, const uint64_t *in_
                         const uint32_t *range_len, void *dst_base, uint64_t dst_cap, uint64_t *dst_off, int32_t *range_status,
                         chip_read_summary *summary, void *stream);
 
-/* ---- LZ4: blocks and frames (additive API, decode only) ------------------- */
+/* ---- LZ4: blocks and frames (additive API, decoding) ---------------------- */
 
 /*
  * CHIP_FMT_LZ4_BLOCK (102): a unit is ONE raw block of the LZ4 block format, delimited by in_len[i]; no prefix, no dictionary.
@@ -1660,6 +1660,59 @@ typedef struct {
 } chip_lz4_parallel_summary;
 int chip_lz4_parallel(const void *in_base, uint64_t len, void *out_base, uint64_t out_cap, uint32_t flags,
                       chip_lz4_parallel_summary *summary, void *stream);
+
+/* ---- LZ4: encoding (additive API) ------------------------------------------ */
+
+/*
+ * chip_encode_batch[_ex], chip_encode_batch_host and chip_encode_bound take CHIP_FMT_LZ4_BLOCK and CHIP_FMT_LZ4; chip_encode_file
+ * takes CHIP_FMT_LZ4.  No reference counterpart: compu has no LZ4.  This is the library's own match finder, not liblz4's: the
+ * bytes differ from liblz4's, and every conformant decoder reads them.
+ *
+ * level: -1 .. 12, the `lz4` command's range (-1 and 0 mean 1); anything else is CHIP_E_INVALID.  Three finder groups:
+ *   1 - 2    greedy, one position per hash slot, a growing skip over incompressible stretches (level 1 grows it faster)
+ *   3 - 5    greedy, two positions per slot
+ *   6 - 12   two positions per slot and a one-step lazy choice (a match gives way to a longer one at the next position)
+ *
+ * THE DUTIES of a block, which liblz4's decoders rely on and every block written here keeps:
+ *   the last 5 bytes are literals; no match starts within the last 12 bytes; a block of fewer than 13 bytes is one literal run;
+ *   offsets are 1 .. 65 535 (never 0, never 65 536); no offset reaches in front of the block (independent blocks only, no
+ *   dictionary); empty input is the one byte 0x00.
+ *
+ * CHIP_FMT_LZ4_BLOCK: a unit becomes ONE raw block.  strategy must be 0.  status[i] = CHIP_ENC_FINISHED with out_len[i], or
+ * CHIP_ENC_NEED_OUTPUT (out_len 0) when out_cap[i] is too small -- no byte is stored at or past out_cap[i] -- or CHIP_ENC_ERROR for
+ * in_len[i] > 0x7E000000 (LZ4_MAX_INPUT_SIZE).  chip_encode_bound = n + n / 255 + 16, the format's own worst case.
+ *
+ * CHIP_FMT_LZ4: a unit becomes ONE frame of the frame format 1.6.x, written by one wave block after block: version 01,
+ * independent blocks, Content_Size always stated, the end mark, and by default a 64 KiB block maximum (BD id 4), the content
+ * checksum and no block checksums.  A block that does not come out smaller than its content is stored (high bit of its header).
+ * An empty unit is header + end mark (+ the checksum of nothing).  strategy carries the options as bits: CHIP_LZ4_S_BLOCK_CHECKSUM,
+ * CHIP_LZ4_S_NO_CONTENT_CHECKSUM and a block-size id (0 = default, else 4 .. 7 = 64 KiB, 256 KiB, 1 MiB, 4 MiB) shifted by
+ * CHIP_LZ4_S_BLOCK_ID_SHIFT; any other value is CHIP_E_INVALID.  Statuses as for blocks.
+ * chip_encode_bound = n + 8 * ceil(n / 65 536) + 23: the 15-byte header, the end mark and the content checksum, and around every
+ * stored 64 KiB block a header and a block checksum -- it covers every option (larger blocks only need less).
+ *
+ * chip_lz4_block_encode_host and chip_lz4_frame_encode_host are the host forms and THE DEFINITION OF THE BYTES: the kernels write
+ * the same bytes for every input, level and option (one source, compu_amd/csrc/lz4_enc_core.h).  in, out, out_len are HOST
+ * pointers.  They answer CHIP_ENC_FINISHED (*out_len = the size), CHIP_ENC_NEED_OUTPUT (cap too small, *out_len = 0; nothing is
+ * stored at or past cap), CHIP_ENC_ERROR (len > 0x7E000000) or CHIP_E_INVALID (out_len NULL, a NULL buffer with a length, a level
+ * or strategy out of range).
+ *
+ * chip_encode_file(CHIP_FMT_LZ4, ..) writes ONE frame across the GPU, the counterpart of chip_lz4_parallel and what the `lz4`
+ * command writes: the 15-byte header (Content_Size always), one block per unit, the end mark.  unit_bytes is the block maximum: 0
+ * (= 65 536), 65 536, 262 144, 1 048 576 or 4 194 304; anything else is CHIP_E_INVALID.  flags, valid with this format only:
+ * CHIP_W_LZ4_CONTENT_CHECKSUM and CHIP_W_LZ4_BLOCK_CHECKSUM.  The content checksum is OFF by default here: XXH32 is one serial chain
+ * that one wave runs over the whole input (0.57 GB/s measured for the decode side).
+ * The passes, on the caller's stream: the units are cut; a CHIP_FMT_LZ4_BLOCK batch encodes them into slots; a block with
+ * out_len >= in_len is stored; chip_xxh32_batch hashes every block's bytes as they will lie in the file (block checksums); a scan
+ * lays the blocks out; ONE destination-driven copy takes each block from its slot or from the input; small kernels write the
+ * block headers and checksums, the frame header, the end mark and the content checksum.  The blocks are the bytes of
+ * chip_lz4_block_encode_host.  len == 0: the empty frame (n_units = 0).  summary.table_off = out_len.  chip_encode_file_bound =
+ * 15 + len + n * (4 + 4 with block checksums) + 4 + (4 with the content checksum), n = ceil(len / unit_bytes).
+ */
+enum { CHIP_LZ4_S_BLOCK_CHECKSUM = 1, CHIP_LZ4_S_NO_CONTENT_CHECKSUM = 2, CHIP_LZ4_S_BLOCK_ID_SHIFT = 4, CHIP_LZ4_S_BLOCK_ID_MASK = 0x70 };
+enum { CHIP_W_LZ4_CONTENT_CHECKSUM = 2, CHIP_W_LZ4_BLOCK_CHECKSUM = 4 };
+int chip_lz4_block_encode_host(const uint8_t *in, uint64_t len, int level, uint8_t *out, uint64_t cap, uint64_t *out_len);
+int chip_lz4_frame_encode_host(const uint8_t *in, uint64_t len, int level, int strategy, uint8_t *out, uint64_t cap, uint64_t *out_len);
 
 /* ---- one large stream: the checkpoint index (additive API) ------------------ */
 

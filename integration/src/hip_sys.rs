@@ -184,7 +184,7 @@ pub struct chip_zstd_parallel_summary {
     pub check: u32,
 }
 
-///LZ4 (decode only, the batch calls only; no compu counterpart): one raw block per unit, one frame per unit
+///LZ4 (the batch calls, decode and encode; no compu counterpart): one raw block per unit, one frame per unit
 pub const CHIP_FMT_LZ4_BLOCK: c_int = 102;
 pub const CHIP_FMT_LZ4: c_int = 103;
 ///per-unit status of an LZ4 unit, beside `CHIP_NEED_INPUT` / `CHIP_NEED_OUTPUT` / `CHIP_FINISHED`
@@ -234,6 +234,14 @@ pub const CHIP_LZ4PAR_PARALLEL: u32 = 1;
 pub const CHIP_LZ4PAR_REFUSED: u32 = 2;
 ///`chip_lz4_parallel` flag: do not verify the content checksum on the parallel path
 pub const CHIP_LZ4PAR_NO_CHECKSUM: u32 = 1;
+///`chip_encode_batch_ex` strategy bits for `CHIP_FMT_LZ4`: block checksums, no content checksum, the block-size id (0, 4..7)
+pub const CHIP_LZ4_S_BLOCK_CHECKSUM: c_int = 1;
+pub const CHIP_LZ4_S_NO_CONTENT_CHECKSUM: c_int = 2;
+pub const CHIP_LZ4_S_BLOCK_ID_SHIFT: c_int = 4;
+pub const CHIP_LZ4_S_BLOCK_ID_MASK: c_int = 0x70;
+///`chip_encode_file` flags for `CHIP_FMT_LZ4`
+pub const CHIP_W_LZ4_CONTENT_CHECKSUM: u32 = 2;
+pub const CHIP_W_LZ4_BLOCK_CHECKSUM: u32 = 4;
 
 ///what `chip_lz4_parallel` did: blocks of the frame, bytes written, input consumed, the exact size to come back with, the one-unit
 ///decode's status, the path taken, the content checksum computed on the parallel path
@@ -885,7 +893,7 @@ extern "C" {
     ///XXH64 (seed 0, all 64 bits) of `n` ranges of device memory, one wave per range; only enqueues
     pub fn chip_xxh64_batch(n: usize, base: *const c_void, off: *const u64, len: *const u32, digest: *mut u64, stream: *mut c_void) -> c_int;
 
-    // ---- LZ4: blocks and frames, decode only (no reference counterpart); the batch calls take CHIP_FMT_LZ4_BLOCK / CHIP_FMT_LZ4
+    // ---- LZ4: blocks and frames, decode and encode (no reference counterpart); the batch calls take CHIP_FMT_LZ4_BLOCK / CHIP_FMT_LZ4
     ///the block rules on host memory, and their definition; returns the unit's status
     pub fn chip_lz4_block_decode_host(input: *const u8, len: u64, out: *mut u8, cap: u64, out_len: *mut u64, in_used: *mut u64) -> c_int;
     ///the blocks of the first LZ4 frame of a host buffer, from headers alone; pure host arithmetic
@@ -899,6 +907,10 @@ extern "C" {
     ///synchronous on `stream`
     pub fn chip_lz4_parallel(in_base: *const c_void, len: u64, out_base: *mut c_void, out_cap: u64, flags: u32, summary: *mut chip_lz4_parallel_summary,
                              stream: *mut c_void) -> c_int;
+    ///one raw LZ4 block of host memory on the host: the definition of the bytes the batch encoder writes; returns `CHIP_ENC_*`
+    pub fn chip_lz4_block_encode_host(input: *const u8, len: u64, level: c_int, out: *mut u8, cap: u64, out_len: *mut u64) -> c_int;
+    ///one LZ4 frame of host memory on the host (`strategy`: `CHIP_LZ4_S_*` bits); returns `CHIP_ENC_*`
+    pub fn chip_lz4_frame_encode_host(input: *const u8, len: u64, level: c_int, strategy: c_int, out: *mut u8, cap: u64, out_len: *mut u64) -> c_int;
     ///`chip_read_ranges(CHIP_FMT_ZSTD, ..)` with the seek table's per-unit checksums verified on the device (`checksum` null: that
     ///call itself); synchronous on `stream`
     pub fn chip_zstd_seek_read(n_units: usize, in_base: *const c_void, in_off: *const u64, in_len: *const u32, out_off: *const u64,
