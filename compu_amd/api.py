@@ -3,399 +3,52 @@
 Names follow the reference: decoder::{Interface, Decoder, Decode, DecodeStatus, DecodeError,
 Detection, ZlibMode, ZstdOptions} (src/decoder/mod.rs, zlib_common.rs, zstd.rs),
 encoder::{Interface, Encoder, Encode, EncodeOp, EncodeStatus, ZlibOptions} (src/encoder/mod.rs,
-zlib_common.rs) and Buffer (src/buffer.rs).  All codec work happens in the HIP library.
+zlib_common.rs) and Buffer (src/buffer.rs).  All codec work happens in the HIP library; its structures, prototypes and
+lib() are in _ffi.py.
 """
 import ctypes as C
 import enum
-import os
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_LIB_NAME = "libcompu_hip.so"
-
-
-def lib_path():
-    # COMPU_HIP_LIB selects another build of the same library (diagnostic builds); never a CPU stand-in
-    return os.environ.get("COMPU_HIP_LIB") or os.path.join(_HERE, _LIB_NAME)
-
-
-class _DecodeResult(C.Structure):
-    _fields_ = [("input_remain", C.c_size_t), ("output_remain", C.c_size_t), ("status", C.c_int32), ("err", C.c_int32)]
-
-
-class _EncodeResult(C.Structure):
-    _fields_ = [("input_remain", C.c_size_t), ("output_remain", C.c_size_t), ("status", C.c_int32)]
-
-
-class _DecoderOpts(C.Structure):
-    _fields_ = [("window_log_max", C.c_int32), ("device", C.c_int32)]
-
-
-class _EncoderOpts(C.Structure):
-    _fields_ = [("mode", C.c_int32), ("compression", C.c_int32), ("device", C.c_int32), ("strategy", C.c_int32), ("mem_level", C.c_int32)]
-
-
-class _ZstdEncoderOpts(C.Structure):
-    _fields_ = [("level", C.c_int32), ("strategy", C.c_int32), ("window_log", C.c_int32), ("device", C.c_int32)]
-
-
-class _BrotliEncoderOpts(C.Structure):
-    _fields_ = [("quality", C.c_int32), ("mode", C.c_int32), ("lgwin", C.c_int32), ("device", C.c_int32)]
-
-
-class _BgzfSummary(C.Structure):
-    _fields_ = [("n_blocks", C.c_uint64), ("total_out", C.c_uint64), ("in_used", C.c_uint64), ("status", C.c_int32), ("eof", C.c_uint32)]
-
-
-class _ZstdPlanSummary(C.Structure):
-    _fields_ = [("n_frames", C.c_uint64), ("n_skippable", C.c_uint64), ("n_unsized", C.c_uint64), ("total_out", C.c_uint64),
-                ("in_used", C.c_uint64), ("status", C.c_int32), ("pad", C.c_uint32)]
-
-
-class _ZstdBlock(C.Structure):
-    _fields_ = [("offset", C.c_uint64), ("size", C.c_uint32), ("lit_regen", C.c_uint32), ("lit_comp", C.c_uint32), ("n_seq", C.c_uint32),
-                ("type", C.c_uint8), ("flags", C.c_uint8), ("lit_type", C.c_uint8), ("mode", C.c_uint8 * 3), ("pad", C.c_uint8 * 2),
-                ("src", C.c_int32 * 4)]
-
-
-class _ZstdBlocksSummary(C.Structure):
-    _fields_ = [("n_blocks", C.c_uint64), ("in_used", C.c_uint64), ("content_size", C.c_uint64), ("window_size", C.c_uint64),
-                ("status", C.c_int32), ("descriptor", C.c_uint32), ("header_bytes", C.c_uint32), ("pad", C.c_uint32)]
-
-
-class _ZstdParallelSummary(C.Structure):
-    _fields_ = [("n_blocks", C.c_uint64), ("n_sequences", C.c_uint64), ("out_len", C.c_uint64), ("in_used", C.c_uint64), ("total_out", C.c_uint64),
-                ("status", C.c_int32), ("path", C.c_uint32), ("rounds", C.c_uint32), ("check", C.c_uint32)]
-
-
-class _Xxh64State(C.Structure):
-    _fields_ = [("acc", C.c_uint64 * 4), ("total", C.c_uint64), ("tail", C.c_uint8 * 32), ("tail_n", C.c_uint32), ("pad", C.c_uint32)]
-
-
-class _ZstdCursor(C.Structure):
-    _fields_ = [("in_total", C.c_uint64), ("out_total", C.c_uint64), ("window_size", C.c_uint64), ("content_size", C.c_uint64),
-                ("hist", C.c_uint64), ("ring", C.c_uint64), ("carry_at", C.c_uint64 * 4), ("carry_len", C.c_uint32 * 4), ("rep", C.c_uint32 * 3),
-                ("phase", C.c_uint32), ("descriptor", C.c_uint32), ("waived", C.c_uint32), ("error", C.c_int32), ("pad", C.c_uint32),
-                ("xxh", _Xxh64State)]
-
-
-class _ZstdNextSummary(C.Structure):
-    _fields_ = [("in_used", C.c_uint64), ("out_len", C.c_uint64), ("need_out", C.c_uint64), ("need_state", C.c_uint64), ("n_blocks", C.c_uint64),
-                ("n_sequences", C.c_uint64), ("status", C.c_int32), ("rounds", C.c_uint32)]
-
-
-class _ZstdSlabSummary(C.Structure):
-    _fields_ = [("n_blocks", C.c_uint64), ("in_used", C.c_uint64), ("status", C.c_int32), ("last", C.c_uint32)]
-
-
-class _GzipPlanSummary(C.Structure):
-    _fields_ = [("n_members", C.c_uint64), ("total_out", C.c_uint64), ("in_used", C.c_uint64), ("status", C.c_int32),
-                ("member_status", C.c_int32)]
-
-
-class _ZipEntry(C.Structure):
-    _fields_ = [("header_off", C.c_uint64), ("data_off", C.c_uint64), ("comp_size", C.c_uint64), ("size", C.c_uint64), ("name_off", C.c_uint64),
-                ("crc32", C.c_uint32), ("name_len", C.c_uint16), ("method", C.c_uint16), ("flags", C.c_uint16), ("pad", C.c_uint16),
-                ("status", C.c_int32)]
-
-
-class _ZipPlanSummary(C.Structure):
-    _fields_ = [("n_entries", C.c_uint64), ("n_ok", C.c_uint64), ("total_size", C.c_uint64), ("cd_off", C.c_uint64), ("cd_size", C.c_uint64),
-                ("eocd_off", C.c_uint64), ("bad_index", C.c_uint64), ("status", C.c_int32), ("zip64", C.c_int32)]
-
-
-class _ZipDecodeSummary(C.Structure):
-    _fields_ = [("n_sel", C.c_uint64), ("n_ok", C.c_uint64), ("n_bad", C.c_uint64), ("first_bad", C.c_uint64), ("total_out", C.c_uint64),
-                ("status", C.c_int32), ("pad", C.c_int32)]
-
-
-class _ZipSource(C.Structure):
-    _fields_ = [("data_off", C.c_uint64), ("size", C.c_uint64), ("name_off", C.c_uint64), ("name_len", C.c_uint16), ("method", C.c_uint16),
-                ("dos_time", C.c_uint16), ("dos_date", C.c_uint16)]
-
-
-class _ZipWriteSummary(C.Structure):
-    _fields_ = [("n_entries", C.c_uint64), ("n_deflated", C.c_uint64), ("out_len", C.c_uint64), ("cd_off", C.c_uint64), ("cd_size", C.c_uint64),
-                ("eocd_off", C.c_uint64), ("bad_index", C.c_uint64), ("status", C.c_int32), ("zip64", C.c_int32)]
-
-
-class _TarEntry(C.Structure):
-    _fields_ = [("group_off", C.c_uint64), ("header_off", C.c_uint64), ("data_off", C.c_uint64), ("size", C.c_uint64), ("name_off", C.c_uint64),
-                ("link_off", C.c_uint64), ("mtime", C.c_int64), ("name_len", C.c_uint32), ("link_len", C.c_uint32), ("mode", C.c_uint32),
-                ("prefix_len", C.c_uint16), ("typeflag", C.c_uint8), ("flags", C.c_uint8)]
-
-
-class _TarPlanSummary(C.Structure):
-    _fields_ = [("n_entries", C.c_uint64), ("n_global", C.c_uint64), ("total_size", C.c_uint64), ("stop_off", C.c_uint64), ("bad_off", C.c_uint64),
-                ("status", C.c_int32), ("zero_blocks", C.c_int32)]
-
-
-class _TarSource(C.Structure):
-    _fields_ = [("data_off", C.c_uint64), ("size", C.c_uint64), ("name_off", C.c_uint64), ("link_off", C.c_uint64), ("mtime", C.c_int64),
-                ("name_len", C.c_uint32), ("link_len", C.c_uint32), ("mode", C.c_uint32), ("uid", C.c_uint32), ("gid", C.c_uint32),
-                ("typeflag", C.c_uint8), ("pad", C.c_uint8 * 3)]
-
-
-class _TarWriteSummary(C.Structure):
-    _fields_ = [("n_entries", C.c_uint64), ("n_ext", C.c_uint64), ("out_len", C.c_uint64), ("end_off", C.c_uint64), ("total_size", C.c_uint64),
-                ("bad_index", C.c_uint64), ("status", C.c_int32), ("pad", C.c_int32)]
-
-
-class _FileSummary(C.Structure):
-    _fields_ = [("n_units", C.c_uint64), ("out_len", C.c_uint64), ("table_off", C.c_uint64), ("status", C.c_int32), ("pad", C.c_uint32)]
-
-
-class _SelectSummary(C.Structure):
-    _fields_ = [("n_sel", C.c_uint64), ("scratch_bytes", C.c_uint64), ("out_len", C.c_uint64), ("n_outside", C.c_uint64),
-                ("bad_index", C.c_uint64), ("status", C.c_int32), ("pad", C.c_uint32)]
-
-
-class _ReadSummary(C.Structure):
-    _fields_ = [("n_units", C.c_uint64), ("out_len", C.c_uint64), ("n_outside", C.c_uint64), ("n_bad", C.c_uint64),
-                ("first_bad", C.c_uint64), ("bad_index", C.c_uint64), ("status", C.c_int32), ("bad_status", C.c_int32)]
-
-
-class _ZstdSeekSummary(C.Structure):
-    _fields_ = [("n_frames", C.c_uint64), ("table_bytes", C.c_uint64), ("frames_bytes", C.c_uint64), ("total_out", C.c_uint64),
-                ("bad_index", C.c_uint64), ("status", C.c_int32), ("checksums", C.c_uint32)]
-
-
-class _InflateIndexSummary(C.Structure):
-    _fields_ = [("n_points", C.c_uint64), ("out_len", C.c_uint64), ("in_used", C.c_uint64), ("end_bit", C.c_uint64), ("status", C.c_int32),
-                ("wrap", C.c_uint32), ("check", C.c_uint32), ("pad", C.c_uint32)]
-
-
-_lib = None
-
-
-class _Lz4Block(C.Structure):
-    _fields_ = [("offset", C.c_uint64), ("size", C.c_uint32), ("flags", C.c_uint32), ("checksum", C.c_uint32), ("pad", C.c_uint32)]
-
-
-class _Lz4BlocksSummary(C.Structure):
-    _fields_ = [("n_blocks", C.c_uint64), ("in_used", C.c_uint64), ("content_size", C.c_uint64), ("block_max", C.c_uint32), ("flg", C.c_uint32),
-                ("bd", C.c_uint32), ("header_bytes", C.c_uint32), ("content_checksum", C.c_uint32), ("status", C.c_int32)]
-
-
-class _Lz4ParallelSummary(C.Structure):
-    _fields_ = [("n_blocks", C.c_uint64), ("out_len", C.c_uint64), ("in_used", C.c_uint64), ("total_out", C.c_uint64), ("status", C.c_int32),
-                ("path", C.c_uint32), ("check", C.c_uint32), ("pad", C.c_uint32)]
-
-
-class _InflateParallelSummary(C.Structure):
-    _fields_ = [("n_points", C.c_uint64), ("out_len", C.c_uint64), ("in_used", C.c_uint64), ("end_bit", C.c_uint64), ("total_out", C.c_uint64),
-                ("n_starts", C.c_uint64), ("n_false", C.c_uint64), ("status", C.c_int32), ("wrap", C.c_uint32), ("check", C.c_uint32),
-                ("path", C.c_uint32)]
-
-
-class _InflateCursor(C.Structure):
-    _fields_ = [("in_total", C.c_uint64), ("out_total", C.c_uint64), ("bit", C.c_uint32), ("phase", C.c_uint32), ("wrap", C.c_uint32),
-                ("check", C.c_uint32), ("hist", C.c_uint32), ("error", C.c_int32)]
-
-
-class _InflateNextSummary(C.Structure):
-    _fields_ = [("in_used", C.c_uint64), ("out_len", C.c_uint64), ("need_out", C.c_uint64), ("n_chunks", C.c_uint64), ("n_starts", C.c_uint64),
-                ("n_false", C.c_uint64), ("status", C.c_int32), ("path", C.c_uint32)]
-
-
-def lib():
-    """Load libcompu_hip.so.  Raises if it has not been built: there is no fallback codec."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    path = lib_path()
-    if not os.path.exists(path):
-        raise RuntimeError(
-            f"{path} is missing: build it with compu_amd/csrc/build.sh (or __graft_entry__.build()); "
-            "compu_amd has no CPU codec to fall back to"
-        )
-    try:  # share torch's HIP runtime when torch is in the process (same SONAME libamdhip64.so.7)
-        import torch  # noqa: F401
-    except Exception:  # pragma: no cover - torch is plumbing only
-        pass
-    L = C.CDLL(path)
-    vp, sz, i32 = C.c_void_p, C.c_size_t, C.c_int32
-    L.chip_device_count.restype = C.c_int
-    L.chip_set_device.argtypes = [C.c_int]
-    L.chip_version.restype = C.c_char_p
-    L.chip_device_alloc.restype = vp
-    L.chip_device_alloc.argtypes = [sz]
-    L.chip_device_free.argtypes = [vp]
-    L.chip_pinned_alloc.restype = vp
-    L.chip_pinned_alloc.argtypes = [sz]
-    L.chip_pinned_free.argtypes = [vp]
-    L.chip_memcpy_h2d.argtypes = [vp, vp, sz, vp]
-    L.chip_memcpy_d2h.argtypes = [vp, vp, sz, vp]
-    L.chip_stream_sync.argtypes = [vp]
-    L.chip_decode_batch_host.restype = C.c_int
-    L.chip_decode_batch_host.argtypes = [C.c_int, C.c_size_t] + [vp] * 9 + [C.c_int, C.c_size_t]
-    L.chip_decode_batch_multi.restype = C.c_int
-    L.chip_decode_batch_multi.argtypes = [C.c_int, C.c_size_t] + [vp] * 9 + [vp, C.c_int, C.c_size_t]
-    L.chip_partition_units.restype = C.c_int
-    L.chip_partition_units.argtypes = [C.c_size_t, vp, vp, C.c_int, vp]
-    L.chip_encode_batch_host.restype = C.c_int
-    L.chip_encode_batch_host.argtypes = [C.c_int, C.c_int, C.c_size_t] + [vp] * 8 + [C.c_int, C.c_size_t]
-    L.chip_trim.restype = C.c_int
-    L.chip_trim.argtypes = []
-    L.chip_decoder_new.restype = vp
-    L.chip_decoder_new.argtypes = [C.c_int, C.POINTER(_DecoderOpts)]
-    L.chip_decode.restype = _DecodeResult
-    L.chip_decode.argtypes = [vp, vp, sz, vp, sz]
-    L.chip_decoder_reset.restype = vp
-    L.chip_decoder_reset.argtypes = [vp]
-    L.chip_decoder_free.argtypes = [vp]
-    L.chip_decoder_footprint.argtypes = [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
-    L.chip_decoder_footprint.restype = None
-    L.chip_set_allocator.argtypes = [vp, vp, vp]
-    L.chip_set_allocator.restype = None
-    L.chip_decoder_strerror.restype = C.c_char_p
-    L.chip_decoder_strerror.argtypes = [C.c_int, i32]
-    L.chip_decode_batch.restype = C.c_int
-    L.chip_decode_batch.argtypes = [C.c_int, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.chip_decode_batch_ex.restype = C.c_int
-    L.chip_decode_batch_ex.argtypes = [C.c_int, C.c_uint32, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.chip_decode_batch_sizes.restype = C.c_int
-    L.chip_decode_batch_sizes.argtypes = [C.c_int, C.c_uint32, sz, vp, vp, vp, vp, vp, vp, vp]
-    L.chip_detect.restype = C.c_int
-    L.chip_detect.argtypes = [vp, sz]
-    L.chip_detect_batch.restype = C.c_int
-    L.chip_detect_batch.argtypes = [sz, vp, vp, vp, vp, vp]
-    L.chip_encoder_new.restype = vp
-    L.chip_encoder_new.argtypes = [C.POINTER(_EncoderOpts)]
-    L.chip_encoder_new_zstd.restype = vp
-    L.chip_encoder_new_zstd.argtypes = [C.POINTER(_ZstdEncoderOpts)]
-    L.chip_encoder_new_brotli.restype = vp
-    L.chip_encoder_new_brotli.argtypes = [C.POINTER(_BrotliEncoderOpts)]
-    L.chip_encode.restype = _EncodeResult
-    L.chip_encode.argtypes = [vp, vp, sz, vp, sz, C.c_int]
-    L.chip_encoder_reset.restype = vp
-    L.chip_encoder_reset.argtypes = [vp]
-    L.chip_encoder_free.argtypes = [vp]
-    L.chip_encode_batch.restype = C.c_int
-    L.chip_encode_batch.argtypes = [C.c_int, C.c_int, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.chip_encode_batch_ex.restype = C.c_int
-    L.chip_encode_batch_ex.argtypes = [C.c_int, C.c_int, C.c_int, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.chip_encode_bound.restype = sz
-    L.chip_encode_bound.argtypes = [C.c_int, sz]
-    L.chip_bgzf_plan_host.restype = C.c_int
-    L.chip_bgzf_plan_host.argtypes = [vp, C.c_uint64, C.c_uint64, vp, vp, vp, vp, C.POINTER(_BgzfSummary)]
-    L.chip_bgzf_plan.restype = C.c_int
-    L.chip_bgzf_plan.argtypes = [vp, C.c_uint64, C.c_uint64, vp, vp, vp, vp, C.POINTER(_BgzfSummary), vp]
-    L.chip_bgzf_eof_block.restype = vp
-    L.chip_bgzf_eof_block.argtypes = [C.POINTER(C.c_size_t)]
-    L.chip_zstd_plan_host.restype = C.c_int
-    L.chip_zstd_plan_host.argtypes = [vp, C.c_uint64, C.c_uint64, vp, vp, vp, vp, C.POINTER(_ZstdPlanSummary)]
-    L.chip_zstd_plan.restype = C.c_int
-    L.chip_zstd_plan.argtypes = [vp, C.c_uint64, C.c_uint64, vp, vp, vp, vp, C.POINTER(_ZstdPlanSummary), vp]
-    L.chip_zstd_blocks_host.restype = C.c_int
-    L.chip_zstd_blocks_host.argtypes = [vp, C.c_uint64, C.c_uint64, vp, C.POINTER(_ZstdBlocksSummary)]
-    L.chip_zstd_parallel.restype = C.c_int
-    L.chip_zstd_parallel.argtypes = [vp, C.c_uint64, vp, C.c_uint64, C.c_int, C.c_uint32, C.POINTER(_ZstdParallelSummary), vp]
-    L.chip_zstd_blocks.restype = C.c_int
-    L.chip_zstd_blocks.argtypes = [vp, C.c_uint64, C.c_uint64, vp, C.POINTER(_ZstdBlocksSummary), vp]
-    L.chip_zstd_parallel_next.restype = C.c_int
-    L.chip_zstd_parallel_next.argtypes = [C.POINTER(_ZstdCursor), vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, C.c_int, C.c_uint32,
-                                          C.POINTER(_ZstdNextSummary), vp]
-    L.chip_zstd_slab_blocks_host.restype = C.c_int
-    L.chip_zstd_slab_blocks_host.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint64, vp, C.POINTER(_ZstdSlabSummary)]
-    L.chip_zstd_cursor_header_host.restype = C.c_int
-    L.chip_zstd_cursor_header_host.argtypes = [C.POINTER(_ZstdCursor), vp, C.c_uint64, C.c_int, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
-    L.chip_xxh64_update_host.restype = C.c_int
-    L.chip_xxh64_update_host.argtypes = [C.POINTER(_Xxh64State), vp, C.c_uint64]
-    L.chip_xxh64_digest_host.restype = C.c_uint64
-    L.chip_xxh64_digest_host.argtypes = [C.POINTER(_Xxh64State)]
-    L.chip_gzip_plan.restype = C.c_int
-    L.chip_gzip_plan.argtypes = [vp, C.c_uint64, C.c_uint64, vp, vp, vp, vp, C.POINTER(_GzipPlanSummary), vp]
-    L.chip_zip_plan_host.restype = C.c_int
-    L.chip_zip_plan_host.argtypes = [vp, C.c_uint64, C.c_uint64, vp, C.POINTER(_ZipPlanSummary)]
-    L.chip_zip_plan.restype = C.c_int
-    L.chip_zip_plan.argtypes = [vp, C.c_uint64, C.c_uint64, vp, C.POINTER(_ZipPlanSummary), vp]
-    L.chip_crc32_batch.restype = C.c_int
-    L.chip_crc32_batch.argtypes = [sz, vp, vp, vp, vp, vp]
-    L.chip_zip_decode.restype = C.c_int
-    L.chip_zip_decode.argtypes = [vp, C.c_uint64, vp, C.c_uint64, C.c_uint64, vp, vp, C.c_uint64, vp, vp, C.POINTER(_ZipDecodeSummary), vp]
-    u64, zws = C.c_uint64, C.POINTER(_ZipWriteSummary)
-    L.chip_zip_assemble_host.restype = C.c_int
-    L.chip_zip_assemble_host.argtypes = [u64, vp, vp, u64, vp, u64, vp, u64, vp, vp, vp, C.c_uint32, vp, u64, vp, zws]
-    L.chip_zip_assemble.restype = C.c_int
-    L.chip_zip_assemble.argtypes = [u64, vp, vp, u64, vp, u64, vp, u64, vp, vp, vp, C.c_uint32, vp, u64, vp, zws, vp]
-    L.chip_zip_write.restype = C.c_int
-    L.chip_zip_write.argtypes = [C.c_int, C.c_uint32, u64, vp, vp, u64, vp, u64, vp, u64, vp, zws, vp]
-    L.chip_zip_write_bound.restype = C.c_uint64
-    L.chip_zip_write_bound.argtypes = [u64, u64, u64]
-    L.chip_tar_plan_host.restype = C.c_int
-    L.chip_tar_plan_host.argtypes = [vp, u64, u64, vp, C.POINTER(_TarPlanSummary)]
-    L.chip_tar_plan.restype = C.c_int
-    L.chip_tar_plan.argtypes = [vp, u64, u64, vp, C.POINTER(_TarPlanSummary), vp]
-    tws = C.POINTER(_TarWriteSummary)
-    L.chip_tar_write_host.restype = C.c_int
-    L.chip_tar_write_host.argtypes = [u64, vp, vp, u64, vp, u64, C.c_uint32, C.c_uint32, vp, u64, vp, tws]
-    L.chip_tar_write.restype = C.c_int
-    L.chip_tar_write.argtypes = [u64, vp, vp, u64, vp, u64, C.c_uint32, C.c_uint32, vp, u64, vp, tws, vp]
-    L.chip_tar_write_bound.restype = C.c_uint64
-    L.chip_tar_write_bound.argtypes = [u64, u64, u64, C.c_uint32]
-    L.chip_layout_units.restype = C.c_int
-    L.chip_layout_units.argtypes = [sz, vp, vp, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), vp]
-    L.chip_pack_units.restype = C.c_int
-    L.chip_pack_units.argtypes = [sz, vp, vp, vp, vp, C.c_uint64, vp, C.POINTER(C.c_uint64), vp]
-    L.chip_encode_file.restype = C.c_int
-    L.chip_encode_file.argtypes = [C.c_int, C.c_int, C.c_uint32, C.c_uint32, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(_FileSummary), vp]
-    L.chip_encode_file_bound.restype = C.c_uint64
-    L.chip_encode_file_bound.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint64]
-    L.chip_select_units_host.restype = C.c_int
-    L.chip_select_units_host.argtypes = [sz, vp, vp, vp, vp, sz, vp, vp, C.c_uint64] + [vp] * 8 + [C.POINTER(_SelectSummary)]
-    L.chip_select_units.restype = C.c_int
-    L.chip_select_units.argtypes = [sz, vp, vp, vp, vp, sz, vp, vp, C.c_uint64] + [vp] * 8 + [C.POINTER(_SelectSummary), vp]
-    L.chip_read_ranges.restype = C.c_int
-    L.chip_read_ranges.argtypes = [C.c_int, sz, vp, vp, vp, vp, vp, sz, vp, vp, vp, C.c_uint64, vp, vp, C.POINTER(_ReadSummary), vp]
-    zss = C.POINTER(_ZstdSeekSummary)
-    L.chip_zstd_seek_plan_host.restype = C.c_int
-    L.chip_zstd_seek_plan_host.argtypes = [vp, u64, u64, u64, vp, vp, vp, vp, vp, zss]
-    L.chip_zstd_seek_plan.restype = C.c_int
-    L.chip_zstd_seek_plan.argtypes = [vp, u64, u64, u64, vp, vp, vp, vp, vp, zss, vp]
-    L.chip_zstd_seek_table_write_host.restype = C.c_int
-    L.chip_zstd_seek_table_write_host.argtypes = [u64, vp, vp, vp, vp, u64, C.POINTER(u64)]
-    L.chip_zstd_seek_table_write.restype = C.c_int
-    L.chip_zstd_seek_table_write.argtypes = [u64, vp, vp, vp, vp, u64, C.POINTER(u64), vp]
-    L.chip_xxh64_batch.restype = C.c_int
-    L.chip_xxh64_batch.argtypes = [sz, vp, vp, vp, vp, vp]
-    L.chip_xxh32_batch.restype = C.c_int
-    L.chip_xxh32_batch.argtypes = [sz, vp, vp, vp, C.c_uint32, vp, vp]
-    L.chip_lz4_block_decode_host.restype = C.c_int
-    L.chip_lz4_block_decode_host.argtypes = [vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64)]
-    L.chip_lz4_blocks_host.restype = C.c_int
-    L.chip_lz4_blocks_host.argtypes = [vp, u64, u64, vp, C.POINTER(_Lz4BlocksSummary)]
-    L.chip_lz4_blocks.restype = C.c_int
-    L.chip_lz4_blocks.argtypes = [vp, u64, u64, vp, C.POINTER(_Lz4BlocksSummary), vp]
-    L.chip_lz4_parallel.restype = C.c_int
-    L.chip_lz4_parallel.argtypes = [vp, u64, vp, u64, C.c_uint32, C.POINTER(_Lz4ParallelSummary), vp]
-    L.chip_lz4_block_encode_host.restype = C.c_int
-    L.chip_lz4_block_encode_host.argtypes = [vp, u64, C.c_int, vp, u64, C.POINTER(u64)]
-    L.chip_lz4_frame_encode_host.restype = C.c_int
-    L.chip_lz4_frame_encode_host.argtypes = [vp, u64, C.c_int, C.c_int, vp, u64, C.POINTER(u64)]
-    L.chip_zstd_seek_read.restype = C.c_int
-    L.chip_zstd_seek_read.argtypes = [sz, vp, vp, vp, vp, vp, vp, sz, vp, vp, vp, u64, vp, vp, C.POINTER(_ReadSummary), vp]
-    L.chip_inflate_index_build.restype = C.c_int
-    L.chip_inflate_index_build.argtypes = [C.c_int, vp, C.c_uint64, vp, C.c_uint64, C.c_uint32, C.c_uint64, vp, vp, vp, vp,
-                                           C.POINTER(_InflateIndexSummary), vp]
-    L.chip_inflate_index_units_host.restype = C.c_int
-    L.chip_inflate_index_units_host.argtypes = [C.c_int, C.c_uint64, C.c_uint64, vp, vp, vp, C.c_uint64, vp, vp, vp, vp, vp, C.POINTER(i32),
-                                                C.POINTER(C.c_uint64)]
-    L.chip_inflate_index_read.restype = C.c_int
-    L.chip_inflate_index_read.argtypes = [C.c_int, vp, C.c_uint64, C.c_uint64, vp, vp, vp, vp, C.c_uint64, sz, vp, vp, vp, C.c_uint64, vp, vp,
-                                          C.POINTER(_ReadSummary), vp]
-    L.chip_inflate_find_starts_host.restype = C.c_int
-    L.chip_inflate_find_starts_host.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint64, vp, C.POINTER(C.c_uint64)]
-    L.chip_inflate_find_starts.restype = C.c_int
-    L.chip_inflate_find_starts.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint64, vp, C.POINTER(C.c_uint64), vp]
-    L.chip_inflate_parallel.restype = C.c_int
-    L.chip_inflate_parallel.argtypes = [C.c_int, vp, C.c_uint64, vp, C.c_uint64, C.c_uint32, C.c_uint64, vp, vp, vp, vp,
-                                        C.POINTER(_InflateParallelSummary), vp]
-    L.chip_inflate_parallel_next.restype = C.c_int
-    L.chip_inflate_parallel_next.argtypes = [C.c_int, C.POINTER(_InflateCursor), vp, vp, C.c_uint64, vp, C.c_uint64, C.c_uint32,
-                                             C.POINTER(_InflateNextSummary), vp]
-    _lib = L
-    return L
-
+from ._ffi import (  # noqa: F401
+    _BgzfSummary,
+    _BrotliEncoderOpts,
+    _DecodeResult,
+    _DecoderOpts,
+    _EncodeResult,
+    _EncoderOpts,
+    _FileSummary,
+    _GzipPlanSummary,
+    _InflateCursor,
+    _InflateIndexSummary,
+    _InflateNextSummary,
+    _InflateParallelSummary,
+    _Lz4Block,
+    _Lz4BlocksSummary,
+    _Lz4ParallelSummary,
+    _ReadSummary,
+    _SelectSummary,
+    _TarEntry,
+    _TarPlanSummary,
+    _TarSource,
+    _TarWriteSummary,
+    _Xxh64State,
+    _ZipDecodeSummary,
+    _ZipEntry,
+    _ZipPlanSummary,
+    _ZipSource,
+    _ZipWriteSummary,
+    _ZstdBlock,
+    _ZstdBlocksSummary,
+    _ZstdCursor,
+    _ZstdEncoderOpts,
+    _ZstdNextSummary,
+    _ZstdParallelSummary,
+    _ZstdPlanSummary,
+    _ZstdSeekSummary,
+    _ZstdSlabSummary,
+    lib,
+    lib_path,
+)
 
 # ---- enums and result types ----------------------------------------------------------------
 
@@ -1254,6 +907,42 @@ def encode_batch(fmt, level, in_buf, in_off, in_len, out_buf, out_off, out_cap, 
     return out_len, status
 
 
+# ---- summaries: a chip_*_summary structure as Python values ------------------------------------
+#
+# A summary class is its docstring and `__slots__ = FIELDS = _fields(_TheStructure)` (FIELDS alone: its values can be
+# assigned), ENUMS for the fields that are wrapped in an enum and FORMATS for those that repr() prints in another base.
+
+
+def _fields(raw_cls):
+    """The field names of a ctypes structure, in its order, without the padding."""
+    return tuple(name for name, _ in raw_cls._fields_ if name != "pad")
+
+
+class _Record:
+    """__init__(raw) and __repr__ over FIELDS: int() of every field, or the enum ENUMS names for it; repr() prints an enum by
+    its name and a field of FORMATS with that format."""
+
+    __slots__ = ()
+    ENUMS, FORMATS = {}, {}
+
+    def __init__(self, raw):
+        for name in self.FIELDS:
+            setattr(self, name, self.ENUMS.get(name, int)(getattr(raw, name)))
+
+    def __repr__(self):
+        show = lambda name, v: v.name if name in self.ENUMS else format(v, self.FORMATS.get(name, ""))  # noqa: E731
+        return f"{type(self).__name__}(" + ", ".join(f"{name}={show(name, getattr(self, name))}" for name in self.FIELDS) + ")"
+
+
+class _Summary(_Record):
+    """A _Record with as_tuple(): the fields in order, enums as int."""
+
+    __slots__ = ()
+
+    def as_tuple(self):
+        return tuple(int(getattr(self, name)) for name in self.FIELDS)
+
+
 # ---- BGZF: from a file to a batch and back (include/compu_hip.h, "BGZF") ------------------------
 
 FMT_BGZF = 131  # CHIP_FMT_BGZF: encode_batch / encode_batch_host / encode_bound only, one BGZF block per unit
@@ -1265,21 +954,12 @@ class BgzfStatus(enum.IntEnum):
     BadHeader = 2
 
 
-class BgzfSummary:
+class BgzfSummary(_Summary):
     """chip_bgzf_summary: n_blocks and total_out of the whole walk, in_used where it stopped, status why, eof = the last block
     has ISIZE 0."""
 
-    __slots__ = ("n_blocks", "total_out", "in_used", "status", "eof")
-
-    def __init__(self, raw):
-        self.n_blocks, self.total_out, self.in_used = int(raw.n_blocks), int(raw.total_out), int(raw.in_used)
-        self.status, self.eof = BgzfStatus(raw.status), int(raw.eof)
-
-    def as_tuple(self):
-        return (self.n_blocks, self.total_out, self.in_used, int(self.status), self.eof)
-
-    def __repr__(self):
-        return f"BgzfSummary(n_blocks={self.n_blocks}, total_out={self.total_out}, in_used={self.in_used}, status={self.status.name}, eof={self.eof})"
+    __slots__ = FIELDS = _fields(_BgzfSummary)
+    ENUMS = {"status": BgzfStatus}
 
 
 def bgzf_eof_block():
@@ -1289,54 +969,104 @@ def bgzf_eof_block():
     return C.string_at(p, n.value)
 
 
-def _plan_host(fn, raw_cls, wrap, count_field, data, max_units):
-    """A chip_*_plan_host call over bytes / a uint8 numpy array: count (max_units None), then fill."""
+def _count_then_fill(fn, call, count, alloc, ptr, max_units):
+    """The protocol of every plan.  `call(m, *pointers)` makes the C call `fn` with room for m units, `count()` reads how many there
+    are from what the call answered, `alloc(m)` makes the arrays of m units and `ptr` turns one into the call's argument.
+    max_units None: a counting call with null arrays, then the fill; a number: the one call.  No room (m == 0) passes null
+    pointers.  Returns the arrays, cut to the first min(m, count) units."""
+
+    def run(m):
+        arrays = alloc(m)
+        rc = call(m, *[ptr(a) if m else None for a in arrays])
+        if rc != 0:
+            raise RuntimeError(f"{fn} failed: {rc}")
+        return arrays
+
+    if max_units is None:
+        run(0)
+        max_units = count()
+    m = int(max_units)
+    arrays = run(m)
+    k = min(m, int(count()))
+    return [a[:k] for a in arrays]
+
+
+def _np_ptr(a):
+    return a.ctypes.data_as(C.c_void_p) if a.size else None
+
+
+def _host_input(data):
+    """bytes / a numpy array as a contiguous uint8 array, and its pointer (None when it is empty)"""
     import numpy as np
 
     buf = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8)
-    raw = raw_cls()
-    p = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None  # noqa: E731
-    call = getattr(lib(), fn)
-    if max_units is None:
-        rc = call(p(buf), buf.size, 0, None, None, None, None, C.byref(raw))
-        if rc != 0:
-            raise RuntimeError(f"{fn} failed: {rc}")
-        max_units = int(getattr(raw, count_field))
-    m = int(max_units)
-    in_off, in_len, out_off, out_cap = np.zeros(m, np.uint64), np.zeros(m, np.uint32), np.zeros(m, np.uint64), np.zeros(m, np.uint32)
-    rc = call(p(buf), buf.size, m, p(in_off), p(in_len), p(out_off), p(out_cap), C.byref(raw))
-    if rc != 0:
-        raise RuntimeError(f"{fn} failed: {rc}")
-    k = min(m, int(getattr(raw, count_field)))
-    return in_off[:k], in_len[:k], out_off[:k], out_cap[:k], wrap(raw)
+    return buf, _np_ptr(buf)
 
 
-def _plan_device(fn, raw_cls, wrap, count_field, in_buf, length, stream, max_units):
-    """A chip_*_plan call over a uint8 device tensor: count (max_units None), then fill."""
+def _device_input(in_buf, length):
+    """(device, length, base pointer) of a uint8 device tensor holding `length` bytes; the base of no bytes is None"""
     import torch
 
     dev = _check_tensors(((in_buf, torch.uint8),))
     length = int(length)
     if length < 0 or length > in_buf.numel():
         raise ValueError(f"length {length} outside the buffer of {in_buf.numel()} bytes")
-    raw = raw_cls()
-    base, sp = (_dp(in_buf) if length else None), _stream_ptr(stream)
-    call = getattr(lib(), fn)
+    return dev, length, (_dp(in_buf) if length else None)
+
+
+def _plan_arrays(m):
+    """a plan's four arrays in host memory, zeroed: in_off, in_len, out_off, out_cap"""
+    import numpy as np
+
+    return np.zeros(m, np.uint64), np.zeros(m, np.uint32), np.zeros(m, np.uint64), np.zeros(m, np.uint32)
+
+
+def _plan_tensors(m, dev):
+    """a plan's four arrays in device memory: in_off, in_len, out_off, out_cap"""
+    import torch
+
+    return tuple(torch.empty(m, dtype=dt, device=dev) for dt in (torch.int64, torch.int32, torch.int64, torch.int32))
+
+
+def _record_array(dtype):
+    """alloc of _plan_host for a plan of records: one zeroed numpy record array"""
+    import numpy as np
+
+    return lambda m: (np.zeros(m, dtype),)
+
+
+def _record_rows(struct, make="empty"):
+    """alloc of _plan_device for a plan of records: one uint8 tensor of shape (m, sizeof(struct))"""
+
+    def alloc(m, dev):
+        import torch
+
+        return (getattr(torch, make)((m, C.sizeof(struct)), dtype=torch.uint8, device=dev),)
+
+    return alloc
+
+
+def _plan_host(fn, raw_cls, wrap, count_field, data, max_units, alloc=_plan_arrays):
+    """A chip_*_plan_host / chip_*_blocks_host call over bytes / a uint8 numpy array: count (max_units None), then fill.  Returns
+    the arrays of `alloc` and the summary."""
+    buf, base = _host_input(data)
+    raw, call = raw_cls(), getattr(lib(), fn)
+    arrays = _count_then_fill(fn, lambda m, *out: call(base, buf.size, m, *out, C.byref(raw)), lambda: getattr(raw, count_field), alloc,
+                              _np_ptr, max_units)
+    return (*arrays, wrap(raw))
+
+
+def _plan_device(fn, raw_cls, wrap, count_field, in_buf, length, stream, max_units, alloc=_plan_tensors):
+    """A chip_*_plan / chip_*_blocks call over a uint8 device tensor: count (max_units None), then fill.  Returns the tensors of
+    `alloc` and the summary."""
+    import torch
+
+    dev, length, base = _device_input(in_buf, length)
+    raw, sp, call = raw_cls(), _stream_ptr(stream), getattr(lib(), fn)
     with torch.cuda.device(dev):
-        if max_units is None:  # count, then fill
-            rc = call(base, length, 0, None, None, None, None, C.byref(raw), sp)
-            if rc != 0:
-                raise RuntimeError(f"{fn} failed: {rc}")
-            max_units = int(getattr(raw, count_field))
-        m = int(max_units)
-        in_off, out_off = torch.empty(m, dtype=torch.int64, device=dev), torch.empty(m, dtype=torch.int64, device=dev)
-        in_len, out_cap = torch.empty(m, dtype=torch.int32, device=dev), torch.empty(m, dtype=torch.int32, device=dev)
-        q = lambda t: _dp(t) if m else None  # noqa: E731
-        rc = call(base, length, m, q(in_off), q(in_len), q(out_off), q(out_cap), C.byref(raw), sp)
-    if rc != 0:
-        raise RuntimeError(f"{fn} failed: {rc}")
-    k = min(m, int(getattr(raw, count_field)))
-    return in_off[:k], in_len[:k], out_off[:k], out_cap[:k], wrap(raw)
+        arrays = _count_then_fill(fn, lambda m, *out: call(base, length, m, *out, C.byref(raw), sp), lambda: getattr(raw, count_field),
+                                  lambda m: alloc(m, dev), _dp, max_units)
+    return (*arrays, wrap(raw))
 
 
 def _whole_plan(plan, ok, refusal, in_buf, length, stream):
@@ -1404,22 +1134,12 @@ class ZstdPlanStatus(enum.IntEnum):
     TooLarge = 3
 
 
-class ZstdPlanSummary:
+class ZstdPlanSummary(_Summary):
     """chip_zstd_plan_summary: n_frames, n_skippable, n_unsized and total_out of the whole walk, in_used where it stopped (the
     start of the frame it stopped at), status why."""
 
-    __slots__ = ("n_frames", "n_skippable", "n_unsized", "total_out", "in_used", "status")
-
-    def __init__(self, raw):
-        self.n_frames, self.n_skippable, self.n_unsized = int(raw.n_frames), int(raw.n_skippable), int(raw.n_unsized)
-        self.total_out, self.in_used, self.status = int(raw.total_out), int(raw.in_used), ZstdPlanStatus(raw.status)
-
-    def as_tuple(self):
-        return (self.n_frames, self.n_skippable, self.n_unsized, self.total_out, self.in_used, int(self.status))
-
-    def __repr__(self):
-        return (f"ZstdPlanSummary(n_frames={self.n_frames}, n_skippable={self.n_skippable}, n_unsized={self.n_unsized}, "
-                f"total_out={self.total_out}, in_used={self.in_used}, status={self.status.name})")
+    __slots__ = FIELDS = _fields(_ZstdPlanSummary)
+    ENUMS = {"status": ZstdPlanStatus}
 
 
 def zstd_plan_host(data, max_frames=None):
@@ -1445,53 +1165,25 @@ def zstd_block_dtype():
     """chip_zstd_block as a numpy record: offset, size, lit_regen, lit_comp, n_seq, type, flags, lit_type, mode[3], src[4]."""
     import numpy as np
 
-    dt = np.dtype([("offset", "<u8"), ("size", "<u4"), ("lit_regen", "<u4"), ("lit_comp", "<u4"), ("n_seq", "<u4"), ("type", "u1"),
-                   ("flags", "u1"), ("lit_type", "u1"), ("mode", "u1", (3,)), ("pad", "u1", (2,)), ("src", "<i4", (4,))])
-    assert dt.itemsize == C.sizeof(_ZstdBlock)
+    dt = np.dtype(_ZstdBlock)
+    assert dt.itemsize == 48
     return dt
 
 
-class ZstdBlocksSummary:
+class ZstdBlocksSummary(_Summary):
     """chip_zstd_blocks_summary: n_blocks the walk counted, in_used (the frame's end, 0 when the walk stopped early), content_size
     (ZBLOCKS_UNSIZED without Frame_Content_Size), window_size, status why the walk stopped, the frame header descriptor and the
     frame header's length."""
 
-    __slots__ = ("n_blocks", "in_used", "content_size", "window_size", "status", "descriptor", "header_bytes")
-
-    def __init__(self, raw):
-        self.n_blocks, self.in_used, self.content_size = int(raw.n_blocks), int(raw.in_used), int(raw.content_size)
-        self.window_size, self.status = int(raw.window_size), ZstdPlanStatus(raw.status)
-        self.descriptor, self.header_bytes = int(raw.descriptor), int(raw.header_bytes)
-
-    def as_tuple(self):
-        return (self.n_blocks, self.in_used, self.content_size, self.window_size, int(self.status), self.descriptor, self.header_bytes)
-
-    def __repr__(self):
-        return (f"ZstdBlocksSummary(n_blocks={self.n_blocks}, in_used={self.in_used}, content_size={self.content_size}, "
-                f"window_size={self.window_size}, status={self.status.name}, descriptor={self.descriptor:#x}, header_bytes={self.header_bytes})")
+    __slots__ = FIELDS = _fields(_ZstdBlocksSummary)
+    ENUMS, FORMATS = {"status": ZstdPlanStatus}, {"descriptor": "#x"}
 
 
 def zstd_blocks_host(data, max_blocks=None):
     """chip_zstd_blocks_host over bytes / a uint8 numpy array in host memory: (blocks, summary) of the FIRST frame -- blocks a
     numpy record array (zstd_block_dtype) of the first min(n_blocks, max_blocks) blocks (None = all of them: one call to count,
     one to fill).  Read from headers alone; nothing is decoded."""
-    import numpy as np
-
-    buf = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8)
-    raw = _ZstdBlocksSummary()
-    p = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None  # noqa: E731
-    call = lib().chip_zstd_blocks_host
-    if max_blocks is None:
-        rc = call(p(buf), buf.size, 0, None, C.byref(raw))
-        if rc != 0:
-            raise RuntimeError(f"chip_zstd_blocks_host failed: {rc}")
-        max_blocks = int(raw.n_blocks)
-    m = int(max_blocks)
-    blocks = np.zeros(m, zstd_block_dtype())
-    rc = call(p(buf), buf.size, m, p(blocks), C.byref(raw))
-    if rc != 0:
-        raise RuntimeError(f"chip_zstd_blocks_host failed: {rc}")
-    return blocks[:min(m, int(raw.n_blocks))], ZstdBlocksSummary(raw)
+    return _plan_host("chip_zstd_blocks_host", _ZstdBlocksSummary, ZstdBlocksSummary, "n_blocks", data, max_blocks, _record_array(zstd_block_dtype()))
 
 
 def zstd_blocks(in_buf, length, stream=None, max_blocks=None):
@@ -1499,27 +1191,8 @@ def zstd_blocks(in_buf, length, stream=None, max_blocks=None):
     a multiple of 4): (blocks, summary), blocks a uint8 device tensor of shape (k, 48) holding the chip_zstd_block records of the
     first k = min(n_blocks, max_blocks) blocks (`.cpu().numpy().view(zstd_block_dtype())` reads them).  Synchronous on `stream`.
     max_blocks None: all of them (one call to count, one to fill)."""
-    import torch
-
-    dev = _check_tensors(((in_buf, torch.uint8),))
-    length = int(length)
-    if length < 0 or length > in_buf.numel():
-        raise ValueError(f"length {length} outside the buffer of {in_buf.numel()} bytes")
-    raw = _ZstdBlocksSummary()
-    base, sp = (_dp(in_buf) if length else None), _stream_ptr(stream)
-    call = lib().chip_zstd_blocks
-    with torch.cuda.device(dev):
-        if max_blocks is None:  # count, then fill
-            rc = call(base, length, 0, None, C.byref(raw), sp)
-            if rc != 0:
-                raise RuntimeError(f"chip_zstd_blocks failed: {rc}")
-            max_blocks = int(raw.n_blocks)
-        m = int(max_blocks)
-        blocks = torch.empty((m, C.sizeof(_ZstdBlock)), dtype=torch.uint8, device=dev)
-        rc = call(base, length, m, _dp(blocks) if m else None, C.byref(raw), sp)
-    if rc != 0:
-        raise RuntimeError(f"chip_zstd_blocks failed: {rc}")
-    return blocks[:min(m, int(raw.n_blocks))], ZstdBlocksSummary(raw)
+    return _plan_device("chip_zstd_blocks", _ZstdBlocksSummary, ZstdBlocksSummary, "n_blocks", in_buf, length, stream, max_blocks,
+                        _record_rows(_ZstdBlock))
 
 
 ZPAR_SERIAL, ZPAR_PARALLEL, ZPAR_REFUSED = 0, 1, 2  # chip_zstd_parallel_summary.path
@@ -1527,24 +1200,15 @@ ZPAR_NO_CHECKSUM = 1  # CHIP_ZPAR_NO_CHECKSUM
 ZPAR_ROUNDS_MAX = 40
 
 
-class ZstdParallelSummary:
+class ZstdParallelSummary(_Summary):
     """chip_zstd_parallel_summary: n_blocks and n_sequences of the frame (parallel path), out_len, in_used, total_out (the size to
     come back with on NeedOutput), status, path (ZPAR_*), rounds of the jump pass, check."""
 
-    __slots__ = ("n_blocks", "n_sequences", "out_len", "in_used", "total_out", "status", "path", "rounds", "check")
-
-    def __init__(self, raw):
-        self.n_blocks, self.n_sequences, self.out_len = int(raw.n_blocks), int(raw.n_sequences), int(raw.out_len)
-        self.in_used, self.total_out, self.status = int(raw.in_used), int(raw.total_out), int(raw.status)
-        self.path, self.rounds, self.check = int(raw.path), int(raw.rounds), int(raw.check)
+    __slots__ = FIELDS = _fields(_ZstdParallelSummary)
 
     def as_tuple(self):
         """everything but `rounds`, which may differ from call to call"""
-        return (self.n_blocks, self.n_sequences, self.out_len, self.in_used, self.total_out, self.status, self.path, self.check)
-
-    def __repr__(self):
-        return (f"ZstdParallelSummary(n_blocks={self.n_blocks}, n_sequences={self.n_sequences}, out_len={self.out_len}, in_used={self.in_used}, "
-                f"total_out={self.total_out}, status={self.status}, path={self.path}, rounds={self.rounds}, check={self.check})")
+        return tuple(getattr(self, name) for name in self.FIELDS if name != "rounds")
 
 
 def zstd_parallel(in_buf, length, out_buf=None, window_log_max=0, checksum=True, stream=None):
@@ -1627,19 +1291,12 @@ class ZstdCursor:
         return "ZstdCursor(" + ", ".join(f"{name}={getattr(self, name)}" for name in self.FIELDS) + f", rep={list(self.raw.rep)})"
 
 
-class ZstdNextSummary:
+class ZstdNextSummary(_Record):
     """chip_zstd_next_summary: in_used bytes of the slab lie in front of the new cursor, out_len bytes were delivered, need_out is the
     decoded size of the block that did not fit, need_state the state bytes to come back with, n_blocks / n_sequences / rounds
     describe the blocks taken, status says why the call stopped (a DecodeStatus value or a negative error)."""
 
-    FIELDS = tuple(name for name, _ in _ZstdNextSummary._fields_)
-
-    def __init__(self, raw):
-        for name in self.FIELDS:
-            setattr(self, name, int(getattr(raw, name)))
-
-    def __repr__(self):
-        return "ZstdNextSummary(" + ", ".join(f"{name}={getattr(self, name)}" for name in self.FIELDS) + ")"
+    FIELDS = _fields(_ZstdNextSummary)
 
 
 def zstd_parallel_next(cursor, in_buf, out_buf, window_log_max=0, checksum=True, stream=None, grow_state=True):
@@ -1672,39 +1329,21 @@ def zstd_parallel_next(cursor, in_buf, out_buf, window_log_max=0, checksum=True,
         cursor.state = state
 
 
-class ZstdSlabSummary:
+class ZstdSlabSummary(_Summary):
     """chip_zstd_slab_summary: the whole blocks in front of where the walk from a block boundary stopped, their bytes, why it stopped
     (ZstdPlanStatus; Truncated is a cut block, no error) and whether the frame's last block is among them."""
 
-    __slots__ = ("n_blocks", "in_used", "status", "last")
-
-    def __init__(self, raw):
-        self.n_blocks, self.in_used, self.status, self.last = int(raw.n_blocks), int(raw.in_used), ZstdPlanStatus(raw.status), int(raw.last)
-
-    def as_tuple(self):
-        return (self.n_blocks, self.in_used, int(self.status), self.last)
-
-    def __repr__(self):
-        return f"ZstdSlabSummary(n_blocks={self.n_blocks}, in_used={self.in_used}, status={self.status.name}, last={self.last})"
+    __slots__ = FIELDS = _fields(_ZstdSlabSummary)
+    ENUMS = {"status": ZstdPlanStatus}
 
 
 def zstd_slab_blocks_host(data, block_max=131072):
     """chip_zstd_slab_blocks_host over bytes that begin at a block boundary of a frame whose Block_Maximum_Size is block_max:
     (blocks, summary), the records as zstd_blocks_host's with slab-relative offsets and sources."""
-    import numpy as np
-
-    buf = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8)
-    raw = _ZstdSlabSummary()
-    p = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None  # noqa: E731
-    call = lib().chip_zstd_slab_blocks_host
-    rc = call(p(buf), buf.size, int(block_max), 0, None, C.byref(raw))
-    if rc != 0:
-        raise RuntimeError(f"chip_zstd_slab_blocks_host failed: {rc}")
-    m = int(raw.n_blocks)
-    blocks = np.zeros(m, zstd_block_dtype())
-    rc = call(p(buf), buf.size, int(block_max), m, p(blocks), C.byref(raw))
-    if rc != 0:
-        raise RuntimeError(f"chip_zstd_slab_blocks_host failed: {rc}")
+    buf, base = _host_input(data)
+    raw, call = _ZstdSlabSummary(), lib().chip_zstd_slab_blocks_host
+    blocks, = _count_then_fill("chip_zstd_slab_blocks_host", lambda m, out: call(base, buf.size, int(block_max), m, out, C.byref(raw)),
+                               lambda: raw.n_blocks, _record_array(zstd_block_dtype()), _np_ptr, None)
     return blocks, ZstdSlabSummary(raw)
 
 
@@ -1744,26 +1383,57 @@ class Xxh64:
         return other
 
 
-def zstd_parallel_stream(source, sink=None, slab_bytes=64 << 20, out_bytes=256 << 20, frames=False, checksum=True, window_log_max=0, device=None):
-    """One zstd frame of ANY length through zstd_parallel_next: `source` (bytes-like, or a binary file object) is uploaded slab after
-    slab, every call's bytes are downloaded and written to `sink` (a binary file object; None: they are returned as bytes).  The
-    slab doubles when a call finds no whole block in it, the room goes to need_out when the next block does not fit, the state is
-    allocated from need_state.  frames=True: behind a finished frame the loop goes on while a zstd or skippable magic follows, as
-    `zstd -d` does, and steps over skippable frames itself.  Raises DecodeError(code) on an error in the frame and EOFError when
-    the source ends inside it.  Returns the bytes, or with a sink the number of bytes written."""
-    import numpy as np
-    import torch
+class _Slabs:
+    """What _slab_stream asks of a format.  The format's own: slab_max and room_max (the limits of one call), eof_text, spare and
+    alloc_in (the input tensor), new_cursor, step, room_now, grow_room and after_finished.  Shared: the two device buffers and the
+    copies to and from them -- new_cursor, upload, room, step and download are all that touches the device."""
 
-    dev = torch.device(device if device is not None else "cuda")
+    spare = 0  # bytes the input tensor has behind the slab
+
+    def __init__(self, device):
+        import torch
+
+        self.dev = torch.device(device if device is not None else "cuda")
+        self.d_in = self.d_out = None
+
+    def upload(self, pending, n, slab):
+        """pending[:n] in device memory; the tensor is kept from call to call and replaced when it is too small"""
+        import numpy as np
+        import torch
+
+        if self.d_in is None or self.d_in.numel() < n + self.spare:
+            self.d_in = self.alloc_in(n, slab)
+        if n:  # straight from the pending bytes (the copy from pageable memory has ended when copy_ returns)
+            self.d_in[:n].copy_(torch.from_numpy(np.frombuffer(pending, dtype=np.uint8, count=n)))
+        return self.d_in[:n]
+
+    def room(self, k):
+        import torch
+
+        if self.d_out is None or self.d_out.numel() < k:
+            self.d_out = torch.empty(k, dtype=torch.uint8, device=self.dev)
+        return self.d_out[:k]
+
+    def download(self, out, k):
+        return out[:k].cpu().numpy().tobytes()
+
+    def room_now(self, cur, pending, room):
+        return room
+
+
+def _slab_stream(slabs, source, sink, slab_bytes, out_bytes):
+    """The loop of zstd_parallel_stream and inflate_parallel_stream over `slabs`, a _Slabs: `source` (bytes-like, or a binary file
+    object) is read into `pending`, a slab of it uploaded, the cursor stepped, the call's bytes downloaded and written to `sink`
+    (None: collected), what the call used cut from `pending`.  Then: a finished unit ends the loop unless slabs.after_finished begins
+    another; an error raises DecodeError; a call that used and gave nothing grows the room (NeedOutput), doubles the slab while the
+    source has more, and is EOFError at its end.  Returns the bytes, or with a sink their number."""
     read = source.read if hasattr(source, "read") else None
     view, taken = (None, 0) if read else (memoryview(source).cast("B"), 0)
     pending, eof = bytearray(), False
     slab, room = max(int(slab_bytes), 1), max(int(out_bytes), 1)
     parts, written = [], 0
-    cur = ZstdCursor(dev)
-    d_in, d_out = None, None
 
-    def fill(want):
+    def fill(want):  # (a short read is not the end: an empty one is)
         nonlocal eof, taken
         while not eof and len(pending) < want:
             if read:
@@ -1775,26 +1445,15 @@ def zstd_parallel_stream(source, sink=None, slab_bytes=64 << 20, out_bytes=256 <
                 eof = True
             pending.extend(piece)
 
+    cur = slabs.new_cursor()
     while True:
-        slab, room = min(slab, 1 << 31), min(room, (1 << 31) - 1)
+        slab, room = min(slab, slabs.slab_max), min(room, slabs.room_max)
         fill(slab)
         n = min(len(pending), slab)  # (below the slab only where the source has ended: the buffers are as large as what there is)
-        left = cur.content_size - cur.out_total if cur.phase and cur.content_size != ZBLOCKS_UNSIZED else ZBLOCKS_UNSIZED
-        if not cur.phase:  # a new frame: what its header says of its size, so that a small frame gets a small room
-            rc, head, _, _ = zstd_cursor_header_host(pending[:18], 31)
-            left = int(head.content_size) if rc == int(DecodeStatus.Finished) else ZBLOCKS_UNSIZED
-        room_now = min(room, max(left, 1)) if 0 <= left < ZBLOCKS_UNSIZED else room
-        if d_in is None or d_in.numel() < n:
-            d_in = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
-        if d_out is None or d_out.numel() < room_now:
-            d_out = torch.empty(room_now, dtype=torch.uint8, device=dev)
-        if n:  # straight from the pending bytes (the copy from pageable memory has ended when copy_ returns)
-            host = torch.from_numpy(np.frombuffer(pending, dtype=np.uint8, count=n))
-            d_in[:n].copy_(host)
-            del host  # (it holds the bytearray's buffer, which is cut below)
-        s = zstd_parallel_next(cur, d_in[:n], d_out[:room_now], window_log_max, checksum)
+        out = slabs.room(slabs.room_now(cur, pending, room))
+        s = slabs.step(cur, slabs.upload(pending, n, slab), out)
         if s.out_len:
-            got = d_out[: s.out_len].cpu().numpy().tobytes()
+            got = slabs.download(out, s.out_len)
             written += len(got)
             if sink is None:
                 parts.append(got)
@@ -1802,39 +1461,82 @@ def zstd_parallel_stream(source, sink=None, slab_bytes=64 << 20, out_bytes=256 <
                 sink.write(got)
         del pending[: s.in_used]
         if s.status == int(DecodeStatus.Finished):
-            again = False
-            while frames:
-                fill(8)
-                magic = int.from_bytes(bytes(pending[:4]), "little") if len(pending) >= 4 else 0
-                if magic & 0xFFFFFFF0 == 0x184D2A50:  # a skippable frame: 8 bytes and what they announce
-                    if len(pending) < 8:
-                        raise EOFError("the source ends inside a skippable frame")
-                    size = 8 + int.from_bytes(bytes(pending[4:8]), "little")
-                    fill(size)
-                    if len(pending) < size:
-                        raise EOFError("the source ends inside a skippable frame")
-                    del pending[:size]
-                    continue
-                again = magic == 0xFD2FB528
+            cur = slabs.after_finished(cur, pending, fill)
+            if cur is None:
                 break
-            if again:
-                cur = ZstdCursor(dev)
-                continue
-            break
+            continue
         if s.status not in (int(DecodeStatus.NeedInput), int(DecodeStatus.NeedOutput)):
             raise DecodeError(s.status)
         if s.in_used == 0 and s.out_len == 0:
             if s.status == int(DecodeStatus.NeedOutput):
-                if s.need_out > (1 << 31) - 1:
-                    raise DecodeError(-5)
-                room = max(room, s.need_out)
+                room = slabs.grow_room(room, s.need_out)
             elif n < len(pending) or not eof:
-                if slab >= 1 << 31:
+                if slab >= slabs.slab_max:
                     raise DecodeError(-5)  # a block beyond a call's slab
                 slab *= 2
             else:
-                raise EOFError("the source ends inside the frame")
+                raise EOFError(slabs.eof_text)
     return b"".join(parts) if sink is None else written
+
+
+class _ZstdSlabs(_Slabs):
+    """zstd_parallel_stream's side of _slab_stream"""
+
+    slab_max, room_max = 1 << 31, (1 << 31) - 1
+    eof_text = "the source ends inside the frame"
+
+    def __init__(self, device, frames, checksum, window_log_max):
+        super().__init__(device)
+        self.frames, self.checksum, self.window_log_max = frames, checksum, window_log_max
+
+    def new_cursor(self):
+        return ZstdCursor(self.dev)
+
+    def alloc_in(self, n, slab):  # uninitialised, exactly what there is
+        import torch
+
+        return torch.empty(max(n, 1), dtype=torch.uint8, device=self.dev)
+
+    def step(self, cur, d_in, d_out):
+        return zstd_parallel_next(cur, d_in, d_out, self.window_log_max, self.checksum)
+
+    def room_now(self, cur, pending, room):
+        left = cur.content_size - cur.out_total if cur.phase and cur.content_size != ZBLOCKS_UNSIZED else ZBLOCKS_UNSIZED
+        if not cur.phase:  # a new frame: what its header says of its size, so that a small frame gets a small room
+            rc, head, _, _ = zstd_cursor_header_host(pending[:18], 31)
+            left = int(head.content_size) if rc == int(DecodeStatus.Finished) else ZBLOCKS_UNSIZED
+        return min(room, max(left, 1)) if 0 <= left < ZBLOCKS_UNSIZED else room
+
+    def grow_room(self, room, need_out):
+        if need_out > (1 << 31) - 1:
+            raise DecodeError(-5)
+        return max(room, need_out)
+
+    def after_finished(self, cur, pending, fill):
+        """frames=True: a new cursor when a zstd magic follows, skippable frames stepped over; else None"""
+        while self.frames:
+            fill(8)
+            magic = int.from_bytes(bytes(pending[:4]), "little") if len(pending) >= 4 else 0
+            if magic & 0xFFFFFFF0 != 0x184D2A50:
+                return self.new_cursor() if magic == 0xFD2FB528 else None
+            if len(pending) < 8:  # a skippable frame: 8 bytes and what they announce
+                raise EOFError("the source ends inside a skippable frame")
+            size = 8 + int.from_bytes(bytes(pending[4:8]), "little")
+            fill(size)
+            if len(pending) < size:
+                raise EOFError("the source ends inside a skippable frame")
+            del pending[:size]
+        return None
+
+
+def zstd_parallel_stream(source, sink=None, slab_bytes=64 << 20, out_bytes=256 << 20, frames=False, checksum=True, window_log_max=0, device=None):
+    """One zstd frame of ANY length through zstd_parallel_next: `source` (bytes-like, or a binary file object) is uploaded slab after
+    slab, every call's bytes are downloaded and written to `sink` (a binary file object; None: they are returned as bytes).  The
+    slab doubles when a call finds no whole block in it, the room goes to need_out when the next block does not fit, the state is
+    allocated from need_state.  frames=True: behind a finished frame the loop goes on while a zstd or skippable magic follows, as
+    `zstd -d` does, and steps over skippable frames itself.  Raises DecodeError(code) on an error in the frame and EOFError when
+    the source ends inside it.  Returns the bytes, or with a sink the number of bytes written."""
+    return _slab_stream(_ZstdSlabs(device, frames, checksum, window_log_max), source, sink, slab_bytes, out_bytes)
 
 
 def layout_units(out_size, stream=None):
@@ -1885,22 +1587,12 @@ class GzipPlanStatus(enum.IntEnum):
     BadMember = 4
 
 
-class GzipPlanSummary:
+class GzipPlanSummary(_Summary):
     """chip_gzip_plan_summary: n_members and total_out of the whole walk, in_used where it stopped (the start of the member it
     stopped at), status why, member_status the size pass's status of that member when status is BadMember (else 0)."""
 
-    __slots__ = ("n_members", "total_out", "in_used", "status", "member_status")
-
-    def __init__(self, raw):
-        self.n_members, self.total_out, self.in_used = int(raw.n_members), int(raw.total_out), int(raw.in_used)
-        self.status, self.member_status = GzipPlanStatus(raw.status), int(raw.member_status)
-
-    def as_tuple(self):
-        return (self.n_members, self.total_out, self.in_used, int(self.status), self.member_status)
-
-    def __repr__(self):
-        return (f"GzipPlanSummary(n_members={self.n_members}, total_out={self.total_out}, in_used={self.in_used}, "
-                f"status={self.status.name}, member_status={self.member_status})")
+    __slots__ = FIELDS = _fields(_GzipPlanSummary)
+    ENUMS = {"status": GzipPlanStatus}
 
 
 def gzip_plan(in_buf, length, stream=None, max_members=None):
@@ -1932,21 +1624,12 @@ class FileStatus(enum.IntEnum):
     NeedOutput = 1
 
 
-class FileSummary:
+class FileSummary(_Summary):
     """chip_file_summary: n_units encoded, out_len the file's length (the exact size needed on NeedOutput), table_off where the
     seek table starts (out_len without one), status."""
 
-    __slots__ = ("n_units", "out_len", "table_off", "status")
-
-    def __init__(self, raw):
-        self.n_units, self.out_len, self.table_off = int(raw.n_units), int(raw.out_len), int(raw.table_off)
-        self.status = FileStatus(raw.status)
-
-    def as_tuple(self):
-        return (self.n_units, self.out_len, self.table_off, int(self.status))
-
-    def __repr__(self):
-        return f"FileSummary(n_units={self.n_units}, out_len={self.out_len}, table_off={self.table_off}, status={self.status.name})"
+    __slots__ = FIELDS = _fields(_FileSummary)
+    ENUMS = {"status": FileStatus}
 
 
 def pack_units(src, src_off, src_len, dst=None, stream=None):
@@ -2036,42 +1719,21 @@ class RangeStatus(enum.IntEnum):
     BadUnit = 2
 
 
-class SelectSummary:
+class SelectSummary(_Summary):
     """chip_select_summary: n_sel units selected, scratch_bytes their decoded size, out_len the ranges' bytes, n_outside ranges
     outside the content, status (BadLayout: bad_index is the first unit that does not follow its predecessor)."""
 
-    __slots__ = ("n_sel", "scratch_bytes", "out_len", "n_outside", "bad_index", "status")
-
-    def __init__(self, raw):
-        self.n_sel, self.scratch_bytes, self.out_len = int(raw.n_sel), int(raw.scratch_bytes), int(raw.out_len)
-        self.n_outside, self.bad_index, self.status = int(raw.n_outside), int(raw.bad_index), ReadStatus(raw.status)
-
-    def as_tuple(self):
-        return (self.n_sel, self.scratch_bytes, self.out_len, self.n_outside, self.bad_index, int(self.status))
-
-    def __repr__(self):
-        return (f"SelectSummary(n_sel={self.n_sel}, scratch_bytes={self.scratch_bytes}, out_len={self.out_len}, "
-                f"n_outside={self.n_outside}, bad_index={self.bad_index}, status={self.status.name})")
+    __slots__ = FIELDS = _fields(_SelectSummary)
+    ENUMS = {"status": ReadStatus}
 
 
-class ReadSummary:
+class ReadSummary(_Summary):
     """chip_read_summary: n_units decoded, out_len bytes of ranges (the exact size needed on NeedOutput), n_outside, n_bad
     selected units that did not decode to their size with first_bad the lowest one's index and bad_status its status, status
     (BadLayout: bad_index says where)."""
 
-    __slots__ = ("n_units", "out_len", "n_outside", "n_bad", "first_bad", "bad_index", "status", "bad_status")
-
-    def __init__(self, raw):
-        self.n_units, self.out_len, self.n_outside = int(raw.n_units), int(raw.out_len), int(raw.n_outside)
-        self.n_bad, self.first_bad, self.bad_index = int(raw.n_bad), int(raw.first_bad), int(raw.bad_index)
-        self.status, self.bad_status = ReadStatus(raw.status), int(raw.bad_status)
-
-    def as_tuple(self):
-        return (self.n_units, self.out_len, self.n_outside, self.n_bad, self.first_bad, self.bad_index, int(self.status), self.bad_status)
-
-    def __repr__(self):
-        return (f"ReadSummary(n_units={self.n_units}, out_len={self.out_len}, n_outside={self.n_outside}, n_bad={self.n_bad}, "
-                f"first_bad={self.first_bad}, bad_index={self.bad_index}, status={self.status.name}, bad_status={self.bad_status})")
+    __slots__ = FIELDS = _fields(_ReadSummary)
+    ENUMS = {"status": ReadStatus}
 
 
 def select_units_host(in_off, in_len, out_off, out_cap, range_lo, range_len, max_sel=None):
@@ -2259,24 +1921,13 @@ class ZstdSeekStatus(enum.IntEnum):
     BadLayout = 5
 
 
-class ZstdSeekSummary:
+class ZstdSeekSummary(_Summary):
     """chip_zstd_seek_summary: n_frames entries in a table of table_bytes (on NeedTail: the tail to come back with), frames_bytes
     and total_out the sums of the compressed and content sizes, bad_index the lowest entry without a size on TooLarge, checksums
     whether the entries carry them, status."""
 
-    __slots__ = ("n_frames", "table_bytes", "frames_bytes", "total_out", "bad_index", "status", "checksums")
-
-    def __init__(self, raw):
-        self.n_frames, self.table_bytes, self.frames_bytes = int(raw.n_frames), int(raw.table_bytes), int(raw.frames_bytes)
-        self.total_out, self.bad_index = int(raw.total_out), int(raw.bad_index)
-        self.status, self.checksums = ZstdSeekStatus(raw.status), int(raw.checksums)
-
-    def as_tuple(self):
-        return (self.n_frames, self.table_bytes, self.frames_bytes, self.total_out, self.bad_index, int(self.status), self.checksums)
-
-    def __repr__(self):
-        return (f"ZstdSeekSummary(n_frames={self.n_frames}, table_bytes={self.table_bytes}, frames_bytes={self.frames_bytes}, "
-                f"total_out={self.total_out}, bad_index={self.bad_index}, status={self.status.name}, checksums={self.checksums})")
+    __slots__ = FIELDS = _fields(_ZstdSeekSummary)
+    ENUMS = {"status": ZstdSeekStatus}
 
 
 def zstd_seek_plan_host(tail, file_len=None, max_frames=None):
@@ -2285,23 +1936,13 @@ def zstd_seek_plan_host(tail, file_len=None, max_frames=None):
     max_frames) entries (None = all of them: one call to count, one to fill).  With a status other than Ok the arrays are empty."""
     import numpy as np
 
-    buf = np.frombuffer(tail, dtype=np.uint8) if not isinstance(tail, np.ndarray) else np.ascontiguousarray(tail, dtype=np.uint8)
+    buf, base = _host_input(tail)
     file_len = buf.size if file_len is None else int(file_len)
-    raw = _ZstdSeekSummary()
-    p = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None  # noqa: E731
-    if max_frames is None:
-        rc = lib().chip_zstd_seek_plan_host(p(buf), buf.size, file_len, 0, None, None, None, None, None, C.byref(raw))
-        if rc != 0:
-            raise RuntimeError(f"chip_zstd_seek_plan_host failed: {rc}")
-        max_frames = int(raw.n_frames) if raw.status == int(ZstdSeekStatus.Ok) else 0
-    m = int(max_frames)
-    in_off, in_len, out_off, out_cap = np.zeros(m, np.uint64), np.zeros(m, np.uint32), np.zeros(m, np.uint64), np.zeros(m, np.uint32)
-    checksum = np.zeros(m, np.uint32)
-    rc = lib().chip_zstd_seek_plan_host(p(buf), buf.size, file_len, m, p(in_off), p(in_len), p(out_off), p(out_cap), p(checksum), C.byref(raw))
-    if rc != 0:
-        raise RuntimeError(f"chip_zstd_seek_plan_host failed: {rc}")
-    k = min(m, int(raw.n_frames)) if raw.status == int(ZstdSeekStatus.Ok) else 0
-    return in_off[:k], in_len[:k], out_off[:k], out_cap[:k], checksum[:k], ZstdSeekSummary(raw)
+    raw, call = _ZstdSeekSummary(), lib().chip_zstd_seek_plan_host
+    arrays = _count_then_fill("chip_zstd_seek_plan_host", lambda m, *out: call(base, buf.size, file_len, m, *out, C.byref(raw)),
+                              lambda: raw.n_frames if raw.status == int(ZstdSeekStatus.Ok) else 0,
+                              lambda m: (*_plan_arrays(m), np.zeros(m, np.uint32)), _np_ptr, max_frames)
+    return (*arrays, ZstdSeekSummary(raw))
 
 
 def zstd_seek_plan(tail, file_len=None, stream=None, max_frames=None):
@@ -2314,24 +1955,13 @@ def zstd_seek_plan(tail, file_len=None, stream=None, max_frames=None):
     dev = _check_tensors(((tail, torch.uint8),))
     tail_len = tail.numel()
     file_len = tail_len if file_len is None else int(file_len)
-    raw = _ZstdSeekSummary()
+    raw, call = _ZstdSeekSummary(), lib().chip_zstd_seek_plan
     base, sp = (_dp(tail) if tail_len else None), _stream_ptr(stream)
-    call = lib().chip_zstd_seek_plan
     with torch.cuda.device(dev):
-        if max_frames is None:
-            rc = call(base, tail_len, file_len, 0, None, None, None, None, None, C.byref(raw), sp)
-            if rc != 0:
-                raise RuntimeError(f"chip_zstd_seek_plan failed: {rc}")
-            max_frames = int(raw.n_frames) if raw.status == int(ZstdSeekStatus.Ok) else 0
-        m = int(max_frames)
-        in_off, out_off = torch.empty(m, dtype=torch.int64, device=dev), torch.empty(m, dtype=torch.int64, device=dev)
-        in_len, out_cap, checksum = (torch.empty(m, dtype=torch.int32, device=dev) for _ in range(3))
-        q = lambda t: _dp(t) if m else None  # noqa: E731
-        rc = call(base, tail_len, file_len, m, q(in_off), q(in_len), q(out_off), q(out_cap), q(checksum), C.byref(raw), sp)
-    if rc != 0:
-        raise RuntimeError(f"chip_zstd_seek_plan failed: {rc}")
-    k = min(m, int(raw.n_frames)) if raw.status == int(ZstdSeekStatus.Ok) else 0
-    return in_off[:k], in_len[:k], out_off[:k], out_cap[:k], checksum[:k], ZstdSeekSummary(raw)
+        arrays = _count_then_fill("chip_zstd_seek_plan", lambda m, *out: call(base, tail_len, file_len, m, *out, C.byref(raw), sp),
+                                  lambda: raw.n_frames if raw.status == int(ZstdSeekStatus.Ok) else 0,
+                                  lambda m: (*_plan_tensors(m, dev), torch.empty(m, dtype=torch.int32, device=dev)), _dp, max_frames)
+    return (*arrays, ZstdSeekSummary(raw))
 
 
 def zstd_seek_table_write_host(c_len, d_len, checksum=None):
@@ -2582,23 +2212,13 @@ class SeekableZstd:
 INDEX_WINDOW = 32768  # bytes of a window slot
 
 
-class InflateIndexSummary:
+class InflateIndexSummary(_Summary):
     """chip_inflate_index_summary: n_points of the whole walk; out_len, in_used and status as decode_batch answers them for the
     unit; wrap 0 raw / 1 zlib / 2 gzip; with status Finished, check = the content's CRC-32 / Adler-32 and end_bit = the bit behind
     the final block."""
 
-    __slots__ = ("n_points", "out_len", "in_used", "end_bit", "status", "wrap", "check")
-
-    def __init__(self, raw):
-        self.n_points, self.out_len, self.in_used, self.end_bit = int(raw.n_points), int(raw.out_len), int(raw.in_used), int(raw.end_bit)
-        self.status, self.wrap, self.check = int(raw.status), int(raw.wrap), int(raw.check)
-
-    def as_tuple(self):
-        return (self.n_points, self.out_len, self.in_used, self.end_bit, self.status, self.wrap, self.check)
-
-    def __repr__(self):
-        return (f"InflateIndexSummary(n_points={self.n_points}, out_len={self.out_len}, in_used={self.in_used}, end_bit={self.end_bit}, "
-                f"status={self.status}, wrap={self.wrap}, check={self.check:#010x})")
+    __slots__ = FIELDS = _fields(_InflateIndexSummary)
+    FORMATS = {"check": "#010x"}
 
 
 class InflateIndex:
@@ -2749,70 +2369,32 @@ def zip_entry_dtype():
     """chip_zip_entry as a numpy record: header_off, data_off, comp_size, size, name_off, crc32, name_len, method, flags, pad, status."""
     import numpy as np
 
-    dt = np.dtype([("header_off", "<u8"), ("data_off", "<u8"), ("comp_size", "<u8"), ("size", "<u8"), ("name_off", "<u8"), ("crc32", "<u4"),
-                   ("name_len", "<u2"), ("method", "<u2"), ("flags", "<u2"), ("pad", "<u2"), ("status", "<i4")])
-    assert dt.itemsize == C.sizeof(_ZipEntry) == 56
+    dt = np.dtype(_ZipEntry)
+    assert dt.itemsize == 56
     return dt
 
 
-class ZipPlanSummary:
+class ZipPlanSummary(_Summary):
     """chip_zip_plan_summary: n_entries, n_ok and total_size (decoded bytes of the OK entries) of the whole walk, the directory's
     place (cd_off, cd_size), the end record's (eocd_off), bad_index (the entry a BadDirectory walk stopped at), status, zip64."""
 
-    __slots__ = ("n_entries", "n_ok", "total_size", "cd_off", "cd_size", "eocd_off", "bad_index", "status", "zip64")
-
-    def __init__(self, raw):
-        self.n_entries, self.n_ok, self.total_size = int(raw.n_entries), int(raw.n_ok), int(raw.total_size)
-        self.cd_off, self.cd_size, self.eocd_off, self.bad_index = int(raw.cd_off), int(raw.cd_size), int(raw.eocd_off), int(raw.bad_index)
-        self.status, self.zip64 = ZipStatus(raw.status), int(raw.zip64)
-
-    def as_tuple(self):
-        return (self.n_entries, self.n_ok, self.total_size, self.cd_off, self.cd_size, self.eocd_off, self.bad_index, int(self.status), self.zip64)
-
-    def __repr__(self):
-        return (f"ZipPlanSummary(n_entries={self.n_entries}, n_ok={self.n_ok}, total_size={self.total_size}, cd_off={self.cd_off}, "
-                f"cd_size={self.cd_size}, eocd_off={self.eocd_off}, bad_index={self.bad_index}, status={self.status.name}, zip64={self.zip64})")
+    __slots__ = FIELDS = _fields(_ZipPlanSummary)
+    ENUMS = {"status": ZipStatus}
 
 
-class ZipDecodeSummary:
+class ZipDecodeSummary(_Summary):
     """chip_zip_decode_summary: n_sel, n_ok (entries that are Finished), n_bad, first_bad (position in the selection), total_out,
     status (ReadStatus.Ok or NeedOutput)."""
 
-    __slots__ = ("n_sel", "n_ok", "n_bad", "first_bad", "total_out", "status")
-
-    def __init__(self, raw):
-        self.n_sel, self.n_ok, self.n_bad, self.first_bad = int(raw.n_sel), int(raw.n_ok), int(raw.n_bad), int(raw.first_bad)
-        self.total_out, self.status = int(raw.total_out), ReadStatus(raw.status)
-
-    def as_tuple(self):
-        return (self.n_sel, self.n_ok, self.n_bad, self.first_bad, self.total_out, int(self.status))
-
-    def __repr__(self):
-        return (f"ZipDecodeSummary(n_sel={self.n_sel}, n_ok={self.n_ok}, n_bad={self.n_bad}, first_bad={self.first_bad}, "
-                f"total_out={self.total_out}, status={self.status.name})")
+    __slots__ = FIELDS = _fields(_ZipDecodeSummary)
+    ENUMS = {"status": ReadStatus}
 
 
 def zip_plan_host(data, max_entries=None):
     """chip_zip_plan_host over bytes / a uint8 numpy array in host memory: (entries, summary), entries a numpy record array
     (zip_entry_dtype) of the first min(n_entries, max_entries) entries (None = all of them: one call to count, one to fill).  Read
     from the directory and the local headers alone; nothing is decoded."""
-    import numpy as np
-
-    buf = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8)
-    raw = _ZipPlanSummary()
-    p = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None  # noqa: E731
-    call = lib().chip_zip_plan_host
-    if max_entries is None:
-        rc = call(p(buf), buf.size, 0, None, C.byref(raw))
-        if rc != 0:
-            raise RuntimeError(f"chip_zip_plan_host failed: {rc}")
-        max_entries = int(raw.n_entries)
-    m = int(max_entries)
-    entries = np.zeros(m, zip_entry_dtype())
-    rc = call(p(buf), buf.size, m, p(entries), C.byref(raw))
-    if rc != 0:
-        raise RuntimeError(f"chip_zip_plan_host failed: {rc}")
-    return entries[:min(m, int(raw.n_entries))], ZipPlanSummary(raw)
+    return _plan_host("chip_zip_plan_host", _ZipPlanSummary, ZipPlanSummary, "n_entries", data, max_entries, _record_array(zip_entry_dtype()))
 
 
 def zip_plan(in_buf, length, stream=None, max_entries=None):
@@ -2820,27 +2402,7 @@ def zip_plan(in_buf, length, stream=None, max_entries=None):
     (entries, summary), entries a uint8 device tensor of shape (k, 56) holding the chip_zip_entry records of the first
     k = min(n_entries, max_entries) entries (`.cpu().numpy().view(zip_entry_dtype())` reads them; zip_decode takes the tensor).
     Synchronous on `stream`.  max_entries None: all of them (one call to count, one to fill)."""
-    import torch
-
-    dev = _check_tensors(((in_buf, torch.uint8),))
-    length = int(length)
-    if length < 0 or length > in_buf.numel():
-        raise ValueError(f"length {length} outside the buffer of {in_buf.numel()} bytes")
-    raw = _ZipPlanSummary()
-    base, sp = (_dp(in_buf) if length else None), _stream_ptr(stream)
-    call = lib().chip_zip_plan
-    with torch.cuda.device(dev):
-        if max_entries is None:  # count, then fill
-            rc = call(base, length, 0, None, C.byref(raw), sp)
-            if rc != 0:
-                raise RuntimeError(f"chip_zip_plan failed: {rc}")
-            max_entries = int(raw.n_entries)
-        m = int(max_entries)
-        entries = torch.empty((m, C.sizeof(_ZipEntry)), dtype=torch.uint8, device=dev)
-        rc = call(base, length, m, _dp(entries) if m else None, C.byref(raw), sp)
-    if rc != 0:
-        raise RuntimeError(f"chip_zip_plan failed: {rc}")
-    return entries[:min(m, int(raw.n_entries))], ZipPlanSummary(raw)
+    return _plan_device("chip_zip_plan", _ZipPlanSummary, ZipPlanSummary, "n_entries", in_buf, length, stream, max_entries, _record_rows(_ZipEntry))
 
 
 def zip_names(entries, summary, directory):
@@ -2956,30 +2518,23 @@ def zip_source_dtype():
     """chip_zip_source as a numpy record: data_off, size, name_off, name_len, method, dos_time, dos_date."""
     import numpy as np
 
-    dt = np.dtype([("data_off", "<u8"), ("size", "<u8"), ("name_off", "<u8"), ("name_len", "<u2"), ("method", "<u2"), ("dos_time", "<u2"),
-                   ("dos_date", "<u2")])
-    assert dt.itemsize == C.sizeof(_ZipSource) == 32
+    dt = np.dtype(_ZipSource)
+    assert dt.itemsize == 32
     return dt
 
 
-class ZipWriteSummary:
+class ZipWriteSummary(_Summary):
     """chip_zip_write_summary: n_entries, n_deflated (entries written with method 8), out_len (the archive's length; the exact room
     to come back with on NeedOutput), the directory's place (cd_off, cd_size), the end record's (eocd_off), bad_index (the lowest
     bad record on BadSource), status, zip64."""
 
-    __slots__ = ("n_entries", "n_deflated", "out_len", "cd_off", "cd_size", "eocd_off", "bad_index", "status", "zip64")
+    __slots__ = FIELDS = _fields(_ZipWriteSummary)
+    ENUMS = {"status": ZipWriteStatus}
 
-    def __init__(self, raw):
-        self.n_entries, self.n_deflated, self.out_len = int(raw.n_entries), int(raw.n_deflated), int(raw.out_len)
-        self.cd_off, self.cd_size, self.eocd_off, self.bad_index = int(raw.cd_off), int(raw.cd_size), int(raw.eocd_off), int(raw.bad_index)
-        self.status, self.zip64 = ZipWriteStatus(raw.status), int(raw.zip64)
 
-    def as_tuple(self):
-        return (self.n_entries, self.n_deflated, self.out_len, self.cd_off, self.cd_size, self.eocd_off, self.bad_index, int(self.status), self.zip64)
-
-    def __repr__(self):
-        return (f"ZipWriteSummary(n_entries={self.n_entries}, n_deflated={self.n_deflated}, out_len={self.out_len}, cd_off={self.cd_off}, "
-                f"cd_size={self.cd_size}, eocd_off={self.eocd_off}, bad_index={self.bad_index}, status={self.status.name}, zip64={self.zip64})")
+# what the archive writers' two-call protocol is told of a format: the raw summary, its wrapper, the entry record and the status
+# enum (with Ok and NeedOutput)
+_ZIP_ARCHIVE = (_ZipWriteSummary, ZipWriteSummary, _ZipEntry, ZipWriteStatus)
 
 
 def zip_write_bound(n, names_total, content_total):
@@ -3016,30 +2571,44 @@ def zip_assemble_host(sources, names, content, crc, comp=None, comp_off=None, co
     p = lambda a: None if a is None or a.size == 0 else a.ctypes.data_as(C.c_void_p)  # noqa: E731
     pc = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
     clen = content.size if content_len is None else int(content_len)
-    raw = _ZipWriteSummary()
-    entries = np.zeros(n, zip_entry_dtype())
 
-    def call(out, cap):
-        rc = lib().chip_zip_assemble_host(n, p(src), p(names), names.size, pc(content) if clen else None, clen, pc(comp), comp_all, pc(comp_off), pc(comp_len),
-                                          p(crc), flags, p(out), cap, p(entries), C.byref(raw))
+    def call(out, cap, ent, raw):
+        return lib().chip_zip_assemble_host(n, p(src), p(names), names.size, pc(content) if clen else None, clen, pc(comp), comp_all, pc(comp_off),
+                                            pc(comp_len), p(crc), flags, out, cap, ent, raw)
+
+    return _archive_host_call("chip_zip_assemble_host", _ZIP_ARCHIVE, call, n, out_cap)
+
+
+def _archive_host_call(what, kind, call, n, out_cap):
+    """the two-call protocol of zip_assemble_host / tar_write_host: `call` makes the C call `what`, given its last four arguments (out,
+    its size, the n entries, summary).  out_cap None: one call for the size, one to write"""
+    import numpy as np
+
+    raw_cls, wrap, entry, status = kind
+    raw, entries = raw_cls(), np.zeros(n, np.dtype(entry))
+
+    def once(out):
+        rc = call(_np_ptr(out), out.size, _np_ptr(entries), C.byref(raw))
         if rc != 0:
-            raise RuntimeError(f"chip_zip_assemble_host failed: {rc}")
+            raise RuntimeError(f"{what} failed: {rc}")
 
     out = np.zeros(0 if out_cap is None else int(out_cap), np.uint8)
-    call(out, out.size)
-    if out_cap is None and raw.status == ZipWriteStatus.NeedOutput:
+    once(out)
+    if out_cap is None and raw.status == status.NeedOutput:
         out = np.zeros(int(raw.out_len), np.uint8)
-        call(out, out.size)
-    summ = ZipWriteSummary(raw)
-    return (out[:summ.out_len].tobytes() if summ.status == ZipWriteStatus.Ok else b""), entries, summ
+        once(out)
+    summ = wrap(raw)
+    return (out[:summ.out_len].tobytes() if summ.status == status.Ok else b""), entries, summ
 
 
-def _zip_device_call(what, call, n, dev, out, stream):
-    """the two-call protocol of zip_assemble / zip_write: `out` None allocates the exact room after a sizing call"""
+def _archive_device_call(what, kind, call, n, dev, out, stream):
+    """the two-call protocol of zip_assemble / zip_write / tar_write: `call` makes the C call `what`, given its last five arguments (out,
+    its size, the n entries, summary, stream).  `out` None allocates the exact room after a sizing call"""
     import torch
 
-    raw = _ZipWriteSummary()
-    entries = torch.empty((n, C.sizeof(_ZipEntry)), dtype=torch.uint8, device=dev)
+    raw_cls, wrap, entry, status = kind
+    raw = raw_cls()
+    entries = torch.empty((n, C.sizeof(entry)), dtype=torch.uint8, device=dev)
 
     def once(o):
         with torch.cuda.device(dev):
@@ -3050,13 +2619,13 @@ def _zip_device_call(what, call, n, dev, out, stream):
     if out is None:
         out = torch.empty(0, dtype=torch.uint8, device=dev)
         once(out)
-        if raw.status == ZipWriteStatus.NeedOutput:
+        if raw.status == status.NeedOutput:
             out = torch.empty(int(raw.out_len), dtype=torch.uint8, device=dev)
             once(out)
     else:
         once(out)
-    summ = ZipWriteSummary(raw)
-    return (out[:summ.out_len] if summ.status == ZipWriteStatus.Ok else out[:0]), entries, summ
+    summ = wrap(raw)
+    return (out[:summ.out_len] if summ.status == status.Ok else out[:0]), entries, summ
 
 
 def zip_assemble(sources, names, content, crc, comp=None, comp_off=None, comp_len=None, flags=0, out=None, stream=None):
@@ -3089,7 +2658,7 @@ def zip_assemble(sources, names, content, crc, comp=None, comp_off=None, comp_le
         return lib().chip_zip_assemble(n, q(sources), q(names), names.numel(), q(content), content.numel(), _dp(comp) if have else None, comp_all,
                                        _dp(comp_off) if have else None, _dp(comp_len) if have else None, q(crc), flags, o, cap, ent, raw, sp)
 
-    return _zip_device_call("chip_zip_assemble", call, n, dev, out, stream)
+    return _archive_device_call("chip_zip_assemble", _ZIP_ARCHIVE, call, n, dev, out, stream)
 
 
 def zip_write(sources, names, content, level=6, flags=0, out=None, stream=None):
@@ -3109,7 +2678,7 @@ def zip_write(sources, names, content, level=6, flags=0, out=None, stream=None):
     def call(o, cap, ent, raw, sp):
         return lib().chip_zip_write(level, flags, n, q(sources), q(names), names.numel(), q(content), content.numel(), o, cap, ent, raw, sp)
 
-    return _zip_device_call("chip_zip_write", call, n, dev, out, stream)
+    return _archive_device_call("chip_zip_write", _ZIP_ARCHIVE, call, n, dev, out, stream)
 
 
 def zip_write_items(items, level=6, flags=0, stream=None, device=None):
@@ -3118,11 +2687,8 @@ def zip_write_items(items, level=6, flags=0, stream=None, device=None):
     the contents land at 4-byte aligned offsets of one device buffer, the DOS date is 1980-01-01.  Returns (the archive as a uint8
     device tensor, entries, ZipWriteSummary) as zip_write does."""
     import numpy as np
-    import torch
 
     items = list(items)
-    tensors = [c for _, c in items if isinstance(c, torch.Tensor)]
-    dev = tensors[0].device if tensors else torch.device("cuda" if device is None else device)
     src = np.zeros(len(items), zip_source_dtype())
     names, at = bytearray(), 0
     for i, (name, c) in enumerate(items):
@@ -3130,12 +2696,32 @@ def zip_write_items(items, level=6, flags=0, stream=None, device=None):
             name, flags = name.encode("utf-8"), flags | ZW_UTF8
         if len(name) > 65535:
             raise ValueError("a name has at most 65535 bytes")
-        size = c.numel() if isinstance(c, torch.Tensor) else len(memoryview(c).cast("B"))
+        size = _item_size(c)
         src[i] = (at, size, len(names), len(name), ZIP_DEFLATE, 0, 0x21)
         names += name
         at += (size + 3) // 4 * 4
-    content = torch.zeros(at, dtype=torch.uint8, device=dev)
-    for row, (_, c) in zip(src, items):
+    d_src, d_names, content = _upload_items(src, names, [c for _, c in items], at, device)
+    return zip_write(d_src, d_names, content, level=level, flags=flags, stream=stream)
+
+
+def _item_size(c):
+    """the bytes of an item's content: bytes-like, or a uint8 device tensor"""
+    import torch
+
+    return c.numel() if isinstance(c, torch.Tensor) else len(memoryview(c).cast("B"))
+
+
+def _upload_items(src, names, contents, total, device):
+    """What zip_write_items and tar_write_items share behind their source records: the contents laid into one zeroed device buffer
+    of `total` bytes at the records' data_off, the records and the names uploaded.  The device is that of the first content that is
+    a tensor, else `device` (None: "cuda").  Returns (the records as a uint8 tensor of one row each, names, content)."""
+    import numpy as np
+    import torch
+
+    tensors = [c for c in contents if isinstance(c, torch.Tensor)]
+    dev = tensors[0].device if tensors else torch.device("cuda" if device is None else device)
+    content = torch.zeros(total, dtype=torch.uint8, device=dev)
+    for row, c in zip(src, contents):
         o, size = int(row["data_off"]), int(row["size"])
         if size:
             if isinstance(c, torch.Tensor):
@@ -3143,9 +2729,9 @@ def zip_write_items(items, level=6, flags=0, stream=None, device=None):
                 content[o:o + size] = c.reshape(-1)
             else:
                 content[o:o + size] = torch.from_numpy(np.frombuffer(memoryview(c).cast("B"), np.uint8).copy()).to(dev)
-    d_src = torch.from_numpy(src.view(np.uint8).reshape(-1, 32).copy()).to(dev)
+    d_src = torch.from_numpy(src.view(np.uint8).reshape(-1, src.dtype.itemsize).copy()).to(dev)
     d_names = torch.from_numpy(np.frombuffer(bytes(names), np.uint8).copy()).to(dev)
-    return zip_write(d_src, d_names, content, level=level, flags=flags, stream=stream)
+    return d_src, d_names, content
 
 
 # ---- one large stream: block starts (include/compu_hip.h, "block starts") -------------------------
@@ -3158,20 +2744,12 @@ def inflate_find_starts_host(data, first_bit, chunk_bytes, max_starts=None):
     one to fill; n).  A start is a candidate, not a confirmed boundary."""
     import numpy as np
 
-    buf = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8)
-    p = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None  # noqa: E731
-    n = C.c_uint64(0)
-    if max_starts is None:
-        rc = lib().chip_inflate_find_starts_host(p(buf), buf.size, int(first_bit), int(chunk_bytes), 0, None, C.byref(n))
-        if rc != 0:
-            raise RuntimeError(f"chip_inflate_find_starts_host failed: {rc}")
-        max_starts = n.value
-    m = int(max_starts)
-    starts = np.zeros(m, np.uint64)
-    rc = lib().chip_inflate_find_starts_host(p(buf), buf.size, int(first_bit), int(chunk_bytes), m, p(starts), C.byref(n))
-    if rc != 0:
-        raise RuntimeError(f"chip_inflate_find_starts_host failed: {rc}")
-    return starts[: min(m, n.value)], int(n.value)
+    buf, base = _host_input(data)
+    n, call = C.c_uint64(0), lib().chip_inflate_find_starts_host
+    starts, = _count_then_fill("chip_inflate_find_starts_host",
+                               lambda m, out: call(base, buf.size, int(first_bit), int(chunk_bytes), m, out, C.byref(n)), lambda: n.value,
+                               lambda m: (np.zeros(m, np.uint64),), _np_ptr, max_starts)
+    return starts, int(n.value)
 
 
 def inflate_find_starts(in_buf, length, first_bit, chunk_bytes, stream=None, max_starts=None):
@@ -3179,44 +2757,24 @@ def inflate_find_starts(in_buf, length, first_bit, chunk_bytes, stream=None, max
     inflate_find_starts_host, one wave per chunk.  Returns (starts int64 device tensor read as u64, n).  Synchronous on `stream`."""
     import torch
 
-    dev = _check_tensors(((in_buf, torch.uint8),))
-    length = int(length)
-    if length < 0 or length > in_buf.numel():
-        raise ValueError(f"length {length} outside the buffer of {in_buf.numel()} bytes")
-    base, sp, n = (_dp(in_buf) if length else None), _stream_ptr(stream), C.c_uint64(0)
+    dev, length, base = _device_input(in_buf, length)
+    sp, n, call = _stream_ptr(stream), C.c_uint64(0), lib().chip_inflate_find_starts
     with torch.cuda.device(dev):
-        if max_starts is None:
-            rc = lib().chip_inflate_find_starts(base, length, int(first_bit), int(chunk_bytes), 0, None, C.byref(n), sp)
-            if rc != 0:
-                raise RuntimeError(f"chip_inflate_find_starts failed: {rc}")
-            max_starts = n.value
-        m = int(max_starts)
-        starts = torch.empty(m, dtype=torch.int64, device=dev)
-        rc = lib().chip_inflate_find_starts(base, length, int(first_bit), int(chunk_bytes), m, _dp(starts) if m else None, C.byref(n), sp)
-    if rc != 0:
-        raise RuntimeError(f"chip_inflate_find_starts failed: {rc}")
-    return starts[: min(m, n.value)], int(n.value)
+        starts, = _count_then_fill("chip_inflate_find_starts",
+                                   lambda m, out: call(base, length, int(first_bit), int(chunk_bytes), m, out, C.byref(n), sp), lambda: n.value,
+                                   lambda m: (torch.empty(m, dtype=torch.int64, device=dev),), _dp, max_starts)
+    return starts, int(n.value)
 
 
 PAR_SERIAL, PAR_PARALLEL = 0, 1  # chip_inflate_parallel_summary::path
 PAR_DEFAULT_CHUNK = 128 << 10
 
 
-class InflateParallelSummary:
+class InflateParallelSummary(_Summary):
     """chip_inflate_parallel_summary: the index build's fields; total_out (with status NeedOutput and out_len 0: the size to come
     back with); n_starts the finder's count, n_false those that were no boundaries; path PAR_SERIAL or PAR_PARALLEL."""
 
-    __slots__ = ("n_points", "out_len", "in_used", "end_bit", "total_out", "n_starts", "n_false", "status", "wrap", "check", "path")
-
-    def __init__(self, raw):
-        for name in self.__slots__:
-            setattr(self, name, int(getattr(raw, name)))
-
-    def as_tuple(self):
-        return tuple(getattr(self, name) for name in self.__slots__)
-
-    def __repr__(self):
-        return "InflateParallelSummary(" + ", ".join(f"{name}={getattr(self, name)}" for name in self.__slots__) + ")"
+    __slots__ = FIELDS = _fields(_InflateParallelSummary)
 
 
 def inflate_parallel(fmt, in_buf, length, out_buf=None, chunk_bytes=0, index=False, stream=None):
@@ -3295,19 +2853,12 @@ class InflateCursor:
         return "InflateCursor(" + ", ".join(f"{name}={getattr(self, name)}" for name in self.FIELDS) + ")"
 
 
-class InflateNextSummary:
+class InflateNextSummary(_Record):
     """chip_inflate_next_summary: in_used bytes of the slab lie in front of the new cursor byte, out_len bytes were delivered, need_out
     is the size of the piece that did not fit (0: not known), n_chunks / n_starts / n_false describe the slab, status says why the
     call stopped (a DecodeStatus value, 3 = needs a dictionary, or a negative error) and path which path decoded."""
 
-    FIELDS = tuple(name for name, _ in _InflateNextSummary._fields_)
-
-    def __init__(self, raw):
-        for name in self.FIELDS:
-            setattr(self, name, int(getattr(raw, name)))
-
-    def __repr__(self):
-        return "InflateNextSummary(" + ", ".join(f"{name}={getattr(self, name)}" for name in self.FIELDS) + ")"
+    FIELDS = _fields(_InflateNextSummary)
 
 
 def inflate_parallel_next(cursor, in_buf, out_buf, chunk_bytes=0, stream=None):
@@ -3328,6 +2879,42 @@ def inflate_parallel_next(cursor, in_buf, out_buf, chunk_bytes=0, stream=None):
     return InflateNextSummary(raw)
 
 
+class _InflateSlabs(_Slabs):
+    """inflate_parallel_stream's side of _slab_stream"""
+
+    slab_max, room_max = GZPLAN_WINDOW, 0xFFFFFFF0
+    eof_text = "the source ends inside the stream"
+    spare = 4
+
+    def __init__(self, device, fmt, members, chunk_bytes):
+        super().__init__(device)
+        self.fmt, self.members, self.chunk_bytes = fmt, members, chunk_bytes
+
+    def new_cursor(self, fmt=None):
+        return InflateCursor(self.fmt if fmt is None else fmt, self.dev)
+
+    def alloc_in(self, n, slab):  # zero-initialised, 4 spare bytes behind the slab
+        import torch
+
+        return torch.zeros(max(slab, n) + 4, dtype=torch.uint8, device=self.dev)
+
+    def step(self, cur, d_in, d_out):
+        return inflate_parallel_next(cur, d_in, d_out, self.chunk_bytes)
+
+    def grow_room(self, room, need_out):
+        if room >= 0xFFFFFFF0:
+            raise DecodeError(-5)  # a piece beyond a call's room
+        return max(2 * room, need_out)
+
+    def after_finished(self, cur, pending, fill):
+        """members=True behind a gzip member: a new gzip cursor when 1f 8b follows; else None"""
+        if self.members and cur.wrap == 2:
+            fill(2)  # (two bytes decide; a short read is not the end)
+            if bytes(pending[:2]) == b"\x1f\x8b":
+                return self.new_cursor(31)
+        return None
+
+
 def inflate_parallel_stream(source, sink=None, slab_bytes=64 << 20, out_bytes=256 << 20, chunk_bytes=0, members=False, fmt=FMT_AUTO, device=None):
     """One gzip / zlib / raw deflate stream of ANY length through inflate_parallel_next: `source` (bytes-like, or a binary file object)
     is uploaded slab after slab, every call's bytes are downloaded and written to `sink` (a binary file object; None: they are
@@ -3335,70 +2922,7 @@ def inflate_parallel_stream(source, sink=None, slab_bytes=64 << 20, out_bytes=25
     next piece does not fit.  members=True: behind a finished gzip member a new one is begun while 1f 8b follows, as gzip -d does.
     Raises DecodeError(code) on an error in the stream and EOFError when the source ends inside the stream.  Returns the bytes, or
     with a sink the number of bytes written."""
-    import numpy as np
-    import torch
-
-    dev = torch.device(device if device is not None else "cuda")
-    read = source.read if hasattr(source, "read") else None
-    view, taken = (None, 0) if read else (memoryview(source).cast("B"), 0)
-    pending, eof = bytearray(), False
-    slab, room = max(int(slab_bytes), 1), max(int(out_bytes), 1)
-    parts, written = [], 0
-    cur = InflateCursor(fmt, dev)
-    d_in, d_out = None, None
-    while True:
-        slab, room = min(slab, GZPLAN_WINDOW), min(room, 0xFFFFFFF0)
-        while not eof and len(pending) < slab:
-            want = slab - len(pending)
-            if read:
-                piece = read(want)
-            else:
-                piece = view[taken : taken + want]
-                taken += len(piece)
-            if not len(piece):
-                eof = True
-            pending += piece
-        n = min(len(pending), slab)
-        if d_in is None or d_in.numel() < n + 4:
-            d_in = torch.zeros(max(slab, n) + 4, dtype=torch.uint8, device=dev)
-        if d_out is None or d_out.numel() < room:
-            d_out = torch.empty(room, dtype=torch.uint8, device=dev)
-        if n:
-            d_in[:n].copy_(torch.from_numpy(np.frombuffer(bytes(pending[:n]), dtype=np.uint8).copy()))
-        s = inflate_parallel_next(cur, d_in[:n], d_out[:room], chunk_bytes)
-        if s.out_len:
-            got = d_out[: s.out_len].cpu().numpy().tobytes()
-            written += len(got)
-            if sink is None:
-                parts.append(got)
-            else:
-                sink.write(got)
-        del pending[: s.in_used]
-        if s.status == int(DecodeStatus.Finished):
-            if members and cur.wrap == 2:
-                while not eof and len(pending) < 2:  # (two bytes decide; a short read is not the end)
-                    piece = read(2 - len(pending)) if read else view[taken : taken + 2 - len(pending)]
-                    taken += 0 if read else len(piece)
-                    eof = not len(piece)
-                    pending += piece
-                if bytes(pending[:2]) == b"\x1f\x8b":
-                    cur = InflateCursor(31, dev)
-                    continue
-            break
-        if s.status not in (int(DecodeStatus.NeedInput), int(DecodeStatus.NeedOutput)):
-            raise DecodeError(s.status)
-        if s.in_used == 0 and s.out_len == 0:
-            if s.status == int(DecodeStatus.NeedOutput):
-                if room >= 0xFFFFFFF0:
-                    raise DecodeError(-5)  # a piece beyond a call's room
-                room = max(2 * room, s.need_out)
-            elif n < len(pending) or not eof:
-                if slab >= GZPLAN_WINDOW:
-                    raise DecodeError(-5)  # a block beyond a call's slab
-                slab *= 2
-            else:
-                raise EOFError("the source ends inside the stream")
-    return b"".join(parts) if sink is None else written
+    return _slab_stream(_InflateSlabs(device, fmt, members, chunk_bytes), source, sink, slab_bytes, out_bytes)
 
 
 # ---- tar archives (include/compu_hip.h, "tar archives") ---------------------------------------------
@@ -3420,53 +2944,25 @@ def tar_entry_dtype():
     prefix_len, typeflag, flags."""
     import numpy as np
 
-    dt = np.dtype([("group_off", "<u8"), ("header_off", "<u8"), ("data_off", "<u8"), ("size", "<u8"), ("name_off", "<u8"), ("link_off", "<u8"),
-                   ("mtime", "<i8"), ("name_len", "<u4"), ("link_len", "<u4"), ("mode", "<u4"), ("prefix_len", "<u2"), ("typeflag", "u1"),
-                   ("flags", "u1")])
-    assert dt.itemsize == C.sizeof(_TarEntry) == 72
+    dt = np.dtype(_TarEntry)
+    assert dt.itemsize == 72
     return dt
 
 
-class TarPlanSummary:
+class TarPlanSummary(_Summary):
     """chip_tar_plan_summary: n_entries (members), n_global (global pax headers stepped over) and total_size (the members' sizes) of
     the whole walk, stop_off (the group or position where the walk stopped), bad_off (the offending header), status, zero_blocks
     (the all-zero blocks seen at the stop: 0, 1 or 2)."""
 
-    __slots__ = ("n_entries", "n_global", "total_size", "stop_off", "bad_off", "status", "zero_blocks")
-
-    def __init__(self, raw):
-        self.n_entries, self.n_global, self.total_size = int(raw.n_entries), int(raw.n_global), int(raw.total_size)
-        self.stop_off, self.bad_off, self.status, self.zero_blocks = int(raw.stop_off), int(raw.bad_off), TarStatus(raw.status), int(raw.zero_blocks)
-
-    def as_tuple(self):
-        return (self.n_entries, self.n_global, self.total_size, self.stop_off, self.bad_off, int(self.status), self.zero_blocks)
-
-    def __repr__(self):
-        return (f"TarPlanSummary(n_entries={self.n_entries}, n_global={self.n_global}, total_size={self.total_size}, stop_off={self.stop_off}, "
-                f"bad_off={self.bad_off}, status={self.status.name}, zero_blocks={self.zero_blocks})")
+    __slots__ = FIELDS = _fields(_TarPlanSummary)
+    ENUMS = {"status": TarStatus}
 
 
 def tar_plan_host(data, max_entries=None):
     """chip_tar_plan_host over bytes / a uint8 numpy array in host memory holding a tar image: (entries, summary), entries a numpy
     record array (tar_entry_dtype) of the first min(n_entries, max_entries) members (None = all of them: one call to count, one to
     fill).  Nothing is copied or decoded: the records say where content and names lie in the image."""
-    import numpy as np
-
-    buf = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8)
-    raw = _TarPlanSummary()
-    p = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None  # noqa: E731
-    call = lib().chip_tar_plan_host
-    if max_entries is None:
-        rc = call(p(buf), buf.size, 0, None, C.byref(raw))
-        if rc != 0:
-            raise RuntimeError(f"chip_tar_plan_host failed: {rc}")
-        max_entries = int(raw.n_entries)
-    m = int(max_entries)
-    entries = np.zeros(m, tar_entry_dtype())
-    rc = call(p(buf), buf.size, m, p(entries), C.byref(raw))
-    if rc != 0:
-        raise RuntimeError(f"chip_tar_plan_host failed: {rc}")
-    return entries[:min(m, int(raw.n_entries))], TarPlanSummary(raw)
+    return _plan_host("chip_tar_plan_host", _TarPlanSummary, TarPlanSummary, "n_entries", data, max_entries, _record_array(tar_entry_dtype()))
 
 
 def tar_plan(in_buf, length, stream=None, max_entries=None):
@@ -3474,27 +2970,7 @@ def tar_plan(in_buf, length, stream=None, max_entries=None):
     (entries, summary), entries a uint8 device tensor of shape (k, 72) holding the chip_tar_entry records of the first
     k = min(n_entries, max_entries) members (`.cpu().numpy().view(tar_entry_dtype())` reads them).  Synchronous on `stream`.
     max_entries None: all of them (one call to count, one to fill)."""
-    import torch
-
-    dev = _check_tensors(((in_buf, torch.uint8),))
-    length = int(length)
-    if length < 0 or length > in_buf.numel():
-        raise ValueError(f"length {length} outside the buffer of {in_buf.numel()} bytes")
-    raw = _TarPlanSummary()
-    base, sp = (_dp(in_buf) if length else None), _stream_ptr(stream)
-    call = lib().chip_tar_plan
-    with torch.cuda.device(dev):
-        if max_entries is None:  # count, then fill
-            rc = call(base, length, 0, None, C.byref(raw), sp)
-            if rc != 0:
-                raise RuntimeError(f"chip_tar_plan failed: {rc}")
-            max_entries = int(raw.n_entries)
-        m = int(max_entries)
-        entries = torch.empty((m, C.sizeof(_TarEntry)), dtype=torch.uint8, device=dev)
-        rc = call(base, length, m, _dp(entries) if m else None, C.byref(raw), sp)
-    if rc != 0:
-        raise RuntimeError(f"chip_tar_plan failed: {rc}")
-    return entries[:min(m, int(raw.n_entries))], TarPlanSummary(raw)
+    return _plan_device("chip_tar_plan", _TarPlanSummary, TarPlanSummary, "n_entries", in_buf, length, stream, max_entries, _record_rows(_TarEntry))
 
 
 def tar_names(entries, source, stream=None):
@@ -3619,29 +3095,21 @@ def tar_source_dtype():
     (the character's code, ord("0") for a file), pad (three bytes, 0)."""
     import numpy as np
 
-    dt = np.dtype([("data_off", "<u8"), ("size", "<u8"), ("name_off", "<u8"), ("link_off", "<u8"), ("mtime", "<i8"), ("name_len", "<u4"),
-                   ("link_len", "<u4"), ("mode", "<u4"), ("uid", "<u4"), ("gid", "<u4"), ("typeflag", "u1"), ("pad", "u1", (3,))])
-    assert dt.itemsize == C.sizeof(_TarSource) == 64
+    dt = np.dtype(_TarSource)
+    assert dt.itemsize == 64
     return dt
 
 
-class TarWriteSummary:
+class TarWriteSummary(_Summary):
     """chip_tar_write_summary: n_entries, n_ext (extension headers written), out_len (the whole image; the exact room to come back
     with on NeedOutput), end_off (where the two zero blocks start), total_size (the sum of the sizes), bad_index (the lowest bad
     record on BadSource), status."""
 
-    __slots__ = ("n_entries", "n_ext", "out_len", "end_off", "total_size", "bad_index", "status")
+    __slots__ = FIELDS = _fields(_TarWriteSummary)
+    ENUMS = {"status": TarWriteStatus}
 
-    def __init__(self, raw):
-        self.n_entries, self.n_ext, self.out_len, self.end_off = int(raw.n_entries), int(raw.n_ext), int(raw.out_len), int(raw.end_off)
-        self.total_size, self.bad_index, self.status = int(raw.total_size), int(raw.bad_index), TarWriteStatus(raw.status)
 
-    def as_tuple(self):
-        return (self.n_entries, self.n_ext, self.out_len, self.end_off, self.total_size, self.bad_index, int(self.status))
-
-    def __repr__(self):
-        return (f"TarWriteSummary(n_entries={self.n_entries}, n_ext={self.n_ext}, out_len={self.out_len}, end_off={self.end_off}, "
-                f"total_size={self.total_size}, bad_index={self.bad_index}, status={self.status.name})")
+_TAR_ARCHIVE = (_TarWriteSummary, TarWriteSummary, _TarEntry, TarWriteStatus)  # for _archive_host_call / _archive_device_call
 
 
 def tar_write_bound(n, names_total, content_total, record_bytes=0):
@@ -3661,24 +3129,13 @@ def tar_write_host(sources, names, content, flags=0, record_bytes=0, out_cap=Non
     src = np.ascontiguousarray(sources, dtype=tar_source_dtype())
     n = src.size
     names, content = u8(names), u8(content)
-    p = lambda a: None if a.size == 0 else a.ctypes.data_as(C.c_void_p)  # noqa: E731
     clen = content.size if content_len is None else int(content_len)
-    raw = _TarWriteSummary()
-    entries = np.zeros(n, tar_entry_dtype())
 
-    def call(out, cap):
-        rc = lib().chip_tar_write_host(n, p(src), p(names), names.size, content.ctypes.data_as(C.c_void_p) if clen else None, clen, flags, record_bytes,
-                                       p(out), cap, p(entries), C.byref(raw))
-        if rc != 0:
-            raise RuntimeError(f"chip_tar_write_host failed: {rc}")
+    def call(out, cap, ent, raw):
+        return lib().chip_tar_write_host(n, _np_ptr(src), _np_ptr(names), names.size, content.ctypes.data_as(C.c_void_p) if clen else None, clen,
+                                         flags, record_bytes, out, cap, ent, raw)
 
-    out = np.zeros(0 if out_cap is None else int(out_cap), np.uint8)
-    call(out, out.size)
-    if out_cap is None and raw.status == TarWriteStatus.NeedOutput:
-        out = np.zeros(int(raw.out_len), np.uint8)
-        call(out, out.size)
-    summ = TarWriteSummary(raw)
-    return (out[:summ.out_len].tobytes() if summ.status == TarWriteStatus.Ok else b""), entries, summ
+    return _archive_host_call("chip_tar_write_host", _TAR_ARCHIVE, call, n, out_cap)
 
 
 def tar_write(sources, names, content, flags=0, record_bytes=0, out=None, stream=None):
@@ -3695,26 +3152,11 @@ def tar_write(sources, names, content, flags=0, record_bytes=0, out=None, stream
     if sources.numel() != n * C.sizeof(_TarSource):
         raise ValueError("sources holds 64-byte records")
     q = lambda t: _dp(t) if t.numel() else None  # noqa: E731
-    raw = _TarWriteSummary()
-    entries = torch.empty((n, C.sizeof(_TarEntry)), dtype=torch.uint8, device=dev)
 
-    def once(o):
-        with torch.cuda.device(dev):
-            rc = lib().chip_tar_write(n, q(sources), q(names), names.numel(), q(content), content.numel(), flags, record_bytes, q(o), o.numel(),
-                                      _dp(entries) if n else None, C.byref(raw), _stream_ptr(stream))
-        if rc != 0:
-            raise RuntimeError(f"chip_tar_write failed: {rc}")
+    def call(o, cap, ent, raw, sp):
+        return lib().chip_tar_write(n, q(sources), q(names), names.numel(), q(content), content.numel(), flags, record_bytes, o, cap, ent, raw, sp)
 
-    if out is None:
-        out = torch.empty(0, dtype=torch.uint8, device=dev)
-        once(out)
-        if raw.status == TarWriteStatus.NeedOutput:
-            out = torch.empty(int(raw.out_len), dtype=torch.uint8, device=dev)
-            once(out)
-    else:
-        once(out)
-    summ = TarWriteSummary(raw)
-    return (out[:summ.out_len] if summ.status == TarWriteStatus.Ok else out[:0]), entries, summ
+    return _archive_device_call("chip_tar_write", _TAR_ARCHIVE, call, n, dev, out, stream)
 
 
 def tar_write_items(items, flags=0, stream=None, device=None):
@@ -3723,11 +3165,8 @@ def tar_write_items(items, flags=0, stream=None, device=None):
     device tensor; mode defaults to 0644 (0755 for a directory), mtime to 0.  The contents land at 16-byte aligned offsets of one
     device buffer.  Returns (the image as a uint8 device tensor, entries, TarWriteSummary) as tar_write does; tar_open reads it back."""
     import numpy as np
-    import torch
 
     items = [tuple(it) for it in items]
-    tensors = [it[1] for it in items if isinstance(it[1], torch.Tensor)]
-    dev = tensors[0].device if tensors else torch.device("cuda" if device is None else device)
     src = np.zeros(len(items), tar_source_dtype())
     names, at = bytearray(), 0
     for i, it in enumerate(items):
@@ -3736,7 +3175,7 @@ def tar_write_items(items, flags=0, stream=None, device=None):
             name = name.encode("utf-8")
         if not 1 <= len(name) <= TARW_NAME_MAX:
             raise ValueError("a name has 1 to 65535 bytes")
-        size = c.numel() if isinstance(c, torch.Tensor) else len(memoryview(c).cast("B"))
+        size = _item_size(c)
         is_dir = name.endswith(b"/")
         if is_dir and size:
             raise ValueError("a directory has no content")
@@ -3745,17 +3184,7 @@ def tar_write_items(items, flags=0, stream=None, device=None):
         src[i] = (at, size, len(names), 0, mtime, len(name), 0, mode, 0, 0, ord("5") if is_dir else ord("0"), (0, 0, 0))
         names += name
         at += (size + 15) // 16 * 16
-    content = torch.zeros(at, dtype=torch.uint8, device=dev)
-    for row, it in zip(src, items):
-        o, size, c = int(row["data_off"]), int(row["size"]), it[1]
-        if size:
-            if isinstance(c, torch.Tensor):
-                _check_tensors(((content, torch.uint8), (c, torch.uint8)))
-                content[o:o + size] = c.reshape(-1)
-            else:
-                content[o:o + size] = torch.from_numpy(np.frombuffer(memoryview(c).cast("B"), np.uint8).copy()).to(dev)
-    d_src = torch.from_numpy(src.view(np.uint8).reshape(-1, 64).copy()).to(dev)
-    d_names = torch.from_numpy(np.frombuffer(bytes(names), np.uint8).copy()).to(dev)
+    d_src, d_names, content = _upload_items(src, names, [it[1] for it in items], at, device)
     return tar_write(d_src, d_names, content, flags=flags, stream=stream)
 
 
@@ -3775,30 +3204,17 @@ def lz4_block_dtype():
     """chip_lz4_block as a numpy record: offset (of the 4-byte block header), size, flags (LZ4BLOCK_*), checksum."""
     import numpy as np
 
-    dt = np.dtype([("offset", "<u8"), ("size", "<u4"), ("flags", "<u4"), ("checksum", "<u4"), ("pad", "<u4")])
-    assert dt.itemsize == C.sizeof(_Lz4Block)
+    dt = np.dtype(_Lz4Block)
+    assert dt.itemsize == 24
     return dt
 
 
-class Lz4BlocksSummary:
+class Lz4BlocksSummary(_Summary):
     """chip_lz4_blocks_summary: n_blocks the walk counted, in_used (the frame's end, 0 when the walk stopped early), content_size
     (LZ4BLOCKS_UNSIZED without C.Size), block_max, the FLG and BD bytes, the header's length, the stored content checksum, status."""
 
-    __slots__ = ("n_blocks", "in_used", "content_size", "block_max", "flg", "bd", "header_bytes", "content_checksum", "status")
-
-    def __init__(self, raw):
-        self.n_blocks, self.in_used, self.content_size = int(raw.n_blocks), int(raw.in_used), int(raw.content_size)
-        self.block_max, self.flg, self.bd, self.header_bytes = int(raw.block_max), int(raw.flg), int(raw.bd), int(raw.header_bytes)
-        self.content_checksum, self.status = int(raw.content_checksum), ZstdPlanStatus(raw.status)
-
-    def as_tuple(self):
-        return (self.n_blocks, self.in_used, self.content_size, self.block_max, self.flg, self.bd, self.header_bytes, self.content_checksum,
-                int(self.status))
-
-    def __repr__(self):
-        return (f"Lz4BlocksSummary(n_blocks={self.n_blocks}, in_used={self.in_used}, content_size={self.content_size}, block_max={self.block_max}, "
-                f"flg={self.flg:#x}, bd={self.bd:#x}, header_bytes={self.header_bytes}, content_checksum={self.content_checksum:#x}, "
-                f"status={self.status.name})")
+    __slots__ = FIELDS = _fields(_Lz4BlocksSummary)
+    ENUMS, FORMATS = {"status": ZstdPlanStatus}, {"flg": "#x", "bd": "#x", "content_checksum": "#x"}
 
 
 def lz4_block_decode_host(data, out_cap):
@@ -3820,23 +3236,7 @@ def lz4_blocks_host(data, max_blocks=None):
     """chip_lz4_blocks_host over bytes / a uint8 numpy array in host memory: (blocks, summary) of the FIRST frame -- blocks a numpy
     record array (lz4_block_dtype) of the first min(n_blocks, max_blocks) blocks (None = all of them: one call to count, one to
     fill).  Read from headers alone; nothing is decoded."""
-    import numpy as np
-
-    buf = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8)
-    raw = _Lz4BlocksSummary()
-    p = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None  # noqa: E731
-    call = lib().chip_lz4_blocks_host
-    if max_blocks is None:
-        rc = call(p(buf), buf.size, 0, None, C.byref(raw))
-        if rc != 0:
-            raise RuntimeError(f"chip_lz4_blocks_host failed: {rc}")
-        max_blocks = int(raw.n_blocks)
-    m = int(max_blocks)
-    blocks = np.zeros(m, lz4_block_dtype())
-    rc = call(p(buf), buf.size, m, p(blocks), C.byref(raw))
-    if rc != 0:
-        raise RuntimeError(f"chip_lz4_blocks_host failed: {rc}")
-    return blocks[:min(m, int(raw.n_blocks))], Lz4BlocksSummary(raw)
+    return _plan_host("chip_lz4_blocks_host", _Lz4BlocksSummary, Lz4BlocksSummary, "n_blocks", data, max_blocks, _record_array(lz4_block_dtype()))
 
 
 def lz4_blocks(in_buf, length, stream=None, max_blocks=None):
@@ -3844,27 +3244,8 @@ def lz4_blocks(in_buf, length, stream=None, max_blocks=None):
     multiple of 4): (blocks, summary), blocks a uint8 device tensor of shape (k, 24) holding the chip_lz4_block records of the first
     k = min(n_blocks, max_blocks) blocks (`.cpu().numpy().view(lz4_block_dtype())` reads them).  Synchronous on `stream`.
     max_blocks None: all of them (one call to count, one to fill)."""
-    import torch
-
-    dev = _check_tensors(((in_buf, torch.uint8),))
-    length = int(length)
-    if length < 0 or length > in_buf.numel():
-        raise ValueError(f"length {length} outside the buffer of {in_buf.numel()} bytes")
-    raw = _Lz4BlocksSummary()
-    base, sp = (_dp(in_buf) if length else None), _stream_ptr(stream)
-    call = lib().chip_lz4_blocks
-    with torch.cuda.device(dev):
-        if max_blocks is None:  # count, then fill
-            rc = call(base, length, 0, None, C.byref(raw), sp)
-            if rc != 0:
-                raise RuntimeError(f"chip_lz4_blocks failed: {rc}")
-            max_blocks = int(raw.n_blocks)
-        m = int(max_blocks)
-        blocks = torch.zeros((m, C.sizeof(_Lz4Block)), dtype=torch.uint8, device=dev)
-        rc = call(base, length, m, _dp(blocks) if m else None, C.byref(raw), sp)
-    if rc != 0:
-        raise RuntimeError(f"chip_lz4_blocks failed: {rc}")
-    return blocks[:min(m, int(raw.n_blocks))], Lz4BlocksSummary(raw)
+    return _plan_device("chip_lz4_blocks", _Lz4BlocksSummary, Lz4BlocksSummary, "n_blocks", in_buf, length, stream, max_blocks,
+                        _record_rows(_Lz4Block, "zeros"))
 
 
 def xxh32_batch(buf, off, length, seed=0, stream=None):
@@ -3887,22 +3268,12 @@ def xxh32_batch(buf, off, length, seed=0, stream=None):
     return digest
 
 
-class Lz4ParallelSummary:
+class Lz4ParallelSummary(_Summary):
     """chip_lz4_parallel_summary: n_blocks of the frame, out_len, in_used, total_out (the size to come back with on NeedOutput),
     status, path (LZ4PAR_*), check (the content checksum computed on the parallel path)."""
 
-    __slots__ = ("n_blocks", "out_len", "in_used", "total_out", "status", "path", "check")
-
-    def __init__(self, raw):
-        self.n_blocks, self.out_len, self.in_used, self.total_out = int(raw.n_blocks), int(raw.out_len), int(raw.in_used), int(raw.total_out)
-        self.status, self.path, self.check = int(raw.status), int(raw.path), int(raw.check)
-
-    def as_tuple(self):
-        return (self.n_blocks, self.out_len, self.in_used, self.total_out, self.status, self.path, self.check)
-
-    def __repr__(self):
-        return (f"Lz4ParallelSummary(n_blocks={self.n_blocks}, out_len={self.out_len}, in_used={self.in_used}, total_out={self.total_out}, "
-                f"status={self.status}, path={self.path}, check={self.check:#x})")
+    __slots__ = FIELDS = _fields(_Lz4ParallelSummary)
+    FORMATS = {"check": "#x"}
 
 
 def lz4_parallel(in_buf, length, out_buf=None, checksum=True, stream=None):
