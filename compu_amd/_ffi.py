@@ -188,6 +188,19 @@ class _Lz4ParallelSummary(C.Structure):
                 ("path", C.c_uint32), ("check", C.c_uint32), ("pad", C.c_uint32)]
 
 
+class _SnappyChunk(C.Structure):
+    _fields_ = [("offset", C.c_uint64), ("size", C.c_uint32), ("type", C.c_uint32), ("crc", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class _SnappyChunksSummary(C.Structure):
+    _fields_ = [("n_chunks", C.c_uint64), ("n_skipped", C.c_uint64), ("in_used", C.c_uint64), ("status", C.c_int32), ("pad", C.c_uint32)]
+
+
+class _SnappyParallelSummary(C.Structure):
+    _fields_ = [("n_chunks", C.c_uint64), ("out_len", C.c_uint64), ("in_used", C.c_uint64), ("total_out", C.c_uint64), ("status", C.c_int32),
+                ("path", C.c_uint32), ("n_skipped", C.c_uint32), ("pad", C.c_uint32)]
+
+
 # ---- the prototypes of include/compu_hip.h: (name, restype, argtypes) ------------------------------
 # restype as the header states it: None for void, a pointer type, a 64-bit type for size_t / uint64_t, c_int for int, the
 # structure where one comes back by value.
@@ -279,6 +292,11 @@ _PROTOTYPES = [
     ("chip_lz4_parallel", ci, [vp, u64, vp, u64, u32, P(_Lz4ParallelSummary), vp]),
     ("chip_lz4_block_encode_host", ci, [vp, u64, ci, vp, u64, P(u64)]),
     ("chip_lz4_frame_encode_host", ci, [vp, u64, ci, ci, vp, u64, P(u64)]),
+    ("chip_snappy_block_decode_host", ci, [vp, u64, vp, u64, P(u64), P(u64)]),
+    ("chip_snappy_chunks_host", ci, [vp, u64, u64, vp, P(_SnappyChunksSummary)]),
+    ("chip_snappy_chunks", ci, [vp, u64, u64, vp, P(_SnappyChunksSummary), vp]),
+    ("chip_crc32c_batch", ci, [sz, vp, vp, vp, vp, vp]),
+    ("chip_snappy_parallel", ci, [vp, u64, vp, u64, u32, P(_SnappyParallelSummary), vp]),
     ("chip_inflate_index_build", ci, [ci, vp, u64, vp, u64, u32, u64, vp, vp, vp, vp, P(_InflateIndexSummary), vp]),
     ("chip_inflate_index_units_host", ci, [ci, u64, u64, vp, vp, vp, u64, vp, vp, vp, vp, vp, P(i32), P(u64)]),
     ("chip_inflate_index_read", ci, [ci, vp, u64, u64, vp, vp, vp, vp, u64, sz, vp, vp, vp, u64, vp, vp, P(_ReadSummary), vp]),

@@ -160,6 +160,8 @@ static bool members_flag_ok(int format, uint32_t flags)
 {
     // LZ4 takes no flag at all: compu has no LZ4 whose return values could be mirrored, and concatenated frames are the caller's loop
     if ((format == CHIP_FMT_LZ4_BLOCK || format == CHIP_FMT_LZ4) && flags) return false;
+    // Snappy likewise: concatenated streams are one stream of the framing format already
+    if ((format == CHIP_FMT_SNAPPY_BLOCK || format == CHIP_FMT_SNAPPY) && flags) return false;
     if (!(flags & CHIP_F_MEMBERS)) return true;
     if (flags & CHIP_F_COMPU_STATUS) return false;
     return format == CHIP_FMT_GZIP || format == CHIP_FMT_AUTO || format == CHIP_FMT_ZSTD || format == CHIP_FMT_DETECT;
@@ -188,6 +190,8 @@ int chip_decode_batch_ex(int format, uint32_t flags, size_t n, const void *in_ba
     case CHIP_FMT_BROTLI: e = launch_brotli_decode(a, (hipStream_t)stream); break;  // CHIP_F_COMPU_STATUS changes nothing
     case CHIP_FMT_LZ4_BLOCK:
     case CHIP_FMT_LZ4: e = launch_lz4(a, nullptr, (hipStream_t)stream); break;
+    case CHIP_FMT_SNAPPY_BLOCK:
+    case CHIP_FMT_SNAPPY: e = launch_snappy(a, nullptr, (hipStream_t)stream); break;
     case CHIP_FMT_DETECT:
         // Detection::detect routes every unit: one pass buckets the batch by format, then each decoder runs over its own
         // (homogeneous) list of units -- all of it one critical section of the (device, stream) slot (inflate.hip)
@@ -212,6 +216,8 @@ int chip_decode_batch_sizes(int format, uint32_t flags, size_t n, const void *in
     case CHIP_FMT_ZSTD:
     case CHIP_FMT_LZ4_BLOCK:
     case CHIP_FMT_LZ4:
+    case CHIP_FMT_SNAPPY_BLOCK:
+    case CHIP_FMT_SNAPPY:
     case CHIP_FMT_DETECT: break;
     default: return CHIP_E_INVALID;  // brotli: a size pass would be a full decode (header)
     }
@@ -224,6 +230,7 @@ int chip_decode_batch_sizes(int format, uint32_t flags, size_t n, const void *in
     hipError_t e;
     if (format == CHIP_FMT_ZSTD) e = launch_zstd(a, out_size, 0, (hipStream_t)stream);
     else if (format == CHIP_FMT_LZ4_BLOCK || format == CHIP_FMT_LZ4) e = launch_lz4(a, out_size, (hipStream_t)stream);
+    else if (format == CHIP_FMT_SNAPPY_BLOCK || format == CHIP_FMT_SNAPPY) e = launch_snappy(a, out_size, (hipStream_t)stream);
     else if (format == CHIP_FMT_DETECT) e = launch_routed(a, out_size, (hipStream_t)stream);  // routed as a decode batch is
     else e = launch_inflate(a, out_size, (hipStream_t)stream);
     return e == hipSuccess ? CHIP_OK : CHIP_E_LAUNCH;
@@ -592,7 +599,7 @@ int chip_decode_batch_multi(int format, size_t n, const void *in_base, const uin
     if (!host_args_ok(n, in_base, in_off, in_len, out_base, out_off, out_cap, out_len, status) || !in_used) return CHIP_E_INVALID;
     switch (format) {
     case CHIP_FMT_DEFLATE: case CHIP_FMT_ZLIB: case CHIP_FMT_GZIP: case CHIP_FMT_AUTO: case CHIP_FMT_ZSTD: case CHIP_FMT_BROTLI:
-    case CHIP_FMT_LZ4_BLOCK: case CHIP_FMT_LZ4: case CHIP_FMT_DETECT: break;
+    case CHIP_FMT_LZ4_BLOCK: case CHIP_FMT_LZ4: case CHIP_FMT_SNAPPY_BLOCK: case CHIP_FMT_SNAPPY: case CHIP_FMT_DETECT: break;
     default: return CHIP_E_INVALID;
     }
     const int visible = chip_device_count();

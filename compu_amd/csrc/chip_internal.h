@@ -104,6 +104,8 @@ hipError_t enqueue_zstd_members_sizes(const BatchArgs &a, uint64_t *out_size, in
 hipError_t launch_lz4(const BatchArgs &a, uint64_t *out_size, hipStream_t stream);
 // (lz4.hip) XXH32, seed 0, of n bytes on one wave, to *got (device memory)
 hipError_t launch_lz4_xxh(const uint8_t *p, uint64_t n, uint32_t *got, hipStream_t stream);
+// snappy.hip: CHIP_FMT_SNAPPY_BLOCK / CHIP_FMT_SNAPPY (a.format), out_size == nullptr decodes the batch, else the size pass; no scratch
+hipError_t launch_snappy(const BatchArgs &a, uint64_t *out_size, hipStream_t stream);
 // lz4_enc.hip: the batch encoder of CHIP_FMT_LZ4_BLOCK / CHIP_FMT_LZ4 (a.format); lz4_encode_args_ok is the refusal that needs no
 // device: level -1 .. 12, strategy 0 for blocks and CHIP_LZ4_S_* bits for frames
 bool lz4_encode_args_ok(int format, int level, int strategy);

@@ -53,6 +53,12 @@ enum {
      * CHIP_F_COMPU_STATUS or CHIP_F_MEMBERS, and the streaming chip_decoder_new does not take them (compu has no LZ4). */
     CHIP_FMT_LZ4_BLOCK = 102,
     CHIP_FMT_LZ4 = 103,
+    /* Snappy ("Snappy: blocks and framed streams" below): one raw block (a varint preamble and elements: what snappy::RawCompress
+     * writes and a Parquet page holds), delimited by in_len[i], and one stream of the framing format (a .sz file).  Decoding only,
+     * the batch calls only (device, host and multi); not part of CHIP_FMT_DETECT routing, not with CHIP_F_COMPU_STATUS or
+     * CHIP_F_MEMBERS, not taken by the streaming objects or by any encode entry point (compu has no Snappy). */
+    CHIP_FMT_SNAPPY_BLOCK = 104,
+    CHIP_FMT_SNAPPY = 105,
     /* chip_encode_batch / _ex / _host and chip_encode_bound only: every unit becomes one BGZF block (below).  Decoding takes
      * CHIP_FMT_GZIP with the arrays of chip_bgzf_plan; the streaming chip_encoder_new does not take this tag. */
     CHIP_FMT_BGZF = 131,
@@ -204,7 +210,7 @@ int chip_decode_batch(int format, size_t n, const void *in_base, const uint64_t 
  * that owns the unit, as gzip -d and ZSTD_decompress do.  For CHIP_FMT_GZIP, CHIP_FMT_AUTO, CHIP_FMT_ZSTD and CHIP_FMT_DETECT (routed:
  * gzip / zlib units and zstd units each go to their member kernel, units that are neither are answered as without the flag).
  * CHIP_E_INVALID, before the device is looked for, with CHIP_FMT_DEFLATE, CHIP_FMT_ZLIB and CHIP_FMT_BROTLI (no concatenation
- * convention), with the LZ4 tags (concatenated frames are the caller's loop) and together with CHIP_F_COMPU_STATUS (compu has
+ * convention), with the LZ4 tags (concatenated frames are the caller's loop), with the Snappy tags and together with CHIP_F_COMPU_STATUS (compu has
  * no multi-member decode to mirror).  No reference counterpart, and
  * batch only: the streaming decoders do not take it (compu's caller sees Finished, calls reset and goes on), nor do
  * chip_decode_batch_host / _multi, which have no flags word.
@@ -259,8 +265,8 @@ int chip_decode_batch_ex(int format, uint32_t flags, size_t n, const void *in_ba
  * with the same flag; out_size[i] is the series' total and may exceed 2^32.
  * `format`: CHIP_FMT_DEFLATE, CHIP_FMT_ZLIB, CHIP_FMT_GZIP, CHIP_FMT_AUTO, CHIP_FMT_ZSTD (window_log_max: the default, as
  * chip_decode_batch), and CHIP_FMT_DETECT, routed exactly as a CHIP_FMT_DETECT decode batch is (units that are neither get
- * CHIP_UNKNOWN_FORMAT / CHIP_NEED_INPUT), and CHIP_FMT_LZ4_BLOCK / CHIP_FMT_LZ4 (flags 0 only; "LZ4: blocks and frames" below says
- * what the pass checks).  CHIP_FMT_BROTLI is CHIP_E_INVALID: brotli's literal context is the two previous
+ * CHIP_UNKNOWN_FORMAT / CHIP_NEED_INPUT), and CHIP_FMT_LZ4_BLOCK / CHIP_FMT_LZ4 and CHIP_FMT_SNAPPY_BLOCK / CHIP_FMT_SNAPPY (flags 0 only; "LZ4: blocks and frames" and
+ * "Snappy: blocks and framed streams" below say what the pass checks).  CHIP_FMT_BROTLI is CHIP_E_INVALID: brotli's literal context is the two previous
  * BYTES, so a brotli size pass is a full decode (it would decode into a ring) -- a different design.  Arguments are checked
  * before the device is looked for (as chip_decode_batch_ex does).
  * The contract:
@@ -1713,6 +1719,161 @@ enum { CHIP_LZ4_S_BLOCK_CHECKSUM = 1, CHIP_LZ4_S_NO_CONTENT_CHECKSUM = 2, CHIP_L
 enum { CHIP_W_LZ4_CONTENT_CHECKSUM = 2, CHIP_W_LZ4_BLOCK_CHECKSUM = 4 };
 int chip_lz4_block_encode_host(const uint8_t *in, uint64_t len, int level, uint8_t *out, uint64_t cap, uint64_t *out_len);
 int chip_lz4_frame_encode_host(const uint8_t *in, uint64_t len, int level, int strategy, uint8_t *out, uint64_t cap, uint64_t *out_len);
+
+/* ---- Snappy: blocks and framed streams (additive API, decoding) -------------- */
+
+/*
+ * CHIP_FMT_SNAPPY_BLOCK (104): a unit is ONE raw block of the Snappy format (format_description.txt): a varint preamble that states
+ * the decoded length, then elements; delimited by in_len[i].  What snappy::RawCompress writes and a Parquet / ORC / Avro page holds.
+ * CHIP_FMT_SNAPPY (105): a unit is ONE stream of the Snappy framing format (framing_format.txt, a .sz file), delimited by
+ * in_len[i]: the format has no end mark.
+ * Both go to chip_decode_batch / _ex / _sizes / _host / _multi, one wave per unit.  Flags must be 0: CHIP_F_COMPU_STATUS and
+ * CHIP_F_MEMBERS with either tag are CHIP_E_INVALID before the device is looked for.  chip_detect / CHIP_FMT_DETECT never route to
+ * them, the streaming objects do not take them, every encode entry point refuses them.  No reference counterpart.
+ *
+ * THE BLOCK RULES, which chip_snappy_block_decode_host defines (p: input cursor, o: bytes produced, len = in_len, cap = out_cap):
+ *   preamble: n = little-endian varint of at most 5 bytes
+ *     the input ends inside it (len == 0 included)  -> CHIP_NEED_INPUT
+ *     5th byte >= 16                                -> CHIP_SNAPPY_E_PREAMBLE  (the continuation bit set, or more than 32 bits)
+ *     non-minimal forms such as 80 00 are valid
+ *     n > cap                                       -> CHIP_NEED_OUTPUT, out_len = 0, in_used = 0, nothing written
+ *       (so the decode never needs a room check per element: o <= n <= cap)
+ *   per element, t = p:
+ *     p == len                                      -> o == n ? CHIP_FINISHED : CHIP_NEED_INPUT
+ *     o == n (bytes remain)                         -> CHIP_SNAPPY_E_LENGTH    (every element produces at least one byte)
+ *     tag = in[p++]
+ *     literal (tag & 3 == 0):
+ *       L = tag >> 2;  L >= 60: nb = L - 59;  len - p < nb -> CHIP_NEED_INPUT;  L = LE(nb bytes);  p += nb
+ *       L += 1  (in 64 bits: the 4-byte form ff ff ff ff is 2^32 and wraps nothing)
+ *       L > len - p                                 -> CHIP_NEED_INPUT         (the input is looked at before the length)
+ *       L > n - o                                   -> CHIP_SNAPPY_E_LENGTH
+ *       copy L bytes;  o += L;  p += L
+ *     copy:
+ *       tag & 3 == 1: 1 more byte,  M = 4 + ((tag >> 2) & 7), offset = ((tag >> 5) << 8) | byte
+ *       tag & 3 == 2: 2 more bytes, M = (tag >> 2) + 1, offset = LE16
+ *       tag & 3 == 3: 4 more bytes, M = (tag >> 2) + 1, offset = LE32
+ *       the bytes are missing                       -> CHIP_NEED_INPUT
+ *       offset == 0 or offset > o                   -> CHIP_SNAPPY_E_OFFSET
+ *       M > n - o                                   -> CHIP_SNAPPY_E_LENGTH
+ *       copy M bytes from o - offset, byte by byte in effect (offset < M repeats a period);  o += M
+ * On CHIP_FINISHED in_used == in_len.  On every other status in_used = t, the offset of the tag of the element in which decoding
+ * stopped (0 inside the preamble), and out_len = o, the complete elements in front of it.  Nothing beyond out_cap is touched.  The
+ * one-byte block 00 decodes to nothing.
+ *
+ * THE FRAME RULES, in the order of the checks (q: input cursor).  A chunk is 1 type byte, a 3-byte little-endian length s of what
+ * follows, and those s bytes:
+ *   len < 4                                         -> CHIP_NEED_INPUT
+ *   the first chunk is not ff 06 00 00 "sNaPpY"     -> CHIP_SNAPPY_E_HEADER  (cut inside it: CHIP_NEED_INPUT, unless the bytes
+ *                                                                            that are present already differ)
+ *   per chunk, b = q:
+ *     q == len                                      -> CHIP_FINISHED, in_used = len
+ *     len - q < 4, or len - q - 4 < s               -> CHIP_NEED_INPUT
+ *     type ff: s != 6 or the six bytes differ       -> CHIP_SNAPPY_E_HEADER;  else stepped over (concatenated streams)
+ *     type fe (padding) and 80..fd (skippable): stepped over
+ *     type 02..7f (reserved, unskippable)           -> CHIP_SNAPPY_E_CHUNK
+ *     type 00 (compressed) and 01 (uncompressed):  s < 4 -> CHIP_SNAPPY_E_CHUNK_SIZE;  c = LE32(q + 4)
+ *       01: s - 4 > 65536                           -> CHIP_SNAPPY_E_CHUNK_SIZE
+ *           s - 4 > cap - o                         -> CHIP_NEED_OUTPUT
+ *           the bytes are copied
+ *       00: the block rules over the s - 4 bytes behind the CRC, with these changes:
+ *           a preamble n > 65536                    -> CHIP_SNAPPY_E_CHUNK_SIZE
+ *           n > cap - o                             -> CHIP_NEED_OUTPUT
+ *           what is CHIP_NEED_INPUT for a lone block -> CHIP_SNAPPY_E_BLOCK  (the chunk's bytes are all present)
+ *       mask(CRC-32C(the chunk's content)) != c     -> CHIP_SNAPPY_E_CHECKSUM;  mask(x) = ((x >> 15) | (x << 17)) + 0xa282ead8
+ *     q += 4 + s
+ * On anything but CHIP_FINISHED in_used = b, the offset of the chunk in which decoding stopped (0 for the first).  out_len: the
+ * chunks in front in full; inside a failing block also that block's complete elements; on CHIP_SNAPPY_E_CHECKSUM the failing
+ * chunk's content is not counted.
+ * The size pass (chip_decode_batch_sizes): every verdict above depends on positions, never on decoded bytes, so the pass is the
+ * parse without the copies and exact on every unit; it is blind only to the CRC-32C comparison (rule 4 of its contract).  The
+ * preamble is not trusted: the elements are walked.
+ */
+enum {
+    CHIP_SNAPPY_E_PREAMBLE = -210,
+    CHIP_SNAPPY_E_OFFSET = -211,
+    CHIP_SNAPPY_E_LENGTH = -212,
+    CHIP_SNAPPY_E_HEADER = -213,
+    CHIP_SNAPPY_E_CHUNK = -214,
+    CHIP_SNAPPY_E_CHUNK_SIZE = -215,
+    CHIP_SNAPPY_E_BLOCK = -216,
+    CHIP_SNAPPY_E_CHECKSUM = -217
+};
+
+/* The block rules on HOST memory, and their definition: returns the status (CHIP_FINISHED, CHIP_NEED_INPUT, CHIP_NEED_OUTPUT,
+ * CHIP_SNAPPY_E_PREAMBLE, _OFFSET, _LENGTH), or CHIP_E_INVALID for a NULL out_len / in_used, a NULL `in` with len > 0 or a NULL
+ * `out` with cap > 0.  len and cap are at most 2^32 - 1 (CHIP_E_INVALID), as a unit's are.  Pure host arithmetic. */
+int chip_snappy_block_decode_host(const uint8_t *in, uint64_t len, uint8_t *out, uint64_t cap, uint64_t *out_len, uint64_t *in_used);
+
+/*
+ * The DATA chunks of a framed buffer, from the chunk headers alone, with chip_lz4_blocks' conventions.  The walk of `len` bytes:
+ *     the first chunk as in the frame rules: len < 4 or cut inside the identifier -> TRUNCATED, another first chunk -> BAD_HEADER
+ *     per chunk, b = q:  q == len -> status CHIP_ZPLAN_OK, in_used = len
+ *                 len - q < 4 or len - q - 4 < s -> TRUNCATED
+ *                 type ff that is not the identifier, types 02..7f, types 00 / 01 with s < 4 -> BAD_HEADER
+ *                 types ff, fe, 80..fd: n_skipped + 1 > CHIP_ZPLAN_MAX_BLOCKS -> TOO_LARGE;  n_skipped++ (the first identifier is
+ *                 not counted)
+ *                 types 00 / 01: n_chunks + 1 > CHIP_ZPLAN_MAX_BLOCKS -> TOO_LARGE;  chunk n: offset = b, size = s, type, crc = the
+ *                 stored (masked) LE32;  n_chunks++
+ *                 q += 4 + s
+ * A walk that stops early keeps what it has counted, with in_used = b: the chunks in front of b are whole.  Nothing deeper is
+ * looked at: no chunk-size limit, no preamble, no CRC.  `chunks` receives the first min(n_chunks, max_chunks) records:
+ * max_chunks = 0 with a NULL array counts, a second call fills.  CHIP_E_INVALID, before the device is looked for: summary NULL, a
+ * NULL buffer with len > 0, a NULL array with max_chunks > 0 (chip_snappy_chunks: in_base not 4-byte aligned, len > 2^40).
+ */
+typedef struct {
+    uint64_t offset; /* of the chunk's 4-byte header in the buffer */
+    uint32_t size;   /* s: the bytes behind the header, the 4 CRC bytes included */
+    uint32_t type;   /* 0 compressed, 1 uncompressed */
+    uint32_t crc;    /* the stored, masked CRC-32C of the content */
+    uint32_t pad;
+} chip_snappy_chunk;
+typedef struct {
+    uint64_t n_chunks, n_skipped, in_used;
+    int32_t status; /* CHIP_ZPLAN_OK, _TRUNCATED, _BAD_HEADER, _TOO_LARGE */
+    uint32_t pad;
+} chip_snappy_chunks_summary;
+int chip_snappy_chunks_host(const uint8_t *in, uint64_t len, uint64_t max_chunks, chip_snappy_chunk *chunks, chip_snappy_chunks_summary *summary);
+/* The same for DEVICE memory: in_base and chunks are DEVICE pointers, summary is a HOST pointer; in_base 4-byte aligned, its
+ * allocation padded to a multiple of 4.  One lane hops over the chunk headers.  SYNCHRONOUS on `stream` (one wait); a launch slot
+ * of its own (the summary only), released by chip_trim(). */
+int chip_snappy_chunks(const void *in_base, uint64_t len, uint64_t max_chunks, chip_snappy_chunk *chunks, chip_snappy_chunks_summary *summary,
+                       void *stream);
+
+/* CRC-32C (Castagnoli, reflected polynomial 0x82F63B78, initial value and final inversion 0xFFFFFFFF) of many ranges of DEVICE
+ * memory, chip_xxh32_batch's sibling: crc[i] = CRC-32C of base[off[i] .. + len32[i]).  UNMASKED: the value iSCSI and ext4 store; the
+ * Snappy framing format stores mask() of it (above).  Every pointer is a DEVICE pointer, off[i] may have any alignment; it only
+ * enqueues on `stream`: no wait, no scratch.  One wave per range (its 64 lanes take 64 pieces and combine them), so one huge range
+ * runs at one wave's rate: only many ranges fill the card.  CHIP_E_INVALID, before the device is looked for: a NULL array or base
+ * with n > 0, n > 2^31 - 1.  n == 0: CHIP_OK, the device is not touched. */
+int chip_crc32c_batch(size_t n, const void *base, const uint64_t *off, const uint32_t *len32, uint32_t *crc, void *stream);
+
+/*
+ * ONE framed stream decoded with a wave per chunk, with chip_lz4_parallel's conventions: in_base and out_base are DEVICE pointers,
+ * in_base 4-byte aligned and its allocation padded to a multiple of 4; summary is a HOST pointer; SYNCHRONOUS on `stream`; scratch
+ * in a launch slot of its own (80 bytes per chunk: its record and its unit arrays), released by chip_trim().  flags must be 0.  A
+ * chunk holds at most 65 536 bytes of content and never refers to another, so the stream is a batch by construction.
+ * The passes, all on `stream`: the walk (chip_snappy_chunks); the size pass over the compressed chunks as CHIP_FMT_SNAPPY_BLOCK
+ * units (an uncompressed chunk is an empty unit that gets its size from s), and one thread per chunk that counts the chunks that
+ * did not finish or exceed 65 536 bytes; chip_layout_units; the block batch straight into out_base; the uncompressed chunks by the
+ * file writer's copy; chip_crc32c_batch over the content ranges, compared by one thread per chunk.
+ * path = CHIP_SNAPPYPAR_PARALLEL when the walk is OK, there are at least two data chunks and every pass is clean: the bytes,
+ * out_len, in_used and status (CHIP_FINISHED) are those of chip_decode_batch(CHIP_FMT_SNAPPY, 1, ..).  The same with
+ * total_out > out_cap: CHIP_NEED_OUTPUT, out_len = 0, total_out the exact size to come back with; nothing is written and no CRC is
+ * compared (the call that has the room compares them).
+ * Anything else: path = CHIP_SNAPPYPAR_SERIAL and the answer is the one-unit CHIP_FMT_SNAPPY decode's of the same buffer, status
+ * and out_len included -- that decode is the arbiter of every verdict -- if a unit can hold the buffer (len and out_cap at most
+ * 2^32 - 1); else path = CHIP_SNAPPYPAR_REFUSED and nothing is written.
+ * CHIP_E_INVALID before the device is looked for: summary NULL, a NULL buffer with a length, in_base misaligned, flags != 0,
+ * len > 2^40.
+ */
+enum { CHIP_SNAPPYPAR_SERIAL = 0, CHIP_SNAPPYPAR_PARALLEL = 1, CHIP_SNAPPYPAR_REFUSED = 2 };
+typedef struct {
+    uint64_t n_chunks, out_len, in_used, total_out;
+    int32_t status;
+    uint32_t path, n_skipped, pad;
+} chip_snappy_parallel_summary;
+int chip_snappy_parallel(const void *in_base, uint64_t len, void *out_base, uint64_t out_cap, uint32_t flags,
+                         chip_snappy_parallel_summary *summary, void *stream);
 
 /* ---- one large stream: the checkpoint index (additive API) ------------------ */
 

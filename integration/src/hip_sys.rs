@@ -258,6 +258,61 @@ pub struct chip_lz4_parallel_summary {
     pub pad: u32,
 }
 
+///Snappy (the decode batch calls only; no compu counterpart): one raw block per unit, one stream of the framing format per unit
+pub const CHIP_FMT_SNAPPY_BLOCK: c_int = 104;
+pub const CHIP_FMT_SNAPPY: c_int = 105;
+///per-unit status of a Snappy unit, beside `CHIP_NEED_INPUT` / `CHIP_NEED_OUTPUT` / `CHIP_FINISHED`
+pub const CHIP_SNAPPY_E_PREAMBLE: i32 = -210;
+pub const CHIP_SNAPPY_E_OFFSET: i32 = -211;
+pub const CHIP_SNAPPY_E_LENGTH: i32 = -212;
+pub const CHIP_SNAPPY_E_HEADER: i32 = -213;
+pub const CHIP_SNAPPY_E_CHUNK: i32 = -214;
+pub const CHIP_SNAPPY_E_CHUNK_SIZE: i32 = -215;
+pub const CHIP_SNAPPY_E_BLOCK: i32 = -216;
+pub const CHIP_SNAPPY_E_CHECKSUM: i32 = -217;
+///`chip_snappy_parallel_summary::path`
+pub const CHIP_SNAPPYPAR_SERIAL: u32 = 0;
+pub const CHIP_SNAPPYPAR_PARALLEL: u32 = 1;
+pub const CHIP_SNAPPYPAR_REFUSED: u32 = 2;
+
+///one data chunk of a framed Snappy stream as `chip_snappy_chunks` describes it: where its 4-byte header lies, the length `s` behind
+///it, its type (0 compressed, 1 uncompressed), the stored masked CRC-32C
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct chip_snappy_chunk {
+    pub offset: u64,
+    pub size: u32,
+    pub r#type: u32,
+    pub crc: u32,
+    pub pad: u32,
+}
+
+///what the walk over a framed Snappy stream's chunk headers found; `status` is a `CHIP_ZPLAN_*` value
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct chip_snappy_chunks_summary {
+    pub n_chunks: u64,
+    pub n_skipped: u64,
+    pub in_used: u64,
+    pub status: i32,
+    pub pad: u32,
+}
+
+///what `chip_snappy_parallel` did: data chunks of the stream, bytes written, input consumed, the exact size to come back with, the
+///one-unit decode's status, the path taken, the chunks stepped over
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct chip_snappy_parallel_summary {
+    pub n_chunks: u64,
+    pub out_len: u64,
+    pub in_used: u64,
+    pub total_out: u64,
+    pub status: i32,
+    pub path: u32,
+    pub n_skipped: u32,
+    pub pad: u32,
+}
+
 ///`chip_gzip_plan_summary::status`
 pub const CHIP_GZPLAN_OK: i32 = 0;
 pub const CHIP_GZPLAN_TRUNCATED: i32 = 1;
@@ -911,6 +966,19 @@ extern "C" {
     pub fn chip_lz4_block_encode_host(input: *const u8, len: u64, level: c_int, out: *mut u8, cap: u64, out_len: *mut u64) -> c_int;
     ///one LZ4 frame of host memory on the host (`strategy`: `CHIP_LZ4_S_*` bits); returns `CHIP_ENC_*`
     pub fn chip_lz4_frame_encode_host(input: *const u8, len: u64, level: c_int, strategy: c_int, out: *mut u8, cap: u64, out_len: *mut u64) -> c_int;
+    // ---- Snappy: blocks and framed streams, decode only (no reference counterpart); the batch calls take CHIP_FMT_SNAPPY_BLOCK / CHIP_FMT_SNAPPY
+    ///the block rules on host memory, and their definition; returns the unit's status
+    pub fn chip_snappy_block_decode_host(input: *const u8, len: u64, out: *mut u8, cap: u64, out_len: *mut u64, in_used: *mut u64) -> c_int;
+    ///the data chunks of a framed stream in a host buffer, from the chunk headers alone; pure host arithmetic
+    pub fn chip_snappy_chunks_host(input: *const u8, len: u64, max_chunks: u64, chunks: *mut chip_snappy_chunk, summary: *mut chip_snappy_chunks_summary) -> c_int;
+    ///the same answer for a buffer in device memory (device records, host summary); synchronous on `stream`
+    pub fn chip_snappy_chunks(in_base: *const c_void, len: u64, max_chunks: u64, chunks: *mut chip_snappy_chunk, summary: *mut chip_snappy_chunks_summary,
+                              stream: *mut c_void) -> c_int;
+    ///CRC-32C (Castagnoli), unmasked, of many device ranges, one wave per range; only enqueues
+    pub fn chip_crc32c_batch(n: usize, base: *const c_void, off: *const u64, len32: *const u32, crc: *mut u32, stream: *mut c_void) -> c_int;
+    ///one framed Snappy stream decoded with a wave per chunk; anything not clean is the one-unit decode's answer; synchronous on `stream`
+    pub fn chip_snappy_parallel(in_base: *const c_void, len: u64, out_base: *mut c_void, out_cap: u64, flags: u32, summary: *mut chip_snappy_parallel_summary,
+                                stream: *mut c_void) -> c_int;
     ///`chip_read_ranges(CHIP_FMT_ZSTD, ..)` with the seek table's per-unit checksums verified on the device (`checksum` null: that
     ///call itself); synchronous on `stream`
     pub fn chip_zstd_seek_read(n_units: usize, in_base: *const c_void, in_off: *const u64, in_len: *const u32, out_off: *const u64,
